@@ -4,6 +4,7 @@
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
 
 One "step" = one pass of the hot path (sola_forward + sola_loss + sola_select through the C ABI) over a batch of
 ``--batch`` independent synthetic (video, expression) samples already resident in HBM.  The conv weights are
@@ -74,7 +75,12 @@ def parse():
     ap.add_argument("--precision", choices=["f32", "f16x3"], default=os.environ.get("SOLA_PRECISION", "f16x3"),
                     help="arithmetic of the convs/projections: exact f32 MFMA, or split-f16 operands (3 f16 MFMAs per product, "
                          "f32 accumulate, ~22-bit products; same 1e-3 parity bar)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------ helpers
@@ -864,6 +870,30 @@ def compact(o, path=()):
     return _sig(o) if len(path) > 1 or path[:1] not in (("value",), ("ms_per_step",)) else o
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: the arrays one timed step hands its caller, as float32 .npy files under ``path``: score_map [B,N], score_tokens
+    [B,N,D], loss [total, bce, alignment], prob and pred [B,N] (ops.select).  score_tokens is written whole when everything fits in
+    DUMP_BYTES, else as a fixed sample of its B*N rows (seed 0, sorted; score_tokens_rows.npy holds the flat row indices, float64)."""
+    sm, st, loss3, prob, pred = (t.detach().float().cpu().numpy() for t in outs)
+    small = {"score_map": sm, "loss": loss3, "prob": prob, "pred": pred}
+    arrays = dict(small)
+    rows = st.reshape(-1, st.shape[-1])
+    room = DUMP_BYTES - sum(a.nbytes for a in small.values())
+    if st.nbytes <= room:
+        arrays["score_tokens"] = st
+    else:
+        k = (room - 1024) // (rows.shape[1] * 4 + 8)  # keep the index array inside the budget too
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=k, replace=False))
+        arrays["score_tokens"] = rows[idx]
+        arrays["score_tokens_rows"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def emit(out):
     full = os.environ.get("SOLA_BENCH_FULL") or os.path.join(ROOT, "gpurun_out", "bench_full.json")
     try:
@@ -936,8 +966,8 @@ def main():
         with torch.no_grad():
             sm, st = m(obj, lang)
             loss3 = track_selection_losses(sm, st, labels, pos, m.negative_token.weight, POS_W, TEMP, ALIGN_W)
-            _prob, pred = ops.select(sm, 0.5)
-        return loss3, pred
+            prob, pred = ops.select(sm, 0.5)
+        return sm, st, loss3, prob, pred
 
     def barrier():
         if world > 1:
@@ -960,10 +990,13 @@ def main():
     _lib.profile_read(reset=True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss3, pred = step()
+        outs = step()
     barrier()
     elapsed = time.perf_counter() - t0
     prof = _lib.profile_read(reset=True)
+    loss3 = outs[2]
+    if args.dump_outputs and rank == 0:  # what the last timed step returned, written before anything else runs on the device
+        dump_outputs(args.dump_outputs, outs)
     _lib.profile_enable(True)
     for _ in range(args.steps):
         step()

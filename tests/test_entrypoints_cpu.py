@@ -134,3 +134,36 @@ def test_staging_pool_bookkeeping(monkeypatch):
     # 48 samples were staged per pass; the second pass (and the duplicates' buffers within the first) came from the pool
     assert staged.pool.hits + staged.pool.misses == 96 and staged.pool.misses <= 48 and staged.pool.hits >= 48
     assert all(buf.numel() % (1 << 20) == 0 for lst in staged.pool._free.values() for buf in lst)
+
+
+def test_bench_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: every array a float32 .npy, the whole dump within bench.DUMP_BYTES, score_tokens whole when it fits and
+    otherwise the same fixed sample of rows on every call (two builds are compared output for output)."""
+    import sys
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    B, N, D = 4, 8, 16
+    outs = (torch.randn(B, N, generator=g), torch.randn(B, N, D, generator=g), torch.randn(3, generator=g),
+            torch.rand(B, N, generator=g), (torch.rand(B, N, generator=g) > 0.5).float())
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert sorted(got) == ["loss", "pred", "prob", "score_map", "score_tokens"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["score_tokens"], outs[1].numpy())
+    np.testing.assert_array_equal(got["score_map"], outs[0].numpy())
+    # the headline shape (B=256, N=64, D=1024): score_tokens alone is 64 MiB, so its rows are sampled
+    big = (torch.zeros(256, 64), torch.arange(256 * 64, dtype=torch.float32)[:, None].expand(256 * 64, 1024).reshape(256, 64, 1024),
+           torch.zeros(3), torch.zeros(256, 64), torch.zeros(256, 64))
+    for tag in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / tag), big)
+    sizes = sum(p.stat().st_size for p in (tmp_path / "b").glob("*.npy"))
+    assert sizes <= bench.DUMP_BYTES, sizes
+    rows = np.load(tmp_path / "b" / "score_tokens_rows.npy")
+    st = np.load(tmp_path / "b" / "score_tokens.npy")
+    assert rows.dtype == np.float64 and st.shape == (len(rows), 1024) and len(rows) > 8192 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(st[:, 0], rows.astype(np.float32))  # each kept row is the row its index names
+    for name in ("score_tokens", "score_tokens_rows"):
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{name}.npy"), np.load(tmp_path / "c" / f"{name}.npy"))
