@@ -485,6 +485,26 @@ int sola_rle_fill_or(const uint32_t* dev_cum, const int64_t* dev_off, int n_fram
  * or runs covering more than `limit` pixels; limit < 0 disables that check). */
 int64_t sola_rle_string_to_cum(const char* str, int64_t len, uint32_t* host_cum, int64_t cap, int64_t limit);
 
+/* Masks -> COCO compressed RLE strings, byte-identical to pycocotools encode + rleToString on {0,1} masks; replaces the
+ * host copy + per-frame pycocotools loop of track_generation/seg_utils.py encode_rle_masklet_torch.  n masks [n,h,w]
+ * row-major; elem_type 0 = uint8 (!= 0), 1 = float32 (!= 0), 2 = float32 tracker logits (> 0).  n >= 1 (any n: launches
+ * are chunked by 65535 frames), h*w < 2^31.  Three calls on one stream, each output sized by the previous one's result:
+ *   1. sola_rle_encode_runs: dev_run_off [n+1] int64 = first run of each frame (dev_run_off[n] = total runs).  dev_scratch
+ *      (>= sola_rle_encode_scratch_bytes(n,h,w) bytes, 4-byte aligned) keeps per-segment offsets for call 2.
+ *   2. sola_rle_encode_cum: the same masks and the scratch as call 1 left it -> dev_cum [total runs] uint32 = each
+ *      frame's inclusive prefix sums of its run lengths (column-major, what sola_rle_fill_or reads with dev_run_off as its
+ *      offsets and K = 1), and dev_char_off [n+1] int64 = first character of each frame (dev_char_off[n] = total).
+ *   3. sola_rle_encode_chars: dev_chars [total characters] = every frame's string back to back (no terminators).  Reads
+ *      dev_cum / dev_run_off / dev_char_off only, so it also encodes prefix sums that did not come from call 2.
+ * Scratch: n * w * ceil(h/64) * 4 bytes, rounded up to 256; 0 for bad sizes (host-only). */
+size_t sola_rle_encode_scratch_bytes(int n, int h, int w);
+int sola_rle_encode_runs(const void* dev_masks, int elem_type, int n, int h, int w, int64_t* dev_run_off,
+                         void* dev_scratch, size_t scratch_bytes, void* stream);
+int sola_rle_encode_cum(const void* dev_masks, int elem_type, int n, int h, int w, const int64_t* dev_run_off,
+                        uint32_t* dev_cum, int64_t* dev_char_off, void* dev_scratch, size_t scratch_bytes, void* stream);
+int sola_rle_encode_chars(const uint32_t* dev_cum, const int64_t* dev_run_off, const int64_t* dev_char_off, int n,
+                          char* dev_chars, void* stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream; used by bench.py's roofline object) ------------ */
 enum { SOLA_PROF_GEMM = 0,      /* gemm_nt_f32_kernel<128,128> */
        SOLA_PROF_ATTN = 1,      /* attn_fwd_f32_kernel */

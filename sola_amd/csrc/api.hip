@@ -1233,6 +1233,32 @@ extern "C" int sola_rle_fill_or(const uint32_t* cum, const int64_t* off, int n_f
                               reinterpret_cast<long long*>(area), as_stream(stream_));
 }
 
+// masks -> COCO compressed RLE (rle_encode.hip)
+extern "C" size_t sola_rle_encode_scratch_bytes(int n, int h, int w) { return rle_encode_scratch_bytes(n, h, w); }
+
+extern "C" int sola_rle_encode_runs(const void* masks, int elem_type, int n, int h, int w, int64_t* run_off, void* scratch,
+                                    size_t scratch_bytes, void* stream_) {
+    SOLA_ARG(masks && run_off && scratch, "rle_encode_runs: null argument");
+    SOLA_ARG((reinterpret_cast<uintptr_t>(scratch) & 3) == 0, "rle_encode_runs: scratch must be 4-byte aligned");
+    return launch_rle_encode_runs(masks, elem_type, n, h, w, reinterpret_cast<long long*>(run_off), scratch, scratch_bytes,
+                                  as_stream(stream_));
+}
+
+extern "C" int sola_rle_encode_cum(const void* masks, int elem_type, int n, int h, int w, const int64_t* run_off, uint32_t* cum,
+                                   int64_t* char_off, void* scratch, size_t scratch_bytes, void* stream_) {
+    SOLA_ARG(masks && run_off && cum && char_off && scratch, "rle_encode_cum: null argument");
+    SOLA_ARG((reinterpret_cast<uintptr_t>(scratch) & 3) == 0, "rle_encode_cum: scratch must be 4-byte aligned");
+    return launch_rle_encode_cum(masks, elem_type, n, h, w, reinterpret_cast<const long long*>(run_off), cum,
+                                 reinterpret_cast<long long*>(char_off), scratch, scratch_bytes, as_stream(stream_));
+}
+
+extern "C" int sola_rle_encode_chars(const uint32_t* cum, const int64_t* run_off, const int64_t* char_off, int n, char* chars,
+                                     void* stream_) {
+    SOLA_ARG(cum && run_off && char_off && chars, "rle_encode_chars: null argument");
+    return launch_rle_encode_chars(cum, reinterpret_cast<const long long*>(run_off), reinterpret_cast<const long long*>(char_off),
+                                   n, chars, as_stream(stream_));
+}
+
 // Host helper (no GPU work): COCO compressed run-length string -> inclusive prefix sums of the run lengths, the form
 // sola_rle_fill_or consumes.  pycocotools rleFrString: 5 data bits + continuation bit per char (offset 48), sign
 // extension from bit 4 of the last char, runs from the 4th on stored as a delta to the run two places back.

@@ -477,3 +477,12 @@ int launch_mask_bilinear_pack(const void* masks, int elem_type, int n, int h, in
 int launch_mask_unpack(const uint32_t* bits, int n, int H, int W, void* out, int elem_type, hipStream_t s);
 int launch_rle_fill_or(const uint32_t* cum, const long long* off, int n_frames, int K, int h, int w, uint8_t* out,
                        uint32_t* bits, long long* area, hipStream_t s);
+
+// ---- masks -> COCO compressed RLE (rle_encode.hip) ----------------------------------------------------------------
+size_t rle_encode_scratch_bytes(int n, int h, int w);
+int launch_rle_encode_runs(const void* masks, int elem_type, int n, int h, int w, long long* run_off, void* scratch,
+                           size_t scratch_bytes, hipStream_t s);
+int launch_rle_encode_cum(const void* masks, int elem_type, int n, int h, int w, const long long* run_off, uint32_t* cum,
+                          long long* char_off, void* scratch, size_t scratch_bytes, hipStream_t s);
+int launch_rle_encode_chars(const uint32_t* cum, const long long* run_off, const long long* char_off, int n, char* chars,
+                            hipStream_t s);

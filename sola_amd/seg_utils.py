@@ -365,3 +365,68 @@ def rle_merge_or(rle_lists, device, packed=False):
     out = torch.empty((T, h, w), device=dev, dtype=torch.uint8)
     check(lib().sola_rle_fill_or(ptr(cum_t), ptr(off_t), T, K, h, w, ptr(out), None, None, stream), "sola_rle_fill_or")
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# masks -> COCO compressed RLE (the track writers' seg_utils.encode_rle_masklet_torch / utils.encode_rle_mask)
+# ----------------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def encode_rle_masklet(masks, logits=False, return_cum=False):
+    """(T,h,w) masks on the GPU -> list of T ``{"size": [h, w], "counts": str}``, byte-identical to pycocotools
+    ``encode`` + ``counts.decode("utf-8")`` per frame (seg_utils.encode_rle_masklet_torch), without the host copy of the
+    masklet.  uint8 / bool / float32 pixels count when != 0; ``logits=True`` takes float32 tracker logits and counts
+    ``> 0`` (the ``(out_mask_logits > 0.0)`` of generate_tokens_grid.py:215).  The host reads two sizes and copies the
+    characters once.  ``return_cum=True`` stops before the characters and returns the device ``(cum, run_off)``: cum
+    int32 [runs] holds the uint32 inclusive prefix sums of every frame's run lengths and run_off int64 [T+1] the first
+    run of each frame, which is what ``sola_rle_fill_or`` reads (offsets = run_off, K = 1)."""
+    masks = _prep(masks)
+    if masks.dim() != 3:
+        raise SolaError(f"encode_rle_masklet: masks must be (T,h,w), got {tuple(masks.shape)}")
+    if logits and masks.dtype != torch.float32:
+        raise SolaError("logits must be float32")
+    et = 2 if logits else _elem_type(masks)
+    n, h, w = masks.shape
+    dev = masks.device
+    offs = torch.zeros((2, n + 1), device=dev, dtype=torch.int64)  # run_off, char_off
+    run_off, char_off = offs[0], offs[1]
+    if n == 0:
+        return (torch.empty((0,), device=dev, dtype=torch.int32), run_off) if return_cum else []
+    L, stream = lib(), current_stream(dev)
+    nb = L.sola_rle_encode_scratch_bytes(n, h, w)
+    scratch = torch.empty((max(nb, 1),), device=dev, dtype=torch.uint8)
+    check(L.sola_rle_encode_runs(ptr(masks), et, n, h, w, ptr(run_off), ptr(scratch), nb, stream), "sola_rle_encode_runs")
+    runs = int(run_off[n])  # host read 1: the size of cum
+    cum = torch.empty((runs,), device=dev, dtype=torch.int32)
+    check(L.sola_rle_encode_cum(ptr(masks), et, n, h, w, ptr(run_off), ptr(cum), ptr(char_off), ptr(scratch), nb, stream),
+          "sola_rle_encode_cum")
+    if return_cum:
+        return cum, run_off
+    coff = char_off.cpu().tolist()  # host read 2: every frame's first character, coff[n] = the size of the string buffer
+    chars = torch.empty((coff[n],), device=dev, dtype=torch.uint8)
+    check(L.sola_rle_encode_chars(ptr(cum), ptr(run_off), ptr(char_off), n, ptr(chars), stream), "sola_rle_encode_chars")
+    text = chars.cpu().numpy().tobytes().decode("ascii")
+    return [{"size": [h, w], "counts": text[coff[i]:coff[i + 1]]} for i in range(n)]
+
+
+encode_rle_masklet_torch = encode_rle_masklet
+
+
+def encode_rle_mask(mask, logits=False):
+    """(h,w) mask on the GPU -> one ``{"size": [h, w], "counts": str}`` (utils.encode_rle_mask)."""
+    if mask.dim() != 2:
+        raise SolaError(f"encode_rle_mask: mask must be (h,w), got {tuple(mask.shape)}")
+    return encode_rle_masklet(mask.unsqueeze(0), logits)[0]
+
+
+@torch.no_grad()
+def encode_rle_masklets(masklets, logits=False):
+    """Every track of a SAM2 batch (list of (T_i,h,w) masklets of one size and dtype) -> list of per-track RLE lists,
+    from ONE encode over the masklets concatenated along frames."""
+    if len(masklets) == 0:
+        return []
+    flat = encode_rle_masklet(torch.cat([_prep(m) for m in masklets]), logits)
+    out, f = [], 0
+    for m in masklets:
+        out.append(flat[f:f + m.shape[0]])
+        f += m.shape[0]
+    return out
