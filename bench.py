@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full               # + every leg listed below the headline's own fields
 
 One "step" = one pass of the hot path (sola_forward + sola_loss + sola_select through the C ABI) over a batch of
 ``--batch`` independent synthetic (video, expression) samples already resident in HBM.  The conv weights are
@@ -18,14 +19,19 @@ Arithmetic of the convs/projections (98 % of the FLOPs), --precision:
         exact-f32 kernels if a value leaves the format's range (include/sola_hip.h: sola_set_split_guard; the guard's
         read-back is inside the timed region).  It meets the same parity bar as exact f32 at every input scale
         (tests/test_gpu_range.py: every row of three 256-sample batches in both modes; the two sit in the same error class).
-  f32   exact v_mfma_f32_32x32x2_f32.  In the default mode the same workload is also timed on this path after the timed
-        region and reported as "exact_f32_mode" with its own roofline entries.
+  f32   exact v_mfma_f32_32x32x2_f32.  With --full, the default mode also times the same workload on this path after the
+        timed region and reports it as "exact_f32_mode" with its own roofline entries.
 
-The ONE JSON line carries the driver's contract plus (rank 0; the legs after the timed region run at N=1 only):
+The ONE JSON line carries the driver's contract plus what the timed region itself yields (rank 0):
   roofline            the dominant kernel of the headline mode.  `achieved` / `frac` are ALGORITHMIC (2MNK per GEMM) against
                       the dense MFMA peak of the instruction the kernel issues; the split-f16 kernel executes 3 f16 MFMA
                       products per algorithmic product, so `achieved_executed` / `frac_executed` give the matrix-pipe view
   roofline_attention  the attention-core kernel named by the north star, against the 8 TB/s HBM peak
+A plain run does nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  Everything that takes runs of its
+own comes with --full (rank 0; the legs after the timed region run at N=1 only):
+  kernel_ms_per_step  per-category kernel time from an untimed pass of the same steps right behind the timed region
+  max_abs_logit_err_vs_oracle / max_abs_logit_err_vs_reference
+                      every row of the timed batch against the fp32 oracle / the reference's own logits (at N > 1: every rank's)
   exact_f32_mode      the same step on the exact-f32 kernels: value + roofline (f32 MFMA peak) + roofline_attention
   stress_T128_N128    BASELINE config C4 (T=128, N=128): value + roofline + roofline_attention
   ragged              sola_forward_ragged on a MeViS-like mix (N 8..80, T 20..200, L 4..24): one expression per video, and
@@ -67,9 +73,12 @@ def parse():
     ap.add_argument("--tracks", type=int, default=64)
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--text-len", type=int, default=16)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--train-steps", type=int, default=5, help="steps of the training_step leg (rank 0, N=1, outside the timed region; 0 = skip)")
-    ap.add_argument("--extra-legs", type=int, default=1, help="0 skips the stress / ragged / iou legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run every other leg (kernel breakdown, parity, exact f32, other shapes and modes, "
+                         "training, CPU baseline); a plain run reports the timed region alone")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--train-steps", type=int, default=5, help="--full: steps of the training_step leg (rank 0, N=1, outside the timed region; 0 = skip)")
+    ap.add_argument("--extra-legs", type=int, default=1, help="--full: 0 skips the stress / ragged / iou legs (profiling runs)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="sola_tune switch for A/B measurements (reported in config.tune; not the default line)")
     ap.add_argument("--cached-ws", action="store_true", help="inference mode: standardise conv weights once (not the headline)")
     ap.add_argument("--precision", choices=["f32", "f16x3"], default=os.environ.get("SOLA_PRECISION", "f16x3"),
@@ -984,7 +993,7 @@ def main():
     barrier()
     # live kernel timing in the timed region: the launches the two rooflines are computed from (GEMMs, attention core).  Every timed
     # launch costs two event records on the stream (2.8 % of the step with all ~120 launches bracketed, tools/prof_overhead.py); the
-    # complete per-category breakdown (kernel_ms_per_step) comes from an UNTIMED pass of the same steps behind the timed region.
+    # complete per-category breakdown (kernel_ms_per_step, --full) comes from an UNTIMED pass of the same steps behind the timed region.
     roof_cats = ["gemm128", "gemm64", "gemm_split", "gemm_split256", "gemm_split256_gn", "attn"]
     _lib.profile_enable(True, categories=roof_cats)
     _lib.profile_read(reset=True)
@@ -997,20 +1006,24 @@ def main():
     loss3 = outs[2]
     if args.dump_outputs and rank == 0:  # what the last timed step returned, written before anything else runs on the device
         dump_outputs(args.dump_outputs, outs)
-    _lib.profile_enable(True)
-    for _ in range(args.steps):
-        step()
-    barrier()
+    prof_all = None
+    if args.full:
+        _lib.profile_enable(True)
+        for _ in range(args.steps):
+            step()
+        barrier()
+        prof_all = _lib.profile_read(reset=True)
     gc.enable()
-    prof_all = _lib.profile_read(reset=True)
     _lib.profile_enable(False)
     assert torch.isfinite(loss3).all()
     fallbacks, guard_bits = m.split_fallbacks()
 
+    dist_parity = None
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if world > 1 and args.full:
         # parity at N > 1 (round 6): every rank that owns a batch the reference's logits are committed for (seeds 1000-1002 = ranks 0-2 at the
         # default batch) checks every row of ITS batch; the worst error over those ranks goes into the line (a 64 KB fixture, no CPU work)
         rg = reference_logits(f"u256.{1000 + rank}") if (B, N, T, L) == (256, 64, 32, 16) else None
@@ -1032,9 +1045,7 @@ def main():
     exact = None
     parity = None
     parity_ref = None
-    if world == 1:
-        dist_parity = None
-    if args.precision == "f16x3" and world == 1:
+    if args.full and args.precision == "f16x3" and world == 1:
         with torch.no_grad():
             sm_split, _ = m(obj, lang)
         m.precision = "f32"
@@ -1078,7 +1089,7 @@ def main():
         m.precision = args.precision
 
     dist_res = None
-    if world > 1 and args.train_steps > 0:  # every rank takes part (collectives); reported by rank 0
+    if args.full and world > 1 and args.train_steps > 0:  # every rank takes part (collectives); reported by rank 0
         try:  # a (symmetric) failure of this extra leg must not cost the headline line
             dist_res = dist_legs(cfg, sd, dev, world, rank, max(2, min(args.train_steps, 5)))
         except Exception as e:  # noqa: BLE001
@@ -1127,9 +1138,12 @@ def main():
                        **({"tune": args.tune} if args.tune else {})},
             "gflop_per_sample": round(fl["total"] / 1e9, 3),
             "model_tflops": round(value * fl["total"] / 1e12, 2),
-            "roofline": roofline, "roofline_attention": roofline_attn, "kernel_ms_per_step": kernel_ms(prof_all, args.steps),
-            "kernel_ms_per_step_source": "untimed pass of the same steps with every launch bracketed by events; the timed region brackets the GEMM and attention launches only",
+            "roofline": roofline, "roofline_attention": roofline_attn,
         }
+        if prof_all is not None:
+            out["kernel_ms_per_step"] = kernel_ms(prof_all, args.steps)
+            out["kernel_ms_per_step_source"] = ("untimed pass of the same steps with every launch bracketed by events; the timed region brackets "
+                                                "the GEMM and attention launches only")
         if args.precision == "f16x3":
             out["split_guard"] = {"enabled": bool(m.split_guard), "calls_repeated_in_f32": fallbacks, "guard_bits_last_call": guard_bits}
         if parity is not None:  # every row of the timed batch against the fp32 oracle (the headline mode; exact_f32_mode carries its own)
@@ -1140,7 +1154,7 @@ def main():
             out["max_abs_logit_err_vs_reference"] = dist_parity
         if exact is not None:
             out["exact_f32_mode"] = exact
-        if world == 1 and args.extra_legs:
+        if args.full and world == 1 and args.extra_legs:
             k = max(3, args.steps // 4)
             out["stress_T128_N128"] = stress_leg(cfg, m, dev, args.precision, k)
             tsd_par = None
@@ -1154,14 +1168,14 @@ def main():
             out["call_pattern"] = call_pattern_leg(cfg, sd, dev, k)
         if dist_res is not None:
             out["training_step_dist"] = dist_res
-        if world == 1 and args.train_steps > 0:
+        if args.full and world == 1 and args.train_steps > 0:
             tsd_par = None
             if args.cpu_seconds > 0:
                 from oracle import sola_oracle  # checker only
 
                 tsd_par = sola_oracle.to_torch_state(sd)
             out["training_step"] = training_leg(cfg, sd, dev, min(B, 64), N, T, L, args.train_steps, tsd_par)
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(cfg, sd, N, T, L, args.cpu_seconds)
         emit(out)
     if world > 1:

@@ -83,6 +83,28 @@ def test_train_on_ragged_batches(tmp_path):
     assert any(not torch.equal(sd1[k], sd2[k]) for k in sd1)
 
 
+def test_bench_plain_run_reports_the_timed_region_alone(tmp_path):
+    """bench.py without --full: set-up, warm-up, the timed steps, --dump-outputs and the line - none of the legs that take runs of
+    their own (kernel breakdown, parity, exact f32, other shapes and modes, training, CPU baseline)."""
+    env = dict(os.environ, PYTHONPATH=ROOT, SOLA_BENCH_FULL=str(tmp_path / "bench_full.json"))
+    env.pop("SOLA_PRECISION", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
+                        "--dump-outputs", str(tmp_path / "dump")], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1500:]
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline",
+              "roofline_attention"):
+        assert k in out, k
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "samples/s" and out["higher_is_better"] is True
+    assert out["value"] > 0 and abs(out["value"] - 4 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    full_only = {"kernel_ms_per_step", "max_abs_logit_err_vs_oracle", "max_abs_logit_err_vs_reference", "exact_f32_mode", "stress_T128_N128",
+                 "ragged", "iou", "f16_storage_mode", "call_pattern", "training_step", "training_step_dist", "cpu_baseline"}
+    assert not full_only & set(out), sorted(full_only & set(out))
+    assert sorted(p.stem for p in (tmp_path / "dump").glob("*.npy")) == ["loss", "pred", "prob", "score_map", "score_tokens"]
+
+
 def test_bench_two_ranks_code_path(tmp_path):
     """bench.py under torch.distributed.run with 2 ranks (gloo, both on cuda:0 - RCCL refuses two ranks per device): the
     barrier / max-over-ranks / whole-job aggregation path the driver uses at N > 1 prints one well-formed JSON line."""
@@ -90,7 +112,8 @@ def test_bench_two_ranks_code_path(tmp_path):
     env.pop("SOLA_PRECISION", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29577", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "4", "--cpu-seconds", "0", "--train-steps", "2"], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", "4", "--cpu-seconds", "0", "--train-steps", "2", "--full"], cwd=tmp_path, env=env, capture_output=True, text=True,
+                       timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-1500:]

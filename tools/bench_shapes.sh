@@ -3,7 +3,7 @@
 # (gpurun_out/r01_shapes.jsonl).  Columns: B N T.
 out=${GRAFT_REPO_ROOT:-/root/repo}/gpurun_out/r01_shapes.jsonl; : > "$out"
 while read -r B N T; do
-  python bench.py --batch "$B" --tracks "$N" --frames "$T" --steps 10 --cpu-seconds 0 2>/dev/null | tail -1 >> "$out"
+  python bench.py --full --batch "$B" --tracks "$N" --frames "$T" --steps 10 --cpu-seconds 0 2>/dev/null | tail -1 >> "$out"
 done <<'CFG'
 4096 8 8
 1024 16 32

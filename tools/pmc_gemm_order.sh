@@ -7,7 +7,7 @@ make -C "$repo/sola_amd/csrc" EXPERIMENTS=1 -j32 > "$repo/gpurun_out/exp_build.l
 cd /tmp && export TMPDIR=/tmp
 for ord in 0 1; do
   out=$repo/gpurun_out/pmc_order_$ord; mkdir -p "$out"
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out" -o pmc_fetch -- python3 "$repo/bench.py" --steps 6 --warmup 2 --cpu-seconds 0 --extra-legs 0 --train-steps 0 --precision f16x3 --tune gemm_order=$ord > "$out/run.log" 2>&1
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out" -o pmc_fetch -- python3 "$repo/bench.py" --full --steps 6 --warmup 2 --cpu-seconds 0 --extra-legs 0 --train-steps 0 --precision f16x3 --tune gemm_order=$ord > "$out/run.log" 2>&1
   tail -c 400 "$out/run.log" | grep -o '"value":[0-9.]*,"unit"[^,]*,[^,]*,[^,]*,[^,]*,"ms_per_step":[0-9.]*' | head -1
 done
 python3 - "$repo" <<'PY' | tee "$repo/gpurun_out/pmc_gemm_order.txt"

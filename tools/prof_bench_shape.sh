@@ -6,7 +6,7 @@ repo=${GRAFT_REPO_ROOT:-/root/repo}
 out=$repo/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o stats -- python3 "$repo/bench.py" --batch "$B" --tracks "$N" --frames "$T" --steps 10 --warmup 2 --cpu-seconds 0 --extra-legs 0 --train-steps 0 > "$out/run.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o stats -- python3 "$repo/bench.py" --full --batch "$B" --tracks "$N" --frames "$T" --steps 10 --warmup 2 --cpu-seconds 0 --extra-legs 0 --train-steps 0 > "$out/run.log" 2>&1
 grep '^{"metric"' "$out/run.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline_attention']['frac'], d['kernel_ms_per_step'])"
 python3 - "$out/stats_kernel_stats.csv" <<'PY'
 import csv, sys, re

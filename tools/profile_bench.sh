@@ -11,7 +11,7 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 # the headline leg only (split-f16 steps + the exact-f32 leg): the stress / ragged / IoU / 16-bit / training legs would mix other shapes
 # into the per-kernel means
-args="--steps 10 --warmup 2 --cpu-seconds 0 --extra-legs 0 --train-steps 0 $*"
+args="--full --steps 10 --warmup 2 --cpu-seconds 0 --extra-legs 0 --train-steps 0 $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o stats -- python3 "$repo/bench.py" $args > "$out/bench_under_rocprof.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out" -o pmc_fetch -- python3 "$repo/bench.py" $args > "$out/pmc_fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out" -o pmc_write -- python3 "$repo/bench.py" $args > "$out/pmc_write.log" 2>&1
