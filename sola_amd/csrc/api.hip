@@ -667,17 +667,15 @@ extern "C" int sola_forward(SolaCtx* c, const float* obj, const float* lang, int
     SOLA_ARG(!c || c->precision != 3, "forward: precision 3 (bf16 GEMM operands) is a TRAINING mode; inference runs precision 0, 1 or 2");
     if (c && B > 0 && N > 0 && T > 0 && few_rows_f32(c, (long long)B * N * T)) {
         PrecScope f32(c, 0);
-        return sola_forward_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s, false);
+        return sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s);
     }
     if (c && split_known_out_of_range(c)) {
         c->split_fallbacks += 1;
         PrecScope f32(c, 0);
-        return sola_forward_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s, false);
+        return sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s);
     }
     if (c && c->precision >= 1) {
-        const int prec = c->precision;
-        if (prec == 2) SOLA_TRY(sola_forward_f16_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s));
-        else SOLA_TRY(sola_forward_fast_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s));
+        SOLA_TRY(sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s));
         bool tripped = false;
         SOLA_TRY(sola_split_guard_tripped(c, s, &tripped));
         if (!tripped) return SOLA_OK;
@@ -685,9 +683,9 @@ extern "C" int sola_forward(SolaCtx* c, const float* obj, const float* lang, int
         // The f32 plan is a subset of the split plan, so the workspace fits.
         c->split_fallbacks += 1;
         PrecScope f32(c, 0);
-        return sola_forward_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s, false);
+        return sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s);
     }
-    return sola_forward_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s, false);
+    return sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s);
 }
 
 extern "C" size_t sola_ragged_workspace_bytes(const SolaCtx* c, const SolaRaggedBatch* batch) {
@@ -790,7 +788,7 @@ extern "C" int sola_split_fallback_count(const SolaCtx* c, int64_t* count, int32
 
 extern "C" int sola_forward_train(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L,
                                   float* score_map, float* score_tokens, void* workspace, size_t ws_bytes, void* stream_) {
-    return sola_forward_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, as_stream(stream_), true);
+    return sola_forward_train_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, as_stream(stream_));
 }
 
 // ---- ragged training step: many samples of different (N, T, L) per optimizer step (train.py:62-137 runs ONE per step) --------
@@ -814,7 +812,7 @@ extern "C" int sola_forward_train_ragged(SolaCtx* c, const float* obj, const flo
         SOLA_TRY(rag_shape(c, batch, r));
         SOLA_ARG(r.identity, "forward_train_ragged: one sample per video, in order (n_samples == n_videos, sample_video[i] == i): "
                              "every training sample runs its own encoder pass under its own dropout masks");
-        return sola_forward_impl(c, obj, lang, 0, 0, 0, 0, score_map, score_tokens, workspace, ws_bytes, as_stream(stream_), true, &r);
+        return sola_forward_train_impl(c, obj, lang, 0, 0, 0, 0, score_map, score_tokens, workspace, ws_bytes, as_stream(stream_), &r);
     } catch (const std::exception& e) {
         sola_set_error("forward_train_ragged: %s", e.what());
         return SOLA_ERR_ARG;

@@ -1,6 +1,6 @@
 // Backward orchestration of the track-selection network (autograd of module/module.py:130-162): host code sequencing
 // gemm.hip (dX via the NT kernel on transposed weights / the transposed-conv gather), gemm_tn.hip (dW, db),
-// attn_bwd.hip, bwd.hip over the activations saved by sola_forward_impl(train = true).  Gradients of all 83
+// attn_bwd.hip, bwd.hip over the activations saved by sola_forward_train_impl.  Gradients of all 83
 // parameters are written to the borrowed buffers registered with sola_set_grad (overwrite semantics).
 #include <math.h>
 #include <stdlib.h>

@@ -169,6 +169,11 @@ constexpr float kLinScale = 64.f;  // backward only (transposed weight casts): l
 // (re)builds the split-f16 copies of the projection weights with a per-matrix power-of-two scale and runs the weight-time
 // range check; no-op unless the copies are stale
 int sola_refresh_lin16(SolaCtx* c, hipStream_t s);
+// (re)standardises the conv weights and casts them into ws16_buf in operand format `fmt` (SolaCtx::ws16_fmt codes) when they
+// changed, when the policy says every forward, when ws16_buf holds another format, or when `force` is set
+int sola_refresh_conv_weights(SolaCtx* c, int fmt, bool force, hipStream_t s);
+// every forward's preamble: all weights set, workspace of at least `need` bytes, 256-byte aligned; `who` prefixes the messages
+int sola_check_forward_args(const SolaCtx* c, const char* who, size_t need, const void* workspace, size_t ws_bytes);
 
 inline const float* ctx_weight(const SolaCtx* c, const std::string& name) {
     auto it = c->index.find(name);
@@ -188,12 +193,12 @@ inline std::string abuf(bool train, int layer, const char* attn, const char* wha
 struct RagShape;
 Plan make_plan(const SolaCtx* c, int B, int N, int T, int L, bool train);
 Plan make_plan_ragged(const SolaCtx* c, const RagShape& r, bool train);
-int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
-                      float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s, bool train, const RagShape* rs = nullptr);
-int sola_forward_fast_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
-                           float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s);
-int sola_forward_f16_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
-                          float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s);
+// training forward (forward.hip); rs != null: a ragged batch
+int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
+                            float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s, const RagShape* rs = nullptr);
+// inference forward of a uniform batch in the ctx's precision 0, 1 or 2 (forward_infer.hip)
+int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
+                            float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s);
 size_t sola_backward_scratch_bytes(const SolaCtx* c, const Plan& p);
 size_t sola_ragged_workspace_bytes_impl(const SolaCtx* c, const SolaRaggedBatch* b, int precision);
 int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, const SolaRaggedBatch* batch, float* score_map,

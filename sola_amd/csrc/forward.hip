@@ -1,6 +1,7 @@
-// Forward orchestration of LanguageAlignedTrackSelectionModule.forward (module/module.py:130-162): host code that
-// sequences the kernels of gemm.hip / attn.hip / norm.hip / head.hip over one workspace arena.  With train = true every
-// attention keeps its own q/k/v/output/residual buffers plus the softmax log-sum-exp, which backward.hip consumes.
+// Training forward of LanguageAlignedTrackSelectionModule.forward (module/module.py:130-162): host code that sequences the
+// kernels of gemm.hip / attn.hip / norm.hip / head.hip over one workspace arena.  Every attention keeps its own
+// q/k/v/output/residual buffers plus the softmax log-sum-exp, which backward.hip consumes.  The workspace plans of both
+// forwards live here too; the inference forward is forward_infer.hip.
 #include <math.h>
 #include <string.h>
 
@@ -47,7 +48,7 @@ void plan_fill(Plan& p, const SolaCtx* c, const PlanSizes& z, bool train) {
     p.add("gn_slots", z.gn_slots, 1);
     p.add("lang", z.BW, D);
     p.add("lbar", z.S, D);
-    if (!train && c->precision >= 1) {  // split-f16 (or f16) copies of the three f32-born GEMM inputs (forward_fast.hip, forward_f16.hip)
+    if (!train && c->precision >= 1) {  // split-f16 (or f16) copies of the three f32-born GEMM inputs (forward_infer.hip)
         p.add("obj_sp", z.rows0, c->cfg.object_token_dim);
         p.add("conv5_sp", z.M, D);
         p.add("lang_sp", z.BW, D);
@@ -129,25 +130,15 @@ Plan make_plan_ragged(const SolaCtx* c, const RagShape& r, bool train) {
     return p;
 }
 
-// rs != null: a ragged TRAINING batch (sola_forward_train_ragged) - the token rows of all samples concatenated, every shape-
-// dependent kernel reads the unit tables built here (ragged.h); B, N, T, L are then ignored.
-int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
-                      float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s, bool train, const RagShape* rs) {
+// rs != null: a ragged batch (sola_forward_train_ragged) - the token rows of all samples concatenated, every shape-dependent
+// kernel reads the unit tables built here (ragged.h); B, N, T, L are then ignored.
+int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
+                            float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s, const RagShape* rs) {
     SOLA_ARG(c && obj && lang && score_map && score_tokens && workspace, "forward: null argument");
-    SOLA_ARG(c->precision != 3 || train, "forward: precision 3 (bf16 GEMM operands) is a TRAINING mode; inference runs precision 0, 1 or 2");
-    if (rs) SOLA_ARG(train && rs->identity, "forward: a ragged training batch has one sample per video (sample_video[i] == i)");
+    if (rs) SOLA_ARG(rs->identity, "forward: a ragged training batch has one sample per video (sample_video[i] == i)");
     else SOLA_ARG(B > 0 && N > 0 && T > 0 && L >= 1, "forward: bad sizes B=%d N=%d T=%d L=%d", B, N, T, L);
-    for (const Weight& w : c->weights)
-        if (!w.ptr) {
-            sola_set_error("forward: weight '%s' has not been set", w.name.c_str());
-            return SOLA_ERR_WEIGHT;
-        }
-    Plan p = rs ? make_plan_ragged(c, *rs, train) : make_plan(c, B, N, T, L, train);
-    if (ws_bytes < p.total) {
-        sola_set_error("forward: workspace %zu bytes < required %zu", ws_bytes, p.total);
-        return SOLA_ERR_WORKSPACE;
-    }
-    SOLA_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "forward: workspace must be 256-byte aligned");
+    Plan p = rs ? make_plan_ragged(c, *rs, true) : make_plan(c, B, N, T, L, true);
+    SOLA_TRY(sola_check_forward_args(c, "forward", p.total, workspace, ws_bytes));
     char* base = static_cast<char*>(workspace);
     auto buf = [&](const std::string& name) { return reinterpret_cast<float*>(base + p.bufs.at(name).off); };
     float* const splitk_ws = p.bufs.count("splitk") ? buf("splitk") : nullptr;
@@ -161,14 +152,14 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
     if (rs) SOLA_TRY(rag_build_tables(c, *rs, base + p.bufs.at("tables").off, true, &rt, s));
     auto level_rows = [&](int lvl) -> long long { return rs ? rs->rows[lvl] : (long long)R * (lvl == 0 ? T : p.Tl[lvl - 1]); };
     const long long text_rows = rs ? rs->LW : (long long)B * Wn;
-    // training forward in the split-f16 mode (sola_set_precision 1): the same GEMM kernels as forward_fast.hip on casts of
+    // training forward in the split-f16 mode (sola_set_precision 1): the same GEMM kernels as the inference forward on casts of
     // the f32 activations, everything the backward reads stays f32
     // (from ~1024 token rows on: below that the step is launch-bound and the extra cast launches cost more than the GEMMs gain)
     // precision 2 ("pure"): the same structure with plain f16 GEMM operands, ONE MFMA per product - mixed-precision training:
     // activations, statistics, softmax, accumulation and everything the backward reads stay f32
     const bool pure = c->precision >= 2;
     const int bf = c->precision == 3 ? 1 : 0;  // precision 3: the 16-bit GEMM operands are bfloat16 (training only; BASELINE config C2)
-    const bool split = train && c->precision >= 1 && D % (pure ? 64 : 32) == 0 && c->cfg.object_token_dim % (pure ? 64 : 32) == 0 && p.M >= g_train_split_min_rows;
+    const bool split = c->precision >= 1 && D % (pure ? 64 : 32) == 0 && c->cfg.object_token_dim % (pure ? 64 : 32) == 0 && p.M >= g_train_split_min_rows;
     const int lowp_arith = pure ? 2 : 1;
     auto cast_auto = [&](const float* in, int ld, float* out, long long rows, int K, float* scal) -> int {
         return pure ? launch_cast_f16(in, ld, out, K, rows, K, 0.f, scal, s, 13, nullptr, bf) : launch_cast_sp16_auto(in, ld, out, K, rows, K, scal, s);
@@ -177,23 +168,8 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
         return pure ? launch_cast_f16(in, ld, out, K, rows, K, scale, nullptr, s, 13, nullptr, bf) : launch_cast_sp16(in, ld, out, K, rows, K, scale, s, side16);
     };
 
-    // a1: weight standardisation (module/ws.py:9-13), every forward like the reference unless the policy says cached
-    if (c->ws_dirty || c->ws_every_forward || train) {
-        WsLayer layers[6];
-        for (int i = 0; i < 6; ++i) {
-            const std::string nm = "short_motion_encoder." + std::to_string(kConvIdx[i]) + ".weight";
-            layers[i] = WsLayer{W(nm), c->ws_buf + c->ws_off[i], c->conv[i].cout, c->conv[i].cin, c->conv[i].k};
-        }
-        SOLA_TRY(launch_ws_standardize(layers, 6, s));
-        c->ws16_fmt = split ? (pure ? 2 + bf : 1) : 0;  // ws_buf is new: ws16_buf is current only if it is rewritten below
-        if (split)
-            for (int i = 0; i < 6; ++i) {
-                const int kc = c->conv[i].k * c->conv[i].cin;
-                float* dst = pure ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(c->ws16_buf) + c->ws_off[i]) : c->ws16_buf + c->ws_off[i];
-                SOLA_TRY(cast_fixed(c->ws_buf + c->ws_off[i], kc, dst, c->conv[i].cout, kc, 1.f));
-            }
-        c->ws_dirty = false;
-    }
+    // a1: weight standardisation (module/ws.py:9-13), every training forward
+    SOLA_TRY(sola_refresh_conv_weights(c, split ? (pure ? 2 + bf : 1) : 0, true, s));
     auto lin_idx = [&](const std::string& attn, int proj) -> int {  // attn = "object_lang_align_layers.<l>.<name>"
         const int l = attn[attn.find('.') + 1] - '0';
         int a3 = 0;
@@ -216,17 +192,12 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
     // into the arena (side16 below): 2 more bytes per value written here, 6 fewer moved by the backward's X cast.
     const bool keep16 = split && pure && g_train_x16_keep != 0;
     const bool side16_on = split && !pure && g_train_x16_keep != 0 && g_train_dw_f16 != 0;
+    // the arena is the CALLER's (sola_set_x16_arena, round 4: an allocation of its own - half of the free device memory at most, grown with a
+    // stream sync and a device-wide free inside the training forward - was memory torch's allocator could neither see nor reclaim);
+    // what a forward asked for in total is read with sola_x16_arena_info; what does not fit is cast again by the backward as before
     c->x16.clear();
-    if (keep16 || side16_on) {
-        // the arena is the CALLER's (sola_set_x16_arena, round 4: an allocation of its own - half of the free device memory at most, grown with a
-        // stream sync and a device-wide free inside the training forward - was memory torch's allocator could neither see nor reclaim);
-        // what a forward asked for in total is read with sola_x16_arena_info; what does not fit is cast again by the backward as before
-        c->x16_used = 0;
-        c->x16_need = 0;
-    } else {
-        c->x16_used = 0;
-        c->x16_need = 0;
-    }
+    c->x16_used = 0;
+    c->x16_need = 0;
     auto side16 = [&](const float* src, long long rows, int cols) -> void* {  // f16x3: where the plain-f16 side copy of `src` goes
         if (!side16_on) return nullptr;
         void* q = c->x16_alloc((size_t)rows * cols * 2);
@@ -289,7 +260,7 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
             nd.n_inst = R; nd.inner = 1; nd.outer_stride = p.Tl[i]; nd.inner_stride = 0; nd.tok_stride = 1;
             nd.ntok = p.Tl[i]; nd.C = g.cout; nd.groups = c->cfg.n_groups; nd.eps = 1e-5f; nd.slope = 0.01f; nd.leaky = 1;
             if (rs) nd.units = rt.u_lvl[i + 1];
-            if (train) nd.drop = c->enc_drop(i);
+            nd.drop = c->enc_drop(i);
             if (gn_fmt && c->conv[i + 1].cin % 64 == 0) {  // conv i+1 takes the cast from here
                 float* dst = slot16(0, nd.y, level_rows(i + 1), g.cout);
                 nd.y_cast = dst; nd.cast_fmt = gn_fmt;
@@ -356,7 +327,7 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
     // the shape (attn_simple.hip's training instantiation; attn_bwd.hip's one-pass kernel)
     c->qkv16.assign((size_t)c->cfg.n_layers * 3, 0);
     auto site16 = [&](const AttnDesc& ad, bool o2l) -> bool {
-        if (!(train && split && pure && bf && g_train_bf16_store)) return false;
+        if (!(split && pure && bf && g_train_bf16_store)) return false;
         // the backward's dW products of these gradients must take the row-major 16-bit kernel (no f32 copy exists to transpose)
         if (!gemm_tn_tr_supported(M, D, D, D, D) || (o2l && !gemm_tn_tr_supported((int)text_rows, D, D, D, D))) return false;
         AttnDesc f = ad;
@@ -457,7 +428,7 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
         nd.tok_stride = tok_stride; nd.ntok = ntok; nd.C = D; nd.groups = c->cfg.n_groups_module;
         nd.eps = 1e-5f; nd.slope = 0.f; nd.leaky = 0;
         nd.units = units;
-        if (train && idx == 2 && g_train_gn_stats) {
+        if (idx == 2 && g_train_gn_stats) {
             const int l = gn_layer;
             int wrote = 0;
             nd.stats_out = buf("l" + std::to_string(l) + "_gn2st");
@@ -473,7 +444,7 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
     // the bf16 operand copy of a sub-block's input, if it sits in the kept-operand arena (a shared cast buffer is overwritten before the
     // out-projection runs) - then the sub-block's pre-norm rows are bfloat16 (out_proj / gn above)
     auto resid16 = [&](const float* resid) -> const void* {
-        if (!(train && split && pure && bf && g_train_bf16_store >= 2 && keep16 && D % 8 == 0)) return nullptr;
+        if (!(split && pure && bf && g_train_bf16_store >= 2 && keep16 && D % 8 == 0)) return nullptr;
         return c->x16_find(resid, D, 1 + bf);
     };
     const float* xin = buf("conv5");
@@ -481,8 +452,7 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
         const std::string lp = "object_lang_align_layers." + std::to_string(l) + ".";
         gn_layer = l;
         const std::string ls = "l" + std::to_string(l);
-        auto ab = [&](int a, const char* what) { return buf(abuf(train, l, kAttnShort[a], what)); };
-        auto lse = [&](int a) -> float* { return train ? ab(a, "lse") : nullptr; };
+        auto ab = [&](int a, const char* what) { return buf(abuf(true, l, kAttnShort[a], what)); };
         float* x_obj = buf(ls + "_obj");
         float* x_pe = buf(ls + "_xpe");
         float* x_mot = buf(ls + "_motion");
@@ -490,9 +460,9 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
         // (i) inter-object attention over the N tracks of each (b, t'): module.py:31-35
         {
             AttnDesc ad{ab(0, "q"), ab(0, "k"), ab(0, "v"), ab(0, "attn"), D, D, D, D, B * Tp, H, DH, N, N, Tp,
-                        (long long)N * Tp, 1, Tp, (long long)N * Tp, 1, Tp, scale, lse(0)};
+                        (long long)N * Tp, 1, Tp, (long long)N * Tp, 1, Tp, scale, ab(0, "lse")};
             if (rs) { ad.G = rt.sumTpS; ad.inner = 1; ad.q_units = rt.u_st; }
-            if (train) ad.drop = c->attn_drop(l, 0);
+            ad.drop = c->attn_drop(l, 0);
             const bool s16 = site16(ad, false);
             SOLA_TRY(linear3(xin, xin, xin, lp + "obj_attn", 3, M, ab(0, "q"), ab(0, "k"), ab(0, "v"), 0, nullptr, s16));
             ad.in_bf16 = s16 ? 1 : 0;
@@ -508,9 +478,9 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
         // (ii) motion attention over T' per track, PE on q and k only: module.py:38-43
         {
             AttnDesc ad{ab(1, "q"), ab(1, "k"), ab(1, "v"), ab(1, "attn"), D, D, D, D, B * N, H, DH, Tp, Tp, 1,
-                        (long long)Tp, 0, 1, (long long)Tp, 0, 1, scale, lse(1)};
+                        (long long)Tp, 0, 1, (long long)Tp, 0, 1, scale, ab(1, "lse")};
             if (rs) { ad.G = rt.sumNS; ad.q_units = rt.u_strk; }
-            if (train) ad.drop = c->attn_drop(l, 1);
+            ad.drop = c->attn_drop(l, 1);
             const bool s16 = site16(ad, false);
             SOLA_TRY(linear3(x_pe, x_pe, x_obj, lp + "motion_attn", 3, M, ab(1, "q"), ab(1, "k"), ab(1, "v"), 0, nullptr, s16));
             ad.in_bf16 = s16 ? 1 : 0;
@@ -526,9 +496,9 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
         // (iii) object -> language cross attention: module.py:46-50
         {
             AttnDesc ad{ab(2, "q"), ab(2, "lk"), ab(2, "lv"), ab(2, "attn"), D, D, D, D, B, H, DH, N * Tp, Wn, 1,
-                        (long long)N * Tp, 0, 1, (long long)Wn, 0, 1, scale, lse(2)};
+                        (long long)N * Tp, 0, 1, (long long)Wn, 0, 1, scale, ab(2, "lse")};
             if (rs) { ad.Sq = rt.maxRowsSample; ad.q_units = rt.u_smp; ad.k_units = rt.u_langk; }
-            if (train) ad.drop = c->attn_drop(l, 2);
+            ad.drop = c->attn_drop(l, 2);
             const bool s16 = site16(ad, true);
             SOLA_TRY(linear3(x_mot, nullptr, nullptr, lp + "object2lang_attn", 1, M, ab(2, "q"), nullptr, nullptr, 0, nullptr, s16));
             SOLA_TRY(linear3(buf("lang"), buf("lang"), nullptr, lp + "object2lang_attn", 2, (int)text_rows, ab(2, "lk"), ab(2, "lv"), nullptr, 1,
@@ -555,6 +525,6 @@ int sola_forward_impl(SolaCtx* c, const float* obj, const float* lang, int B, in
     c->last = p;
     c->last_rag = rt;
     c->last_ws = workspace;
-    c->last_obj = train ? obj : nullptr;
+    c->last_obj = obj;
     return SOLA_OK;
 }

@@ -23,7 +23,7 @@
 
 int launch_attention_f16(const AttnDesc& d, hipStream_t s);
 
-extern int g_attn_split_min_keys;  // forward_fast.hip
+extern int g_attn_split_min_keys;  // forward_infer.hip
 
 namespace {
 
@@ -373,13 +373,8 @@ size_t sola_ragged_workspace_bytes_impl(const SolaCtx* c, const SolaRaggedBatch*
 int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, const SolaRaggedBatch* batch, float* score_map,
                              float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s) {
     SOLA_ARG(c && obj && lang && batch && score_map && score_tokens && workspace, "forward_ragged: null argument");
-    for (const Weight& w : c->weights)
-        if (!w.ptr) {
-            sola_set_error("forward_ragged: weight '%s' has not been set", w.name.c_str());
-            return SOLA_ERR_WEIGHT;
-        }
     const bool sp = c->precision == 1;
-    // precision 2: 16-bit activation STORAGE (forward_f16.hip's arithmetic on the ragged layout): every activation between two
+    // precision 2: 16-bit activation STORAGE (forward_infer.hip's arithmetic on the ragged layout): every activation between two
     // kernels a plain _Float16 in the first half of its f32-sized buffer, one f16 MFMA per product, f32 statistics / softmax
     const bool h16 = c->precision == 2;
     if (h16)
@@ -392,11 +387,7 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
     RagShape r;
     SOLA_TRY(rag_shape(c, batch, r));
     const RagPlan p = rag_plan(c, r, c->precision);
-    if (ws_bytes < p.total) {
-        sola_set_error("forward_ragged: workspace %zu bytes < required %zu", ws_bytes, p.total);
-        return SOLA_ERR_WORKSPACE;
-    }
-    SOLA_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "forward_ragged: workspace must be 256-byte aligned");
+    SOLA_TRY(sola_check_forward_args(c, "forward_ragged", p.total, workspace, ws_bytes));
     char* base = static_cast<char*>(workspace);
     auto raw = [&](const std::string& name) { return base + p.off.at(name); };
     auto buf = [&](const std::string& name) { return reinterpret_cast<float*>(raw(name)); };
@@ -422,27 +413,7 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
     };
 
     // ---- weights
-    if (c->ws_dirty || c->ws_every_forward || (sp && c->ws16_fmt != 1) || (h16 && c->ws16_fmt != 2)) {
-        WsLayer layers[6];
-        for (int i = 0; i < 6; ++i) {
-            const std::string nm = "short_motion_encoder." + std::to_string(kConvIdx[i]) + ".weight";
-            layers[i] = WsLayer{W(nm), c->ws_buf + c->ws_off[i], c->conv[i].cout, c->conv[i].cin, c->conv[i].k};
-        }
-        SOLA_TRY(launch_ws_standardize(layers, 6, s));
-        if (sp)
-            for (int i = 0; i < 6; ++i) {
-                const int kc = c->conv[i].k * c->conv[i].cin;
-                SOLA_TRY(launch_cast_sp16(c->ws_buf + c->ws_off[i], kc, c->ws16_buf + c->ws_off[i], kc, c->conv[i].cout, kc, 1.f, s));
-            }
-        if (h16)
-            for (int i = 0; i < 6; ++i) {
-                const int kc = c->conv[i].k * c->conv[i].cin;
-                SOLA_TRY(launch_cast_f16(c->ws_buf + c->ws_off[i], kc, reinterpret_cast<_Float16*>(c->ws16_buf) + c->ws_off[i], kc, c->conv[i].cout, kc, 1.f,
-                                         nullptr, s));
-            }
-        c->ws_dirty = false;
-        c->ws16_fmt = sp ? 1 : (h16 ? 2 : 0);
-    }
+    SOLA_TRY(sola_refresh_conv_weights(c, sp ? 1 : (h16 ? 2 : 0), false, s));
     if (sp || h16) {
         SOLA_TRY(sola_refresh_lin16(c, s));
         SOLA_HIP(hipMemsetAsync(c->guard, 0, sizeof(int), s));
@@ -469,7 +440,7 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
         SOLA_TRY(launch_cast_sp16_auto(obj, d_in, buf("obj_sp"), d_in, r.rows[0], d_in, c->scal_pair(0), s));
         x = buf("obj_sp");
     }
-    if (h16) {  // largest magnitude -> [2^6, 2^7), capped at 2^8; conv0's output stays in the scaled units (forward_f16.hip)
+    if (h16) {  // largest magnitude -> [2^6, 2^7), capped at 2^8; conv0's output stays in the scaled units (forward_infer.hip)
         SOLA_TRY(launch_cast_f16(obj, d_in, buf("obj_sp"), d_in, r.rows[0], d_in, 256.f, c->scal_pair(0), s, 6, c->scal_extra(0)));
         x = buf("obj_sp");
     }
@@ -575,7 +546,7 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
         if (h16) { ad.o_sp16 = 0; ad.in_sp16 = 0; ad.split_math = 0; return launch_attention_f16(ad, s); }
         return launch_attention(ad, s);
     };
-    // q/k/v leave the projection already split where the attention runs the split-f16 MFMA shape (forward_fast.hip: units of
+    // q/k/v leave the projection already split where the attention runs the split-f16 MFMA shape (forward_infer.hip: units of
     // more than g_attn_split_min_keys keys; never the packed short-sequence shape)
     const int obj_in_sp = (sp && r.maxN > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;
     const int mot_in_sp = (sp && maxTp > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;

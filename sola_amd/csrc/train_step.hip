@@ -97,7 +97,7 @@ extern "C" int sola_train_step(SolaCtx* c, const float* obj, const float* lang, 
         SOLA_ARG(neg && g_neg, "train_step: negative_token.weight / its gradient are not bound");
         // forward (activations kept in train_ws), the three losses on the negative tokens themselves (train.py:92 repeats them per sample:
         // the shared-table form of sola_loss), d(total) / d(score_map, score_tokens, negative tokens)
-        SOLA_TRY(sola_forward_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, train_ws, train_ws_bytes, s, true));
+        SOLA_TRY(sola_forward_train_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, train_ws, train_ws_bytes, s));
         // one sample (the reference's batch): the [1, n_neg, D] table of train.py:92 - per-sample form, as the autograd path passes it
         const int64_t stride = B == 1 ? (int64_t)n_neg * D : 0;
         SOLA_TRY(sola_loss(score_map, score_tokens, labels, pos, neg, stride, B, N, D, n_neg, positive_weight, temperature, alignment_weight, loss3,

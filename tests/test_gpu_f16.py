@@ -217,3 +217,42 @@ def test_f16_mode_unsupported_config_is_an_error():
         m(cuda(inp["object_tokens"]), cuda(inp["lang_tokens"]))
     sm, _ = m(cuda(inp["object_tokens"]), cuda(inp["lang_tokens"]))  # with autograd on this is a training forward: exact f32 under this mode
     assert sm.requires_grad and torch.isfinite(sm).all()
+
+
+def test_switching_inference_precisions_gives_each_mode_its_own_bits():
+    """One module switched f32 -> f16x3 -> f16 -> f16x3 -> f32 with unchanged weights: every call is bit-identical to a fresh module's
+    call in that precision.  The conv weights' 16-bit copy (SolaCtx::ws16_fmt) must be rebuilt whenever the format the call needs is not
+    the one it holds - after a precision switch and after an f16x3 call that ran the exact-f32 kernels (one sample: the few-row route)."""
+    cfg = synth.DEFAULT_MODEL_CFG
+    big = synth.make_inputs(cfg, 4, 32, 40, 8, seed=700)  # 5120 object-token rows: the f16x3 call stays split-f16
+    one = synth.make_inputs(cfg, 1, 8, 16, 4, seed=701)   # 128 rows: f16x3 takes the few-row exact-f32 route
+    rng = np.random.Generator(np.random.PCG64(702))
+    shapes, lens, sample_video = [(9, 24), (20, 40), (64, 32), (70, 17), (12, 150)], [5, 8, 3, 16, 4, 40], [0, 1, 1, 2, 3, 4]
+    videos = [cuda(rng.standard_normal((n, t, cfg["object_token_dim"])).astype(np.float32)) for n, t in shapes]
+    texts = [cuda(rng.standard_normal((l, cfg["lang_token_dim"])).astype(np.float32)) for l in lens]
+
+    def calls(m, order):  # [(what, score_map, score_tokens)] in call order
+        out = []
+        with torch.no_grad():
+            for what in order:
+                if what == "ragged":
+                    sms, sts = m.forward_ragged(videos, texts, sample_video)
+                    out.append((what, torch.cat(sms), torch.cat(sts)))
+                else:
+                    inp = big if what == "big" else one
+                    out.append((what, *m(cuda(inp["object_tokens"]), cuda(inp["lang_tokens"]))))
+        return out
+
+    try:
+        _lib.check(_lib.lib().sola_tune(b"infer_f32_rows", 4096), "tune")  # the default routing (conftest.py switches it off)
+        ref = {prec: {w: (sm, st) for w, sm, st in calls(build(prec), ("big", "one", "ragged"))} for prec in ("f32", "f16x3", "f16")}
+        m = build("f32")
+        for prec in ("f32", "f16x3", "f16", "f16x3", "f32"):
+            m.precision = prec
+            for i, (what, sm, st) in enumerate(calls(m, ("one", "big", "ragged", "big"))):
+                assert torch.equal(sm, ref[prec][what][0]) and torch.equal(st, ref[prec][what][1]), (prec, i, what)
+        assert m.split_fallbacks()[0] == 0
+    finally:
+        _lib.check(_lib.lib().sola_tune(b"infer_f32_rows", 0), "tune")
+    assert torch.equal(ref["f16x3"]["one"][0], ref["f32"]["one"][0])  # the one-sample f16x3 call did take the exact-f32 route
+    assert not torch.equal(ref["f16x3"]["big"][0], ref["f32"]["big"][0])

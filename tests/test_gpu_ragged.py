@@ -218,7 +218,7 @@ def test_random_ragged_batches_equal_per_sample(small, seed):
 
 def test_ragged_under_the_16_bit_storage_mode():
     """precision "f16" on the ragged path (round 3; inference.py / eval.py only call this path): the 16-bit storage arithmetic of
-    forward_f16.hip on concatenated rows - f16 activations, one f16 MFMA per product, the f16 attention kernel on unit tables.
+    forward_infer.hip on concatenated rows - f16 activations, one f16 MFMA per product, the f16 attention kernel on unit tables.
     A reduced-precision mode with the stated tolerance of tests/test_gpu_f16.py against the exact-f32 ragged call: logits within
     TOL_LOGIT everywhere and 1.5 % rms, decisions equal away from the threshold; served by the f16 kernels (no guard repeat)."""
     from test_gpu_f16 import TOL_LOGIT, TOL_RMS
