@@ -6,7 +6,19 @@
 Reports the losses and track-level TP/FP/FN/TN of the valid split and writes ``<eval_output_dir>/track_metrics.json``.
 Scoring runs on ragged batches (sola_forward_ragged: up to ``--ragged_max_samples`` samples of different shapes per launch,
 one pass of the text-independent half per video); every sample's losses are its own means, as at the reference's batch
-size of 1.  Mask-level J&F (evaluator.py:174-247) is outside the accelerated path.
+size of 1.
+
+Mask-level J&F (evaluator.py:174-247): each sample's selection vector comes back with one host copy per batch; a track is
+selected when its prediction is > 0, as in get_sam2_masklet.  The expressions of a video are then scored by ONE
+seg_utils.compute_JF_batch call: every referenced track and GT masklet decoded once on the GPU, every (expression, frame)
+counted in one launch.  Writes ``<eval_output_dir>/<data_type>_JF_metrics_<K>epoch.json`` as ``{video: {exp_id: {expression,
+J, F, JF}}}`` and adds ``mean_J`` / ``mean_F`` / ``mean_JF`` to track_metrics.json and the printed line; with several ranks
+rank 0 gathers every rank's entries.  J is the mean over frames of inter / union (1.0 for an empty union), F the pixel F1
+over the whole masklet (0.0 without a true positive) - the reference's definition, not the DAVIS boundary F.  Counts are
+exact int64 (the reference's float32 sums are exact below 2^24).  An expression without GT ids scores against an all-zero
+ground truth (the reference fails there).  J&F needs mask ground truth: MeViS with a ``mask_dict.json``.  Without it
+(synthetic data, the MeViS ``valid`` test split, Ref-DAVIS, whose reference GT loader gives every object the last object's
+masks) or with ``--jf false`` one line says why J&F was skipped and the outputs are the loss / track metrics alone.
 
 BCE convention: ``bce`` / ``total`` follow train.py:98-113 (BCE-with-logits on the LOGITS, what the
 network is trained and validated with).  The reference's evaluator applies binary_cross_entropy_with_logits to the
@@ -15,7 +27,9 @@ already SIGMOID-ed scores (evaluator.py:101,107-111) - a double sigmoid; that nu
 """
 import json
 import os
+from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from sola_amd import dist as sdist
@@ -24,6 +38,68 @@ from sola_amd.data import make_ragged_batches
 from sola_amd.module import LanguageAlignedTrackSelectionModule
 from sola_amd.text import TextEncoder
 from train import run_split_ragged
+
+
+def jf_skip_reason(cfg, ds):
+    """Why J&F cannot be computed for this run, or None."""
+    if not cfg.get("jf", True):
+        return "--jf false"
+    if cfg.get("synthetic", False):
+        return "synthetic tracks have no masks"
+    if getattr(ds, "data_name", None) == "ref-davis":
+        return "Ref-DAVIS mask ground truth is not supported"
+    if not getattr(ds, "has_mask_gt", False):
+        return f"no mask ground truth (mask_dict.json) for {getattr(ds, 'data_type', 'this split')}"
+    return None
+
+
+class SelectionCollector:
+    """run_split_ragged's on_batch: keeps (video, expression id, expression, selected [N] bool) per sample."""
+
+    def __init__(self):
+        self.rows = []
+
+    def __call__(self, batch, pred):
+        sel = (pred > 0).cpu().numpy()  # one host copy per batch
+        o = 0
+        for s, v in zip(batch["samples"], batch["sample_video"]):
+            n = int(batch["videos"][v].shape[0])
+            self.rows.append((s["video_id"], s["expression_id"], s["expression"], sel[o:o + n]))
+            o += n
+
+
+def jf_entries(ds, rows, device):
+    """[(video, expression id, {expression, J, F, JF})] in the order of ``rows``, one compute_JF_batch call per video."""
+    from sola_amd import seg_utils
+    by_video = OrderedDict()
+    for r in rows:
+        by_video.setdefault(r[0], []).append(r)
+    out = []
+    for vid, rs in by_video.items():
+        masklets, index = [], {}
+
+        def idx(rle_list):  # shared tracks / GT objects are the same list objects: decoded once per video
+            k = id(rle_list)
+            if k not in index:
+                index[k] = len(masklets)
+                masklets.append(rle_list)
+            return index[k]
+
+        pred_sets, gt_sets, no_tracks = [], [], []
+        for _, eid, _, sel in rs:
+            tracks = ds.track_rles(vid, eid)
+            if len(tracks) != len(sel):
+                raise RuntimeError(f"{vid}/{eid}: {len(tracks)} track files but {len(sel)} predictions")
+            ids = [idx(t) for t in tracks]
+            pred_sets.append([ids[j] for j in np.flatnonzero(sel)])
+            gt_sets.append([idx(g) for g in ds.gt_rles(vid, eid)])
+            no_tracks.append(not tracks)
+        scores = seg_utils.compute_JF_batch(masklets, pred_sets, gt_sets, device) if masklets else [(0.0, 0.0, 0.0)] * len(rs)
+        for (_, eid, exp, _), (J, F, JF), empty in zip(rs, scores, no_tracks):
+            if empty:  # no track files at all: get_sam2_masklet returns None and the evaluator scores 0
+                J = F = JF = 0.0
+            out.append((vid, eid, {"expression": exp, "J": J, "F": F, "JF": JF}))
+    return out
 
 
 @torch.no_grad()
@@ -36,14 +112,33 @@ def evaluate(cfg):
     module = module.to(device).eval()
     text = TextEncoder(cfg["model"]["roberta_version"], cfg["model"]["lang_token_dim"], device,
                        allow_standin=bool(cfg.get("synthetic", False)))
-    batches, _ = make_ragged_batches(cfg["dataset"], "valid", rank, world, cfg.get("synthetic", None), cfg["model"])
+    batches, ds = make_ragged_batches(cfg["dataset"], "valid", rank, world, cfg.get("synthetic", None), cfg["model"])
     tcfg = dict(cfg["train"])
     tcfg["pred_threshold"] = cfg["eval"]["pred_threshold"]
-    m = run_split_ragged(module, text, batches, tcfg, device, world)
+    skip = jf_skip_reason(cfg, ds)
+    selections = None if skip else SelectionCollector()
+    m = run_split_ragged(module, text, batches, tcfg, device, world, on_batch=selections)
     m["text_encoder"] = text.kind
     m["precision"] = m["tp"] / max(m["tp"] + m["fp"], 1.0)
     m["recall"] = m["tp"] / max(m["tp"] + m["fn"], 1.0)
+    if selections is not None:
+        entries = jf_entries(ds, selections.rows, device)
+        if world > 1:
+            gathered = [None] * world
+            torch.distributed.all_gather_object(gathered, entries)
+            entries = [e for part in gathered for e in part]
+        if rank == 0:
+            jf = OrderedDict()
+            for vid, eid, e in entries:
+                jf.setdefault(vid, OrderedDict())[eid] = e
+            for key in ("J", "F", "JF"):
+                m[f"mean_{key}"] = float(np.mean([e[key] for _, _, e in entries])) if entries else 0.0
+            name = f"{cfg['dataset']['valid']['data_type']}_JF_metrics_{cfg['eval']['weight_epoch']}epoch.json"
+            with open(os.path.join(cfg["results"]["eval_output_dir"], name), "w") as f:
+                json.dump(jf, f, indent=4)
     if rank == 0:
+        if skip:
+            print(f"J&F skipped: {skip}")
         print(json.dumps(m))
         with open(os.path.join(cfg["results"]["eval_output_dir"], "track_metrics.json"), "w") as f:
             json.dump(m, f, indent=2)

@@ -485,6 +485,31 @@ int sola_rle_fill_or(const uint32_t* dev_cum, const int64_t* dev_off, int n_fram
  * or runs covering more than `limit` pixels; limit < 0 disables that check). */
 int64_t sola_rle_string_to_cum(const char* str, int64_t len, uint32_t* host_cum, int64_t cap, int64_t limit);
 
+/* ---- mask-level J&F (evaluator.py:174-247): decode once per video, count every (expression, frame) in one launch --------
+ * Column-major bit planes, internal to this path (never mixed with the row-major planes of sola_mask_pack): bit j of word i
+ * is the pixel at COCO position 32*i + j (position = x*h + y), a plane is words_stride = sola_jf_plane_words(h, w) words
+ * (a multiple of 4: planes start on 16 bytes), tail and pad bits are zero.  Mask m at frame t is plane m*T + t.
+ *   sola_rle_pack_cm: n_planes masks given as sola_rle_fill_or's dev_cum / dev_off (plane p owns runs dev_off[p] ..
+ *     dev_off[p+1]; an empty range is an absent frame = all zeros) -> dev_bits [n_planes, words_stride] (16-byte aligned).
+ *     Any n_planes.  Runs covering fewer than h*w pixels follow sola_rle_fill_or's rule (value = parity of the run ends at
+ *     or before the position), so the two decoders agree everywhere.
+ *   sola_mask_select_counts: for every expression e < E and frame t < T, p = OR of the planes of the masks
+ *     dev_pred_idx[dev_pred_off[e] .. dev_pred_off[e+1]), g = the same over dev_gt_idx / dev_gt_off (int32 CSR lists of
+ *     mask ids < n_masks; an empty list is an all-zero mask, ids may repeat and appear in both lists; ids outside
+ *     [0, n_masks) are ignored) -> dev_counts [E, T, 3] int64 = (popc(p & g), popc(p), popc(g)), exact.
+ *   sola_rle_strings_to_cum_batch (host only): n compressed strings back to back in `chars`, string i at
+ *     chars[str_off[i] .. str_off[i+1]) -> host_cum (prefix sums, as sola_rle_string_to_cum, runs <= limit pixels each
+ *     string) and run_off [n+1] int64 (string i owns host_cum[run_off[i] .. run_off[i+1])).  An empty string has no runs.
+ *     Returns the total number of runs (<= cap) or a negative status naming the string. */
+int64_t sola_jf_plane_words(int h, int w);
+int sola_rle_pack_cm(const uint32_t* dev_cum, const int64_t* dev_off, int64_t n_planes, int h, int w, int64_t words_stride,
+                     uint32_t* dev_bits, void* stream);
+int sola_mask_select_counts(const uint32_t* dev_bits, int64_t words_stride, int n_masks, int T, const int32_t* dev_pred_off,
+                            const int32_t* dev_pred_idx, const int32_t* dev_gt_off, const int32_t* dev_gt_idx, int E,
+                            int64_t* dev_counts, void* stream);
+int64_t sola_rle_strings_to_cum_batch(const char* chars, const int64_t* str_off, int64_t n, uint32_t* host_cum, int64_t cap,
+                                      int64_t limit, int64_t* run_off);
+
 /* Masks -> COCO compressed RLE strings, byte-identical to pycocotools encode + rleToString on {0,1} masks; replaces the
  * host copy + per-frame pycocotools loop of track_generation/seg_utils.py encode_rle_masklet_torch.  n masks [n,h,w]
  * row-major; elem_type 0 = uint8 (!= 0), 1 = float32 (!= 0), 2 = float32 tracker logits (> 0).  n >= 1 (any n: launches

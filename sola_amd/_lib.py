@@ -127,6 +127,10 @@ SIGNATURES = {
     "sola_mask_unpack": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "sola_rle_fill_or": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sola_rle_string_to_cum": (_i64, [C.c_char_p, _i64, _vp, _i64, _i64]),
+    "sola_jf_plane_words": (_i64, [_i, _i]),
+    "sola_rle_pack_cm": (_i, [_vp, _vp, _i64, _i, _i, _i64, _vp, _vp]),
+    "sola_mask_select_counts": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "sola_rle_strings_to_cum_batch": (_i64, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
     "sola_rle_encode_scratch_bytes": (_sz, [_i, _i, _i]),
     "sola_rle_encode_runs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "sola_rle_encode_cum": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -185,6 +185,53 @@ class TrackDataset(torch.utils.data.Dataset):
             return torch.from_numpy(np.ascontiguousarray(merged, dtype=np.uint8)).to(device)
         return merged
 
+    def track_rles(self, video_id, expression_id):
+        """The RLE masklets (lists of per-frame COCO dicts) of the sample's tracks, in its track order: roots in order, then
+        sorted file names, as ``merged_masklet`` and ``__getitem__`` list them.  A masklet directory is read once while it
+        stays among the last few read (a video's grid tracks serve all its expressions), and repeated calls return the same
+        list objects."""
+        from collections import OrderedDict
+        cache = self.__dict__.setdefault("_rle_cache", OrderedDict())
+        out = []
+        for root in self.roots:
+            mdir, _ = self._dirs(root, video_id, expression_id)
+            rles = cache.get(mdir)
+            if rles is None:
+                rles = []
+                for name in sorted(os.listdir(mdir)):
+                    with open(os.path.join(mdir, name), "r") as f:
+                        rles.append(json.load(f)["rle"])
+                cache[mdir] = rles
+                while len(cache) > 8:
+                    cache.popitem(last=False)
+            else:
+                cache.move_to_end(mdir)
+            out += rles
+        return out
+
+    def _mask_dict_path(self):
+        return os.path.join(self.data_root, self.data_name, self.data_type, "mask_dict.json")
+
+    @property
+    def has_mask_gt(self):
+        """True when the split has mask ground truth for J&F: MeViS with a ``mask_dict.json`` (the ``valid`` test split has
+        none).  Ref-DAVIS is not supported: the reference's loader (dataloader.py:262-276) stores one shared array under every
+        object id, so every object would get the last object's masks."""
+        return self.data_name == "mevis" and os.path.isfile(self._mask_dict_path())
+
+    def gt_rles(self, video_id, expression_id):
+        """The RLE masklets of the expression's ``anno_id`` objects from MeViS ``mask_dict.json`` (read once, on first use;
+        dataloader.py:251-299).  Their OR is the expression's ground truth; an expression without GT ids gets an empty list,
+        an all-zero ground truth (the reference fails there)."""
+        if not self.has_mask_gt:
+            raise ValueError(f"{self.data_name}/{self.data_type} has no mask ground truth")
+        md = self.__dict__.get("_mask_dict")
+        if md is None:
+            with open(self._mask_dict_path(), "r") as f:
+                md = self._mask_dict = json.load(f)
+        ids = self.meta["videos"][video_id]["expressions"][expression_id].get("anno_id", [])
+        return [md[str(a)] for a in ids if int(a) >= 0]
+
 
 class SyntheticTracks(torch.utils.data.Dataset):
     """Deterministic stand-in with the real sample dictionary: N tracks x T frames of N(0,1) tokens, IoU labels with

@@ -368,6 +368,160 @@ def rle_merge_or(rle_lists, device, packed=False):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# mask-level J&F of a whole video (evaluator.py:174-247): decode every referenced masklet once, count every expression
+# ----------------------------------------------------------------------------------------------------------------
+def rle_strings_to_cum(strings, limit=-1):
+    """Compressed COCO RLE strings (str / bytes) -> (cum uint32 [runs], run_off int64 [n+1]) from one library call
+    (sola_rle_strings_to_cum_batch): string i's inclusive prefix sums of its run lengths are cum[run_off[i]:run_off[i+1]].
+    An empty string has no runs.  Malformed strings, and runs covering more than ``limit`` pixels, raise SolaError."""
+    import numpy as np
+    enc = [s.encode("ascii") if isinstance(s, str) else bytes(s) for s in strings]
+    str_off = np.zeros(len(enc) + 1, np.int64)
+    np.cumsum([len(s) for s in enc], out=str_off[1:])
+    chars = np.frombuffer(b"".join(enc) or b"\0", np.uint8)
+    cum = np.empty(max(1, int(str_off[-1])), np.uint32)  # a run takes at least one character
+    run_off = np.empty(len(enc) + 1, np.int64)
+    n = lib().sola_rle_strings_to_cum_batch(chars.ctypes.data, str_off.ctypes.data, len(enc), cum.ctypes.data, len(cum), limit,
+                                           run_off.ctypes.data)
+    if n < 0:
+        check(int(n), "sola_rle_strings_to_cum_batch")
+    return cum[:n], run_off
+
+
+def _masklet_geometry(masklets):
+    """(T, (h, w) or None) shared by every masklet; SolaError when they differ."""
+    T = len(masklets[0])
+    size = None
+    for m in masklets:
+        if len(m) != T:
+            raise SolaError(f"masklet_select_counts: masklets have {len(m)} and {T} frames")
+        for r in m:
+            if isinstance(r, dict):
+                s = tuple(r["size"])
+                if size is None:
+                    size = s
+                elif s != size:
+                    raise SolaError(f"masklet_select_counts: frame size {s} != {size}")
+    return T, size
+
+
+def _planes_cum(masklets, ids, T, hw):
+    """Host side of one decode launch: the run prefix sums of masks ``ids`` (plane k*T + t = frame t of ids[k]), from one
+    parse of all their compressed strings; uncompressed count lists are summed by numpy and spliced in."""
+    import numpy as np
+    frames = [masklets[m][t] for m in ids for t in range(T)]
+    lists = {}
+    strings = []
+    for p, r in enumerate(frames):
+        c = r["counts"] if isinstance(r, dict) else ""
+        if not isinstance(c, (str, bytes, bytearray)):
+            lists[p] = c
+            c = ""
+        strings.append(c)
+    cum, off = rle_strings_to_cum(strings, hw)
+    if lists:
+        pieces = []
+        for p in range(len(frames)):
+            if p in lists:
+                c = np.cumsum(np.asarray(lists[p], dtype=np.int64))
+                if len(c) and (c[-1] > hw or np.any(np.diff(c) < 0) or c[0] < 0):
+                    raise SolaError("masklet_select_counts: runs are negative or exceed the image")
+                pieces.append(c.astype(np.uint32))
+            else:
+                pieces.append(cum[off[p]:off[p + 1]])
+        off = np.zeros(len(frames) + 1, np.int64)
+        np.cumsum([len(x) for x in pieces], out=off[1:])
+        cum = np.concatenate(pieces) if pieces else cum[:0]
+    return cum, off
+
+
+@torch.no_grad()
+def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=2 << 30):
+    """Every expression of a video against its ground truth, per frame: int64 [E, T, 3] (intersection, n_pred, n_gt) on the
+    host, where expression e's prediction is the OR of ``masklets[i]`` for i in ``pred_sets[e]`` and its ground truth the OR
+    over ``gt_sets[e]`` (dataloader.py:251-351 get_gt_masklet / get_sam2_masklet, evaluator.py:227-247).
+
+    ``masklets``: M RLE masklets, each a list of T per-frame COCO dicts (a non-dict is a missing frame = zeros), all of one
+    T and (h, w).  Only the masks some list references are decoded, once each, into column-major bit planes (sola_rle_pack_cm)
+    and every (expression, frame) is counted by one launch (sola_mask_select_counts): one host parse, one decode launch, one
+    count launch and one copy.  The planes of one launch are capped at ``max_plane_bytes``: expressions are grouped in order
+    under that budget (an expression that alone exceeds it runs by itself).  An empty list is an all-zero masklet.  Counts
+    are exact int64; the reference sums float32 tensors, which is exact while every count is below 2^24."""
+    import numpy as np
+    E = len(pred_sets)
+    if len(gt_sets) != E:
+        raise SolaError(f"masklet_select_counts: {E} prediction sets but {len(gt_sets)} GT sets")
+    M = len(masklets)
+    if M == 0:
+        raise SolaError("masklet_select_counts: no masklets")
+    for s in list(pred_sets) + list(gt_sets):
+        for i in s:
+            if not 0 <= int(i) < M:
+                raise SolaError(f"masklet_select_counts: index {i} outside the {M} masklets")
+    T, size = _masklet_geometry(masklets)
+    if E == 0:
+        return torch.zeros((0, T, 3), dtype=torch.int64)
+    if size is None or T == 0:  # every frame of every masklet is missing: all masks are empty
+        return torch.zeros((E, T, 3), dtype=torch.int64)
+    h, w = size
+    L = lib()
+    stride = L.sola_jf_plane_words(h, w)
+    mask_bytes = T * stride * 4
+    groups, cur, cur_ids = [], [], set()
+    for e in range(E):
+        ids = set(int(i) for i in pred_sets[e]) | set(int(i) for i in gt_sets[e])
+        if cur and len(cur_ids | ids) * mask_bytes > max_plane_bytes:
+            groups.append(cur)
+            cur, cur_ids = [], set()
+        cur.append(e)
+        cur_ids |= ids
+    groups.append(cur)
+    dev = torch.device(device)
+    stream = current_stream(dev)
+    outs = []
+    for grp in groups:
+        ids = sorted(set(int(i) for e in grp for i in list(pred_sets[e]) + list(gt_sets[e])))
+        local = {m: k for k, m in enumerate(ids)}
+        csr = []
+        for sets in (pred_sets, gt_sets):
+            off, idx = [0], []
+            for e in grp:
+                idx += [local[int(i)] for i in sets[e]]
+                off.append(len(idx))
+            csr.append((off, idx))
+        (poff, pidx), (goff, gidx) = csr
+        ints = torch.tensor(poff + goff + pidx + gidx + [0], dtype=torch.int32).to(dev)  # one copy for the four lists
+        Eg = len(grp)
+        d_poff, d_goff = ints[:Eg + 1], ints[Eg + 1:2 * Eg + 2]
+        d_pidx, d_gidx = ints[2 * Eg + 2:2 * Eg + 2 + len(pidx)], ints[2 * Eg + 2 + len(pidx):]
+        counts = torch.empty((Eg, T, 3), device=dev, dtype=torch.int64)
+        if ids:
+            cum, off = _planes_cum(masklets, ids, T, h * w)
+            cum_t = torch.from_numpy((cum if len(cum) else np.zeros(1, np.uint32)).view(np.int32)).to(dev)
+            off_t = torch.from_numpy(off).to(dev)
+            bits = torch.empty((len(ids) * T, stride), device=dev, dtype=torch.int32)
+            check(L.sola_rle_pack_cm(ptr(cum_t), ptr(off_t), len(ids) * T, h, w, stride, ptr(bits), stream), "sola_rle_pack_cm")
+        else:  # no expression of the group references a mask: every count is 0
+            bits = torch.zeros((1, 4), device=dev, dtype=torch.int32)
+        check(L.sola_mask_select_counts(ptr(bits), stride if ids else 4, len(ids), T, ptr(d_poff), ptr(d_pidx), ptr(d_goff),
+                                        ptr(d_gidx), Eg, ptr(counts), stream), "sola_mask_select_counts")
+        outs.append(counts)
+    return (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu()
+
+
+def compute_JF_batch(masklets, pred_sets, gt_sets, device, **kw):
+    """[(J, F, (J + F) / 2)] per expression from masklet_select_counts: evaluator.py:196-199,227-247 for every expression of
+    a video in one counting pass.  J is the mean over frames of inter / union (1.0 for an empty union), F the pixel F1 over
+    the whole masklet (0.0 when there is no true positive); not the DAVIS boundary F."""
+    counts = masklet_select_counts(masklets, pred_sets, gt_sets, device, **kw)
+    out = []
+    for c in counts:
+        J, F = float(J_from_counts(c)), float(F_from_counts(c))
+        out.append((J, F, (J + F) / 2))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # masks -> COCO compressed RLE (the track writers' seg_utils.encode_rle_masklet_torch / utils.encode_rle_mask)
 # ----------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
