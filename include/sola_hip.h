@@ -551,9 +551,16 @@ enum { SOLA_PROF_GEMM = 0,      /* gemm_nt_f32_kernel<128,128> */
  * values and what each was measured to do lives in docs/tune_keys.md; an unknown key returns SOLA_ERR_ARG.  Except under the *_ablate keys
  * (measurement only), results are identical across variants up to f32 summation order. */
 int sola_tune(const char* key, int value);
+/* Read a key back without changing it; either pointer may be null, an unknown key returns SOLA_ERR_ARG as in sola_tune.  `value` is the
+ * argument that, handed to sola_tune now, leaves the library as it is (so a borrower queries, sets, and hands the queried value back);
+ * `default_value` is the same report taken when the library was loaded, before any sola_tune call.  For most keys both are simply the
+ * switch; the keys whose setter clamps or writes two switches report as sola_amd/csrc/tune.h says. */
+int sola_tune_query(const char* key, int* value, int* default_value);
+/* The index-th key of this build (0, 1, ...), NULL past the end. */
+const char* sola_tune_key(int index);
 /* 1 when the library was built with EXPERIMENTS=1 (make -C sola_amd/csrc EXPERIMENTS=1): the closed experiments' kernels and their
- * sola_tune keys (gemm_pp, gemm_nw4, gemm_k16, gemm_stagger, gemm_order, gemm_trace, gemm_ld, gemm_gn_fuse, gemm_ablate, attn_bwd_ablate,
- * attn_reg_minw, attn_res_splitm, gemm_f32p_ablate) exist only there; the default library rejects those keys. */
+ * sola_tune keys (SOLA_TUNE_EXPERIMENT_KEYS in sola_amd/csrc/tune.h; marked (EXPERIMENTS) in docs/tune_keys.md) exist only there; the
+ * default library rejects those keys. */
 int sola_has_experiments(void);
 /* Self-test of the library's cross-lane primitives on the current device: wave sums / maxima on v_permlane*_swap + DPP against the
  * ds_bpermute butterfly, every lane of every step bit for bit (synchronises the stream).  SOLA_OK or SOLA_ERR_STATE + sola_last_error(). */

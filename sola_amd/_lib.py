@@ -5,6 +5,7 @@ compute entry point raises ``SolaLibraryError`` with the build command.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -143,6 +144,8 @@ SIGNATURES = {
     "sola_set_x16_arena": (_i, [_vp, _vp, _sz]),
     "sola_x16_arena_info": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "sola_tune": (_i, [C.c_char_p, _i]),
+    "sola_tune_query": (_i, [C.c_char_p, C.POINTER(_i), C.POINTER(_i)]),
+    "sola_tune_key": (C.c_char_p, [_i]),
     "sola_has_experiments": (_i, []),
     "sola_selftest": (_i, [_vp]),
     "sola_adamw_bind": (_i, [_vp, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i]),
@@ -197,6 +200,31 @@ def lib():
 def has_experiments():
     """True when the library was built with EXPERIMENTS=1 (closed experiments' kernels and their sola_tune keys compiled in)."""
     return bool(lib().sola_has_experiments())
+
+
+def tune_query(key):
+    """(value, default) of a sola_tune key: the argument that restores the present state, and the one the library was loaded with."""
+    value, default = _i(), _i()
+    check(lib().sola_tune_query(key.encode(), C.byref(value), C.byref(default)), f"sola_tune_query {key!r}")
+    return value.value, default.value
+
+
+def tune_default(key):
+    return tune_query(key)[1]
+
+
+@contextlib.contextmanager
+def tuned(**keys):
+    """Borrow sola_tune switches: ``with tuned(iou_fused=0, gemm_glds=1): ...`` sets them and, however the block ends, hands back what
+    each was before, last set first.  A key this build does not have raises before anything is changed."""
+    before = [(k, tune_query(k)[0]) for k in keys]
+    try:
+        for k, v in keys.items():
+            check(lib().sola_tune(k.encode(), int(v)), f"sola_tune {k!r}")
+        yield
+    finally:  # (handing a key its queried value is a no-op by definition, so this is right wherever the block stopped)
+        for k, old in reversed(before):
+            check(lib().sola_tune(k.encode(), old), f"sola_tune {k!r}")
 
 
 def check(status, what=""):

@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "ragged.h"
+#include "tune.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // errors
@@ -267,73 +268,6 @@ extern "C" int sola_set_stage_dropout(float p, uint64_t seed) {
     return SOLA_OK;
 }
 
-void sola_gemm_set_variant(int v);
-void sola_gemm_set_glds(int v);
-void sola_gemm_set_splitk(int v);
-void sola_gemm_set_splitk_max(int v);
-void sola_gemm_set_small_rows(int v);
-void sola_gemm_set_small_nw8(int v);
-void sola_gemm_set_f32_nw8(int v);
-void sola_gemm_set_f32_persist(int v);
-void sola_gemm_tn_set_persist(int v);
-#ifdef SOLA_EXPERIMENTS
-extern int g_gemm_f32p_ablate;
-#endif
-void sola_gemm_tn_set_nw8(int v);
-extern int g_gemm_nw4, g_gemm_pp, g_gemm_k16, g_train_tn_tr, g_train_x16_keep, g_train_attn_cast;
-extern int g_gemm_stagger, g_gemm_order, g_gemm_trace, g_gemm_ld;
-extern int g_bwd_side_rows, g_bwd_group_rows, g_lang_shared_neg;
-extern int g_infer_f32_rows;
-void sola_gemm_set_ablate(int v);
-void sola_gemm_set_persist(int v);
-void sola_set_train_split_min_rows(int v);
-void sola_gemm_set_glds_force(int v);
-void sola_gn_set_variant(int v);
-void sola_bilinear_set_staged(int v);
-void sola_attn_set_variant(int v);
-void sola_attn_set_target_blocks(int v);
-void sola_iou_set_fused(int v);
-void sola_attn_set_split_min_keys(int v);
-void sola_attn_set_bwd_fused(int v);
-void sola_attn_set_bwd_ablate(int v);
-void sola_attn_set_bwd_bf16_mfma(int v);
-void sola_train_set_gn_stats(int v);
-void sola_gemm_set_slack_stagger(int v);
-void sola_iou_set_packed(int v);
-void sola_attn_set_f16_small(int v);
-void sola_gn_set_h8(int v);
-void sola_attn_set_spin(int v);
-void sola_train_set_dw_f16(int v);
-void sola_train_set_gn_cast(int v);
-void sola_attn_set_splitm(int v);
-void sola_attn_set_reg(int v);
-void sola_attn_set_reg_minw(int v);
-void sola_attn_set_res(int v);
-void sola_attn_set_res_tiles(int v);
-void sola_attn_set_res_shape(int v);
-void sola_attn_set_res_splitm(int v);
-void sola_attn_set_bwd_small(int v);
-void sola_attn_set_bwd_blk(int v);
-void sola_attn_set_bwd_rag_wave(int v);
-void sola_attn_set_simple_train(int v);
-void sola_gn_set_bwd_reg(int v);
-void sola_gn_set_slices(int v);
-void sola_gn_set_wide(int v);
-void sola_gemm_set_gn_fuse(int v);
-void sola_set_bwd_dual_cast(int v);
-void sola_set_bwd_fused_bf16_cast(int v);
-void sola_attn_set_ring(int v);
-void sola_attn_set_f16_qpb(int v);
-void sola_attn_set_ring_blocks(int v);
-void sola_attn_set_ring_remap(int v);
-void sola_attn_set_ring_ablate(int v);
-void sola_attn_set_simple_remap(int v);
-void sola_iou_set_shape(int v);
-extern int g_train_bf16_store;
-void sola_attn_set_bf16_mfma(int v);
-void sola_attn_set_simple_db(int v);
-void sola_pack_set_resample_lds(int v);
-static int g_stage_split_math = 0;
 // ---- self-test of the cross-lane primitives (common.h): wave_sum / wave_max run on v_permlane*_swap + DPP; every lane of every butterfly
 // step must equal the ds_bpermute (__shfl_xor) form bit for bit - a compiler that folds a swap's two results (seen with the builtin form,
 // common.h) or a wrong rotation would show here, not as a tolerance drift three kernels later
@@ -391,90 +325,58 @@ extern "C" int sola_has_experiments(void) {
 #endif
 }
 
+// ---- sola_tune: the keys are the rows of tune.h, scanned in order
+static int g_stage_split_math = 0;
+static void sola_set_stage_split_math(int v) { g_stage_split_math = v != 0; }
+#define TUNE_EXTERN(key) extern int g_##key;
+#define TUNE_NONE(key, setter, report)
+SOLA_TUNE_KEYS(TUNE_EXTERN, TUNE_NONE)
+#ifdef SOLA_EXPERIMENTS
+SOLA_TUNE_EXPERIMENT_KEYS(TUNE_EXTERN, TUNE_NONE)
+#endif
+namespace {
+struct TuneKey {
+    const char* key;
+    void (*set)(int);
+    int (*report)();
+    int initial;  // the report when the library was loaded: the globals' initialisers, before any sola_tune call
+};
+#define TUNE_PLAIN(key) {#key, [](int v) { g_##key = v; }, []() -> int { return g_##key; }, g_##key},
+#define TUNE_SPECIAL(key, setter, report) {#key, setter, []() -> int { return report; }, report},
+const TuneKey g_tune_keys[] = {
+    SOLA_TUNE_KEYS(TUNE_PLAIN, TUNE_SPECIAL)
+#ifdef SOLA_EXPERIMENTS
+    SOLA_TUNE_EXPERIMENT_KEYS(TUNE_PLAIN, TUNE_SPECIAL)
+#endif
+};
+constexpr int kTuneKeys = sizeof(g_tune_keys) / sizeof(g_tune_keys[0]);
+
+const TuneKey* tune_find(const char* key) {
+    for (const TuneKey& k : g_tune_keys)
+        if (!strcmp(key, k.key)) return &k;
+    sola_set_error("tune: unknown key '%s'%s", key, sola_has_experiments() ? "" : " (experiment keys exist in EXPERIMENTS=1 builds only)");
+    return nullptr;
+}
+}  // namespace
+
 extern "C" int sola_tune(const char* key, int value) {
     SOLA_ARG(key, "tune: null key");
-    if (!strcmp(key, "attn_stage_split_math")) { g_stage_split_math = value != 0; return SOLA_OK; }
-    if (!strcmp(key, "gemm_variant")) { sola_gemm_set_variant(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_glds")) { sola_gemm_set_glds(value); return SOLA_OK; }
-    if (!strcmp(key, "bwd_side_rows")) { g_bwd_side_rows = value; return SOLA_OK; }
-    if (!strcmp(key, "bwd_group_rows")) { g_bwd_group_rows = value; return SOLA_OK; }
-    if (!strcmp(key, "lang_shared_neg")) { g_lang_shared_neg = value; return SOLA_OK; }
-    if (!strcmp(key, "train_tn_tr")) { g_train_tn_tr = value; return SOLA_OK; }
-    if (!strcmp(key, "train_x16_keep")) { g_train_x16_keep = value; return SOLA_OK; }
-    if (!strcmp(key, "train_attn_cast")) { g_train_attn_cast = value; return SOLA_OK; }
-    if (!strcmp(key, "gemm_splitk")) { sola_gemm_set_splitk(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_splitk_max")) { sola_gemm_set_splitk_max(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_small_rows")) { sola_gemm_set_small_rows(value); return SOLA_OK; }
-    if (!strcmp(key, "infer_f32_rows")) { g_infer_f32_rows = value; return SOLA_OK; }
-    if (!strcmp(key, "gemm_small_nw8")) { sola_gemm_set_small_nw8(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_f32_nw8")) { sola_gemm_set_f32_nw8(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_f32_persist")) { sola_gemm_set_f32_persist(value); return SOLA_OK; }
-#ifdef SOLA_EXPERIMENTS
-    if (!strcmp(key, "gemm_f32p_ablate")) { g_gemm_f32p_ablate = value; return SOLA_OK; }
-#endif
-    if (!strcmp(key, "gemm_tn_nw8")) { sola_gemm_tn_set_nw8(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_tn_persist")) { sola_gemm_tn_set_persist(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_glds_force")) { sola_gemm_set_glds_force(value); return SOLA_OK; }
-    if (!strcmp(key, "train_split_min_rows")) { sola_set_train_split_min_rows(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_persist")) { sola_gemm_set_persist(value); return SOLA_OK; }
-    if (!strcmp(key, "gn_variant")) { sola_gn_set_variant(value); return SOLA_OK; }
-    if (!strcmp(key, "bilinear_staged")) { sola_bilinear_set_staged(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_variant")) { sola_attn_set_variant(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_target_blocks")) { sola_attn_set_target_blocks(value); return SOLA_OK; }
-    if (!strcmp(key, "iou_fused")) { sola_iou_set_fused(value); return SOLA_OK; }
-    if (!strcmp(key, "iou_shape")) { sola_iou_set_shape(value); return SOLA_OK; }
-    if (!strcmp(key, "train_bf16_store")) { g_train_bf16_store = value; return SOLA_OK; }
-    if (!strcmp(key, "attn_bf16_mfma")) { sola_attn_set_bf16_mfma(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_bwd_bf16_mfma")) { sola_attn_set_bwd_bf16_mfma(value); return SOLA_OK; }
-    if (!strcmp(key, "train_gn_stats")) { sola_train_set_gn_stats(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_slack_stagger")) { sola_gemm_set_slack_stagger(value); return SOLA_OK; }
-    if (!strcmp(key, "iou_packed")) { sola_iou_set_packed(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_split_min_keys")) { sola_attn_set_split_min_keys(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_splitm")) { sola_attn_set_splitm(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_reg")) { sola_attn_set_reg(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_res")) { sola_attn_set_res(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_res_tiles")) { sola_attn_set_res_tiles(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_res_shape")) { sola_attn_set_res_shape(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_bwd_small")) { sola_attn_set_bwd_small(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_bwd_blk")) { sola_attn_set_bwd_blk(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_bwd_rag_wave")) { sola_attn_set_bwd_rag_wave(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_bwd_fused")) { sola_attn_set_bwd_fused(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_f16_small")) { sola_attn_set_f16_small(value); return SOLA_OK; }
-    if (!strcmp(key, "gn_h8")) { sola_gn_set_h8(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_spin")) { sola_attn_set_spin(value); return SOLA_OK; }
-    if (!strcmp(key, "train_dw_f16")) { sola_train_set_dw_f16(value); return SOLA_OK; }
-    if (!strcmp(key, "train_gn_cast")) { sola_train_set_gn_cast(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_simple_train")) { sola_attn_set_simple_train(value); return SOLA_OK; }
-    if (!strcmp(key, "gn_bwd_reg")) { sola_gn_set_bwd_reg(value); return SOLA_OK; }
-    if (!strcmp(key, "gn_slices")) { sola_gn_set_slices(value); return SOLA_OK; }
-    if (!strcmp(key, "gn_wide")) { sola_gn_set_wide(value); return SOLA_OK; }
-    if (!strcmp(key, "bwd_dual_cast")) { sola_set_bwd_dual_cast(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_f16_qpb")) { sola_attn_set_f16_qpb(value); return SOLA_OK; }
-    if (!strcmp(key, "bwd_fused_bf16_cast")) { sola_set_bwd_fused_bf16_cast(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_simple_remap")) { sola_attn_set_simple_remap(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_simple_db")) { sola_attn_set_simple_db(value); return SOLA_OK; }
-    if (!strcmp(key, "pack_resample_lds")) { sola_pack_set_resample_lds(value); return SOLA_OK; }
-#ifdef SOLA_EXPERIMENTS  // closed experiments and measurement switches: EXPERIMENTS=1 builds only (make -C sola_amd/csrc EXPERIMENTS=1)
-    if (!strcmp(key, "gemm_pp")) { g_gemm_pp = value; return SOLA_OK; }
-    if (!strcmp(key, "gemm_nw4")) { g_gemm_nw4 = value; return SOLA_OK; }
-    if (!strcmp(key, "gemm_k16")) { g_gemm_k16 = value; return SOLA_OK; }
-    if (!strcmp(key, "gemm_stagger")) { g_gemm_stagger = value; return SOLA_OK; }
-    if (!strcmp(key, "gemm_order")) { g_gemm_order = value; return SOLA_OK; }
-    if (!strcmp(key, "gemm_trace")) { g_gemm_trace = value; return SOLA_OK; }
-    if (!strcmp(key, "gemm_ld")) { g_gemm_ld = value; return SOLA_OK; }
-    if (!strcmp(key, "gemm_ablate")) { sola_gemm_set_ablate(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_reg_minw")) { sola_attn_set_reg_minw(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_res_splitm")) { sola_attn_set_res_splitm(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_ring")) { sola_attn_set_ring(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_ring_blocks")) { sola_attn_set_ring_blocks(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_ring_remap")) { sola_attn_set_ring_remap(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_ring_ablate")) { sola_attn_set_ring_ablate(value); return SOLA_OK; }
-    if (!strcmp(key, "attn_bwd_ablate")) { sola_attn_set_bwd_ablate(value); return SOLA_OK; }
-    if (!strcmp(key, "gemm_gn_fuse")) { sola_gemm_set_gn_fuse(value); return SOLA_OK; }
-#endif
-    sola_set_error("tune: unknown key '%s'%s", key, sola_has_experiments() ? "" : " (experiment keys exist in EXPERIMENTS=1 builds only)");
-    return SOLA_ERR_ARG;
+    const TuneKey* k = tune_find(key);
+    if (!k) return SOLA_ERR_ARG;
+    k->set(value);
+    return SOLA_OK;
 }
+
+extern "C" int sola_tune_query(const char* key, int* value, int* default_value) {
+    SOLA_ARG(key, "tune: null key");
+    const TuneKey* k = tune_find(key);
+    if (!k) return SOLA_ERR_ARG;
+    if (value) *value = k->report();
+    if (default_value) *default_value = k->initial;
+    return SOLA_OK;
+}
+
+extern "C" const char* sola_tune_key(int index) { return index >= 0 && index < kTuneKeys ? g_tune_keys[index].key : nullptr; }
 
 extern "C" int sola_set_ws_policy(SolaCtx* c, int every) {
     SOLA_ARG(c, "set_ws_policy: null ctx");

@@ -507,11 +507,13 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
     }
 }
 
+}  // namespace: sola_tune switches are extern (tune.h)
 int g_attn_target_blocks = 512;  // resident-K/V mode: blocks per launch (measured flat from 256 to 1024, worse above)
 int g_attn_resident_blocks = 512;  // shared mode: grid size cap (2 blocks per CU x 256 CUs)
 int g_attn_variant = 1;  // 1 (default): packed short sequences, high-occupancy shape for units of <= 128 queries, q-block loop over
                          // resident K/V otherwise; 0: one unit per wave / one q-block per block (baseline); 2: high-occupancy shape
                          // wherever it applies; 3: never the high-occupancy shape (A/B)
+namespace {
 
 template <int DH, int NW, bool SPLIT, int MINB = 2>
 static int launch_shared(const AttnArgs& a, long long blocks, size_t lds, hipStream_t s) {
@@ -592,9 +594,6 @@ int launch_dh(const AttnArgs& a0, hipStream_t s) {
 
 int g_attn_splitm = 0;  // sola_tune "attn_splitm": 1 = f16-MFMA triples on f32 inputs in the split precision mode (measured slower:
                         // 1.49 vs 1.39 ms of attention per 256-sample step - every wave re-converts the K/V fragments it reads)
-void sola_attn_set_splitm(int v) { g_attn_splitm = v; }
-void sola_attn_set_variant(int v) { g_attn_variant = v; }
-void sola_attn_set_target_blocks(int v) { g_attn_target_blocks = v; }
 
 bool attention_simple_supported(const AttnDesc& d);
 int launch_attention_simple(const AttnDesc& d, hipStream_t s);

@@ -1220,6 +1220,7 @@ __global__ __launch_bounds__(256) void attn_bwd_part_reduce_kernel(const AttnBwd
 }
 
 
+}  // namespace: sola_tune switches are extern (tune.h)
 int g_attn_bwd_rag_wave = 96;  // sola_tune "attn_bwd_rag_wave": ragged batches whose LONGEST unit has at most this many queries and keys take
                                // the per-wave kernels in their RAG form (0 = never)
 int g_attn_bwd_blk = 1;    // sola_tune "attn_bwd_blk": 0 = per-wave staging (the round-1 kernels) for every shape (A/B)
@@ -1228,6 +1229,7 @@ int g_attn_bwd_ablate = 0;  // measurement only (sola_tune "attn_bwd_ablate"): 1
 int g_attn_bwd_fused = 1;  // sola_tune "attn_bwd_fused": 0 = two-pass kernels for the units of <= 128 queries and keys too (A/B)
 
 int g_attn_bwd_bf16_mfma = 1;  // sola_tune "attn_bwd_bf16_mfma": 0 = the bf16-row launches keep the f32 products (bit-identical to the f32 kernel on the widened values)
+namespace {
 template <int NWU, bool IO16, bool MF = false, bool G16 = false, bool O16 = false>
 static int launch_bwd_fused_n(const AttnBwdArgs& a, int chunks, hipStream_t s) {
     constexpr int LD = 128 + 4;
@@ -1406,12 +1408,6 @@ size_t attention_bwd_part_floats(long long q_rows, int G, int H, int Sk) {
     return (size_t)(q_rows / (16 * qc) + G + 1) * H * 2 * 64 * 128;
 }
 
-void sola_attn_set_bwd_small(int v) { g_attn_bwd_small = v; }
-void sola_attn_set_bwd_blk(int v) { g_attn_bwd_blk = v; }
-void sola_attn_set_bwd_rag_wave(int v) { g_attn_bwd_rag_wave = v; }
-void sola_attn_set_bwd_fused(int v) { g_attn_bwd_fused = v; }
-void sola_attn_set_bwd_ablate(int v) { g_attn_bwd_ablate = v; }
-void sola_attn_set_bwd_bf16_mfma(int v) { g_attn_bwd_bf16_mfma = v; }
 bool attention_bwd_dout_bf16_enabled() { return g_attn_bwd_bf16_mfma != 0; }
 
 // bf16 q / k / v in and bf16 dQ / dK / dV out (AttnBwdDesc::io_bf16): the one-pass kernel's shapes, 8-value-aligned rows

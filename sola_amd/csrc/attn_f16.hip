@@ -54,8 +54,10 @@ __device__ __forceinline__ _Float16 cvt_16(float x) {
     else return (_Float16)x;
 }
 
+}  // namespace: sola_tune switches are extern (tune.h)
 int g_attn_f16_small = 1;
 int g_attn_f16_qpb = 4;  // sola_tune "attn_f16_qpb": q-blocks per block against <= 64 keys, at most (1 = every q-block stages the unit's K / V itself; < 0: exactly -v, tests)  // sola_tune "attn_f16_small": 0 = the MFMA shape for sequences of <= 4 steps too (A/B)
+namespace {
 
 struct GeoH { long long q0, k0, q_rs, k_rs; int Sq, Sk; };
 __device__ __forceinline__ GeoH geo_h(const AttnHArgs& a, int grp) {
@@ -474,7 +476,6 @@ int launch_h_bf16_train(const AttnHArgs& a0, hipStream_t s) {
 }  // namespace
 
 int g_attn_bf16_mfma = 1;  // sola_tune "attn_bf16_mfma": 1 = bf16 training forward on the bf16 MFMA (this file); 0 = the f32-MFMA kernel on widened values (attn_simple.hip)
-void sola_attn_set_bf16_mfma(int v) { g_attn_bf16_mfma = v; }
 // AttnDesc::in_bf16 launches this kernel takes: head_dim 128 / 64, 16-byte aligned rows, no shared keys, f32 and / or bf16 (o_cast_fmt 3) output
 bool attention_bf16_mfma_supported(const AttnDesc& d) {
     return g_attn_bf16_mfma && d.in_bf16 && !d.o_sp16 && !d.in_sp16 && !d.k_private && (d.DH == 128 || d.DH == 64) && d.ldq % 8 == 0 && d.ldk % 8 == 0 &&
@@ -498,7 +499,6 @@ int launch_attention_bf16_train(const AttnDesc& d, hipStream_t s) {
     return d.DH == 128 ? launch_h_bf16_train<128>(a, s) : launch_h_bf16_train<64>(a, s);
 }
 
-void sola_attn_set_f16_small(int v) { g_attn_f16_small = v; }
 void sola_attn_set_f16_qpb(int v) { g_attn_f16_qpb = v == 0 ? 1 : v; }
 
 // AttnDesc with q / k / v / o pointing at _Float16 matrices and ld* counting halfs

@@ -245,8 +245,6 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_f32_reg_kernel(const AttnR
 
 int g_attn_reg = 1;       // sola_tune "attn_reg": 0 = never this shape, 2 = wherever it can run (A/B, tests)
 int g_attn_reg_minw = 2;  // waves per SIMD the kernel is compiled for: 2 = 256 VGPRs, no spills (3 and 4 spill: 1.3x / 2.4x slower)
-void sola_attn_set_reg(int v) { g_attn_reg = v; }
-void sola_attn_set_reg_minw(int v) { g_attn_reg_minw = v; }
 
 // f32 q / k / v at head_dim 128, no dropout; more than 4 queries or keys (attn_fwd_small_kernel has those).
 // Where it wins (tools/attn_probe3.py, standalone launches, us):  motion attention of 16 steps (T = 128) 237 vs 292 for the

@@ -382,10 +382,7 @@ int g_attn_res_splitm = 0;      // sola_tune "attn_res_splitm": 1 = f16-MFMA tri
                                 // 181 -> 175 us at 256 x 48, 163 -> 165 us at 2048 x 48 - removing 3/4 of the matrix-pipe time buys almost
                                 // nothing, so the pipe is not what bounds this shape (its 64-byte pieces per row and instruction are); off
 int g_attn_res_shape = 0;        // 0 = auto, 1 = 8 waves / 128 VGPRs / no prefetch, 2 = 4 waves / 168 VGPRs / next-tile prefetch
-void sola_attn_set_res(int v) { g_attn_res = v; }
 void sola_attn_set_res_tiles(int v) { g_attn_res_tiles = v < 0 ? 0 : v; }
-void sola_attn_set_res_shape(int v) { g_attn_res_shape = v; }
-void sola_attn_set_res_splitm(int v) { g_attn_res_splitm = v; }
 
 // f32 q / k / v at head_dim 128, no dropout, at most 64 keys and enough queries per unit to pay for staging K/V
 bool attention_res_supported(const AttnDesc& d) {

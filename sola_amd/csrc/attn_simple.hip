@@ -777,7 +777,9 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
     if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
 }
 
+}  // namespace: sola_tune switches are extern (tune.h)
 int g_attn_spin_db = 1;  // sola_tune "attn_spin" 2 = single-buffered 32-key stages (A/B)
+namespace {
 int launch_spin(const AttnSArgs& a0, hipStream_t s) {
     AttnSArgs a = a0;
     constexpr int TK = 32;
@@ -807,8 +809,10 @@ int launch_splitm(const AttnSArgs& a0, hipStream_t s) {
     return SOLA_OK;
 }
 
+}  // namespace: sola_tune switches are extern (tune.h)
 int g_attn_simple_db = 1;  // sola_tune "attn_simple_db": 1 = double-buffered 16-key stages with register prefetch
 int g_attn_simple_remap = 0;  // sola_tune "attn_simple_remap": XCD-contiguous block order; measured no gain (273.8 vs 275.8 us at 64 tracks, 392 vs 400 at 128)
+namespace {
 
 template <int DH>
 int launch_s(const AttnSArgs& a0, hipStream_t s) {
@@ -844,8 +848,6 @@ int launch_s(const AttnSArgs& a0, hipStream_t s) {
 
 }  // namespace
 
-void sola_attn_set_simple_remap(int v) { g_attn_simple_remap = v; }
-void sola_attn_set_simple_db(int v) { g_attn_simple_db = v; }
 
 // sequences of <= 4 steps at head_dim 128, inference (no log-sum-exp, no dropout), f32 q / k / v
 bool attention_small_supported(const AttnDesc& d) {
@@ -894,7 +896,6 @@ bool attention_in_bf16_supported(const AttnDesc& d) {
     return g_attn_simple_train && !d.o_sp16 && !d.in_sp16 && !d.k_private && (d.Sq > 16 || d.Sk > 16) && (d.DH == 128 || d.DH == 64) &&
            d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 8 == 0;
 }
-void sola_attn_set_simple_train(int v) { g_attn_simple_train = v; }
 
 int launch_attention_simple(const AttnDesc& d, hipStream_t s) {
     AttnSArgs a = make_sargs(d);

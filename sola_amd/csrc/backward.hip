@@ -14,9 +14,7 @@
 
 extern int g_train_split_min_rows;
 int g_bwd_dual_cast = 1;  // sola_tune "bwd_dual_cast": the transposing cast of a gradient matrix also writes its row-major cast (A/B)
-void sola_set_bwd_dual_cast(int v) { g_bwd_dual_cast = v; }
 int g_bwd_fused_bf16_cast = 1;  // sola_tune "bwd_fused_bf16_cast": bf16 storage - the gradient statistics pass is the cast as well (A/B)
-void sola_set_bwd_fused_bf16_cast(int v) { g_bwd_fused_bf16_cast = v; }
 
 // sola_tune "train_dw_f16" (default 1, round 3): in the split-f16 training step (precision 1) the weight-gradient products
 // dW = dY^T X run on PLAIN f16 casts of dY and X (one MFMA per product, f32 accumulation) instead of split pairs (three); forward and
@@ -25,7 +23,6 @@ void sola_set_bwd_fused_bf16_cast(int v) { g_bwd_fused_bf16_cast = v; }
 // (64 samples; 1.1e-5 -> 2.3e-4 at 8), the worst tensor (1.9e-3 / 4.9e-3: the forward's softmax near-ties) and the cosine of the
 // whole gradient (0.999999) do not move; the step is 14 % faster on the ragged mix.  0 = split pairs everywhere.
 int g_train_dw_f16 = 1;
-void sola_train_set_dw_f16(int v) { g_train_dw_f16 = v; }
 // sola_tune "bwd_side_rows" (round 4): exact-f32 backward of at most this many token rows (the few-sample regime; the reference trains at
 // batch size 1) runs its weight-gradient products dW = dY^T X - leaves of the graph, a third of the step's kernel time there - on a side
 // stream beside the dX chain.  Kernels of 64-512 blocks leave most of the chip idle, so the two streams really overlap.  0 = off.

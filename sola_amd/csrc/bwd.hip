@@ -707,7 +707,6 @@ int launch_segsum_rows(const float* in, float* out, const int32_t* off, int segm
 }
 
 int g_gn_bwd_reg = 1;  // sola_tune "gn_bwd_reg": 0 = three-pass kernel for every shape (A/B)
-void sola_gn_set_bwd_reg(int v) { g_gn_bwd_reg = v; }
 
 // which kernel launch_group_norm_bwd picks for units of at most `ntok` tokens: the 1024-thread register shape (17..32 float4 per lane of a
 // 256-thread block) has no bfloat16-dy2 code

@@ -126,7 +126,6 @@ int sola_check_forward_args(const SolaCtx* c, const char* who, size_t need, cons
 // vs 256 at 64) the attention wins from 64 keys on, but the q/k/v GEMM pays ~70 us per launch for the split-pair epilogue: net
 // gain at 128 tracks (14.41 -> 14.30 ms per step, attention 0.43 -> 0.49 of the HBM peak), net loss at 80 and 64.  96.
 int g_attn_split_min_keys = 96;
-void sola_attn_set_split_min_keys(int v) { g_attn_split_min_keys = v; }
 
 int g_lang_shared_neg = 1;  // sola_tune "lang_shared_neg": 0 = the negative tokens repeated per sample through the text-side projections (A/B)
 

@@ -631,7 +631,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void gemm_nt_f32_small_ke
     *reinterpret_cast<float4*>(pr.C + (long long)m * a.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
+}  // namespace: sola_tune switches are extern (tune.h)
 int g_gemm_small_rows = 2048;  // sola_tune "gemm_small_rows": exact-f32 GEMMs of at most this many rows take the 32x32 in-block split-K shape (0 = never)
+namespace {
 static bool gemm_small_applies(const GemmDesc& d) {
     if (d.r_sp16 || d.c_sp16 || d.gn_gamma) return false;  // the kernel reads R and writes C as plain f32 rows, no fused norm
     if (d.w_nn_rows) {  // NN form: one problem, plain rows, whole 32-row steps inside each stacked matrix, 16-byte aligned rows
@@ -649,7 +651,9 @@ static bool gemm_small_applies(const GemmDesc& d) {
     }
     return true;
 }
+}  // namespace: sola_tune switches are extern (tune.h)
 int g_gemm_small_nw8 = 1;  // sola_tune "gemm_small_nw8": 0 = always four waves per tile (A/B)
+namespace {
 template <int NW, bool CONV, bool NN = false>
 static int launch_small_n(const GemmArgs& a, int nprob, hipStream_t s) {
     constexpr size_t lds = (size_t)NW * 2 * 2 * 32 * SM_LD * sizeof(float);  // NW waves x two stages (73.7 / 147.5 KB); the reduction reuses it
@@ -701,26 +705,20 @@ int launch_tile(const GemmArgs& base, int nprob, hipStream_t s) {
     return SOLA_OK;
 }
 
+}  // namespace
+
 int g_gemm_splitk = 1;  // 0 disables the split-K of small grids (A/B)
 int g_gemm_f32_nw8 = 1;         // sola_tune "gemm_f32_nw8": the exact-f32 128x128 shape with eight waves per block (0 = four; A/B)
 int g_gemm_splitk_max = 8;      // sola_tune "gemm_splitk_max": most K ranges per tile (A/B)
 int g_gemm_splitk_tiles = 512;  // grids with fewer 64x64 tiles than this are split (target: twice as many blocks)
 int g_gemm_variant = -1;  // -1 auto (measured: simple schedule wins on 128x128 by 5%, mid-tile staging on 64x64 by 6%), 0 / 1 force
 
-}  // namespace
-
 bool gemm_nn_supported(const GemmDesc& d) { return d.w_nn_rows > 0 && gemm_small_applies(d); }
 
 int g_gemm_glds = 3;  // split-f16 GEMM, direct-to-LDS staging (gemm_glds.hip): 0 off, 1 128x128 blocks, 4 256x256 blocks, 3 auto
 int g_gemm_glds_force = 0;  // tests: take the direct-to-LDS kernels for grids of any size
-void sola_gemm_set_glds_force(int v) { g_gemm_glds_force = v; }
-void sola_gemm_set_variant(int v) { g_gemm_variant = v; }
 void sola_gemm_set_splitk(int v) { g_gemm_splitk = v != 0; if (v > 1) g_gemm_splitk_tiles = v; }
 void sola_gemm_set_splitk_max(int v) { g_gemm_splitk_max = v < 2 ? 2 : v; }
-void sola_gemm_set_small_rows(int v) { g_gemm_small_rows = v; }
-void sola_gemm_set_small_nw8(int v) { g_gemm_small_nw8 = v; }
-void sola_gemm_set_f32_nw8(int v) { g_gemm_f32_nw8 = v; }
-void sola_gemm_set_glds(int v) { g_gemm_glds = v; }
 bool gemm_split_glds_supported(const GemmDesc& d);
 int launch_splitk_reduce(const float* part, int ksplit, int nprob, float* const* C, int M, int N, int ldc, const float* out_scale_dev,
                          const float* scale_dev, hipStream_t s) {

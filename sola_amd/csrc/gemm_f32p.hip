@@ -519,7 +519,6 @@ extern "C" int sola_gemm_f32p_trace_read(unsigned long long* host, int words) {
 }
 #endif
 int g_gemm_f32_persist = 1;  // sola_tune "gemm_f32_persist": 0 = the 128x128 one-tile-per-block kernel for every exact-f32 launch (A/B)
-void sola_gemm_set_f32_persist(int v) { g_gemm_f32_persist = v; }
 
 // Shapes the persistent kernel takes: plain rows or the conv window gather (not the transposed-conv gather), 16-byte rows, whole k-tiles,
 // and a grid whose rounds of one 256x128 tile per CU are at least as full as the 128x128 kernel's rounds of two blocks per CU.

@@ -2053,17 +2053,14 @@ static int launch_glds(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
 // change in the interior epilogue; the repeatability stress in the GPU suite), but a ~2 % step-time gain does not justify shipping an
 // unexplained fault's containment as the default.
 int g_gemm_gn_fuse = 0;
-void sola_gemm_set_gn_fuse(int v) { g_gemm_gn_fuse = v; }
 int g_gemm_pp = 0;  // experiment (sola_tune "gemm_pp"): 1 = ping-pong kernel where it applies
 int g_gemm_nw4 = 0;  // experiment (sola_tune "gemm_nw4"): plain f32-output launches on 256x128 tiles with four waves, one per SIMD
 int g_gemm_k16 = 0;  // experiment (sola_tune "gemm_k16"): 256x128 tiles, 16-deep k-tiles, two four-wave blocks per CU
 int g_gemm_persist = 1;  // 256x256 shape: 1 = persistent kernel (one block per CU walks the tiles), 0 = one tile per block
-void sola_gemm_set_persist(int v) { g_gemm_persist = v; }
 // measurement switches of the persistent kernel (sola_tune "gemm_stagger" / "gemm_order" / "gemm_trace"), all off in production
 int g_gemm_stagger = 0, g_gemm_order = 0, g_gemm_trace = 0, g_gemm_ld = 0;
 int g_gemm_slack_stagger = 40;  // sola_tune "gemm_slack_stagger": s_sleep(1) periods per k-tile at phase 1 for the blocks with a tile of slack (16-bit launches; 0 = off;
                                 // A/B on one box, ragged bf16 step: 0 -> 17.64-17.73 ms, 40 -> 17.46-17.51, 75 -> 17.54)
-void sola_gemm_set_slack_stagger(int v) { g_gemm_slack_stagger = v; }
 static unsigned long long* g_trace_buf = nullptr;  // [1024 blocks][8 waves][gemm_trace_words], allocated on first use
 constexpr size_t TRACE_BYTES = (size_t)1024 * 8 * gemm_trace_words * 8;
 // copies the trace of the LAST traced launch to the host (synchronises the device); returns the number of bytes written, < 0 on error
@@ -2243,7 +2240,6 @@ static int launch_shape(GldsArgs& a, int shape, int M, int N, int nprob, hipStre
 }
 
 int g_gemm_ablate = 0;
-void sola_gemm_set_ablate(int v) { g_gemm_ablate = v; }
 
 extern int g_gemm_glds;
 int gemm_split_glds_shape(const GemmDesc& d);

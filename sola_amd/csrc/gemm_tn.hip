@@ -433,7 +433,6 @@ int launch_colsum_jobs(const ColsumJobsDesc& d, hipStream_t s) {
 }
 
 int g_gemm_tn_nw8 = 1;  // sola_tune "gemm_tn_nw8": the exact-f32 weight-gradient kernels with eight waves per block (0 = four; A/B)
-void sola_gemm_tn_set_nw8(int v) { g_gemm_tn_nw8 = v; }
 static int tn_splits(int M, int N, int K) {
     const long long tiles = (long long)((N + TB - 1) / TB) * ((K + TB - 1) / TB);
     int splits = (int)((768 + tiles - 1) / tiles);

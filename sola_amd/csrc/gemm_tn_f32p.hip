@@ -332,7 +332,6 @@ int launch_tnp_t(const TnpArgs& a, hipStream_t s) {
 }  // namespace
 
 int g_gemm_tn_persist = 1;  // sola_tune "gemm_tn_persist": 0 = the 128x128 one-tile kernel for every exact-f32 weight gradient (A/B)
-void sola_gemm_tn_set_persist(int v) { g_gemm_tn_persist = v; }
 
 // The row splits of the persistent kernel for an M x (N x K) weight gradient, from the sizes alone (gemm_tn_scratch_bytes sizes the partial
 // sums with it): whole rounds of one work item per CU, at least 256 rows per split.  0 = not the kernel's shape.

@@ -508,7 +508,6 @@ __global__ __launch_bounds__(256) void mask_iou_onepass_kernel(const OnepassArgs
 }  // namespace
 
 int g_iou_shape = 0;  // sola_tune "iou_shape": 0 = by R; else 16 * G + nb (G in {1, 2, 4} slices in flight, nb batches per block; G * nb <= 12)
-void sola_iou_set_shape(int v) { g_iou_shape = v; }
 static void onepass_shape(int R, int* G, int* nb) {
     if (g_iou_shape > 0 && (g_iou_shape >> 4) * (g_iou_shape & 15) <= 12 && (g_iou_shape & 15) > 0 &&
         ((g_iou_shape >> 4) == 1 || (g_iou_shape >> 4) == 2 || (g_iou_shape >> 4) == 4)) {
@@ -528,9 +527,7 @@ size_t mask_iou_fused_scratch_bytes(int P, int R, long long words) {
 }
 
 int g_iou_packed = 1;  // sola_tune "iou_packed": 0 = the ticket form for every mask size (A/B, tests)
-void sola_iou_set_packed(int v) { g_iou_packed = v; }
 int g_iou_fused = 1;  // sola_tune "iou_fused": 0 forces the pack + pair path (A/B, tests)
-void sola_iou_set_fused(int v) { g_iou_fused = v; }
 
 // true if the call was served by the one-launch kernel
 bool launch_mask_iou_fused(const void* am, const void* bm, int elem_type, int P, int R, int H, int W, int h, int w, long long* inter,
@@ -592,7 +589,6 @@ static bool resample_lds_ok(const void* masks, int elem_type, int h, int w, int 
     const size_t es = elem_type ? 4 : 1;
     return w % 32 == 0 && (reinterpret_cast<uintptr_t>(masks) & 15) == 0 && ((size_t)h * w * es) % 16 == 0;
 }  // sola_tune "pack_resample_lds": 0 = the generic per-pixel kernel for resampled packs (A/B, tests)
-void sola_pack_set_resample_lds(int v) { g_pack_resample_lds = v; }
 
 int launch_mask_pack(const void* masks, int elem_type, int n, int h, int w, int H, int W, uint32_t* bits,
                      long long* area, hipStream_t s) {

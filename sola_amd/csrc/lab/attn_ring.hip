@@ -369,10 +369,7 @@ int g_attn_ring_blocks = 2;  // sola_tune "attn_ring_blocks": persistent blocks 
 int g_attn_ring_remap = 1;   // sola_tune "attn_ring_remap": consecutive work items on one XCD
 int g_attn_ring_ablate = 0;  // sola_tune "attn_ring_ablate"
 void sola_attn_set_ring_blocks(int v) { g_attn_ring_blocks = v < 1 ? 1 : v; }
-void sola_attn_set_ring_remap(int v) { g_attn_ring_remap = v; }
-void sola_attn_set_ring_ablate(int v) { g_attn_ring_ablate = v; }
 int g_attn_ring = 0;  // sola_tune "attn_ring": 1 = this shape where attn_simple.hip's applies, 2 = also in place of attn_res.hip's (A/B)
-void sola_attn_set_ring(int v) { g_attn_ring = v; }
 
 // f32 q / k / v, head_dim 128, inference (no log-sum-exp, no dropout), more than 16 keys or queries; the byte offsets inside a unit fit
 // the buffer instructions' 32-bit offsets

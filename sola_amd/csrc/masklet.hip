@@ -255,7 +255,6 @@ static void launch_bilinear(const BilinearArgs& a, int n, bool aligned, size_t s
 
 int g_bilinear_staged = 1;  // 0 = always the direct-load version, 1 = stage uint8 sources (measured: 77 -> 58 us per 64 720p
                             // frames; float sources gain nothing at 720p and lose at 1080p, their loop is VALU-bound), 2 = stage all
-void sola_bilinear_set_staged(int v) { g_bilinear_staged = v; }
 
 int launch_mask_bilinear_pack(const void* masks, int elem_type, int n, int h, int w, int H, int W, uint32_t* bits,
                               long long* area, hipStream_t s) {

@@ -709,9 +709,7 @@ int launch_ws_standardize(const WsLayer* layers, int n_layers, hipStream_t s) {
 
 int g_gn_variant = 1;  // 0 = always the three-pass kernel (A/B), 1 = register-resident shapes where the unit fits
 int g_gn_wide = 1;     // sola_tune "gn_wide": 1024-thread blocks for units of 64-128 KiB (A/B)
-void sola_gn_set_wide(int v) { g_gn_wide = v; }
 int g_gn_slices = 1;   // sola_tune "gn_slices": 0 = three-pass kernel for units that do not fit the registers (A/B)
-void sola_gn_set_slices(int v) { g_gn_slices = v; }
 // Library-owned scratch of the sliced shape for callers that pass none (the per-stage entry point; the forward orchestrators hand
 // over a piece of the caller's workspace): one buffer per (device, stream), so launches on different streams never share slots - a
 // stream's launches are ordered among themselves - and a mutex around the table.  Allocated on first use, grown when a launch
@@ -735,8 +733,6 @@ static float2* gn_slice_scratch(size_t bytes, hipStream_t s) {
     return sl.buf;
 }
 int g_gn_h8 = 1;  // sola_tune "gn_h8": 0 = four channels per lane in the 16-bit storage mode too (A/B)
-void sola_gn_set_h8(int v) { g_gn_h8 = v; }
-void sola_gn_set_variant(int v) { g_gn_variant = v; }
 
 int launch_group_norm(const GroupNormDesc& d, hipStream_t s) {
     SOLA_ARG(d.groups > 0 && d.C % d.groups == 0, "group_norm: C=%d groups=%d", d.C, d.groups);

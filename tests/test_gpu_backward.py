@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 from conftest import case_dict  # noqa: E402
 from oracle import sola_oracle  # noqa: E402
 from sola_amd import ops, synth  # noqa: E402
+from sola_amd._lib import tuned  # noqa: E402
 from sola_amd.loss import track_selection_losses  # noqa: E402
 from sola_amd.module import LanguageAlignedTrackSelectionModule  # noqa: E402
 
@@ -289,14 +290,12 @@ def test_full_gradient_norms_vs_reference(full_golden, full_model, ci, precision
     cfg = synth.DEFAULT_MODEL_CFG
     B, N, T, L = [int(v) for v in full_golden["cases"][ci]]
     g = case_dict(full_golden, ci)
-    from sola_amd import _lib
     m.precision = precision
     try:
-        _lib.check(_lib.lib().sola_tune(b"train_split_min_rows", 0), "tune")  # these cases are below the production size gate
-        _, loss3, grads = train_step_grads(m, cfg, B, N, T, L, 200 + ci)
+        with tuned(train_split_min_rows=0):  # these cases are below the production size gate
+            _, loss3, grads = train_step_grads(m, cfg, B, N, T, L, 200 + ci)
     finally:
         m.precision = "f32"
-        _lib.check(_lib.lib().sola_tune(b"train_split_min_rows", 1024), "tune")
     np.testing.assert_allclose(loss3.detach().cpu().numpy().astype(np.float64), g["loss"], rtol=2e-4, atol=2e-4)
     total = float(dict(zip([str(k) for k in g["grad_norm_keys"]], g["grad_norm_vals"]))["total_grad_norm"])
     bad = {}
@@ -319,7 +318,6 @@ def test_split_training_gradients_match_exact_f32(full_model):
     encoder stage one of them regularly lies within rounding distance of LeakyReLU's kink, the two forwards then disagree
     on its sign and ONE output channel's weight / bias gradient moves by a few percent of the tensor's largest entry -
     either path does that against float64 autograd, at different channels: tools/train_grad_dbg.py.)"""
-    from sola_amd import _lib
     m, _ = full_model
     cfg = synth.DEFAULT_MODEL_CFG
     grads = {}
@@ -345,7 +343,6 @@ def test_split_training_weight_gradient_products_on_f16_operands(full_model):
     forward and dX keep the split pairs.  Against the exact-f32 step the weight matrices' median relative error rises from ~1e-5 to
     ~2e-4 (operand rounding averaged over >= 1024 rows), the worst tensor and the whole-gradient cosine do not move; with the switch
     off the median is back at the split level."""
-    from sola_amd import _lib
     m, _ = full_model
     cfg = synth.DEFAULT_MODEL_CFG
     out = {}
@@ -355,16 +352,15 @@ def test_split_training_weight_gradient_products_on_f16_operands(full_model):
         ref = {k: v.double().clone() for k, v in g.items()}
         total = math.sqrt(sum(float(v.pow(2).sum()) for v in ref.values()))
         for dw in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"train_dw_f16", dw), "tune")
             m.precision = "f16x3"
-            _, _, g = train_step_grads(m, cfg, 8, 40, 32, 10, 77)
+            with tuned(train_dw_f16=dw):
+                _, _, g = train_step_grads(m, cfg, 8, 40, 32, 10, 77)
             got = {k: v.double().clone() for k, v in g.items()}
             rel = sorted(float((got[k] - ref[k]).norm()) / (float(ref[k].norm()) + 1e-6 * total) for k in ref if k.endswith("weight") and ref[k].dim() >= 2)
             n = math.sqrt(sum(float(v.pow(2).sum()) for v in got.values()))
             out[dw] = (rel[len(rel) // 2], rel[-1], sum(float((got[k] * ref[k]).sum()) for k in ref) / (total * n))
     finally:
         m.precision = "f32"
-        _lib.check(_lib.lib().sola_tune(b"train_dw_f16", 1), "tune")
     print("weight matrices, (median, worst) relative error and gradient cosine: f16 dW", out[1], "split dW", out[0])
     assert out[1][0] <= 1e-3 and out[1][1] <= 1e-2 and out[1][2] >= 0.9999, out
     assert out[0][0] <= 5e-5 and out[0][1] <= 1e-2 and out[0][2] >= 0.9999, out
@@ -396,7 +392,6 @@ def test_f16_operand_training_vs_exact_f32(full_model, full_golden, mode):
     every tensor within 35 %, median within 3 %, total gradient norm within 5 % of the REFERENCE's.
     precision "bf16" (library precision 3) is the same step with bfloat16 operands (v_mfma_f32_32x32x16_bf16) - the format
     BASELINE config C2 names; its bounds are the second row of LOWP_TRAIN_TOL."""
-    from sola_amd import _lib
     m, _ = full_model
     cfg = synth.DEFAULT_MODEL_CFG
     l_rtol, min_cos, worst_tol, median_tol, norm_rtol = LOWP_TRAIN_TOL[mode]
@@ -424,12 +419,11 @@ def test_f16_operand_training_vs_exact_f32(full_model, full_golden, mode):
     g = case_dict(full_golden, ci)
     m.precision = mode
     try:
-        _lib.check(_lib.lib().sola_tune(b"train_split_min_rows", 0), "tune")
-        _, loss3, _ = train_step_grads(m, cfg, B, N, T, L, 200 + ci)
-        gnd = m.get_grad_norm_dict()
+        with tuned(train_split_min_rows=0):
+            _, loss3, _ = train_step_grads(m, cfg, B, N, T, L, 200 + ci)
+            gnd = m.get_grad_norm_dict()
     finally:
         m.precision = "f32"
-        _lib.check(_lib.lib().sola_tune(b"train_split_min_rows", 1024), "tune")
     gref = dict(zip([str(k) for k in g["grad_norm_keys"]], g["grad_norm_vals"]))
     print(f"{mode}-operand training, golden case {ci}: loss {loss3.detach().cpu().numpy()} vs {g['loss']}, total gradient norm "
           f"{gnd['total_grad_norm']:.5f} vs {gref['total_grad_norm']:.5f}")
@@ -448,7 +442,6 @@ def test_16_bit_operand_training_on_weights_with_an_unsaturated_softmax(mode):
     scaled by 1/64 (synth.make_state_dict_variant "lin_div64": attention scores x 1/4096, a nearly uniform softmax) - the regime of a
     network whose attention is not an arg-max - and the 16-bit operand steps are held to much tighter bounds against the exact-f32 step
     (measured, round 4: f16 cosine 0.99950, worst tensor 4.5 %, median 0.038 %; bf16 0.99522, 13.7 %, 0.29 %; at random init 0.985 / 0.744)."""
-    from sola_amd import _lib
     cfg = synth.DEFAULT_MODEL_CFG
     m = LanguageAlignedTrackSelectionModule(cfg)
     sd = synth.make_state_dict_variant(cfg, 42, "lin_div64")
@@ -481,21 +474,23 @@ def test_kept_operand_casts_give_the_same_gradients_bit_for_bit(full_model, mode
     need: the SECOND step is the one that reuses the casts.  Dropout off (eval mode): the two runs see the same step.  (Round 6: the bf16
     step's bfloat16 pre-norm rows read their residual from the kept casts, so that part of the storage mode - sola_tune "train_bf16_store" 2 -
     exists only with the arena; this A/B of the arena runs at level 1.)"""
-    from sola_amd import _lib
-    _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 1), "tune")
+    with tuned(train_bf16_store=1):
+        _kept_casts_checks(full_model, mode)
+
+
+def _kept_casts_checks(full_model, mode):
     m, _ = full_model
     cfg = synth.DEFAULT_MODEL_CFG
     got = {}
     try:
         m.precision = mode
         for keep in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"train_x16_keep", keep), "tune")
-            for _ in range(2):
-                _, l3, g = train_step_grads(m, cfg, 8, 40, 32, 10, 77)
+            with tuned(train_x16_keep=keep):
+                for _ in range(2):
+                    _, l3, g = train_step_grads(m, cfg, 8, 40, 32, 10, 77)
             got[keep] = ({k: v.clone() for k, v in g.items()}, l3.detach().clone())
     finally:
         m.precision = "f32"
-        _lib.check(_lib.lib().sola_tune(b"train_x16_keep", 1), "tune")
     assert torch.equal(got[1][1], got[0][1])
     bad = [k for k in got[1][0] if not torch.equal(got[1][0][k], got[0][0][k])]
     assert not bad, bad
@@ -506,16 +501,14 @@ def test_kept_operand_casts_give_the_same_gradients_bit_for_bit(full_model, mode
         m.train()
         m.precision = mode
         for keep in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"train_x16_keep", keep), "tune")
-            for _ in range(2):
-                torch.manual_seed(7)
-                _, l3, g = train_step_grads(m, cfg, 8, 40, 32, 10, 77)
+            with tuned(train_x16_keep=keep):
+                for _ in range(2):
+                    torch.manual_seed(7)
+                    _, l3, g = train_step_grads(m, cfg, 8, 40, 32, 10, 77)
             got[keep] = ({k: v.clone() for k, v in g.items()}, l3.detach().clone())
     finally:
         m.eval()
         m.precision = "f32"
-        _lib.check(_lib.lib().sola_tune(b"train_x16_keep", 1), "tune")
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 3), "tune")
     assert torch.equal(got[1][1], got[0][1])
     bad = [k for k in got[1][0] if not torch.equal(got[1][0][k], got[0][0][k])]
     assert not bad, bad
@@ -528,21 +521,17 @@ def test_bf16_statistics_pass_that_is_the_cast_gives_the_same_gradients_bit_for_
     products, so every gradient must keep its bits with the switch off.  (Round 6: with the step's bf16 STORAGE on, the producers write the
     bfloat16 rows themselves and the bias sums are taken from those rounded rows - as autocast's grad_output.sum(0) is - so this A/B of
     the pass runs with sola_tune "train_bf16_store" 0.)"""
-    from sola_amd import _lib
     m, _ = full_model
     cfg = synth.DEFAULT_MODEL_CFG
     got = {}
     try:
         m.precision = "bf16"
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 0), "tune")
         for fused in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"bwd_fused_bf16_cast", fused), "tune")
-            _, l3, g = train_step_grads(m, cfg, 8, 40, 32, 10, 77)
+            with tuned(train_bf16_store=0, bwd_fused_bf16_cast=fused):
+                _, l3, g = train_step_grads(m, cfg, 8, 40, 32, 10, 77)
             got[fused] = ({k: v.clone() for k, v in g.items()}, l3.detach().clone())
     finally:
         m.precision = "f32"
-        _lib.check(_lib.lib().sola_tune(b"bwd_fused_bf16_cast", 1), "tune")
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 3), "tune")
     assert torch.equal(got[1][1], got[0][1])
     bad = [k for k in got[1][0] if not torch.equal(got[1][0][k], got[0][0][k])]
     assert not bad, bad
@@ -659,22 +648,16 @@ def test_side_stream_weight_gradients_are_bit_identical(full_model):
     """Round 4: in the few-sample exact-f32 backward (the reference's batch size of 1) the weight-gradient products run on a side stream
     beside the dX chain (sola_tune "bwd_side_rows").  Same kernels in the same per-gradient order: all 83 gradients, the losses and a
     second step's gradients must equal the single-stream run bit for bit."""
-    from sola_amd import _lib
     m, _ = full_model
     cfg = synth.DEFAULT_MODEL_CFG
     out = {}
-    try:
-        _lib.check(_lib.lib().sola_tune(b"bwd_group_rows", 0), "tune")  # the side lane runs the per-matrix slab form: compare like with like
-        for rows in (0, 4096):
-            _lib.check(_lib.lib().sola_tune(b"bwd_side_rows", rows), "tune")
+    for rows in (0, 4096):  # 0 is the default (off: the lane costs the host more than it saves)
+        with tuned(bwd_group_rows=0, bwd_side_rows=rows):  # the side lane runs the per-matrix slab form: compare like with like
             res = []
             for seed in (5, 6):
                 _, l3, g = train_step_grads(m, cfg, 1, 64, 32, 16, seed)
                 res.append((l3.detach().clone(), {k: v.clone() for k, v in g.items()}))
-            out[rows] = res
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"bwd_side_rows", 0), "tune")  # the default (off: the lane costs the host more than it saves)
-        _lib.check(_lib.lib().sola_tune(b"bwd_group_rows", 2048), "tune")
+        out[rows] = res
     for (la, ga), (lb, gb) in zip(out[0], out[4096]):
         assert torch.equal(la, lb)
         assert set(ga) == set(gb) and len(ga) == 83
@@ -689,18 +672,14 @@ def test_grouped_few_sample_weight_gradients_equal_the_slab_form(full_model, sha
     all rows of its problem), and - round 5 - reads the weights of its dX GEMMs where they lie (sola_gemm_nn's form: no transposed copies).  Against the per-matrix slab form (0): the same
     losses, the gradients nothing was deferred for bit for bit, the deferred ones (and what flows from the same dX chain: identical) within
     f32 summation-order noise - 2e-6 of each tensor's norm - and twice in a row the same bits (fixed order, no atomics)."""
-    from sola_amd import _lib
     m, _ = full_model
     cfg = synth.DEFAULT_MODEL_CFG
     B, N, T, L = shape
     out = {}
-    try:
-        for rows in (0, 2048, -2048):  # -2048: the grouped form once more (repeatability)
-            _lib.check(_lib.lib().sola_tune(b"bwd_group_rows", abs(rows)), "tune")
+    for rows in (0, 2048, -2048):  # -2048: the grouped form once more (repeatability)
+        with tuned(bwd_group_rows=abs(rows)):
             _, l3, g = train_step_grads(m, cfg, B, N, T, L, 11)
-            out[rows] = (l3.detach().clone(), {k: v.clone() for k, v in g.items()})
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"bwd_group_rows", 2048), "tune")
+        out[rows] = (l3.detach().clone(), {k: v.clone() for k, v in g.items()})
     (l0, g0), (l1, g1), (l2, g2) = out[0], out[2048], out[-2048]
     assert torch.equal(l0, l1) and torch.equal(l1, l2)
     assert set(g0) == set(g1) and len(g0) == 83

@@ -17,7 +17,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from sola_amd import _lib, ops, synth  # noqa: E402
-from sola_amd._lib import check, current_stream, lib, ptr  # noqa: E402
+from sola_amd._lib import check, current_stream, lib, ptr, tuned  # noqa: E402
 from sola_amd.loss import track_selection_losses_ragged  # noqa: E402
 from sola_amd.module import LanguageAlignedTrackSelectionModule  # noqa: E402
 
@@ -29,11 +29,8 @@ def bf(t):
 def attention_f32_high_occupancy(*args, **kw):
     """ops.attention through attn_simple.hip's kernel for every shape (sola_tune attn_variant 2) - the kernel whose bf16 instantiation is
     under test; the default routing sends some of these shapes to kernels with another (equally valid) summation order"""
-    check(lib().sola_tune(b"attn_variant", 2), "tune")
-    try:
+    with tuned(attn_variant=2):
         return ops.attention(*args, **kw)
-    finally:
-        check(lib().sola_tune(b"attn_variant", 1), "tune")
 
 
 @pytest.mark.parametrize("M,N,K", [(4096, 1024, 1024), (8192, 512, 768), (300, 256, 128), (2048, 1024, 3072)])
@@ -125,11 +122,8 @@ def test_attention_forward_on_the_bf16_mfma(case):
 @pytest.mark.parametrize("case", ATTN_CASES)
 def test_attention_forward_on_bf16_rows_equals_the_f32_kernel_on_the_widened_values(case):
     """(sola_tune "attn_bf16_mfma" 0: the f32-MFMA kernel of attn_simple.hip on bfloat16 rows - the shapes the bf16-MFMA kernel does not take)"""
-    check(lib().sola_tune(b"attn_bf16_mfma", 0), "tune")
-    try:
+    with tuned(attn_bf16_mfma=0):
         _forward_f32_mfma_case(case)
-    finally:
-        check(lib().sola_tune(b"attn_bf16_mfma", 1), "tune")
 
 
 def _forward_f32_mfma_case(case):
@@ -165,11 +159,8 @@ def _forward_f32_mfma_case(case):
 @pytest.mark.parametrize("case", ATTN_CASES + ["motion_4", "motion_3x2"])
 def test_attention_backward_on_bf16_rows_equals_the_f32_kernel_and_writes_the_rounded_gradients(case):
     """(sola_tune "attn_bwd_bf16_mfma" 0: the f32 products on bfloat16 rows - bit-identical to the f32 kernel on the widened values)"""
-    check(lib().sola_tune(b"attn_bwd_bf16_mfma", 0), "tune")
-    try:
+    with tuned(attn_bwd_bf16_mfma=0):
         _backward_case(case, exact=True)
-    finally:
-        check(lib().sola_tune(b"attn_bwd_bf16_mfma", 1), "tune")
 
 
 @pytest.mark.parametrize("case", ATTN_CASES)
@@ -296,13 +287,10 @@ def test_ragged_bf16_step_with_bf16_q_k_v_storage(variant):
     res = {}
     for tag, prec, store in (("f32", "f32", 3), ("operands", "bf16", 0), ("stored", "bf16", 3)):
         m.precision = prec
-        check(lib().sola_tune(b"train_bf16_store", store), "tune")
-        try:
+        with tuned(train_bf16_store=store):
             if tag == "stored":  # the bfloat16 pre-norm rows (level 2) read their residual from the kept-operand arena, sized from the
                 _ragged_step(m, smp, 98)  # previous step's need: the second step of a run is the first with the whole storage mode on
             res[tag] = _ragged_step(m, smp, 99)
-        finally:
-            check(lib().sola_tune(b"train_bf16_store", 3), "tune")
     m.precision = "f32"
     l32, g32, _ = res["f32"]
     out = {}

@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 from conftest import case_dict  # noqa: E402
 from sola_amd import _lib, synth  # noqa: E402
-from sola_amd._lib import check, current_stream, lib, ptr  # noqa: E402
+from sola_amd._lib import check, current_stream, lib, ptr, tune_default, tuned  # noqa: E402
 from sola_amd.module import LanguageAlignedTrackSelectionModule  # noqa: E402
 
 # Stated tolerance of the mode (round 3, from EVERY row of three 256-sample batches against the oracle -
@@ -115,15 +115,12 @@ def test_f16_attention_walking_several_query_blocks_over_staged_keys(Sq, Sk, qpb
     k = torch.from_numpy(rng.standard_normal((G * Sk, D)).astype(np.float32)).half().cuda()
     v = torch.from_numpy(rng.standard_normal((G * Sk, D)).astype(np.float32)).half().cuda()
     outs = {}
-    try:
-        for mode in (1, -qpb):
-            check(lib().sola_tune(b"attn_f16_qpb", mode), "tune")
+    for mode in (1, -qpb):
+        with tuned(attn_f16_qpb=mode):
             o = torch.zeros((G * Sq, D), device="cuda", dtype=torch.float16)
             check(lib().sola_attention_f16(ptr(q), D, ptr(k), D, ptr(v), D, ptr(o), D, G, H, DH, Sq, Sk, 1, Sq, 0, 1, Sk, 0, 1, 1.0 / math.sqrt(DH),
                                            current_stream(o.device)), "sola_attention_f16")
-            outs[mode] = o
-    finally:
-        check(lib().sola_tune(b"attn_f16_qpb", 4), "tune")
+        outs[mode] = o
     assert not torch.isnan(outs[-qpb].float()).any()
     assert torch.equal(outs[1], outs[-qpb])
 
@@ -243,8 +240,7 @@ def test_switching_inference_precisions_gives_each_mode_its_own_bits():
                     out.append((what, *m(cuda(inp["object_tokens"]), cuda(inp["lang_tokens"]))))
         return out
 
-    try:
-        _lib.check(_lib.lib().sola_tune(b"infer_f32_rows", 4096), "tune")  # the default routing (conftest.py switches it off)
+    with tuned(infer_f32_rows=tune_default("infer_f32_rows")):  # the default routing (conftest.py switches it off)
         ref = {prec: {w: (sm, st) for w, sm, st in calls(build(prec), ("big", "one", "ragged"))} for prec in ("f32", "f16x3", "f16")}
         m = build("f32")
         for prec in ("f32", "f16x3", "f16", "f16x3", "f32"):
@@ -252,7 +248,5 @@ def test_switching_inference_precisions_gives_each_mode_its_own_bits():
             for i, (what, sm, st) in enumerate(calls(m, ("one", "big", "ragged", "big"))):
                 assert torch.equal(sm, ref[prec][what][0]) and torch.equal(st, ref[prec][what][1]), (prec, i, what)
         assert m.split_fallbacks()[0] == 0
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"infer_f32_rows", 0), "tune")
     assert torch.equal(ref["f16x3"]["one"][0], ref["f32"]["one"][0])  # the one-sample f16x3 call did take the exact-f32 route
     assert not torch.equal(ref["f16x3"]["big"][0], ref["f32"]["big"][0])

@@ -12,7 +12,8 @@ pytestmark = pytest.mark.gpu
 
 from conftest import case_dict  # noqa: E402
 from oracle import sola_oracle  # noqa: E402
-from sola_amd import ops, synth  # noqa: E402
+from sola_amd import _lib, ops, synth  # noqa: E402
+from sola_amd._lib import tune_default, tuned  # noqa: E402
 from sola_amd.loss import track_selection_losses  # noqa: E402
 from sola_amd.module import LanguageAlignedTrackSelectionModule  # noqa: E402
 
@@ -89,12 +90,10 @@ def test_few_row_calls_of_the_default_mode_run_exact_f32(full_fast, full_f32):
     """Round 4 (sola_tune "infer_f32_rows", default 4096 object-token rows - conftest.py switches it off for the other tests): one sample per
     call in the default precision runs the exact-f32 kernels (faster there since the few-row GEMM shape, no guard read-back) - the output of
     the "f16x3" module IS the "f32" module's, uniform and ragged; larger calls and the key at 0 take the split-f16 pass as before."""
-    from sola_amd import _lib
     mf, _ = full_fast
     m32, _ = full_f32
     cfg = synth.DEFAULT_MODEL_CFG
-    try:
-        _lib.check(_lib.lib().sola_tune(b"infer_f32_rows", 4096), "tune")
+    with tuned(infer_f32_rows=tune_default("infer_f32_rows")):
         _, sm_a, st_a, _, _ = run(mf, cfg, 1, 64, 32, 16, 77)      # 2048 rows: routed
         _, sm_b, st_b, _, _ = run(m32, cfg, 1, 64, 32, 16, 77)
         assert torch.equal(sm_a, sm_b) and torch.equal(st_a, st_b)
@@ -107,11 +106,9 @@ def test_few_row_calls_of_the_default_mode_run_exact_f32(full_fast, full_f32):
             ra = mf.forward_ragged([obj], [lang])
             rb = m32.forward_ragged([obj], [lang])
         assert all(torch.equal(x, y) for x, y in zip(ra[0], rb[0]))
-        _lib.check(_lib.lib().sola_tune(b"infer_f32_rows", 0), "tune")
-        _, sm_e, _, _, _ = run(mf, cfg, 1, 64, 32, 16, 77)
+        with tuned(infer_f32_rows=0):
+            _, sm_e, _, _, _ = run(mf, cfg, 1, 64, 32, 16, 77)
         assert not torch.equal(sm_e, sm_b) and float((sm_e - sm_b).abs().max()) < 1e-3
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"infer_f32_rows", 0), "tune")
 
 
 @pytest.mark.parametrize("ci", range(5))
@@ -119,16 +116,12 @@ def test_full_cases_vs_golden_in_the_shipped_routing(full_golden, full_fast, ci)
     """the golden cases through the PRODUCTION configuration of the default mode - sola_tune "infer_f32_rows" at its shipped
     4096 (conftest.py switches it off for the other tests), so the few-row cases take the exact-f32 route inside the "f16x3" module and the
     larger ones the split-f16 pass - against the reference's outputs, not against another module of this library."""
-    from sola_amd import _lib
     m, _ = full_fast
     cfg = synth.DEFAULT_MODEL_CFG
     B, N, T, L = [int(v) for v in full_golden["cases"][ci]]
     g = case_dict(full_golden, ci)
-    try:
-        _lib.check(_lib.lib().sola_tune(b"infer_f32_rows", 4096), "tune")
+    with tuned(infer_f32_rows=tune_default("infer_f32_rows")):
         _, sm, st, loss3, argmax = run(m, cfg, B, N, T, L, 200 + ci)
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"infer_f32_rows", 0), "tune")
     assert np.abs(sm.cpu().numpy() - g["score_map"]).max() <= 1e-3
     assert np.abs(st.cpu().numpy() - g["score_tokens"]).max() <= 1e-3
     np.testing.assert_allclose(loss3.cpu().numpy().astype(np.float64), g["loss"], rtol=2e-4, atol=2e-4)
@@ -243,20 +236,7 @@ def test_split_gemm_split_output():
         assert err <= 2.0 ** -21 * ref.abs().max().item() + 1e-7, (M, N, K, err)
 
 
-EXPERIMENT_KEYS = ("gemm_gn_fuse", "gemm_k16", "gemm_pp", "gemm_ld", "gemm_nw4")  # exist in EXPERIMENTS=1 builds of the library only
-
-
-def _tune(**kv):
-    from sola_amd import _lib
-    for k, v in kv.items():
-        if k in EXPERIMENT_KEYS and not _lib.has_experiments():
-            assert int(v) == 0, k  # the default build has the experiment off by construction
-            continue
-        _lib.check(_lib.lib().sola_tune(k.encode(), int(v)), "sola_tune")
-
-
 def _needs_experiments():
-    from sola_amd import _lib
     if not _lib.has_experiments():
         pytest.skip("closed experiment: compiled in EXPERIMENTS=1 builds of the library only (make -C sola_amd/csrc EXPERIMENTS=1)")
 
@@ -274,8 +254,7 @@ def test_split_gemm_block_shapes_bit_identical(M, N, K):
     asp, wsp, bd, rd = ops.cast_sp16(cuda(a)), ops.cast_sp16(cuda(w), 64.0), cuda(b), cuda(r)
     rsp = ops.cast_sp16(rd) if N % 8 == 0 else None
     settings = [dict(gemm_glds=1, gemm_persist=0), dict(gemm_glds=4, gemm_persist=0), dict(gemm_glds=4, gemm_persist=1)]
-    try:
-        _tune(gemm_glds_force=1)  # these grids are far too small for the direct-to-LDS kernels to be chosen
+    with tuned(gemm_glds_force=1):  # these grids are far too small for the direct-to-LDS kernels to be chosen
         for res, res_split, out_split in [(None, False, False), (rd, False, False), (rsp, True, False), (None, False, True), (rsp, True, True)]:
             if res_split and rsp is None:
                 continue
@@ -283,17 +262,15 @@ def test_split_gemm_block_shapes_bit_identical(M, N, K):
                 continue
             outs = []
             for st in settings:
-                _tune(**st)
-                outs.append(ops.gemm_nt_split(asp, wsp, bd, res, res_split, 1.0 / 64.0, out_split).clone())
+                with tuned(**st):
+                    outs.append(ops.gemm_nt_split(asp, wsp, bd, res, res_split, 1.0 / 64.0, out_split).clone())
             torch.cuda.synchronize()
             for o in outs[1:]:
                 assert torch.equal(outs[0].view(torch.int32), o.view(torch.int32)), (res is not None, res_split, out_split)
-        _tune(gemm_glds=4, gemm_persist=1)
-        got = ops.gemm_nt_split(asp, wsp, bd, rd, False, 1.0 / 64.0).cpu().numpy()
+        with tuned(gemm_glds=4, gemm_persist=1):
+            got = ops.gemm_nt_split(asp, wsp, bd, rd, False, 1.0 / 64.0).cpu().numpy()
         ref = ops.decode_sp16(asp).double().cpu().numpy() @ (ops.decode_sp16(wsp).double().cpu().numpy() / 64.0).T + b + r
         assert np.abs(got - ref).max() <= 2e-6 * max(1.0, np.abs(ref).max())
-    finally:
-        _tune(gemm_glds=3, gemm_persist=1, gemm_glds_force=0)
 
 
 @pytest.mark.parametrize("seed", range(10))
@@ -308,21 +285,19 @@ def test_split_gemm_block_shapes_random(seed):
     r = rng.standard_normal((M, N)).astype(np.float32)
     asp, wsp, bd, rd = ops.cast_sp16(cuda(a)), ops.cast_sp16(cuda(w), 64.0), cuda(b), cuda(r)
     rsp = ops.cast_sp16(rd)
-    try:
-        _tune(gemm_glds_force=1)
+    with tuned(gemm_glds_force=1):
         for res, res_split, out_split in [(None, False, False), (rd, False, False), (rsp, True, False), (rsp, True, True)]:
             outs = []
             for st in [dict(gemm_glds=1, gemm_persist=0), dict(gemm_glds=4, gemm_persist=0), dict(gemm_glds=4, gemm_persist=1)]:
-                _tune(**st)
-                outs.append(ops.gemm_nt_split(asp, wsp, bd, res, res_split, 1.0 / 64.0, out_split).clone())
+                with tuned(**st):
+                    outs.append(ops.gemm_nt_split(asp, wsp, bd, res, res_split, 1.0 / 64.0, out_split).clone())
             torch.cuda.synchronize()
             for o in outs[1:]:
                 assert torch.equal(outs[0].view(torch.int32), o.view(torch.int32)), (M, N, K, res is not None, res_split, out_split)
-        got = ops.gemm_nt_split(asp, wsp, bd, rd, False, 1.0 / 64.0).cpu().numpy()
+        with tuned(gemm_glds=4, gemm_persist=1):  # (the persistent kernel, as the last of the three above)
+            got = ops.gemm_nt_split(asp, wsp, bd, rd, False, 1.0 / 64.0).cpu().numpy()
         ref = ops.decode_sp16(asp).double().cpu().numpy() @ (ops.decode_sp16(wsp).double().cpu().numpy() / 64.0).T + b + r
         assert np.abs(got - ref).max() <= 2e-6 * max(1.0, np.abs(ref).max()), (M, N, K)
-    finally:
-        _tune(gemm_glds=3, gemm_persist=1, gemm_glds_force=0)
 
 
 def test_forward_identical_across_gemm_kernels(full_fast):
@@ -332,16 +307,15 @@ def test_forward_identical_across_gemm_kernels(full_fast):
     inp = synth.make_inputs(synth.DEFAULT_MODEL_CFG, 8, 40, 32, 12, 5)
     obj, lang = torch.from_numpy(inp["object_tokens"]).cuda(), torch.from_numpy(inp["lang_tokens"]).cuda()
     outs = []
-    try:
-        _tune(gemm_glds_force=1, gemm_gn_fuse=0)  # the norm applied in the persistent kernel's epilogue exists in that kernel only
+    # the norm applied in the persistent kernel's epilogue exists in that kernel only (and in EXPERIMENTS=1 builds only: the default build
+    # has no such key, the experiment is off by construction)
+    fuse_off = {"gemm_gn_fuse": 0} if _lib.has_experiments() else {}
+    with tuned(gemm_glds_force=1, **fuse_off):
         for st in [dict(gemm_glds=4, gemm_persist=1), dict(gemm_glds=4, gemm_persist=0), dict(gemm_glds=1, gemm_persist=0)]:
-            _tune(**st)
-            with torch.no_grad():
+            with tuned(**st), torch.no_grad():
                 sm, tok = m(obj, lang)
             outs.append((sm.clone(), tok.clone()))
         torch.cuda.synchronize()
-    finally:
-        _tune(gemm_glds=3, gemm_persist=1, gemm_glds_force=0, gemm_gn_fuse=0)
     for sm, tok in outs[1:]:
         assert torch.equal(outs[0][0], sm) and torch.equal(outs[0][1], tok)
 
@@ -374,7 +348,6 @@ def test_fused_norm_epilogue_is_repeatable_and_matches_the_unfused_activations()
     element of a strip's last row uncentred, and SLP-vectorised statistics that returned garbage rows; tools/gnf_stress.py
     is the longer version."""
     _needs_experiments()  # round 5: the fused norm is closed (bit-repeatable, but no gain on the power-bound launch - profiles/r05_gnf_decision.txt)
-    from sola_amd import _lib
     cfg = synth.DEFAULT_MODEL_CFG
     m = LanguageAlignedTrackSelectionModule(cfg)
     m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in synth.make_state_dict(cfg, 42).items()})
@@ -387,23 +360,20 @@ def test_fused_norm_epilogue_is_repeatable_and_matches_the_unfused_activations()
         return (h[:, :, 0, :] + h[:, :, 1, :]).reshape(t.shape[0], -1)
 
     def run(fuse):
-        _lib.check(_lib.lib().sola_tune(b"gemm_gn_fuse", fuse), "tune")
-        with torch.no_grad():
-            m(inp["object_tokens"], inp["lang_tokens"])
-        torch.cuda.synchronize()
-        return {nm: m.workspace_tap(nm) for nm in names}
+        with tuned(gemm_gn_fuse=fuse):
+            with torch.no_grad():
+                m(inp["object_tokens"], inp["lang_tokens"])
+            torch.cuda.synchronize()
+            return {nm: m.workspace_tap(nm) for nm in names}
 
-    try:
-        ref = run(0)
-        first = run(1)
+    ref = run(0)
+    first = run(1)
+    for nm in names:
+        assert float((unsplit(first[nm]) - unsplit(ref[nm])).abs().max()) <= 2e-5, nm
+    for _ in range(11):
+        t = run(1)
         for nm in names:
-            assert float((unsplit(first[nm]) - unsplit(ref[nm])).abs().max()) <= 2e-5, nm
-        for _ in range(11):
-            t = run(1)
-            for nm in names:
-                assert torch.equal(t[nm].view(torch.int32), first[nm].view(torch.int32)), nm
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"gemm_gn_fuse", 0), "tune")  # the library's default: opt-in
+            assert torch.equal(t[nm].view(torch.int32), first[nm].view(torch.int32)), nm
     assert m.split_fallbacks()[1] == 0
 
 
@@ -448,21 +418,16 @@ def test_norm_fused_into_the_conv_epilogue_matches_the_separate_launch():
     (gemm_glds.hip, GNT).  128 samples of the headline shape: conv0 / conv1 / conv2 all qualify; the logits must agree with the
     same forward running the separate GroupNorm launches (sola_tune gemm_gn_fuse 0) to f32 summation noise, decisions equal."""
     _needs_experiments()
-    from sola_amd import _lib
     cfg = synth.DEFAULT_MODEL_CFG
     m = LanguageAlignedTrackSelectionModule(cfg)
     m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in synth.make_state_dict(cfg, 42).items()})
     m = m.cuda().eval(); m.precision = "f16x3"
     inp = {k: torch.from_numpy(v).cuda() for k, v in synth.make_inputs(cfg, 128, 64, 32, 16, 31).items()}
     outs = {}
-    try:
-        for fuse in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"gemm_gn_fuse", fuse), "tune")
-            with torch.no_grad():
-                sm, st = m(inp["object_tokens"], inp["lang_tokens"])
-            outs[fuse] = (sm.clone(), st.clone())
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"gemm_gn_fuse", 0), "tune")  # the library's default: opt-in
+    for fuse in (1, 0):
+        with tuned(gemm_gn_fuse=fuse), torch.no_grad():
+            sm, st = m(inp["object_tokens"], inp["lang_tokens"])
+        outs[fuse] = (sm.clone(), st.clone())
     assert m.split_fallbacks()[1] == 0
     d_sm = float((outs[1][0] - outs[0][0]).abs().max()); d_st = float((outs[1][1] - outs[0][1]).abs().max())
     # f32 rounding noise reaches the logits amplified ~1000x (the reference itself sits 1e-4 from a float64 evaluation at this
@@ -477,18 +442,13 @@ def test_negative_token_projections_shared_across_samples(full_fast, shape):
     same key / value projections for every sample - the text-side GEMMs of the default forward take B * L + 32 rows instead of B * (L + 32)
     and the object -> language attention reads the shared rows (AttnDesc::k_private).  Same products per row: logits and tokens are
     BIT-identical to the repeated form (small batches keep the repeated form: the few-row GEMM's split over K depends on the row count)."""
-    from sola_amd import _lib
     m, _ = full_fast
     B, N, T, L = shape
     inp = synth.make_inputs(synth.DEFAULT_MODEL_CFG, B, N, T, L, 17)
     obj, lang = torch.from_numpy(inp["object_tokens"]).cuda(), torch.from_numpy(inp["lang_tokens"]).cuda()
     outs = []
-    try:
-        for v in (0, 1):
-            _lib.check(_lib.lib().sola_tune(b"lang_shared_neg", v), "tune")
-            with torch.no_grad():
-                sm, tok = m(obj, lang)
-            outs.append((sm.clone(), tok.clone()))
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"lang_shared_neg", 1), "tune")
+    for v in (0, 1):
+        with tuned(lang_shared_neg=v), torch.no_grad():
+            sm, tok = m(obj, lang)
+        outs.append((sm.clone(), tok.clone()))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])

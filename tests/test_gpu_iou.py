@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import iou_oracle  # noqa: E402
 from sola_amd import seg_utils  # noqa: E402
+from sola_amd._lib import tuned  # noqa: E402
 
 
 def unpack(a, w):
@@ -116,8 +117,6 @@ def test_fused_one_launch_path_equals_pack_and_pair(P, R, H, W):
     per-block count rows + a ticket per prompt group, iou.hip); its counts are the oracle's and the three-kernel path's, including
     empty masks, a mask equal to its partner, a last chunk that is mostly out of range (1080 x 1920: 127 chunks; 8 x 4: one word)
     and prompt counts that leave the last group ragged."""
-    from sola_amd import _lib
-
     rng = np.random.default_rng(P * 1000 + R)
     A = (rng.uniform(size=(P, H, W)) < 0.3).astype(np.uint8)
     B = (rng.uniform(size=(R, H, W)) < 0.5).astype(np.uint8) * rng.integers(1, 255, size=(R, H, W)).astype(np.uint8)  # any non-zero byte counts
@@ -128,10 +127,9 @@ def test_fused_one_launch_path_equals_pack_and_pair(P, R, H, W):
     ri, ru = iou_oracle.iou_matrix(A, (B != 0).astype(np.uint8))
     outs = []
     for fused in (2, 0):  # 2 = the fused kernel for any R (by default it serves calls with up to 32 prompts)
-        _lib.check(_lib.lib().sola_tune(b"iou_fused", fused), "sola_tune")
-        inter, union = seg_utils.mask_iou_matrix(cuda(A), cuda(B))
-        outs.append((inter.cpu().numpy(), union.cpu().numpy()))
-    _lib.check(_lib.lib().sola_tune(b"iou_fused", 1), "sola_tune")
+        with tuned(iou_fused=fused):
+            inter, union = seg_utils.mask_iou_matrix(cuda(A), cuda(B))
+            outs.append((inter.cpu().numpy(), union.cpu().numpy()))
     for inter, union in outs:
         np.testing.assert_array_equal(inter, ri)
         np.testing.assert_array_equal(union, ru)
@@ -147,8 +145,6 @@ def test_packed_pair_words_at_the_largest_counts(R):
     fields, an atomic add that returns the old word; sola_tune "iou_packed" 0 = the ticket form).  540 x 960 = 518 400 pixels is 1.1 % below
     the field's range: all-ones masks put every field at its largest value; and the two forms agree on random masks, call after call (the
     words go back to zero)."""
-    from sola_amd import _lib
-
     H, W = 540, 960
     rng = np.random.default_rng(R)
     A = np.ones((4, H, W), np.uint8)
@@ -159,30 +155,24 @@ def test_packed_pair_words_at_the_largest_counts(R):
     ri, ru = iou_oracle.iou_matrix(A, B)
     assert ri.max() == H * W
     for packed in (1, 0, 1):
-        _lib.check(_lib.lib().sola_tune(b"iou_packed", packed), "sola_tune")
-        try:
+        with tuned(iou_packed=packed):
             for _ in range(3):
                 inter, union = seg_utils.mask_iou_matrix(cuda(A), cuda(B))
                 np.testing.assert_array_equal(inter.cpu().numpy(), ri)
                 np.testing.assert_array_equal(union.cpu().numpy(), ru)
-        finally:
-            _lib.check(_lib.lib().sola_tune(b"iou_packed", 1), "sola_tune")
 
 
 def test_one_launch_kernel_on_two_streams_at_once():
     """The one-launch kernel's tickets live in the library (a ring range per launch): calls in flight on two streams at the same
     time take disjoint ranges - 200 interleaved calls of different sizes, every result equal to the pack + pair path's."""
-    from sola_amd import _lib
-
     rng = np.random.default_rng(7)
     sets = []
     for R in (16, 70):
         A = (rng.uniform(size=(4, 540, 960)) < 0.3).astype(np.uint8)
         B = (rng.uniform(size=(R, 540, 960)) < 0.4).astype(np.uint8)
         a, b = cuda(A), cuda(B)
-        _lib.check(_lib.lib().sola_tune(b"iou_fused", 0), "sola_tune")
-        ref = seg_utils.mask_iou_matrix(a, b)
-        _lib.check(_lib.lib().sola_tune(b"iou_fused", 1), "sola_tune")
+        with tuned(iou_fused=0):
+            ref = seg_utils.mask_iou_matrix(a, b)
         sets.append((a, b, ref))
     torch.cuda.synchronize()
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
@@ -203,16 +193,13 @@ def test_one_launch_kernel_on_two_streams_at_once():
 def test_lds_staged_resample_pack_equals_per_pixel_pack(dtype, h, w, H, W):
     """The LDS-staged nearest-resample pack (rows of any alignment, uint8 and float32 sources, sources wider than its LDS rows
     fall back) writes the bits and areas of the per-pixel kernel, which the ATen index maps of the fixture pin."""
-    from sola_amd import _lib
-
     rng = np.random.default_rng(h + w)
     src = ((rng.uniform(size=(3, h, w)) < 0.4) * rng.integers(1, 200, size=(3, h, w))).astype(dtype)
     outs = []
     for lds in (2, 0):  # 2 = the LDS-staged kernel for every source width (by default unaligned rows keep the gather kernel)
-        _lib.check(_lib.lib().sola_tune(b"pack_resample_lds", lds), "sola_tune")
-        bits, area = seg_utils.pack_masks(cuda(src), (H, W))
-        outs.append((bits.clone(), area.clone()))
-    _lib.check(_lib.lib().sola_tune(b"pack_resample_lds", 1), "sola_tune")
+        with tuned(pack_resample_lds=lds):
+            bits, area = seg_utils.pack_masks(cuda(src), (H, W))
+            outs.append((bits.clone(), area.clone()))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     ref = iou_oracle.nearest_resize((src != 0).astype(np.uint8), H, W)
     np.testing.assert_array_equal(outs[0][1].cpu().numpy(), ref.reshape(3, -1).sum(axis=1))

@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import sola_oracle  # noqa: E402
 from sola_amd import _lib, ops  # noqa: E402
+from sola_amd._lib import tuned  # noqa: E402
 
 
 def cuda(x):
@@ -57,7 +58,6 @@ def test_gemm_nt_few_rows_shape(M, N, K):
     the split over K inside the block (four waves, wave-private stages, one ordered sum in LDS), no partial sums in memory, no reduce
     launch.  Against float64 at the bound of every f32 GEMM here, and against the 64 x 64 + split-K shape it replaces (sola_tune
     "gemm_small_rows" 0): the same products in another summation order - 2e-6 of the result's norm; twice the same bits."""
-    from sola_amd import _lib
     rng = np.random.default_rng(7 * M + N + K)
     a, w, b, r = rnd(rng, M, K), rnd(rng, N, K, scale=0.05), rnd(rng, N), rnd(rng, M, N)
     ref = a.astype(np.float64) @ w.astype(np.float64).T + b + r
@@ -66,11 +66,8 @@ def test_gemm_nt_few_rows_shape(M, N, K):
     assert torch.equal(got, ops.gemm_nt(cuda(a), cuda(w), cuda(b), cuda(r)))
     plain = ops.gemm_nt(cuda(a), cuda(w))
     assert_close(plain, a.astype(np.float64) @ w.astype(np.float64).T, name="few-row gemm, no bias / residual")
-    try:
-        _lib.check(_lib.lib().sola_tune(b"gemm_small_rows", 0), "tune")
+    with tuned(gemm_small_rows=0):
         old = ops.gemm_nt(cuda(a), cuda(w), cuda(b), cuda(r))
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"gemm_small_rows", 2048), "tune")
     rel = float((got.double() - old.double()).norm() / old.double().norm())
     assert rel < 2e-6, rel
 
@@ -82,7 +79,6 @@ def test_gemm_nn_few_rows_shape(M, N, w_rows, nw, has_res):
     exact-f32 kernel with the weights read in their own row-major layout (sola_gemm_nn: up to three stacked matrices) instead of a
     transposed copy: against float64, and BIT-IDENTICAL to sola_gemm_nt on the transposed, concatenated copy (the same products in the
     same order - the one-sample training step dropped its 49 weight transpositions for this)."""
-    from sola_amd import _lib
     from sola_amd._lib import check, current_stream, lib, ptr
     K = w_rows * nw
     rng = np.random.default_rng(M + N + K + nw)
@@ -125,17 +121,13 @@ def test_gemm_nt_persistent_f32_kernel(M, N, K, has_res):
     buffer-load DMA with scalar offsets, no vector arithmetic in the k-loop.  Same products in the same order as the 128 x 128 one-tile
     kernel (sola_tune "gemm_f32_persist" 0): BIT-identical, interior and edge tiles (rows past M, columns past N), with bias and residual;
     against float64 on sampled rows; twice the same bits."""
-    from sola_amd import _lib
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     a = torch.randn(M, K, device="cuda", generator=g); w = torch.randn(N, K, device="cuda", generator=g) * 0.05
     b = torch.randn(N, device="cuda", generator=g); r = torch.randn(M, N, device="cuda", generator=g) if has_res else None
     got = ops.gemm_nt(a, w, b, r)
     assert torch.equal(got, ops.gemm_nt(a, w, b, r))
-    try:
-        _lib.check(_lib.lib().sola_tune(b"gemm_f32_persist", 0), "tune")
+    with tuned(gemm_f32_persist=0):
         old = ops.gemm_nt(a, w, b, r)
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"gemm_f32_persist", 1), "tune")
     assert torch.equal(got, old)
     rows = torch.tensor([0, 1, 255, 256, M // 2, M - 257, M - 2, M - 1], device="cuda")
     ref = a[rows].double() @ w.double().t() + b.double() + (r[rows].double() if has_res else 0.0)
@@ -146,16 +138,12 @@ def test_gemm_nt_persistent_f32_kernel(M, N, K, has_res):
 def test_conv1d_cl_persistent_f32_kernel(R, T, cin, cout, k, s, p):
     """The persistent kernel's conv rows (window start from the geometry, taps outside the sequence as out-of-range offsets that come back as
     zeros): bit-identical to the one-tile kernel's gather, and against the float64 oracle on the first sequences."""
-    from sola_amd import _lib
     g = torch.Generator(device="cuda").manual_seed(R + T + cin)
     x = torch.randn(R, T, cin, device="cuda", generator=g); wk = torch.randn(cout, k * cin, device="cuda", generator=g) * 0.05
     b = torch.randn(cout, device="cuda", generator=g)
     got = ops.conv1d_cl(x, wk, b, k, s, p)
-    try:
-        _lib.check(_lib.lib().sola_tune(b"gemm_f32_persist", 0), "tune")
+    with tuned(gemm_f32_persist=0):
         old = ops.conv1d_cl(x, wk, b, k, s, p)
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"gemm_f32_persist", 1), "tune")
     assert torch.equal(got, old)
     w3 = wk[:, :].reshape(cout, k, cin).permute(0, 2, 1).contiguous()
     ref = sola_oracle.conv1d_cl(x[:4].double().cpu(), w3.double().cpu(), b.double().cpu(), s, p)
@@ -167,18 +155,14 @@ def test_gemm_tn_persistent_f32_kernel(M, N, K, wb):
     """Round 5 (gemm_tn_f32p.hip): the exact-f32 weight gradient dW = dY^T X as a persistent direct-to-LDS kernel over (256 x 128 tile, row
     split) work items - buffer-load DMA, fragments read across the columns, partial sums folded in split order - with the bias gradient as
     a column-sum pass of its own.  Against float64 (on 64 output rows) at the one-tile kernel's own distance from it, twice the same bits."""
-    from sola_amd import _lib
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     a = torch.randn(M, N, device="cuda", generator=g); b = torch.randn(M, K, device="cuda", generator=g)
     got = ops.gemm_tn(a, b, wb)
     again = ops.gemm_tn(a, b, wb)
     dw = got[0] if wb else got
     assert torch.equal(dw, again[0] if wb else again)
-    try:
-        _lib.check(_lib.lib().sola_tune(b"gemm_tn_persist", 0), "tune")
+    with tuned(gemm_tn_persist=0):
         old = ops.gemm_tn(a, b, wb)
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"gemm_tn_persist", 1), "tune")
     dw_old = old[0] if wb else old
     ref = (a[:, :64].double().t() @ b.double()).float()
     e_new, e_old = float((dw[:64] - ref).abs().max()), float((dw_old[:64] - ref).abs().max())
@@ -216,7 +200,6 @@ def test_conv1d_cl(R, T, cin, cout, k, s, p):
 def test_conv1d_cl_few_rows_shape(R, T, cin, cout, k, s, p):
     """The few-row GEMM's conv gather (gemm_nt_f32_small_kernel<., true>: a window = first tap's address + valid-tap bits, zeros outside the
     sequence) against the float64 oracle, and against the 64 x 64 + split-K kernel's gather (sola_tune "gemm_small_rows" 0) at 2e-6."""
-    from sola_amd import _lib
     rng = np.random.default_rng(R * T + cin + cout)
     x, w, b = rnd(rng, R, T, cin), rnd(rng, cout, cin, k, scale=0.1), rnd(rng, cout)
     ref = sola_oracle.conv1d_cl(torch.tensor(x, dtype=torch.float64), torch.tensor(w, dtype=torch.float64),
@@ -224,11 +207,8 @@ def test_conv1d_cl_few_rows_shape(R, T, cin, cout, k, s, p):
     wk = np.ascontiguousarray(np.transpose(w, (0, 2, 1)).reshape(cout, k * cin))
     got = ops.conv1d_cl(cuda(x), cuda(wk), cuda(b), k, s, p)
     assert_close(got, ref.numpy(), name="few-row conv")
-    try:
-        _lib.check(_lib.lib().sola_tune(b"gemm_small_rows", 0), "tune")
+    with tuned(gemm_small_rows=0):
         old = ops.conv1d_cl(cuda(x), cuda(wk), cuda(b), k, s, p)
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"gemm_small_rows", 2048), "tune")
     assert float((got.double() - old.double()).norm() / old.double().norm()) < 2e-6
 
 
@@ -281,9 +261,8 @@ def _attn_ref(q, k, v, H):
 def attn_reg_mode(request):
     """sola_tune attn_reg: 1 = default routing (register-only shape up to its key limit), 0 = LDS shapes only, 2 = register-only
     shape for every key count (online softmax over 64-key passes)."""
-    _lib.check(_lib.lib().sola_tune(b"attn_reg", request.param), "sola_tune")
-    yield request.param
-    _lib.check(_lib.lib().sola_tune(b"attn_reg", 1), "sola_tune")
+    with tuned(attn_reg=request.param):
+        yield request.param
 
 
 @pytest.mark.parametrize("B,N,Tp,D", [(2, 5, 3, 128), (1, 64, 4, 1024), (2, 80, 1, 1024), (1, 7, 16, 128), (1, 130, 2, 128),
@@ -378,11 +357,9 @@ def test_attention_split_math_on_f32_inputs(B, N, Tp):
     k[0, N // 2, 0] = 3.0 * q[0, 1, 0]  # a dominant key in a later tile: forces the rescale
     q64, k64, v64 = (t.astype(np.float64) for t in (q, k, v))
     qc, kc, vc = (cuda(t).reshape(B * N * Tp, D) for t in (q, k, v))
-    _lib.check(_lib.lib().sola_tune(b"attn_stage_split_math", 1), "sola_tune")
-    _lib.check(_lib.lib().sola_tune(b"attn_splitm", 1), "sola_tune")      # both split-math shapes are off by default (measured slower /
-    if _lib.has_experiments():
-        _lib.check(_lib.lib().sola_tune(b"attn_res_splitm", 1), "sola_tune")  # no faster than exact f32): forced here (EXPERIMENTS=1 builds)
-    try:
+    # both split-math shapes are off by default (measured slower / no faster than exact f32): forced here (attn_res.hip's in EXPERIMENTS=1 builds)
+    res_splitm = {"attn_res_splitm": 1} if _lib.has_experiments() else {}
+    with tuned(attn_stage_split_math=1, attn_splitm=1, **res_splitm):
         tr = lambda t: np.transpose(t, (0, 2, 1, 3)).reshape(B * Tp, N, D)
         ref = _attn_ref(tr(q64), tr(k64), tr(v64), H).reshape(B, Tp, N, D).transpose(0, 2, 1, 3)
         got = ops.attention(qc, kc, vc, B * Tp, H, N, N, Tp, (N * Tp, 1, Tp), (N * Tp, 1, Tp))
@@ -397,11 +374,6 @@ def test_attention_split_math_on_f32_inputs(B, N, Tp):
             ref = _attn_ref(q64.reshape(B, N * Tp, D), lk.astype(np.float64), lv.astype(np.float64), H).reshape(B, N, Tp, D)
             got = ops.attention(qc, cuda(lk).reshape(B * Wn, D), cuda(lv).reshape(B * Wn, D), B, H, N * Tp, Wn, 1, (N * Tp, 0, 1), (Wn, 0, 1))
             assert_close(got.reshape(B, N, Tp, D), ref, rel=2e-5, name=f"o2l attention (split math) W={Wn}")
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"attn_stage_split_math", 0), "sola_tune")
-        _lib.check(_lib.lib().sola_tune(b"attn_splitm", 0), "sola_tune")
-        if _lib.has_experiments():
-            _lib.check(_lib.lib().sola_tune(b"attn_res_splitm", 0), "sola_tune")
 
 
 @pytest.mark.parametrize("bf16", [False, True])
@@ -411,7 +383,6 @@ def test_weight_gradient_gemm_on_row_major_16bit_operands(shape, bf16):
     gemm_tn_tr_kernel transposes them in the LDS read (ds_read_b64_tr_b16) - no transposed copies; other shapes (264
     here) and sola_tune train_tn_tr 0 take the transposing casts + NT GEMM.  Both against the f64 product of the same rounded
     operands (the f32 accumulation order is all that differs), ragged row counts included (rows beyond M read the zero page)."""
-    from sola_amd import _lib
     M, N, K = shape
     torch.manual_seed(11)
     a = torch.randn(M, N, device="cuda") * 1e-4
@@ -419,24 +390,18 @@ def test_weight_gradient_gemm_on_row_major_16bit_operands(shape, bf16):
     dt = torch.bfloat16 if bf16 else torch.float16
     sc = 2.0 ** (13 - int(torch.floor(torch.log2(a.abs().max())).item()))  # cast.hip's data-dependent power-of-two scale
     ref = ((a * sc).to(dt).double().t() @ b.to(dt).double()) / sc
-    try:
-        # (bf16, sola_tune "train_bf16_store" 3 - the default: the row-major kernel's split-K partial sums leave as bfloat16 slabs, folded in
-        # f32; checked below.  The f32-accumulation statement is made at level 2.)
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 2), "tune")
+    # (bf16, sola_tune "train_bf16_store" 3 - the default: the row-major kernel's split-K partial sums leave as bfloat16 slabs, folded in
+    # f32; checked below.  The f32-accumulation statement is made at level 2.)
+    with tuned(train_bf16_store=2):
         for route in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"train_tn_tr", route), "tune")
-            out = ops.gemm_tn_f16(a, b, bf16)
-            err = float((out.double() - ref).abs().max() / ref.abs().max())
-            assert err < 5e-6, (route, err)
-        _lib.check(_lib.lib().sola_tune(b"train_tn_tr", 1), "tune")
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 3), "tune")
-        if bf16:  # each of the (at most 16) partial sums rounded to bfloat16: 2^-9 of its own size, summed in f32
-            out = ops.gemm_tn_f16(a, b, bf16)
-            err = float((out.double() - ref).abs().max() / ref.abs().max())
-            assert err < 2.0 ** -7, err
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"train_tn_tr", 1), "tune")
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 3), "tune")
+            with tuned(train_tn_tr=route):
+                out = ops.gemm_tn_f16(a, b, bf16)
+                err = float((out.double() - ref).abs().max() / ref.abs().max())
+                assert err < 5e-6, (route, err)
+    if bf16:  # each of the (at most 16) partial sums rounded to bfloat16: 2^-9 of its own size, summed in f32
+        out = ops.gemm_tn_f16(a, b, bf16)
+        err = float((out.double() - ref).abs().max() / ref.abs().max())
+        assert err < 2.0 ** -7, err
 
 
 @pytest.mark.parametrize("geom", [(512, 32, 256, 512, 3, 2, 1), (300, 16, 512, 512, 3, 2, 1), (1024, 4, 512, 1024, 3, 1, 1), (77, 9, 256, 256, 5, 1, 2)])
@@ -444,7 +409,6 @@ def test_conv_weight_gradient_on_row_major_16bit_operands(geom):
     """sola_conv1d_cl_wgrad_f16: the encoder convs' dW on f16 operands.  gemm_tn_tr_kernel gathers the taps (implicit im2col, zero
     padding in time, strides) in its DMA addresses from ONE row-major cast of the conv input; sola_tune train_tn_tr 0 = one transposing
     cast per tap + the NT GEMM.  Both against the f64 product of the same rounded operands over an explicit im2col."""
-    from sola_amd import _lib
     R, T, cin, cout, k, stride, pad = geom
     torch.manual_seed(13)
     x = torch.randn(R, T, cin, device="cuda")
@@ -454,14 +418,11 @@ def test_conv_weight_gradient_on_row_major_16bit_operands(geom):
     xp = torch.nn.functional.pad(x.half().double(), (0, 0, pad, pad))
     cols = torch.stack([xp[:, kk:kk + (t_out - 1) * stride + 1:stride, :] for kk in range(k)], dim=2).reshape(R * t_out, k * cin)
     ref = ((dy * sc).half().double().reshape(R * t_out, cout).t() @ cols) / sc
-    try:
-        for route in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"train_tn_tr", route), "tune")
+    for route in (1, 0):
+        with tuned(train_tn_tr=route):
             out = ops.conv1d_cl_wgrad_f16(x, dy, k, stride, pad)
             err = float((out.double() - ref).abs().max() / ref.abs().max())
             assert err < 5e-6, (route, err)
-    finally:
-        _lib.check(_lib.lib().sola_tune(b"train_tn_tr", 1), "tune")
 
 
 def test_profiler_category_mask():
@@ -495,37 +456,31 @@ def test_experimental_k16_gemm_is_bit_identical():
     from sola_amd.module import LanguageAlignedTrackSelectionModule
     if not _lib.has_experiments():
         pytest.skip("closed experiment: compiled in EXPERIMENTS=1 builds of the library only (make -C sola_amd/csrc EXPERIMENTS=1)")
-    lib = _lib.lib()
     torch.manual_seed(5)
-    try:
-        _lib.check(lib.sola_tune(b"gemm_glds", 4), "tune")
+    with tuned(gemm_glds=4):
         for (M, N, K, res, osp) in [(16384, 1024, 1024, 0, 0), (16384, 1024, 1024, 1, 0), (16384, 1024, 768, 1, 1), (16384 - 77, 1024, 512, 1, 0),
                                     (16384, 1024 - 8, 256, 0, 1), (32768, 512, 32, 0, 0), (32768, 512, 96, 1, 1)]:
             a = ops.cast_sp16(torch.randn(M, K, device="cuda")); w = ops.cast_sp16(torch.randn(N, K, device="cuda") * 0.03, 64.0)
             b = torch.randn(N, device="cuda"); r = ops.cast_sp16(torch.randn(M, N, device="cuda")) if res else None
             outs = []
             for on in (0, 1):
-                _lib.check(lib.sola_tune(b"gemm_k16", on), "tune")
-                outs.append(ops.gemm_nt_split(a, w, b, r, True, 1 / 64, bool(osp)).clone())
+                with tuned(gemm_k16=on):
+                    outs.append(ops.gemm_nt_split(a, w, b, r, True, 1 / 64, bool(osp)).clone())
             assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), (M, N, K, res, osp)
-        _lib.check(lib.sola_tune(b"gemm_glds", 3), "tune")
-        cfg = synth.DEFAULT_MODEL_CFG
-        sd = synth.make_state_dict(cfg, 42)
-        m = LanguageAlignedTrackSelectionModule(cfg)
-        m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()})
-        m = m.cuda().eval()
-        inp = synth.make_inputs(cfg, 16, 64, 32, 16, 0)
-        ot, lt = torch.from_numpy(inp["object_tokens"]).cuda(), torch.from_numpy(inp["lang_tokens"]).cuda()
-        got = []
-        for on in (0, 1):
-            _lib.check(lib.sola_tune(b"gemm_k16", on), "tune")
+    cfg = synth.DEFAULT_MODEL_CFG
+    sd = synth.make_state_dict(cfg, 42)
+    m = LanguageAlignedTrackSelectionModule(cfg)
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()})
+    m = m.cuda().eval()
+    inp = synth.make_inputs(cfg, 16, 64, 32, 16, 0)
+    ot, lt = torch.from_numpy(inp["object_tokens"]).cuda(), torch.from_numpy(inp["lang_tokens"]).cuda()
+    got = []
+    for on in (0, 1):
+        with tuned(gemm_k16=on):
             with torch.no_grad():
                 sm, st = m(ot, lt)
             got.append((sm.clone(), st.clone()))
-        assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
-    finally:
-        _lib.check(lib.sola_tune(b"gemm_k16", 0), "tune")
-        _lib.check(lib.sola_tune(b"gemm_glds", 3), "tune")
+    assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
 
 
 @pytest.mark.parametrize("key", ["gemm_nw4", "gemm_pp"])
@@ -537,23 +492,18 @@ def test_experimental_four_wave_gemm_kernels_are_bit_identical(key, out_split):
     from sola_amd import _lib
     if not _lib.has_experiments():
         pytest.skip("closed experiment: compiled in EXPERIMENTS=1 builds of the library only (make -C sola_amd/csrc EXPERIMENTS=1)")
-    lib = _lib.lib()
     torch.manual_seed(3)
     outs = {}
     try:
-        _lib.check(lib.sola_tune(b"gemm_glds", 4), "tune")  # the 256x256 family whatever the grid
-        for M, N, K in ((65536, 512, 768), (16384, 1024, 1024)):  # 4 and 2 tiles per CU: the draining k-tiles and the final drain both run
-            x = torch.randn(M, K, device="cuda"); wt = torch.randn(N, K, device="cuda") * 0.03; b = torch.randn(N, device="cuda")
-            a, w = ops.cast_sp16(x), ops.cast_sp16(wt, 64.0)
-            for on in (0, 1):
-                _lib.check(lib.sola_tune(key.encode(), on), "tune")
-                _lib.check(lib.sola_tune(b"gemm_glds_force", 1), "tune")
-                _lib.profile_enable(True)
-                outs[on] = ops.gemm_nt_split(a, w, b, out_scale=1 / 64, out_split=out_split).clone()
-            assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), (M, N, K)
-        assert _lib.profile_read(reset=True)["gemm_split256"]["launches"] == 4  # all four launches took the 256-row kernels
+        with tuned(gemm_glds=4):  # the 256x256 family whatever the grid
+            for M, N, K in ((65536, 512, 768), (16384, 1024, 1024)):  # 4 and 2 tiles per CU: the draining k-tiles and the final drain both run
+                x = torch.randn(M, K, device="cuda"); wt = torch.randn(N, K, device="cuda") * 0.03; b = torch.randn(N, device="cuda")
+                a, w = ops.cast_sp16(x), ops.cast_sp16(wt, 64.0)
+                for on in (0, 1):
+                    with tuned(**{key: on}, gemm_glds_force=1):
+                        _lib.profile_enable(True)
+                        outs[on] = ops.gemm_nt_split(a, w, b, out_scale=1 / 64, out_split=out_split).clone()
+                assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), (M, N, K)
+            assert _lib.profile_read(reset=True)["gemm_split256"]["launches"] == 4  # all four launches took the 256-row kernels
     finally:
         _lib.profile_enable(False)
-        _lib.check(lib.sola_tune(key.encode(), 0), "tune")
-        _lib.check(lib.sola_tune(b"gemm_glds_force", 0), "tune")
-        _lib.check(lib.sola_tune(b"gemm_glds", 3), "tune")

@@ -235,12 +235,9 @@ def test_float_images_that_are_not_binary_keep_aten_arithmetic(su, staged):
     """elem_type float32 with values outside {0,1}: the `> 0.5` mask equals the oracle's float resample (ATen's rule),
     also when only ONE pixel of the image is soft - with the direct kernel (default for float sources) and with the
     LDS-staged one, whose blocks fall back to float taps when they meet a non-binary value."""
-    from sola_amd import _lib
-    _lib.lib().sola_tune(b"bilinear_staged", staged)
-    try:
+    from sola_amd._lib import tuned
+    with tuned(bilinear_staged=staged):
         _soft_mask_checks(su)
-    finally:
-        _lib.lib().sola_tune(b"bilinear_staged", 1)
 
 
 def _soft_mask_checks(su):

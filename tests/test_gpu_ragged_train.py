@@ -19,6 +19,7 @@ from conftest import _load  # noqa: E402
 
 from conftest import case_dict  # noqa: E402,F401
 from sola_amd import SolaError, _lib, synth  # noqa: E402
+from sola_amd._lib import tuned  # noqa: E402
 from sola_amd.loss import track_selection_losses, track_selection_losses_ragged  # noqa: E402
 from sola_amd.module import LanguageAlignedTrackSelectionModule  # noqa: E402
 
@@ -47,9 +48,8 @@ def full():
 @pytest.fixture(autouse=True)
 def no_size_gate():
     """the test batches are below the production size gate of the reduced-precision training GEMMs"""
-    _lib.check(_lib.lib().sola_tune(b"train_split_min_rows", 0), "tune")
-    yield
-    _lib.check(_lib.lib().sola_tune(b"train_split_min_rows", 1024), "tune")
+    with tuned(train_split_min_rows=0):
+        yield
 
 
 def sample_inputs(cfg, N, T, L, seed):
@@ -220,30 +220,28 @@ def test_kept_operand_casts_give_the_same_ragged_gradients_bit_for_bit(full, pre
     full.precision = precision
     got = {}
     try:
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 1), "tune")
-        samples = [sample_inputs(cfg, N, T, L, 400 + i) for i, (N, T, L) in enumerate(FULL_SHAPES)]
-        for keep in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"train_x16_keep", keep), "tune")
-            full.release_x16_arena()
-            for _ in range(2):  # the arena is sized from the previous step's need: the second step reuses the casts
-                loss, g, _ = ragged_step(full, samples)
-            got[keep] = (g, loss)
-            if keep:  # round 4: the arena is a torch tensor of the module (sola_set_x16_arena), 1/8 above what the first step asked for
-                assert full.x16_arena_bytes() > 0
-                held = full.x16_arena_bytes()
-                full.x16_arena_max_bytes = 1 << 20  # a cap below the need: the arena is not grown past it, the backward casts what did not fit
-                full.release_x16_arena()
-                for _ in range(2):
-                    loss_c, g_c, _ = ragged_step(full, samples)
-                assert 0 < full.x16_arena_bytes() <= (1 << 20) < held
-                assert torch.equal(loss_c, loss) and all(torch.equal(g_c[k], g[k]) for k in g)
-                full.x16_arena_max_bytes = None
-            else:
-                assert full.x16_arena_bytes() == 0  # nothing is kept, nothing is asked for
+        with tuned(train_bf16_store=1):
+            samples = [sample_inputs(cfg, N, T, L, 400 + i) for i, (N, T, L) in enumerate(FULL_SHAPES)]
+            for keep in (1, 0):
+                with tuned(train_x16_keep=keep):
+                    full.release_x16_arena()
+                    for _ in range(2):  # the arena is sized from the previous step's need: the second step reuses the casts
+                        loss, g, _ = ragged_step(full, samples)
+                    got[keep] = (g, loss)
+                    if keep:  # round 4: the arena is a torch tensor of the module (sola_set_x16_arena), 1/8 above what the first step asked for
+                        assert full.x16_arena_bytes() > 0
+                        held = full.x16_arena_bytes()
+                        full.x16_arena_max_bytes = 1 << 20  # a cap below the need: the arena is not grown past it, the backward casts what did not fit
+                        full.release_x16_arena()
+                        for _ in range(2):
+                            loss_c, g_c, _ = ragged_step(full, samples)
+                        assert 0 < full.x16_arena_bytes() <= (1 << 20) < held
+                        assert torch.equal(loss_c, loss) and all(torch.equal(g_c[k], g[k]) for k in g)
+                        full.x16_arena_max_bytes = None
+                    else:
+                        assert full.x16_arena_bytes() == 0  # nothing is kept, nothing is asked for
     finally:
         full.precision = "f32"
-        _lib.check(_lib.lib().sola_tune(b"train_x16_keep", 1), "tune")
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 3), "tune")
     assert torch.equal(got[1][1], got[0][1])
     bad = [k for k in got[1][0] if not torch.equal(got[1][0][k], got[0][0][k])]
     assert not bad, bad
@@ -258,16 +256,14 @@ def test_bf16_statistics_pass_that_is_the_cast_gives_the_same_ragged_gradients_b
     full.precision = "bf16"
     got = {}
     try:
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 0), "tune")
-        samples = [sample_inputs(cfg, N, T, L, 450 + i) for i, (N, T, L) in enumerate(FULL_SHAPES)]
-        for fused in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"bwd_fused_bf16_cast", fused), "tune")
-            loss, g, _ = ragged_step(full, samples)
-            got[fused] = (g, loss)
+        with tuned(train_bf16_store=0):
+            samples = [sample_inputs(cfg, N, T, L, 450 + i) for i, (N, T, L) in enumerate(FULL_SHAPES)]
+            for fused in (1, 0):
+                with tuned(bwd_fused_bf16_cast=fused):
+                    loss, g, _ = ragged_step(full, samples)
+                    got[fused] = (g, loss)
     finally:
         full.precision = "f32"
-        _lib.check(_lib.lib().sola_tune(b"bwd_fused_bf16_cast", 1), "tune")
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 3), "tune")
     assert torch.equal(got[1][1], got[0][1])
     bad = [k for k in got[1][0] if not torch.equal(got[1][0][k], got[0][0][k])]
     assert not bad, bad
@@ -288,19 +284,17 @@ def test_attention_written_operand_casts_give_the_same_ragged_step_bit_for_bit(f
     try:
         # (bf16, train_bf16_store 3: where the attention kernel writes the bf16 rows itself it writes ONLY them, and D = dO . O sees the rounded
         # rows - a different, equally valid step; this A/B is about the cast's route, so it runs at level 2)
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 2), "tune")
-        samples = [sample_inputs(cfg, N, T, L, 450 + i) for i, (N, T, L) in enumerate(FULL_SHAPES)]
-        for fold in (2, 0):  # 2: the split-f16 step too (1, the default, covers the f16 / bf16 operand steps only)
-            _lib.check(_lib.lib().sola_tune(b"train_attn_cast", fold), "tune")
-            torch.manual_seed(1234)  # the dropout masks' seeds come from torch's CPU generator: the same two masks for both settings
-            for _ in range(2):
-                loss, g, _ = ragged_step(full, samples)
-            got[fold] = (g, loss)
+        with tuned(train_bf16_store=2):
+            samples = [sample_inputs(cfg, N, T, L, 450 + i) for i, (N, T, L) in enumerate(FULL_SHAPES)]
+            for fold in (2, 0):  # 2: the split-f16 step too (1, the default, covers the f16 / bf16 operand steps only)
+                with tuned(train_attn_cast=fold):
+                    torch.manual_seed(1234)  # the dropout masks' seeds come from torch's CPU generator: the same two masks for both settings
+                    for _ in range(2):
+                        loss, g, _ = ragged_step(full, samples)
+                    got[fold] = (g, loss)
     finally:
         full.precision = "f32"
         full.train(was_training)
-        _lib.check(_lib.lib().sola_tune(b"train_attn_cast", 1), "tune")
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 3), "tune")
     assert torch.equal(got[2][1], got[0][1])
     bad = [k for k in got[2][0] if not torch.equal(got[2][0][k], got[0][0][k])]
     assert not bad, bad
@@ -318,17 +312,15 @@ def test_row_major_weight_gradient_route_equals_the_transposed_copy_route_on_a_r
     try:
         # (round 6: the bf16 step's q / k / v storage exists on the row-major route only - there is no f32 gradient to transpose - so it is
         # switched off for this A/B of the two dW routes on the SAME operand values)
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 0), "tune")
-        samples = [sample_inputs(cfg, N, T, L, 500 + i) for i, (N, T, L) in enumerate(FULL_SHAPES)]
-        for route in (1, 0):
-            _lib.check(_lib.lib().sola_tune(b"train_tn_tr", route), "tune")
-            for _ in range(2):
-                loss, g, _ = ragged_step(full, samples)
-            got[route] = g
+        with tuned(train_bf16_store=0):
+            samples = [sample_inputs(cfg, N, T, L, 500 + i) for i, (N, T, L) in enumerate(FULL_SHAPES)]
+            for route in (1, 0):
+                with tuned(train_tn_tr=route):
+                    for _ in range(2):
+                        loss, g, _ = ragged_step(full, samples)
+                    got[route] = g
     finally:
         full.precision = "f32"
-        _lib.check(_lib.lib().sola_tune(b"train_tn_tr", 1), "tune")
-        _lib.check(_lib.lib().sola_tune(b"train_bf16_store", 3), "tune")
     worst = max((float((got[1][k].double() - got[0][k].double()).norm()) / (float(got[0][k].double().norm()) + 1e-30), k) for k in got[0])
     print("row-major vs transposed-copy dW route, worst tensor:", worst)
     assert worst[0] < 2e-5, worst

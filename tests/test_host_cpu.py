@@ -474,3 +474,152 @@ def test_collated_ragged_batches_are_read_where_they_lie():
     assert _rows_of([v[1], v[0]], 4).data_ptr() != v[1].data_ptr()  # out of order
     half = [t.double() for t in v]
     assert _rows_of(half, 4).dtype == torch.float32
+
+
+# ---- sola_tune: one table of keys (sola_amd/csrc/tune.h), read back through sola_tune_query, borrowed through _lib.tuned
+# The keys and defaults below are written out from the sola_tune chain and the globals' initialisers as they stood before the table
+# existed.  They are the pin that no key left and no default moved; tests and tools ask tune_default() instead of repeating them.
+TUNE_DEFAULTS = {
+    "attn_stage_split_math": 0, "gemm_variant": -1, "gemm_glds": 3, "bwd_side_rows": 0, "bwd_group_rows": 2048, "lang_shared_neg": 1,
+    "train_tn_tr": 1, "train_x16_keep": 1, "train_attn_cast": 1,
+    "gemm_splitk": 512,  # g_gemm_splitk = 1 with g_gemm_splitk_tiles = 512: on, reported as the threshold (tune.h)
+    "gemm_splitk_max": 8, "gemm_small_rows": 2048, "infer_f32_rows": 4096, "gemm_small_nw8": 1, "gemm_f32_nw8": 1, "gemm_f32_persist": 1,
+    "gemm_tn_nw8": 1, "gemm_tn_persist": 1, "gemm_glds_force": 0, "train_split_min_rows": 1024, "gemm_persist": 1, "gn_variant": 1,
+    "bilinear_staged": 1, "attn_variant": 1, "attn_target_blocks": 512, "iou_fused": 1, "iou_shape": 0, "train_bf16_store": 3,
+    "attn_bf16_mfma": 1, "attn_bwd_bf16_mfma": 1, "train_gn_stats": 1, "gemm_slack_stagger": 40, "iou_packed": 1, "attn_split_min_keys": 96,
+    "attn_splitm": 0, "attn_reg": 1, "attn_res": 1, "attn_res_tiles": 0, "attn_res_shape": 0, "attn_bwd_small": 1, "attn_bwd_blk": 1,
+    "attn_bwd_rag_wave": 96, "attn_bwd_fused": 1, "attn_f16_small": 1, "gn_h8": 1,
+    "attn_spin": 1,  # g_attn_spin = 1, g_attn_spin_db = 1
+    "train_dw_f16": 1, "train_gn_cast": 1, "attn_simple_train": 1, "gn_bwd_reg": 1, "gn_slices": 1, "gn_wide": 1, "bwd_dual_cast": 1,
+    "attn_f16_qpb": 4, "bwd_fused_bf16_cast": 1, "attn_simple_remap": 0, "attn_simple_db": 1, "pack_resample_lds": 1,
+}
+TUNE_EXPERIMENT_DEFAULTS = {
+    "gemm_f32p_ablate": 0, "gemm_pp": 0, "gemm_nw4": 0, "gemm_k16": 0, "gemm_stagger": 0, "gemm_order": 0, "gemm_trace": 0, "gemm_ld": 0,
+    "gemm_ablate": 0, "attn_reg_minw": 2, "attn_res_splitm": 0, "attn_ring": 0, "attn_ring_blocks": 2, "attn_ring_remap": 1,
+    "attn_ring_ablate": 0, "attn_bwd_ablate": 0, "gemm_gn_fuse": 0,
+}
+TUNE_SPECIAL = ["attn_spin", "gemm_splitk", "gemm_splitk_max", "attn_f16_qpb", "attn_res_tiles", "attn_ring_blocks", "attn_stage_split_math"]
+TUNE_ARGS = (-1, 0, 1, 2, 64)
+
+
+def _tune_table():
+    assert len(TUNE_DEFAULTS) == 58 and len(TUNE_EXPERIMENT_DEFAULTS) == 17
+    return {**TUNE_DEFAULTS, **(TUNE_EXPERIMENT_DEFAULTS if _lib.has_experiments() else {})}
+
+
+def _tune_keys_of_the_build():
+    h, keys = _lib.lib(), []
+    while h.sola_tune_key(len(keys)) is not None:
+        keys.append(h.sola_tune_key(len(keys)).decode())
+    return keys
+
+
+def test_tune_keys_are_the_ones_sola_tune_always_had():
+    keys = _tune_keys_of_the_build()
+    assert keys == list(_tune_table()), set(keys) ^ set(_tune_table())
+    assert _lib.lib().sola_tune_key(-1) is None and _lib.lib().sola_tune_key(len(keys) + 5) is None
+
+
+def test_tune_defaults_did_not_move():
+    # (conftest.py holds "infer_f32_rows" at 0 for the session: the default is what the library was loaded with, not the present value)
+    got = {k: _lib.tune_default(k) for k in _tune_table()}
+    assert got == _tune_table(), {k: (v, _tune_table()[k]) for k, v in got.items() if v != _tune_table()[k]}
+
+
+def test_tune_query_hands_back_an_argument_that_changes_nothing():
+    h = _lib.lib()
+    for k in _tune_table():
+        v, d = _lib.tune_query(k)
+        _lib.check(h.sola_tune(k.encode(), v), k)
+        assert _lib.tune_query(k) == (v, d), k
+    import ctypes as C
+    one = C.c_int(-12345)  # either pointer may be null
+    assert h.sola_tune_query(b"gemm_glds", one, None) == 0 and one.value == _lib.tune_query("gemm_glds")[0]
+    assert h.sola_tune_query(b"gemm_glds", None, one) == 0 and one.value == 3
+    assert h.sola_tune_query(b"gemm_glds", None, None) == 0
+
+
+def test_tuned_sets_and_restores_every_key():
+    for k in _tune_table():
+        before = _lib.tune_query(k)
+        for arg in TUNE_ARGS:
+            with _lib.tuned(**{k: arg}):  # (raises if sola_tune rejected the argument)
+                inside = _lib.tune_query(k)[0]
+                if k not in TUNE_SPECIAL:
+                    assert inside == arg, (k, arg, inside)
+            assert _lib.tune_query(k) == before, (k, arg)
+
+
+def test_tuned_nests_on_the_keys_with_a_setter():
+    for k in TUNE_SPECIAL:
+        if k not in _tune_table():
+            continue
+        before = _lib.tune_query(k)
+        for outer in TUNE_ARGS:
+            for inner in TUNE_ARGS:
+                with _lib.tuned(**{k: outer}):
+                    mid = _lib.tune_query(k)
+                    with _lib.tuned(**{k: inner}):
+                        pass
+                    assert _lib.tune_query(k) == mid, (k, outer, inner)
+                assert _lib.tune_query(k) == before, (k, outer, inner)
+
+
+def test_tuned_restores_both_switches_behind_gemm_splitk_and_attn_spin():
+    """The two keys that write two globals: the globals themselves (exported data symbols) return, not only the report.  set(8), set(0),
+    restore, restore is the case the report `on ? tiles : 0` was chosen for."""
+    import ctypes as C
+    h = _lib.lib()
+    state = lambda *names: tuple(C.c_int.in_dll(h, n).value for n in names)  # noqa: E731
+    splitk = ("g_gemm_splitk", "g_gemm_splitk_tiles")
+    first = state(*splitk)
+    assert first == (1, 512)
+    with _lib.tuned(gemm_splitk=8):
+        assert state(*splitk) == (1, 8)
+        with _lib.tuned(gemm_splitk=0):
+            assert state(*splitk) == (0, 8)
+        assert state(*splitk) == (1, 8)
+    assert state(*splitk) == first
+    spin = ("g_attn_spin", "g_attn_spin_db")
+    assert state(*spin) == (1, 1)
+    for outer, s_outer in ((0, (0, 1)), (2, (1, 0)), (1, (1, 1)), (64, (1, 1))):
+        with _lib.tuned(attn_spin=outer):
+            assert state(*spin) == s_outer
+            for inner in (0, 1, 2):
+                with _lib.tuned(attn_spin=inner):
+                    pass
+                assert state(*spin) == s_outer
+        assert state(*spin) == (1, 1)
+
+
+def test_tuned_rejects_an_unknown_key_before_it_changes_anything():
+    before = {k: _lib.tune_query(k) for k in _tune_table()}
+    ran = []
+    with pytest.raises(SolaError, match="unknown key 'no_such_key'"):
+        with _lib.tuned(gemm_glds=1, no_such_key=1, iou_fused=0):
+            ran.append(1)
+    assert not ran and {k: _lib.tune_query(k) for k in _tune_table()} == before
+    assert _lib.lib().sola_tune(b"no_such_key", 1) == -1 and _lib.lib().sola_tune_query(b"no_such_key", None, None) == -1
+    hint = b"EXPERIMENTS=1 builds only" in _lib.lib().sola_last_error()
+    assert hint == (not _lib.has_experiments())
+
+
+def test_tuned_restores_when_its_body_raises():
+    before = (_lib.tune_query("gemm_glds"), _lib.tune_query("attn_spin"))
+    with pytest.raises(ZeroDivisionError):
+        with _lib.tuned(gemm_glds=1, attn_spin=2):
+            assert (_lib.tune_query("gemm_glds")[0], _lib.tune_query("attn_spin")[0]) == (1, 2)
+            1 / 0
+    assert (_lib.tune_query("gemm_glds"), _lib.tune_query("attn_spin")) == before
+
+
+def test_every_tune_key_is_in_the_catalogue():
+    """docs/tune_keys.md names every key in the quoted form, and marks the experiment keys where it introduces them."""
+    doc = open(os.path.join(ROOT, "docs", "tune_keys.md")).read()
+    missing = [k for k in {**TUNE_DEFAULTS, **TUNE_EXPERIMENT_DEFAULTS} if f'"{k}"' not in doc]
+    assert not missing, missing
+    entries = re.split(r"^\* ", doc, flags=re.M)[1:]
+    for k, experiment in [(k, False) for k in TUNE_DEFAULTS] + [(k, True) for k in TUNE_EXPERIMENT_DEFAULTS]:
+        first = next(e for e in entries if f'"{k}"' in e)  # the entry that introduces the key
+        marked = re.search(r'"%s"`? \*\(EXPERIMENTS\)\*' % k, first) is not None
+        assert marked == experiment, (k, first[:80])
