@@ -14,9 +14,15 @@ seg_utils.compute_JF_batch call: every referenced track and GT masklet decoded o
 counted in one launch.  Writes ``<eval_output_dir>/<data_type>_JF_metrics_<K>epoch.json`` as ``{video: {exp_id: {expression,
 J, F, JF}}}`` and adds ``mean_J`` / ``mean_F`` / ``mean_JF`` to track_metrics.json and the printed line; with several ranks
 rank 0 gathers every rank's entries.  J is the mean over frames of inter / union (1.0 for an empty union), F the pixel F1
-over the whole masklet (0.0 without a true positive) - the reference's definition, not the DAVIS boundary F.  Counts are
+over the whole masklet (0.0 without a true positive) - the reference's definition; the DAVIS boundary F is behind
+``--boundary_f`` below.  Counts are
 exact int64 (the reference's float32 sums are exact below 2^24).  An expression without GT ids scores against an all-zero
-ground truth (the reference fails there).  J&F needs mask ground truth: MeViS with a ``mask_dict.json``.  Without it
+ground truth (the reference fails there).  ``--boundary_f true`` (``--boundary_th``, default 0.008) adds the benchmark's
+F: every entry gains ``F_boundary`` (mean over frames of the DAVIS contour F-measure: boundary maps of prediction and
+ground truth, each matched against the other dilated by a disk of ``boundary_th`` of the image diagonal; no void pixels)
+and ``JF_boundary`` = (J + F_boundary) / 2, track_metrics.json and the printed line ``mean_F_boundary`` /
+``mean_JF_boundary`` / ``boundary_th``, from one more launch on the planes the J pass decoded
+(sola_mask_select_boundary_counts).  J&F needs mask ground truth: MeViS with a ``mask_dict.json``.  Without it
 (synthetic data, the MeViS ``valid`` test split, Ref-DAVIS, whose reference GT loader gives every object the last object's
 masks) or with ``--jf false`` one line says why J&F was skipped and the outputs are the loss / track metrics alone.
 
@@ -68,8 +74,9 @@ class SelectionCollector:
             o += n
 
 
-def jf_entries(ds, rows, device):
-    """[(video, expression id, {expression, J, F, JF})] in the order of ``rows``, one compute_JF_batch call per video."""
+def jf_entries(ds, rows, device, boundary=None):
+    """[(video, expression id, {expression, J, F, JF})] in the order of ``rows``, one compute_JF_batch call per video;
+    with ``boundary`` (the DAVIS bound_th) every entry also has F_boundary and JF_boundary."""
     from sola_amd import seg_utils
     by_video = OrderedDict()
     for r in rows:
@@ -94,11 +101,13 @@ def jf_entries(ds, rows, device):
             pred_sets.append([ids[j] for j in np.flatnonzero(sel)])
             gt_sets.append([idx(g) for g in ds.gt_rles(vid, eid)])
             no_tracks.append(not tracks)
-        scores = seg_utils.compute_JF_batch(masklets, pred_sets, gt_sets, device) if masklets else [(0.0, 0.0, 0.0)] * len(rs)
-        for (_, eid, exp, _), (J, F, JF), empty in zip(rs, scores, no_tracks):
+        keys = ("J", "F", "JF") if boundary is None else ("J", "F", "JF", "F_boundary", "JF_boundary")
+        scores = (seg_utils.compute_JF_batch(masklets, pred_sets, gt_sets, device, boundary=boundary) if masklets
+                  else [(0.0,) * len(keys)] * len(rs))
+        for (_, eid, exp, _), score, empty in zip(rs, scores, no_tracks):
             if empty:  # no track files at all: get_sam2_masklet returns None and the evaluator scores 0
-                J = F = JF = 0.0
-            out.append((vid, eid, {"expression": exp, "J": J, "F": F, "JF": JF}))
+                score = (0.0,) * len(keys)
+            out.append((vid, eid, {"expression": exp, **dict(zip(keys, score))}))
     return out
 
 
@@ -122,7 +131,8 @@ def evaluate(cfg):
     m["precision"] = m["tp"] / max(m["tp"] + m["fp"], 1.0)
     m["recall"] = m["tp"] / max(m["tp"] + m["fn"], 1.0)
     if selections is not None:
-        entries = jf_entries(ds, selections.rows, device)
+        boundary = float(cfg.get("boundary_th", 0.008)) if cfg.get("boundary_f", False) else None
+        entries = jf_entries(ds, selections.rows, device, boundary)
         if world > 1:
             gathered = [None] * world
             torch.distributed.all_gather_object(gathered, entries)
@@ -131,8 +141,10 @@ def evaluate(cfg):
             jf = OrderedDict()
             for vid, eid, e in entries:
                 jf.setdefault(vid, OrderedDict())[eid] = e
-            for key in ("J", "F", "JF"):
+            for key in ("J", "F", "JF") + (() if boundary is None else ("F_boundary", "JF_boundary")):
                 m[f"mean_{key}"] = float(np.mean([e[key] for _, _, e in entries])) if entries else 0.0
+            if boundary is not None:
+                m["boundary_th"] = boundary
             name = f"{cfg['dataset']['valid']['data_type']}_JF_metrics_{cfg['eval']['weight_epoch']}epoch.json"
             with open(os.path.join(cfg["results"]["eval_output_dir"], name), "w") as f:
                 json.dump(jf, f, indent=4)

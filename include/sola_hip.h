@@ -510,6 +510,22 @@ int sola_mask_select_counts(const uint32_t* dev_bits, int64_t words_stride, int 
 int64_t sola_rle_strings_to_cum_batch(const char* chars, const int64_t* str_off, int64_t n, uint32_t* host_cum, int64_t cap,
                                       int64_t limit, int64_t* run_off);
 
+/* ---- DAVIS boundary (contour) F on the same planes and id lists (no void pixels, both masks of one size) ----------------
+ * For every expression e < E and frame t < T, fg / gt = the ORs sola_mask_select_counts forms.  The boundary map B(m) is 1
+ * where m differs from an in-image neighbour among east (y, x+1), south (y+1, x) and south-east (y+1, x+1); dil(B) is B
+ * dilated by the disk dy*dy + dx*dx <= radius*radius, positions outside the image contributing nothing (radius 0 = B
+ * itself; the benchmark's radius is ceil(0.008 * sqrt(h*h + w*w))).  dev_counts [E, T, 4] int64 =
+ * (|B(fg)|, |B(gt)|, |B(fg) & dil(B(gt))|, |B(gt) & dil(B(fg))|), exact; every entry is written.  0 <= radius <= 64,
+ * h*w < 2^31, words_stride a multiple of 4 and >= sola_jf_plane_words(h, w), planes 16-byte aligned, E*T < 2^31; a frame
+ * too tall for one column strip of 2*radius + 2 columns to fit a CU's LDS is refused (at radius 18 that is h > 8512).
+ * Asynchronous on the stream.  The workspace is sized by sola_boundary_counts_workspace_bytes, which answers 0 (the strips
+ * of a frame meet in int64 atomics after a memset of dev_counts on the stream): workspace may be NULL. */
+int sola_mask_select_boundary_counts(const uint32_t* dev_bits, int64_t words_stride, int n_masks, int T, int h, int w, int radius,
+                                     const int32_t* dev_pred_off, const int32_t* dev_pred_idx, const int32_t* dev_gt_off,
+                                     const int32_t* dev_gt_idx, int E, int64_t* dev_counts, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+size_t sola_boundary_counts_workspace_bytes(int h, int w, int radius, int E, int T);
+
 /* Masks -> COCO compressed RLE strings, byte-identical to pycocotools encode + rleToString on {0,1} masks; replaces the
  * host copy + per-frame pycocotools loop of track_generation/seg_utils.py encode_rle_masklet_torch.  n masks [n,h,w]
  * row-major; elem_type 0 = uint8 (!= 0), 1 = float32 (!= 0), 2 = float32 tracker logits (> 0).  n >= 1 (any n: launches

@@ -276,6 +276,34 @@ def F_from_counts(counts):
     return 2 * precision * recall / (precision + recall)
 
 
+def boundary_radius(h, w, bound_th=0.008):
+    """Disk radius of the DAVIS contour measure: ``bound_th`` itself when >= 1, else ceil(bound_th * image diagonal)."""
+    import numpy as np
+    return int(bound_th if bound_th >= 1 else np.ceil(bound_th * np.sqrt(np.float64(h * h + w * w))))
+
+
+def F_boundary_from_counts(counts):
+    """DAVIS contour F of a masklet: mean over frames of the F-measure of boundary precision and recall, from the
+    [T,4] counts (n_fg, n_gt, fg_match, gt_match) of sola_mask_select_boundary_counts."""
+    import numpy as np
+    Fs = []
+    for n_fg, n_gt, fg_match, gt_match in counts.tolist():
+        if n_fg == 0 and n_gt > 0:
+            precision, recall = 1, 0
+        elif n_fg > 0 and n_gt == 0:
+            precision, recall = 0, 1
+        elif n_fg == 0 and n_gt == 0:
+            precision, recall = 1, 1
+        else:
+            precision, recall = fg_match / n_fg, gt_match / n_gt
+        Fs.append(0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall))
+    return np.mean(Fs)
+
+
+def _boundary_th(boundary):
+    return 0.008 if boundary is True else boundary
+
+
 def compute_J(pred_masklet, gt_masklet):
     return J_from_counts(frame_counts(pred_masklet, gt_masklet))
 
@@ -289,6 +317,33 @@ def compute_JF(pred_masklet, gt_masklet):
     c = frame_counts(pred_masklet, gt_masklet)
     J, F = float(J_from_counts(c)), float(F_from_counts(c))
     return J, F, (J + F) / 2
+
+
+@torch.no_grad()
+def compute_F_boundary(pred_masklet, gt_masklet, bound_th=0.008):
+    """DAVIS contour F of two dense (T,h,w) masklets on the GPU (the counterpart of compute_F for the benchmark's F): the
+    transposed frames go through pack_masks, which makes them the column-major planes sola_mask_select_boundary_counts
+    reads, prediction t against ground truth t."""
+    pred_masklet, gt_masklet = _prep(pred_masklet), _prep(gt_masklet)
+    if pred_masklet.shape != gt_masklet.shape or pred_masklet.dim() != 3:
+        raise SolaError(f"masklets must be (T,h,w) of one shape: {tuple(pred_masklet.shape)} vs {tuple(gt_masklet.shape)}")
+    if _elem_type(pred_masklet) != _elem_type(gt_masklet):
+        gt_masklet = gt_masklet.to(pred_masklet.dtype)
+    T, h, w = pred_masklet.shape
+    dev = pred_masklet.device
+    L = lib()
+    stride = L.sola_jf_plane_words(h, w)
+    packed, _ = pack_masks(torch.cat([pred_masklet, gt_masklet]).transpose(1, 2).contiguous())  # [2T, ceil(h*w/32)]
+    bits = torch.zeros((2 * T, stride), device=dev, dtype=torch.int32)
+    bits[:, :packed.shape[1]] = packed
+    # 2T masks of one frame each: "expression" t selects mask t and is scored against mask T + t
+    ints = torch.arange(T + 1, dtype=torch.int32, device=dev)
+    gidx = ints[:T] + T
+    counts = torch.empty((T, 1, 4), device=dev, dtype=torch.int64)
+    check(L.sola_mask_select_boundary_counts(ptr(bits), stride, 2 * T, 1, h, w, boundary_radius(h, w, bound_th), ptr(ints), ptr(ints),
+                                             ptr(ints), ptr(gidx), T, ptr(counts), None, 0, current_stream(dev)),
+          "sola_mask_select_boundary_counts")
+    return F_boundary_from_counts(counts[:, 0].cpu())
 
 
 @torch.no_grad()
@@ -436,7 +491,7 @@ def _planes_cum(masklets, ids, T, hw):
 
 
 @torch.no_grad()
-def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=2 << 30):
+def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=2 << 30, boundary=None):
     """Every expression of a video against its ground truth, per frame: int64 [E, T, 3] (intersection, n_pred, n_gt) on the
     host, where expression e's prediction is the OR of ``masklets[i]`` for i in ``pred_sets[e]`` and its ground truth the OR
     over ``gt_sets[e]`` (dataloader.py:251-351 get_gt_masklet / get_sam2_masklet, evaluator.py:227-247).
@@ -446,7 +501,12 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
     and every (expression, frame) is counted by one launch (sola_mask_select_counts): one host parse, one decode launch, one
     count launch and one copy.  The planes of one launch are capped at ``max_plane_bytes``: expressions are grouped in order
     under that budget (an expression that alone exceeds it runs by itself).  An empty list is an all-zero masklet.  Counts
-    are exact int64; the reference sums float32 tensors, which is exact while every count is below 2^24."""
+    are exact int64; the reference sums float32 tensors, which is exact while every count is below 2^24.
+
+    ``boundary`` = the DAVIS ``bound_th`` (``True`` = 0.008): returns ``(counts, bcounts)`` with bcounts int64 [E, T, 4] =
+    (n_fg, n_gt, fg_match, gt_match), the boundary pixels of prediction and ground truth and those within the disk of
+    boundary_radius(h, w, bound_th) of the other's (sola_mask_select_boundary_counts on the planes of the same decode
+    launch; F_boundary_from_counts turns a [T,4] table into the benchmark's F)."""
     import numpy as np
     E = len(pred_sets)
     if len(gt_sets) != E:
@@ -459,12 +519,12 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
             if not 0 <= int(i) < M:
                 raise SolaError(f"masklet_select_counts: index {i} outside the {M} masklets")
     T, size = _masklet_geometry(masklets)
-    if E == 0:
-        return torch.zeros((0, T, 3), dtype=torch.int64)
-    if size is None or T == 0:  # every frame of every masklet is missing: all masks are empty
-        return torch.zeros((E, T, 3), dtype=torch.int64)
+    if E == 0 or size is None or T == 0:  # (no size: every frame of every masklet is missing, all masks are empty)
+        counts = torch.zeros((E, T, 3), dtype=torch.int64)
+        return counts if boundary is None else (counts, torch.zeros((E, T, 4), dtype=torch.int64))
     h, w = size
     L = lib()
+    radius = None if boundary is None else boundary_radius(h, w, _boundary_th(boundary))
     stride = L.sola_jf_plane_words(h, w)
     mask_bytes = T * stride * 4
     groups, cur, cur_ids = [], [], set()
@@ -478,7 +538,7 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
     groups.append(cur)
     dev = torch.device(device)
     stream = current_stream(dev)
-    outs = []
+    outs, bouts = [], []
     for grp in groups:
         ids = sorted(set(int(i) for e in grp for i in list(pred_sets[e]) + list(gt_sets[e])))
         local = {m: k for k, m in enumerate(ids)}
@@ -506,18 +566,37 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
         check(L.sola_mask_select_counts(ptr(bits), stride if ids else 4, len(ids), T, ptr(d_poff), ptr(d_pidx), ptr(d_goff),
                                         ptr(d_gidx), Eg, ptr(counts), stream), "sola_mask_select_counts")
         outs.append(counts)
-    return (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu()
+        if radius is not None:
+            bcounts = torch.empty((Eg, T, 4), device=dev, dtype=torch.int64)
+            # (without ids no plane is read: the stride is the frame's over the dummy plane)
+            check(L.sola_mask_select_boundary_counts(ptr(bits), stride, len(ids), T, h, w, radius, ptr(d_poff), ptr(d_pidx),
+                                                     ptr(d_goff), ptr(d_gidx), Eg, ptr(bcounts), None, 0, stream),
+                  "sola_mask_select_boundary_counts")
+            bouts.append(bcounts)
+    counts = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu()
+    if radius is None:
+        return counts
+    return counts, (bouts[0] if len(bouts) == 1 else torch.cat(bouts)).cpu()
 
 
-def compute_JF_batch(masklets, pred_sets, gt_sets, device, **kw):
+def compute_JF_batch(masklets, pred_sets, gt_sets, device, boundary=None, **kw):
     """[(J, F, (J + F) / 2)] per expression from masklet_select_counts: evaluator.py:196-199,227-247 for every expression of
     a video in one counting pass.  J is the mean over frames of inter / union (1.0 for an empty union), F the pixel F1 over
-    the whole masklet (0.0 when there is no true positive); not the DAVIS boundary F."""
-    counts = masklet_select_counts(masklets, pred_sets, gt_sets, device, **kw)
+    the whole masklet (0.0 when there is no true positive): the reference evaluator's F.  The DAVIS boundary F comes with
+    ``boundary`` = its ``bound_th`` (``True`` = 0.008): every entry is then (J, F, JF, F_boundary, JF_boundary), F_boundary
+    the mean over frames of the contour F-measure and JF_boundary = (J + F_boundary) / 2, the benchmark's J&F."""
+    counts = masklet_select_counts(masklets, pred_sets, gt_sets, device, boundary=boundary, **kw)
+    bcounts = None
+    if boundary is not None:
+        counts, bcounts = counts
     out = []
-    for c in counts:
+    for e, c in enumerate(counts):
         J, F = float(J_from_counts(c)), float(F_from_counts(c))
-        out.append((J, F, (J + F) / 2))
+        if bcounts is None:
+            out.append((J, F, (J + F) / 2))
+        else:
+            Fb = float(F_boundary_from_counts(bcounts[e]))
+            out.append((J, F, (J + F) / 2, Fb, (J + Fb) / 2))
     return out
 
 
