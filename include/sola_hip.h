@@ -546,6 +546,33 @@ int sola_rle_encode_cum(const void* dev_masks, int elem_type, int n, int h, int 
 int sola_rle_encode_chars(const uint32_t* dev_cum, const int64_t* dev_run_off, const int64_t* dev_char_off, int n,
                           char* dev_chars, void* stream);
 
+/* Masks -> the zlib streams of 8-bit greyscale PNG files (pixel 255 where the mask is set, else 0), one per frame; replaces
+ * the host copy of the masklet + one general PNG encode per frame in inference.py.  n masks [n,h,w] row-major, elem_type as
+ * sola_rle_encode_runs (0 = uint8 != 0, 1 = float32 != 0, 2 = float32 logits > 0).  n >= 1 (any n: launches are chunked by
+ * 65535 frames), h*(w+1) < 2^31.
+ * Format, fixed: bytes 78 01, ONE DEFLATE block (BFINAL=1, BTYPE=01: the fixed Huffman table), Adler-32 (big endian) of
+ * the raw stream.  Raw stream = per row one byte 0 (filter None) then w pixel bytes.  It is cut into maximal runs of equal
+ * bytes across row ends; a run of value v and length r is the literal v, then L = r-1 bytes as distance-1 matches: while
+ * L > 0: L == 258 or L >= 261 -> 258; L in {259, 260} -> L-3; 3 <= L <= 257 -> L; L in {1, 2} -> L literals.  Then
+ * end-of-block and zero bits to the byte boundary.  A frame's stream is at most 6 + (9*h*(w+1) + 17) / 8 bytes.  The
+ * caller adds the PNG signature, IHDR, the IDAT length and CRC-32 (which covers the compressed bytes only) and IEND.
+ * Two calls on one stream with one host read between them:
+ *   1. sola_png_deflate_sizes: reads the masks once; dev_byte_off [n+1] int64 = first byte of each frame's complete stream
+ *      (dev_byte_off[n] = total bytes), dev_adler [n] uint32 = Adler-32 of each raw stream (exact 64-bit sums on the GPU,
+ *      reduced mod 65521 at the end).  dev_scratch (>= sola_png_deflate_scratch_bytes(n,h,w) bytes, 8-byte aligned) keeps
+ *      the raw streams as bitmaps and the per-workgroup bit offsets for call 2.
+ *   2. sola_png_deflate_write: dev_bytes [dev_byte_off[n]] = every frame's stream back to back.  Takes the scratch as call
+ *      1 left it, with the same n, h, w, and does not read the masks again.  EVERY byte of dev_bytes is written with
+ *      plain stores (each byte has one owning workgroup): nothing depends on what the buffer held.  A scratch or offsets
+ *      that do not belong together give missing bytes, never a store outside a frame's [dev_byte_off[i], dev_byte_off[i+1]).
+ * Both are asynchronous on the stream.  Scratch: n * (ceil(h*(w+1)/64) * 8 + ceil(h*(w+1)/16384) * 28) bytes, rounded up to
+ * 256; 0 for bad sizes (host-only).  Bad arguments are refused before any launch. */
+size_t sola_png_deflate_scratch_bytes(int n, int h, int w);
+int sola_png_deflate_sizes(const void* dev_masks, int elem_type, int n, int h, int w, int64_t* dev_byte_off,
+                           uint32_t* dev_adler, void* dev_scratch, size_t scratch_bytes, void* stream);
+int sola_png_deflate_write(const void* dev_masks, int elem_type, int n, int h, int w, const int64_t* dev_byte_off,
+                           const uint32_t* dev_adler, uint8_t* dev_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream; used by bench.py's roofline object) ------------ */
 enum { SOLA_PROF_GEMM = 0,      /* gemm_nt_f32_kernel<128,128> */
        SOLA_PROF_ATTN = 1,      /* attn_fwd_f32_kernel */

@@ -138,6 +138,9 @@ SIGNATURES = {
     "sola_rle_encode_runs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "sola_rle_encode_cum": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sola_rle_encode_chars": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "sola_png_deflate_scratch_bytes": (_sz, [_i, _i, _i]),
+    "sola_png_deflate_sizes": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "sola_png_deflate_write": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sola_mask_iou_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "sola_mask_iou_matrix": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sola_grad_sqnorms_scratch_bytes": (_sz, [_i, _vp]),

@@ -6,6 +6,7 @@ coerced, bare flags -> True).  Output directories follow the reference layout (S
     train      results.output_dir/<exp_name>/<train.data_name>/epoch_K.pth
     eval       results.eval_output_dir/<exp_name>/<valid.data_name>/pred_threshold_<t>/epoch_K/
     inference  results.test_output_dir/<exp_name>/<test.data_name>/pred_threshold_<t>/epoch_K/<video>/<exp>/<frame>.png
+               (``--gpu_png true`` -> ``configs["gpu_png"]``: the same files written from the GPU deflate, inference.py)
 """
 from __future__ import annotations
 

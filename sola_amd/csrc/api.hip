@@ -1159,6 +1159,25 @@ extern "C" int sola_rle_encode_chars(const uint32_t* cum, const int64_t* run_off
                                    n, chars, as_stream(stream_));
 }
 
+// masks -> zlib streams of greyscale PNG files (png_encode.hip)
+extern "C" size_t sola_png_deflate_scratch_bytes(int n, int h, int w) { return png_deflate_scratch_bytes(n, h, w); }
+
+extern "C" int sola_png_deflate_sizes(const void* masks, int elem_type, int n, int h, int w, int64_t* byte_off, uint32_t* adler,
+                                      void* scratch, size_t scratch_bytes, void* stream_) {
+    SOLA_ARG(masks && byte_off && adler && scratch, "png_deflate_sizes: null argument");
+    SOLA_ARG((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "png_deflate_sizes: scratch must be 8-byte aligned");
+    return launch_png_deflate_sizes(masks, elem_type, n, h, w, reinterpret_cast<long long*>(byte_off), adler, scratch, scratch_bytes,
+                                    as_stream(stream_));
+}
+
+extern "C" int sola_png_deflate_write(const void* masks, int elem_type, int n, int h, int w, const int64_t* byte_off,
+                                      const uint32_t* adler, uint8_t* bytes, void* scratch, size_t scratch_bytes, void* stream_) {
+    SOLA_ARG(masks && byte_off && adler && bytes && scratch, "png_deflate_write: null argument");
+    SOLA_ARG((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "png_deflate_write: scratch must be 8-byte aligned");
+    return launch_png_deflate_write(masks, elem_type, n, h, w, reinterpret_cast<const long long*>(byte_off), adler, bytes, scratch,
+                                    scratch_bytes, as_stream(stream_));
+}
+
 // Host helper (no GPU work): COCO compressed run-length string -> inclusive prefix sums of the run lengths, the form
 // sola_rle_fill_or consumes.  pycocotools rleFrString: 5 data bits + continuation bit per char (offset 48), sign
 // extension from bit 4 of the last char, runs from the 4th on stored as a delta to the run two places back.

@@ -486,3 +486,10 @@ int launch_rle_encode_cum(const void* masks, int elem_type, int n, int h, int w,
                           long long* char_off, void* scratch, size_t scratch_bytes, hipStream_t s);
 int launch_rle_encode_chars(const uint32_t* cum, const long long* run_off, const long long* char_off, int n, char* chars,
                             hipStream_t s);
+
+// ---- masks -> zlib streams of greyscale PNG files (png_encode.hip) -------------------------------------------------
+size_t png_deflate_scratch_bytes(int n, int h, int w);
+int launch_png_deflate_sizes(const void* masks, int elem_type, int n, int h, int w, long long* byte_off, uint32_t* adler,
+                             void* scratch, size_t scratch_bytes, hipStream_t s);
+int launch_png_deflate_write(const void* masks, int elem_type, int n, int h, int w, const long long* byte_off,
+                             const uint32_t* adler, uint8_t* bytes, void* scratch, size_t scratch_bytes, hipStream_t s);

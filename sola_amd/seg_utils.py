@@ -5,6 +5,9 @@ Masks are torch CUDA tensors, uint8 or float32 with values {0,1}.  Counts are ex
 float division exactly as in the reference, so ``iou > miou_thresh`` decisions are bit-identical."""
 from __future__ import annotations
 
+import struct
+import zlib
+
 import torch
 
 from ._lib import SolaError, check, current_stream, lib, ptr, require_cuda
@@ -658,6 +661,83 @@ def encode_rle_masklets(masklets, logits=False):
     if len(masklets) == 0:
         return []
     flat = encode_rle_masklet(torch.cat([_prep(m) for m in masklets]), logits)
+    out, f = [], 0
+    for m in masklets:
+        out.append(flat[f:f + m.shape[0]])
+        f += m.shape[0]
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# masks -> PNG files (inference.py's writer: 8-bit greyscale, 255 where the mask is set)
+# ----------------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def png_deflate_masklet(masks, logits=False, out=None):
+    """(T,h,w) masks on the GPU -> ``(bytes, offsets)``: every frame's zlib stream (``78 01``, one fixed-Huffman DEFLATE
+    block of distance-1 matches over the filter-0 scanlines, Adler-32; include/sola_hip.h gives the format) back to back,
+    frame t at ``bytes[offsets[t]:offsets[t + 1]]``.  Two library calls, one host read of the T+1 offsets between them and
+    one copy of the streams; the masklet itself never leaves the device.  ``out``: a uint8 device tensor of at least
+    ``offsets[T]`` bytes to write into (tests: every byte is written whatever it held)."""
+    masks = _prep(masks)
+    if masks.dim() != 3:
+        raise SolaError(f"png_deflate_masklet: masks must be (T,h,w), got {tuple(masks.shape)}")
+    if logits and masks.dtype != torch.float32:
+        raise SolaError("logits must be float32")
+    et = 2 if logits else _elem_type(masks)
+    n, h, w = masks.shape
+    if n == 0:
+        return b"", [0]
+    dev = masks.device
+    L, stream = lib(), current_stream(dev)
+    nb = L.sola_png_deflate_scratch_bytes(n, h, w)
+    scratch = torch.empty((max(nb, 8) + 7) // 8, device=dev, dtype=torch.int64)
+    byte_off = torch.empty((n + 1,), device=dev, dtype=torch.int64)
+    adler = torch.empty((n,), device=dev, dtype=torch.int32)
+    check(L.sola_png_deflate_sizes(ptr(masks), et, n, h, w, ptr(byte_off), ptr(adler), ptr(scratch), nb, stream),
+          "sola_png_deflate_sizes")
+    offs = byte_off.cpu().tolist()  # the host read: every frame's first byte, offs[n] = the size of the buffer
+    if out is None:
+        out = torch.empty((offs[n],), device=dev, dtype=torch.uint8)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= offs[n]):
+        raise SolaError(f"png_deflate_masklet: out must be a contiguous uint8 device tensor of >= {offs[n]} bytes")
+    check(L.sola_png_deflate_write(ptr(masks), et, n, h, w, ptr(byte_off), ptr(adler), ptr(out), ptr(scratch), nb, stream),
+          "sola_png_deflate_write")
+    return out[:offs[n]].cpu().numpy().tobytes(), offs
+
+
+def _png_chunk(kind, body):
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body))
+
+
+def encode_png_masklet(masks, logits=False):
+    """(T,h,w) masks on the GPU -> list of T complete PNG files (bytes): 8-bit greyscale, 255 where the mask is set - what
+    ``Image.fromarray(mask * 255).save(..., "PNG")`` stores, mode ``L`` - from png_deflate_masklet.  The host adds the
+    signature, IHDR, the IDAT length and CRC-32 (over the compressed bytes only) and IEND.  uint8 / bool / float32 pixels
+    count when != 0; ``logits=True`` counts float32 ``> 0``.  The files use the fixed Huffman table: larger than a general
+    encoder's, equal pixels."""
+    data, offs = png_deflate_masklet(masks, logits)
+    if len(offs) == 1:
+        return []
+    h, w = masks.shape[1:]
+    head = b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0))
+    tail = _png_chunk(b"IEND", b"")
+    return [head + _png_chunk(b"IDAT", data[offs[i]:offs[i + 1]]) + tail for i in range(len(offs) - 1)]
+
+
+def encode_png_mask(mask, logits=False):
+    """(h,w) mask on the GPU -> one PNG file (bytes)."""
+    if mask.dim() != 2:
+        raise SolaError(f"encode_png_mask: mask must be (h,w), got {tuple(mask.shape)}")
+    return encode_png_masklet(mask.unsqueeze(0), logits)[0]
+
+
+@torch.no_grad()
+def encode_png_masklets(masklets, logits=False):
+    """list of (T_i,h,w) masklets of one size and dtype -> list of per-masklet PNG lists, from ONE encode over the masklets
+    concatenated along frames."""
+    if len(masklets) == 0:
+        return []
+    flat = encode_png_masklet(torch.cat([_prep(m) for m in masklets]), logits)
     out, f = [], 0
     for m in masklets:
         out.append(flat[f:f + m.shape[0]])
