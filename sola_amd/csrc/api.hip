@@ -1,5 +1,6 @@
 // C ABI of libsola_hip.so (see include/sola_hip.h): context + weight registry, thin wrappers over the orchestration in
-// forward.hip / backward.hip and over the kernel launchers, and the HIP-event profiler.
+// forward.hip / forward_infer.hip / backward.hip and over the kernel launchers, the precision policy of the inference calls
+// (guarded_inference), and the HIP-event profiler.
 #include <math.h>
 #include <stdarg.h>
 #include <string.h>
@@ -443,7 +444,6 @@ extern "C" int sola_gemm_nt_split(const float* a_sp, int lda, const float* w_sp,
 }
 
 // ---- 16-bit storage mode building blocks (tests) ----------------------------------------------------------------
-int launch_attention_f16(const AttnDesc& d, hipStream_t s);
 extern "C" int sola_cast_f16(const float* in, int ld_in, void* out, int ld_out, int64_t rows, int K, float scale, float* dev_scal, void* stream_) {
     return launch_cast_f16(in, ld_in, out, ld_out, rows, K, scale, dev_scal, as_stream(stream_));
 }
@@ -563,31 +563,43 @@ struct PrecScope {
 };
 static bool few_rows_f32(const SolaCtx* c, long long rows0) { return c->precision == 1 && g_infer_f32_rows > 0 && rows0 <= g_infer_f32_rows; }
 
+// An inference call under the precision policy of include/sola_hip.h; `run` invokes the impl in the ctx's CURRENT arithmetic.  Precision 1
+// over at most infer_f32_rows object-token rows (`rows0`; kRowsUnknown = never) or with weights known to be out of range runs once, on the
+// exact-f32 kernels; every other 16-bit call runs, reads the guard words and, when one is set - a value left the range the 16-bit formats
+// cover, or the weights say it would - runs again on the exact-f32 kernels (the f32 plan fits the workspace of the 16-bit one).
+// The host-side plans allocate: nothing may throw across the ABI.
+constexpr long long kRowsUnknown = 1ll << 62;
+template <class Run>
+static int guarded_inference(SolaCtx* c, const char* who, long long rows0, hipStream_t s, Run run) {
+    SOLA_ARG(!c || c->precision != 3, "%s: precision 3 (bf16 GEMM operands) is a TRAINING mode; inference runs precision 0, 1 or 2", who);
+    try {
+        if (!c || c->precision < 1) return run();  // no ctx: the impl says so
+        bool exact = few_rows_f32(c, rows0);
+        if (!exact && split_known_out_of_range(c)) {
+            c->split_fallbacks += 1;
+            exact = true;
+        }
+        if (!exact) {
+            SOLA_TRY(run());
+            bool tripped = false;
+            SOLA_TRY(sola_split_guard_tripped(c, s, &tripped));
+            if (!tripped) return SOLA_OK;
+            c->split_fallbacks += 1;
+        }
+        PrecScope f32(c, 0);
+        return run();
+    } catch (const std::exception& e) {
+        sola_set_error("%s: %s", who, e.what());
+        return SOLA_ERR_ARG;
+    }
+}
+
 extern "C" int sola_forward(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
                             float* score_tokens, void* workspace, size_t ws_bytes, void* stream_) {
     hipStream_t s = as_stream(stream_);
-    SOLA_ARG(!c || c->precision != 3, "forward: precision 3 (bf16 GEMM operands) is a TRAINING mode; inference runs precision 0, 1 or 2");
-    if (c && B > 0 && N > 0 && T > 0 && few_rows_f32(c, (long long)B * N * T)) {
-        PrecScope f32(c, 0);
-        return sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s);
-    }
-    if (c && split_known_out_of_range(c)) {
-        c->split_fallbacks += 1;
-        PrecScope f32(c, 0);
-        return sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s);
-    }
-    if (c && c->precision >= 1) {
-        SOLA_TRY(sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s));
-        bool tripped = false;
-        SOLA_TRY(sola_split_guard_tripped(c, s, &tripped));
-        if (!tripped) return SOLA_OK;
-        // a value left the range the split-f16 pairs cover (or the weights say it would): same call, exact-f32 kernels.
-        // The f32 plan is a subset of the split plan, so the workspace fits.
-        c->split_fallbacks += 1;
-        PrecScope f32(c, 0);
-        return sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s);
-    }
-    return sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s);
+    const long long rows0 = (B > 0 && N > 0 && T > 0) ? (long long)B * N * T : kRowsUnknown;
+    return guarded_inference(c, "forward", rows0, s,
+                             [&] { return sola_forward_infer_impl(c, obj, lang, B, N, T, L, score_map, score_tokens, workspace, ws_bytes, s); });
 }
 
 extern "C" size_t sola_ragged_workspace_bytes(const SolaCtx* c, const SolaRaggedBatch* batch) {
@@ -606,33 +618,13 @@ extern "C" size_t sola_ragged_workspace_bytes(const SolaCtx* c, const SolaRagged
 extern "C" int sola_forward_ragged(SolaCtx* c, const float* obj, const float* lang, const SolaRaggedBatch* batch, float* score_map,
                                    float* score_tokens, void* workspace, size_t ws_bytes, void* stream_) {
     hipStream_t s = as_stream(stream_);
-    SOLA_ARG(!c || c->precision != 3, "forward_ragged: precision 3 (bf16 GEMM operands) is a TRAINING mode; inference runs precision 0, 1 or 2");
-    try {  // the host-side plan allocates; nothing may throw across the ABI
-        if (c && batch && c->precision == 1 && batch->n_videos > 0 && batch->video_tracks && batch->video_frames) {
-            long long rows0 = 0;
-            for (int v = 0; v < batch->n_videos; ++v) rows0 += (long long)batch->video_tracks[v] * batch->video_frames[v];
-            if (few_rows_f32(c, rows0)) {  // see g_infer_f32_rows
-                PrecScope f32(c, 0);
-                return sola_forward_ragged_impl(c, obj, lang, batch, score_map, score_tokens, workspace, ws_bytes, s);
-            }
-        }
-        if (c && split_known_out_of_range(c)) {
-            c->split_fallbacks += 1;
-            PrecScope f32(c, 0);
-            return sola_forward_ragged_impl(c, obj, lang, batch, score_map, score_tokens, workspace, ws_bytes, s);
-        }
-        SOLA_TRY(sola_forward_ragged_impl(c, obj, lang, batch, score_map, score_tokens, workspace, ws_bytes, s));
-        if (c->precision < 1) return SOLA_OK;
-        bool tripped = false;
-        SOLA_TRY(sola_split_guard_tripped(c, s, &tripped));
-        if (!tripped) return SOLA_OK;
-        c->split_fallbacks += 1;
-        PrecScope f32(c, 0);
-        return sola_forward_ragged_impl(c, obj, lang, batch, score_map, score_tokens, workspace, ws_bytes, s);
-    } catch (const std::exception& e) {
-        sola_set_error("forward_ragged: %s", e.what());
-        return SOLA_ERR_ARG;
+    long long rows0 = kRowsUnknown;
+    if (batch && batch->n_videos > 0 && batch->video_tracks && batch->video_frames) {
+        rows0 = 0;
+        for (int v = 0; v < batch->n_videos; ++v) rows0 += (long long)batch->video_tracks[v] * batch->video_frames[v];
     }
+    return guarded_inference(c, "forward_ragged", rows0, s,
+                             [&] { return sola_forward_ragged_impl(c, obj, lang, batch, score_map, score_tokens, workspace, ws_bytes, s); });
 }
 
 extern "C" int sola_loss_ragged(const float* score_map, const float* score_tokens, const float* labels, const float* pos,
@@ -699,7 +691,7 @@ extern "C" size_t sola_train_ragged_workspace_bytes(const SolaCtx* c, const Sola
     try {
         RagShape r;
         if (rag_shape(c, batch, r) != SOLA_OK) return 0;
-        return make_plan_ragged(c, r, true).total;
+        return make_plan_ragged(c, r).total;
     } catch (const std::exception& e) {
         sola_set_error("train_ragged_workspace_bytes: %s", e.what());
         return 0;

@@ -1,4 +1,4 @@
-// Context, weight registry and workspace plan shared by api.hip / forward.hip / backward.hip.
+// Context, weight registry and workspace plan shared by api.hip / forward.hip / forward_infer.hip / backward.hip.
 #pragma once
 #include <string>
 #include <unordered_map>
@@ -56,7 +56,7 @@ struct RagTables {
     bool identity = false;
 };
 
-struct SolaRagStage;  // pinned staging ring of the ragged forward's descriptor upload (forward_ragged.hip)
+struct SolaRagStage;  // pinned staging ring of the ragged forwards' descriptor upload (ragged.hip)
 void sola_rag_stage_free(SolaRagStage* st);
 
 struct SolaCtx {
@@ -192,11 +192,11 @@ inline std::string abuf(bool train, int layer, const char* attn, const char* wha
 
 struct RagShape;
 Plan make_plan(const SolaCtx* c, int B, int N, int T, int L, bool train);
-Plan make_plan_ragged(const SolaCtx* c, const RagShape& r, bool train);
+Plan make_plan_ragged(const SolaCtx* c, const RagShape& r);  // ragged TRAINING batch
 // training forward (forward.hip); rs != null: a ragged batch
 int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
                             float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s, const RagShape* rs = nullptr);
-// inference forward of a uniform batch in the ctx's precision 0, 1 or 2 (forward_infer.hip)
+// inference forwards of a uniform and of a ragged batch in the ctx's precision 0, 1 or 2 (forward_infer.hip)
 int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
                             float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s);
 size_t sola_backward_scratch_bytes(const SolaCtx* c, const Plan& p);

@@ -108,10 +108,10 @@ Plan make_plan(const SolaCtx* c, int B, int N, int T, int L, bool train) {
 
 // Plan of a ragged TRAINING batch (sola_forward_train_ragged): the same buffers over the concatenated rows, plus the table
 // region.  B = samples; N, T, L, W, Tl, Tp hold the LARGEST extents (they only select kernel shapes); M = all layer rows.
-Plan make_plan_ragged(const SolaCtx* c, const RagShape& r, bool train) {
+Plan make_plan_ragged(const SolaCtx* c, const RagShape& r) {
     Plan p;
     p.rag = true;
-    p.B = r.S; p.N = r.maxN; p.T = r.maxT[0]; p.L = r.maxW - c->cfg.n_negative; p.train = train;
+    p.B = r.S; p.N = r.maxN; p.T = r.maxT[0]; p.L = r.maxW - c->cfg.n_negative; p.train = true;
     p.W = r.maxW;
     for (int i = 0; i < 6; ++i) p.Tl[i] = r.maxT[i + 1];
     p.Tp = r.maxT[6];
@@ -121,8 +121,8 @@ Plan make_plan_ragged(const SolaCtx* c, const RagShape& r, bool train) {
     for (int i = 0; i < 6; ++i) z.rows[i] = r.rows[i + 1];
     z.M = r.Ms; z.BW = r.LW; z.S = r.S;
     z.gn_slots = (int64_t)(rag_gn_slots_bytes(r) / 4 + 64);
-    z.tables = rag_tables_bytes(r, train);
-    plan_fill(p, c, z, train);
+    z.tables = rag_tables_bytes(r, true);
+    plan_fill(p, c, z, true);
     return p;
 }
 
@@ -133,7 +133,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     SOLA_ARG(c && obj && lang && score_map && score_tokens && workspace, "forward: null argument");
     if (rs) SOLA_ARG(rs->identity, "forward: a ragged training batch has one sample per video (sample_video[i] == i)");
     else SOLA_ARG(B > 0 && N > 0 && T > 0 && L >= 1, "forward: bad sizes B=%d N=%d T=%d L=%d", B, N, T, L);
-    Plan p = rs ? make_plan_ragged(c, *rs, true) : make_plan(c, B, N, T, L, true);
+    Plan p = rs ? make_plan_ragged(c, *rs) : make_plan(c, B, N, T, L, true);
     SOLA_TRY(sola_check_forward_args(c, "forward", p.total, workspace, ws_bytes));
     char* base = static_cast<char*>(workspace);
     auto buf = [&](const std::string& name) { return reinterpret_cast<float*>(base + p.bufs.at(name).off); };

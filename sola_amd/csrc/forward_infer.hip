@@ -1,6 +1,8 @@
-// Inference forward of a uniform batch (sola_forward) in all three inference precisions (sola_set_precision(ctx, 0 / 1 / 2)).
-// Same network, same kernels and the same single [B,N,T',D] layout as the training forward (forward.hip) without what only
-// its backward reads; the modes differ in the arithmetic of the dense contractions (98 % of the FLOPs) and in the storage.
+// Inference forwards - of a uniform batch (sola_forward) and of a ragged one (sola_forward_ragged) - in all three inference
+// precisions (sola_set_precision(ctx, 0 / 1 / 2)).  Same network, same kernels and the same single [B,N,T',D] layout as the
+// training forward (forward.hip) without what only its backward reads; the modes differ in the arithmetic of the dense
+// contractions (98 % of the FLOPs) and in the storage.  Both sequences are written on ONE set of layer builders (InferBuilder
+// below), which holds everything that depends on the mode; a sequence adds the geometry: strides or the unit tables of ragged.hip.
 //
 // Precision 0: exact f32 MFMA on f32 activations.
 //
@@ -24,7 +26,7 @@
 
 #include <algorithm>
 
-#include "ctx.h"
+#include "ragged.h"
 
 // Split-f16 copies of the 12 * n_layers projection weights, each with its own power-of-two scale (max|w| -> [2^13, 2^14),
 // found on the device: a trained matrix may be far from the U(-1/32, 1/32) of the default init, and a few outliers must not
@@ -129,53 +131,219 @@ int g_attn_split_min_keys = 96;
 
 int g_lang_shared_neg = 1;  // sola_tune "lang_shared_neg": 0 = the negative tokens repeated per sample through the text-side projections (A/B)
 
-int launch_attention_f16(const AttnDesc& d, hipStream_t s);
+namespace {
 
+const char* const kProj[4] = {"q_proj", "k_proj", "v_proj", "out_proj"};
+
+// What the two inference sequences below (uniform batch, ragged batch) have in common: the ctx's precision mode, written ONCE
+// into every descriptor.  The methods fill everything but the geometry - strides or unit tables, instance counts, sequence
+// lengths - which the sequence adds before the launch.
+struct InferBuilder {
+    SolaCtx* c;
+    hipStream_t s;
+    bool sp, h16, op16;  // split-f16 operands; 16-bit storage; either (activations and weights in a 16-bit operand format)
+    int* guard;
+    int D, H, DH;
+    float scale;
+    // pieces of the sequence's workspace (use_workspace)
+    float* splitk_ws = nullptr;
+    size_t splitk_bytes = 0;
+    void* gn_slots = nullptr;
+    size_t gn_slots_bytes = 0;
+    const float* pe = nullptr;
+    float *attn = nullptr, *res = nullptr;  // attention output / pre-norm rows of the current sub-block
+
+    InferBuilder(SolaCtx* ctx, hipStream_t stream)
+        : c(ctx), s(stream), sp(ctx->precision == 1), h16(ctx->precision == 2), op16(sp || h16), guard(op16 ? ctx->guard : nullptr),
+          D(ctx->cfg.lang_token_dim), H(ctx->cfg.num_heads), DH(D / H), scale(1.0f / sqrtf((float)DH)) {}
+
+    const float* W(const std::string& name) const { return ctx_weight(c, name); }
+
+    int check_mode() const {
+        if (sp)
+            SOLA_ARG(c->cfg.object_token_dim % 8 == 0 && (c->cfg.lang_token_dim / c->cfg.n_groups_module) % 8 == 0 &&
+                         (2 * c->cfg.object_token_dim / c->cfg.n_groups) % 8 == 0 && (c->cfg.lang_token_dim / c->cfg.n_groups) % 8 == 0,
+                     "split-f16 mode needs channel counts per GroupNorm group that are multiples of 8");
+        if (h16)
+            SOLA_ARG(c->cfg.object_token_dim % 64 == 0 && c->cfg.lang_token_dim % 64 == 0,
+                     "16-bit storage mode needs object_token_dim and lang_token_dim to be multiples of 64");
+        return SOLA_OK;
+    }
+    void use_workspace(float* splitk, size_t splitk_b, void* slots, size_t slots_b, const float* pe_, float* attn_, float* res_) {
+        splitk_ws = h16 ? nullptr : splitk;  // the 16-bit GEMMs never split K
+        splitk_bytes = splitk_ws ? splitk_b : 0;
+        gn_slots = slots; gn_slots_bytes = slots_b; pe = pe_; attn = attn_; res = res_;
+    }
+    // The projection weights are used as they are by the reference (no per-forward transform), so their 16-bit copies are
+    // refreshed only when a weight pointer or value changed (sola_set_weight / sola_weights_changed).
+    int prepare_weights() const {
+        SOLA_TRY(sola_refresh_conv_weights(c, sp ? 1 : (h16 ? 2 : 0), false, s));
+        if (op16) {
+            SOLA_TRY(sola_refresh_lin16(c, s));
+            SOLA_HIP(hipMemsetAsync(c->guard, 0, sizeof(int), s));  // per-call range guard word (ctx.h)
+        }
+        return SOLA_OK;
+    }
+
+    // ---- the weights in the mode's operand format: f32 as set, split-f16 pairs (D*D floats per matrix) or plain f16 (D*D halfs)
+    const float* ws_w(int i) const {
+        if (h16) return reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->ws16_buf) + c->ws_off[i]);
+        return sp ? c->ws16_buf + c->ws_off[i] : c->ws_buf + c->ws_off[i];
+    }
+    std::string lin_name(int layer, int attn_i, int proj) const {
+        return "object_lang_align_layers." + std::to_string(layer) + "." + kAttnLong[attn_i] + "." + kProj[proj];
+    }
+    GemmProblem lin_problem(const float* a, int layer, int attn_i, int proj, const float* r, float* out) const {
+        const std::string nm = lin_name(layer, attn_i, proj);
+        const size_t at = ((size_t)(layer * 3 + attn_i) * 4 + proj) * D * D;
+        const float* w = sp ? c->lin16_buf + at
+                       : h16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->lin16_buf) + at)
+                             : W(nm + ".weight");
+        return GemmProblem{a, w, W(nm + ".bias"), r, out, op16 ? c->lin_inv_scale(layer, attn_i, proj) : nullptr};
+    }
+
+    // ---- the caller's tensors.  Their magnitude is unknown (SAM2 memory-attention features here, anything elsewhere).  Split-f16:
+    // the largest entry is mapped into [2^13, 2^14) by a power of two found on the device and the first GEMM's epilogue undoes it.
+    // 16-bit storage: largest magnitude -> [2^6, 2^7), and conv0's output STAYS in those scaled units (its standardised weights
+    // have a gain of sqrt(k*cin) = 28: tokens at 1e3 would leave the f16 range if the scale were undone here, tokens at 1e-5 would
+    // sink into subnormals): the bias is multiplied by the scale in conv0's epilogue and the first GroupNorm multiplies by the
+    // inverse while it reads, so its statistics (and eps) see the true values.  The scale is capped at 2^8: conv0's bias rides
+    // along multiplied by it (tokens of 1e-5 would ask for 2^21 and carry a bias of 0.03 to 75 000); below the cap the smallest
+    // token entries lose some of their 11 bits to f16 subnormals.
+    int cast_obj(const float* obj, float* obj_sp, long long rows) const {
+        const int d_in = c->cfg.object_token_dim;
+        if (sp) return launch_cast_sp16_auto(obj, d_in, obj_sp, d_in, rows, d_in, c->scal_pair(0), s);
+        return launch_cast_f16(obj, d_in, obj_sp, d_in, rows, d_in, 256.f, c->scal_pair(0), s, 6, c->scal_extra(0));
+    }
+    int cast_lang(const float* lang, float* lang_sp, long long rows) const {
+        if (sp) return launch_cast_sp16_auto(lang, D, lang_sp, D, rows, D, c->scal_pair(1), s);
+        return launch_cast_f16(lang, D, lang_sp, D, rows, D, 1.f, c->scal_pair(1), s, 6);
+    }
+    const float* lang_inv_scale() const { return op16 ? c->scal_pair(1) + 1 : nullptr; }  // undone by the text-side projections
+
+    // ---- GEMMs
+    GemmDesc gemm(long long rows, int N, int K) const {
+        GemmDesc gd{};
+        gd.M = (int)rows; gd.N = N; gd.K = K; gd.ldc = N;
+        if (op16) { gd.arith = sp ? 1 : 2; gd.out_scale = 1.f; }
+        gd.splitk_ws = splitk_ws; gd.splitk_bytes = splitk_bytes;
+        return gd;
+    }
+    // Encoder conv i over `rows` output rows (module/module.py:74-96).  conv5 (no norm behind it) feeds layer 0 both as the
+    // projections' A operand and as the first residual: in the 16-bit modes its epilogue writes the operand format directly, no f32
+    // copy and no cast pass.  (Split pairs need cout % 8 == 0: conv5's cout is lang_token_dim, a multiple of 8 * n_groups_module
+    // under check_mode, so the mode always has it.)
+    GemmDesc conv_gemm(int i, const float* x, float* out, long long rows) const {
+        const ConvGeom& g = c->conv[i];
+        GemmDesc gd = gemm(rows, g.cout, g.k * g.cin);
+        gd.nprob = 1;
+        gd.p[0] = GemmProblem{x, ws_w(i), W("short_motion_encoder." + std::to_string(kConvIdx[i]) + ".bias"), nullptr, out};
+        gd.lda = g.cin;
+        gd.conv = g.k > 1 ? 1 : 0;
+        gd.stride = g.stride; gd.pad = g.pad; gd.Cin = g.cin;
+        gd.guard = guard;
+        if (sp) {
+            gd.c_sp16 = i == 5 ? 1 : 0;
+            if (i == 0) gd.out_scale_dev = c->scal_pair(0) + 1;
+        }
+        if (h16) {
+            gd.c_f16 = 1;
+            if (i == 0) gd.bias_scale_dev = c->scal_extra(0);
+        }
+        return gd;
+    }
+    // nprob projections first_proj.. of one attention in one launch.  out_sp16: split-f16 q/k/v for the split attention kernel
+    // (the 16-bit storage mode writes f16 always, f32 ignores it)
+    int linear3(const float* a0, const float* a1, const float* a2, int layer, int attn_i, int nprob, long long rows, float* o0, float* o1,
+                float* o2, int first_proj, int out_sp16, const float* a_inv_scale = nullptr) const {
+        const float* as[3] = {a0, a1, a2};
+        float* os[3] = {o0, o1, o2};
+        GemmDesc gd = gemm(rows, D, D);
+        gd.nprob = nprob;
+        for (int j = 0; j < nprob; ++j) gd.p[j] = lin_problem(as[j], layer, attn_i, first_proj + j, nullptr, os[j]);
+        gd.lda = D;
+        gd.guard = guard;
+        if (op16) gd.out_scale_dev = a_inv_scale;
+        if (sp) gd.c_sp16 = out_sp16;
+        if (h16) gd.c_f16 = 1;
+        return launch_gemm(gd, s);
+    }
+    // res = attn * W_out^T + bias + resid; every residual of the path is in the mode's operand format
+    int out_proj(int layer, int attn_i, long long rows, const float* resid) const {
+        GemmDesc gd = gemm(rows, D, D);
+        gd.nprob = 1;
+        gd.p[0] = lin_problem(attn, layer, attn_i, 3, resid, res);
+        gd.lda = D; gd.ldr = D;
+        if (sp) gd.r_sp16 = 1;
+        if (h16) { gd.r_f16 = 1; gd.c_f16 = 1; gd.guard = guard; }
+        return launch_gemm(gd, s);
+    }
+
+    // ---- GroupNorms.  out16: y / y2 in the mode's 16-bit storage (split pairs or f16); f32 ignores it
+    GroupNormDesc norm(const std::string& name, const float* x, float* y, int C, int groups, int out16) const {
+        GroupNormDesc nd{};
+        nd.slice_ws = gn_slots; nd.slice_ws_bytes = gn_slots_bytes;
+        nd.x = x; nd.y = y;
+        nd.gamma = W(name + ".weight"); nd.beta = W(name + ".bias");
+        nd.C = C; nd.groups = groups; nd.eps = 1e-5f;
+        nd.guard = guard;
+        if (sp) nd.out_sp16 = out16;
+        if (h16) { nd.in_f16 = 1; nd.out_f16 = out16; }
+        return nd;
+    }
+    GroupNormDesc encoder_norm(int i, const float* x, float* y) const {
+        GroupNormDesc nd = norm("short_motion_encoder." + std::to_string(kNormIdx[i]), x, y, c->conv[i].cout, c->cfg.n_groups, 1);
+        nd.slope = 0.01f; nd.leaky = 1;
+        if (h16 && i == 0) nd.in_scale_dev = c->scal_pair(0) + 1;  // conv0's output is in the scaled units of the tokens
+        return nd;
+    }
+    GroupNormDesc layer_norm(int layer, int idx, float* y, float* y2, int out16) const {  // y2: optional y + positional encoding
+        GroupNormDesc nd = norm("object_lang_align_layers." + std::to_string(layer) + ".norm." + std::to_string(idx), res, y, D,
+                                c->cfg.n_groups_module, out16);
+        nd.y2 = y2; nd.pe = y2 ? pe : nullptr;
+        return nd;
+    }
+
+    // ---- attention.  in_sp16: q/k/v left the projection GEMM as split pairs
+    AttnDesc attention(const float* q, const float* k, const float* v, int in_sp16) const {
+        AttnDesc ad{};
+        ad.q = q; ad.k = k; ad.v = v; ad.o = attn;
+        ad.ldq = ad.ldk = ad.ldv = ad.ldo = D;
+        ad.H = H; ad.DH = DH; ad.scale = scale;
+        ad.o_sp16 = sp ? 1 : 0; ad.in_sp16 = in_sp16; ad.split_math = sp ? 1 : 0;
+        ad.guard = guard;
+        return ad;
+    }
+    int launch(const AttnDesc& ad) const { return h16 ? launch_attention_f16(ad, s) : launch_attention(ad, s); }
+};
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------
+// uniform batch: strided geometry on ONE [B,N,T',D] layout
+// ---------------------------------------------------------------------------------------------------------------
 int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int B, int N, int T, int L, float* score_map,
                             float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s) {
     SOLA_ARG(c && obj && lang && score_map && score_tokens && workspace, "forward: null argument");
     SOLA_ARG(B > 0 && N > 0 && T > 0 && L >= 1, "forward: bad sizes B=%d N=%d T=%d L=%d", B, N, T, L);
-    const bool sp = c->precision == 1;   // split-f16 operands
-    const bool h16 = c->precision == 2;  // 16-bit storage
-    if (sp)
-        SOLA_ARG(c->cfg.object_token_dim % 8 == 0 && (c->cfg.lang_token_dim / c->cfg.n_groups_module) % 8 == 0 &&
-                     (2 * c->cfg.object_token_dim / c->cfg.n_groups) % 8 == 0 && (c->cfg.lang_token_dim / c->cfg.n_groups) % 8 == 0,
-                 "split-f16 mode needs channel counts per GroupNorm group that are multiples of 8");
-    if (h16)
-        SOLA_ARG(c->cfg.object_token_dim % 64 == 0 && c->cfg.lang_token_dim % 64 == 0,
-                 "16-bit storage mode needs object_token_dim and lang_token_dim to be multiples of 64");
+    InferBuilder b(c, s);
+    SOLA_TRY(b.check_mode());
+    const bool sp = b.sp;
     Plan p = make_plan(c, B, N, T, L, false);
     SOLA_TRY(sola_check_forward_args(c, "forward", p.total, workspace, ws_bytes));
     char* base = static_cast<char*>(workspace);
     // buffers are sized for 4 bytes per element; the 16-bit storage mode keeps its halfs in their first half
     auto buf = [&](const std::string& name) { return reinterpret_cast<float*>(base + p.bufs.at(name).off); };
-    float* const splitk_ws = (!h16 && p.bufs.count("splitk")) ? buf("splitk") : nullptr;  // the 16-bit GEMMs never split K
-    const size_t splitk_bytes = splitk_ws ? (size_t)p.bufs.at("splitk").rows * p.bufs.at("splitk").cols * sizeof(float) : 0;
-    auto W = [&](const std::string& name) { return ctx_weight(c, name); };
-    const int D = c->cfg.lang_token_dim, H = c->cfg.num_heads, DH = D / H, d_in = c->cfg.object_token_dim;
+    auto bytes = [&](const char* name) { return (size_t)p.bufs.at(name).rows * p.bufs.at(name).cols * sizeof(float); };
+    const bool has_splitk = p.bufs.count("splitk") != 0;
+    b.use_workspace(has_splitk ? buf("splitk") : nullptr, has_splitk ? bytes("splitk") : 0, buf("gn_slots"), bytes("gn_slots"), buf("pe"),
+                    buf("attn"), buf("res"));
+    const int D = b.D, H = b.H, DH = b.DH;
     const int Tp = p.Tp, M = p.M, Wn = p.W;
     const int R = B * N;
-    int* const guard = (sp || h16) ? c->guard : nullptr;
-    // the weights in the mode's operand format: f32 as set, split-f16 pairs (D*D floats per matrix) or plain f16 (D*D halfs)
-    auto ws_w = [&](int i) -> const float* {
-        if (h16) return reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->ws16_buf) + c->ws_off[i]);
-        return sp ? c->ws16_buf + c->ws_off[i] : c->ws_buf + c->ws_off[i];
-    };
-    auto lin_w = [&](const std::string& an, const char* proj_name, int layer, int attn, int proj) -> const float* {
-        const size_t idx = (size_t)(layer * 3 + attn) * 4 + proj;
-        if (sp) return c->lin16_buf + idx * D * D;
-        if (h16) return reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->lin16_buf) + idx * D * D);
-        return W(an + "." + proj_name + ".weight");
-    };
-    auto lin_inv = [&](int layer, int attn, int proj) -> const float* { return (sp || h16) ? c->lin_inv_scale(layer, attn, proj) : nullptr; };
 
-    // ---- weights.  The projection weights are used as they are by the reference (no per-forward transform), so their 16-bit
-    // copies are refreshed only when a weight pointer or value changed (sola_set_weight / sola_weights_changed).
-    SOLA_TRY(sola_refresh_conv_weights(c, sp ? 1 : (h16 ? 2 : 0), false, s));
-    if (sp || h16) {
-        SOLA_TRY(sola_refresh_lin16(c, s));
-        SOLA_HIP(hipMemsetAsync(c->guard, 0, sizeof(int), s));  // per-call range guard word (ctx.h)
-    } else {
+    SOLA_TRY(b.prepare_weights());
+    if (!b.op16) {
         // exact f32 resets the kept-operand arena's record (sola_x16_arena_info sizes the 16-bit training arena by it); the 16-bit modes keep it
         c->x16.clear();
         c->x16_used = 0;
@@ -183,80 +351,44 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
     }
 
     // ---- encoder (module/module.py:74-96,137-140)
-    // The caller's tokens come with an unknown magnitude (SAM2 memory-attention features here, anything elsewhere).  Split-f16:
-    // their largest entry is mapped into [2^13, 2^14) by a power of two found on the device and conv0's epilogue undoes it.
-    // 16-bit storage: largest magnitude -> [2^6, 2^7), and conv0's output STAYS in those scaled units (its standardised weights
-    // have a gain of sqrt(k*cin) = 28: tokens at 1e3 would leave the f16 range if the scale were undone here, tokens at 1e-5 would
-    // sink into subnormals): the bias is multiplied by the scale in conv0's epilogue and the first GroupNorm multiplies by the
-    // inverse while it reads, so its statistics (and eps) see the true values.  The scale is capped at 2^8: conv0's bias rides
-    // along multiplied by it (tokens of 1e-5 would ask for 2^21 and carry a bias of 0.03 to 75 000); below the cap the smallest
-    // token entries lose some of their 11 bits to f16 subnormals.
     const float* x = obj;
-    if (sp) SOLA_TRY(launch_cast_sp16_auto(obj, d_in, buf("obj_sp"), d_in, (long long)R * T, d_in, c->scal_pair(0), s));
-    if (h16) SOLA_TRY(launch_cast_f16(obj, d_in, buf("obj_sp"), d_in, (long long)R * T, d_in, 256.f, c->scal_pair(0), s, 6, c->scal_extra(0)));
-    if (sp || h16) x = buf("obj_sp");
-    // conv5 (no norm behind it) feeds layer 0 both as the projections' A operand and as the first residual: in the 16-bit modes its
-    // epilogue writes the operand format directly, no f32 copy and no cast pass (split pairs need cout % 8 == 0)
-    const bool conv5_16 = h16 || (sp && c->conv[5].cout % 8 == 0);
+    if (b.op16) {
+        SOLA_TRY(b.cast_obj(obj, buf("obj_sp"), (long long)R * T));
+        x = buf("obj_sp");
+    }
     int t_in = T;
     for (int i = 0; i < 6; ++i) {
-        const ConvGeom& g = c->conv[i];
-        const std::string cp = "short_motion_encoder." + std::to_string(kConvIdx[i]);
-        const bool to16 = i == 5 && conv5_16;
-        GemmDesc gd{};
-        gd.nprob = 1;
-        gd.p[0] = GemmProblem{x, ws_w(i), W(cp + ".bias"), nullptr, to16 ? buf("conv5_sp") : buf("conv" + std::to_string(i))};
-        gd.M = R * p.Tl[i]; gd.N = g.cout; gd.K = g.k * g.cin;
-        gd.lda = g.cin; gd.ldr = 0; gd.ldc = g.cout;
-        gd.conv = g.k > 1 ? 1 : 0;
-        gd.T_in = t_in; gd.T_out = p.Tl[i]; gd.stride = g.stride; gd.pad = g.pad; gd.Cin = g.cin;
-        if (sp) {
-            gd.arith = 1; gd.out_scale = 1.f; gd.c_sp16 = to16 ? 1 : 0; gd.guard = guard;
-            if (i == 0) gd.out_scale_dev = c->scal_pair(0) + 1;
-        }
-        if (h16) {
-            gd.arith = 2; gd.out_scale = 1.f; gd.c_f16 = 1; gd.guard = guard;
-            if (i == 0) gd.bias_scale_dev = c->scal_extra(0);
-        }
-        gd.splitk_ws = splitk_ws; gd.splitk_bytes = splitk_bytes;
+        const std::string is = std::to_string(i);
+        // conv5 in the 16-bit modes: the layers' operand buffer
+        GemmDesc gd = b.conv_gemm(i, x, (i == 5 && b.op16) ? buf("conv5_sp") : buf("conv" + is), (long long)R * p.Tl[i]);
+        gd.T_in = t_in; gd.T_out = p.Tl[i];
         // split-f16, conv0-2 at GPU-filling batches: the norm behind the conv (64 channels per group, 16 / 8 / 4 tokens per instance)
         // is applied in the GEMM's epilogue and the activation written as split-f16 pairs directly (gemm_glds.hip, GNF)
         bool fused_norm = false;
         if (sp && i < 5) {
             GemmDesc probe = gd;
             probe.c_sp16 = 1;
-            if (gemm_gn_fusable(probe, g.cout / c->cfg.n_groups, p.Tl[i])) {
+            if (gemm_gn_fusable(probe, c->conv[i].cout / c->cfg.n_groups, p.Tl[i])) {
                 const std::string np = "short_motion_encoder." + std::to_string(kNormIdx[i]);
                 gd.c_sp16 = 1;
-                gd.p[0].C = buf("act" + std::to_string(i));
-                gd.gn_gamma = W(np + ".weight"); gd.gn_beta = W(np + ".bias");
+                gd.p[0].C = buf("act" + is);
+                gd.gn_gamma = b.W(np + ".weight"); gd.gn_beta = b.W(np + ".bias");
                 gd.gn_tokens = p.Tl[i]; gd.gn_eps = 1e-5f; gd.gn_slope = 0.01f;
                 fused_norm = true;
             }
         }
         SOLA_TRY(launch_gemm(gd, s));
         if (i < 5 && !fused_norm) {
-            const std::string np = "short_motion_encoder." + std::to_string(kNormIdx[i]);
-            GroupNormDesc nd{};
-            nd.slice_ws = buf("gn_slots"); nd.slice_ws_bytes = (size_t)p.bufs.at("gn_slots").rows * p.bufs.at("gn_slots").cols * sizeof(float);
-            nd.x = buf("conv" + std::to_string(i)); nd.y = buf("act" + std::to_string(i));
-            nd.gamma = W(np + ".weight"); nd.beta = W(np + ".bias");
-            nd.n_inst = R; nd.inner = 1; nd.outer_stride = p.Tl[i]; nd.inner_stride = 0; nd.tok_stride = 1;
-            nd.ntok = p.Tl[i]; nd.C = g.cout; nd.groups = c->cfg.n_groups; nd.eps = 1e-5f; nd.slope = 0.01f; nd.leaky = 1;
-            nd.out_sp16 = sp ? 1 : 0; nd.guard = guard;
-            if (h16) {
-                nd.in_f16 = 1; nd.out_f16 = 1;
-                if (i == 0) nd.in_scale_dev = c->scal_pair(0) + 1;
-            }
+            GroupNormDesc nd = b.encoder_norm(i, buf("conv" + is), buf("act" + is));
+            nd.n_inst = R; nd.inner = 1; nd.outer_stride = p.Tl[i]; nd.inner_stride = 0; nd.tok_stride = 1; nd.ntok = p.Tl[i];
             SOLA_TRY(launch_group_norm(nd, s));
         }
-        if (i < 5) x = buf("act" + std::to_string(i));
+        if (i < 5) x = buf("act" + is);
         t_in = p.Tl[i];
     }
-    if (sp && !conv5_16) SOLA_TRY(launch_cast_sp16(buf("conv5"), D, buf("conv5_sp"), D, M, D, 1.f, s));
 
     // ---- positional table; text tokens ++ negative tokens and their mean (module/module.py:143-147)
-    SOLA_TRY(launch_pos_encoding(W("positional_encoding_gaussian_matrix"), D, Tp, c->cfg.max_temporal_length, buf("pe"), s));
+    SOLA_TRY(launch_pos_encoding(b.W("positional_encoding_gaussian_matrix"), D, Tp, c->cfg.max_temporal_length, buf("pe"), s));
     // round 5, split-f16 (sola_tune "lang_shared_neg", default 1): the negative tokens' key / value rows are the same for every sample -
     // project them once (B * L + n_neg rows through the two text-side GEMMs of a layer instead of B * (L + n_neg)) and let the object ->
     // language attention read the shared rows behind each sample's L own ones.  Same products per row, same bits - from 1024 text rows on:
@@ -269,69 +401,29 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
         shared_neg = attention_shared_keys_supported(probe);
     }
     const long long lang_rows = shared_neg ? (long long)B * L + c->cfg.n_negative : (long long)B * Wn;
-    if (shared_neg) SOLA_TRY(launch_lang_concat_shared(lang, W("negative_token.weight"), buf("lang"), buf("lbar"), B, L, c->cfg.n_negative, D, s));
-    else SOLA_TRY(launch_lang_concat(lang, W("negative_token.weight"), buf("lang"), buf("lbar"), B, L, c->cfg.n_negative, D, s));
-    if (sp) SOLA_TRY(launch_cast_sp16_auto(buf("lang"), D, buf("lang_sp"), D, lang_rows, D, c->scal_pair(1), s));
-    if (h16) SOLA_TRY(launch_cast_f16(buf("lang"), D, buf("lang_sp"), D, lang_rows, D, 1.f, c->scal_pair(1), s, 6));
-    const float* const lang_in = (sp || h16) ? buf("lang_sp") : buf("lang");
+    if (shared_neg) SOLA_TRY(launch_lang_concat_shared(lang, b.W("negative_token.weight"), buf("lang"), buf("lbar"), B, L, c->cfg.n_negative, D, s));
+    else SOLA_TRY(launch_lang_concat(lang, b.W("negative_token.weight"), buf("lang"), buf("lbar"), B, L, c->cfg.n_negative, D, s));
+    const float* lang_in = buf("lang");
+    if (b.op16) {
+        SOLA_TRY(b.cast_lang(buf("lang"), buf("lang_sp"), lang_rows));
+        lang_in = buf("lang_sp");
+    }
 
     // ---- alignment layers (module/module.py:22-52)
-    const float scale = 1.0f / sqrtf((float)DH);
-    // out16: split-f16 q/k/v for the split attention kernel (the 16-bit storage mode writes f16 always, f32 ignores it)
-    auto linear3 = [&](const float* a0, const float* a1, const float* a2, int layer, int attn, int nprob, int rows, float* o0,
-                       float* o1, float* o2, int first_proj, int out_sp16, const float* a_inv_scale = nullptr) -> int {
-        static const char* pn[3] = {"q_proj", "k_proj", "v_proj"};
-        const std::string an = "object_lang_align_layers." + std::to_string(layer) + "." + kAttnLong[attn];
-        const float* as[3] = {a0, a1, a2};
-        float* os[3] = {o0, o1, o2};
-        GemmDesc gd{};
-        gd.nprob = nprob;
-        for (int j = 0; j < nprob; ++j)
-            gd.p[j] = GemmProblem{as[j], lin_w(an, pn[first_proj + j], layer, attn, first_proj + j), W(an + "." + pn[first_proj + j] + ".bias"),
-                                  nullptr, os[j], lin_inv(layer, attn, first_proj + j)};
-        gd.M = rows; gd.N = D; gd.K = D; gd.lda = D; gd.ldr = 0; gd.ldc = D;
-        if (sp) { gd.arith = 1; gd.out_scale = 1.f; gd.out_scale_dev = a_inv_scale; gd.c_sp16 = out_sp16; gd.guard = guard; }
-        if (h16) { gd.arith = 2; gd.out_scale = 1.f; gd.out_scale_dev = a_inv_scale; gd.c_f16 = 1; gd.guard = guard; }
-        gd.splitk_ws = splitk_ws; gd.splitk_bytes = splitk_bytes;
-        return launch_gemm(gd, s);
-    };
-    auto out_proj = [&](int layer, int attn, const float* resid, int resid_sp16) -> int {
-        const std::string an = "object_lang_align_layers." + std::to_string(layer) + "." + kAttnLong[attn];
-        GemmDesc gd{};
-        gd.nprob = 1;
-        gd.p[0] = GemmProblem{buf("attn"), lin_w(an, "out_proj", layer, attn, 3), W(an + ".out_proj.bias"), resid, buf("res"), lin_inv(layer, attn, 3)};
-        gd.M = M; gd.N = D; gd.K = D; gd.lda = D; gd.ldr = D; gd.ldc = D;
-        if (sp) { gd.arith = 1; gd.out_scale = 1.f; gd.r_sp16 = resid_sp16; }
-        if (h16) { gd.arith = 2; gd.out_scale = 1.f; gd.r_f16 = 1; gd.c_f16 = 1; gd.guard = guard; }
-        gd.splitk_ws = splitk_ws; gd.splitk_bytes = splitk_bytes;
-        return launch_gemm(gd, s);
-    };
-    // out16: y / y2 in the mode's 16-bit storage (split pairs or f16); f32 ignores it
-    auto gn = [&](const std::string& lp, int idx, float* y, float* y2, int out16, int n_inst, int inner, long long outer,
-                  long long inner_stride, long long tok_stride, int ntok) -> int {
-        GroupNormDesc nd{};
-        nd.slice_ws = buf("gn_slots"); nd.slice_ws_bytes = (size_t)p.bufs.at("gn_slots").rows * p.bufs.at("gn_slots").cols * sizeof(float);
-        nd.x = buf("res"); nd.y = y; nd.y2 = y2; nd.pe = y2 ? buf("pe") : nullptr;
-        nd.gamma = W(lp + "norm." + std::to_string(idx) + ".weight");
-        nd.beta = W(lp + "norm." + std::to_string(idx) + ".bias");
-        nd.n_inst = n_inst; nd.inner = inner; nd.outer_stride = outer; nd.inner_stride = inner_stride;
-        nd.tok_stride = tok_stride; nd.ntok = ntok; nd.C = D; nd.groups = c->cfg.n_groups_module;
-        nd.eps = 1e-5f; nd.slope = 0.f; nd.leaky = 0; nd.guard = guard;
-        if (sp) nd.out_sp16 = out16;
-        if (h16) { nd.in_f16 = 1; nd.out_f16 = out16; }
-        return launch_group_norm(nd, s);
-    };
-    auto attention = [&](const float* q, const float* k, const float* v, int G, int Sq, int Sk, int inner, long long qo,
-                         long long qi, long long qr, long long ko, long long ki, long long kr, int in_sp16, int k_private = 0,
+    auto attention = [&](const float* q, const float* k, const float* v, int G, int Sq, int Sk, int inner, long long qo, long long qi,
+                         long long qr, long long ko, long long ki, long long kr, int in_sp16, int k_private = 0,
                          long long k_shared_row = 0) -> int {
-        AttnDesc ad{q, k, v, buf("attn"), D, D, D, D, G, H, DH, Sq, Sk, inner, qo, qi, qr, ko, ki, kr, scale, nullptr};
-        ad.k_private = k_private;
-        ad.k_shared_row = k_shared_row;
-        ad.o_sp16 = sp ? 1 : 0;
-        ad.in_sp16 = in_sp16;
-        ad.guard = guard;
-        ad.split_math = sp ? 1 : 0;
-        return h16 ? launch_attention_f16(ad, s) : launch_attention(ad, s);
+        AttnDesc ad = b.attention(q, k, v, in_sp16);
+        ad.G = G; ad.Sq = Sq; ad.Sk = Sk; ad.inner = inner;
+        ad.q_outer = qo; ad.q_inner = qi; ad.q_rs = qr; ad.k_outer = ko; ad.k_inner = ki; ad.k_rs = kr;
+        ad.k_private = k_private; ad.k_shared_row = k_shared_row;
+        return b.launch(ad);
+    };
+    auto gn = [&](int layer, int idx, float* y, float* y2, int out16, int n_inst, int inner, long long outer, long long inner_stride,
+                  long long tok_stride, int ntok) -> int {
+        GroupNormDesc nd = b.layer_norm(layer, idx, y, y2, out16);
+        nd.n_inst = n_inst; nd.inner = inner; nd.outer_stride = outer; nd.inner_stride = inner_stride; nd.tok_stride = tok_stride; nd.ntok = ntok;
+        return launch_group_norm(nd, s);
     };
     // split-f16: q/k/v leave the projection GEMM already split when the attention that reads them runs the split-f16 MFMA shape.
     // Measured (tools/attn_probe.py): with <= 64 keys per unit the exact-f32 MFMA kernel is as fast or faster (the kernel is then
@@ -340,38 +432,33 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
     const int mot_sp = (sp && Tp > g_attn_split_min_keys && Tp > 16 && DH % 16 == 0) ? 1 : 0;
     const int o2l_sp = (sp && Wn > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;
 
-    const float* xin = (sp || h16) ? buf("conv5_sp") : buf("conv5");  // A operand of the layer
-    const float* xres = conv5_16 ? buf("conv5_sp") : buf("conv5");     // residual of the first sub-block
-    int xres_sp = conv5_16 ? 1 : 0;
+    const float* xin = b.op16 ? buf("conv5_sp") : buf("conv5");  // A operand of the layer and residual of its first sub-block
+    float *q = buf("q"), *k = buf("k"), *v = buf("v");
     for (int l = 0; l < c->cfg.n_layers; ++l) {
-        const std::string lp = "object_lang_align_layers." + std::to_string(l) + ".";
         const std::string ls = "l" + std::to_string(l);
         const bool last = l + 1 == c->cfg.n_layers;
-        float *q = buf("q"), *k = buf("k"), *v = buf("v");
         float* x_obj = buf(ls + "_obj");
         float* x_pe = buf(ls + "_xpe");
         float* x_mot = buf(ls + "_motion");
         float* x_o2l = buf(ls + "_o2l");
         // (i) inter-object attention over the N tracks of each (b, t'): module.py:31-35
-        SOLA_TRY(linear3(xin, xin, xin, l, 0, 3, M, q, k, v, 0, obj_sp));
+        SOLA_TRY(b.linear3(xin, xin, xin, l, 0, 3, M, q, k, v, 0, obj_sp));
         SOLA_TRY(attention(q, k, v, B * Tp, N, N, Tp, (long long)N * Tp, 1, Tp, (long long)N * Tp, 1, Tp, obj_sp));
-        SOLA_TRY(out_proj(l, 0, xres, xres_sp));
-        SOLA_TRY(gn(lp, 0, x_obj, x_pe, 1, B * Tp, Tp, (long long)N * Tp, 1, Tp, N));
+        SOLA_TRY(b.out_proj(l, 0, M, xin));
+        SOLA_TRY(gn(l, 0, x_obj, x_pe, 1, B * Tp, Tp, (long long)N * Tp, 1, Tp, N));
         // (ii) motion attention over T' per track, PE on q and k only: module.py:38-43
-        SOLA_TRY(linear3(x_pe, x_pe, x_obj, l, 1, 3, M, q, k, v, 0, mot_sp));
+        SOLA_TRY(b.linear3(x_pe, x_pe, x_obj, l, 1, 3, M, q, k, v, 0, mot_sp));
         SOLA_TRY(attention(q, k, v, B * N, Tp, Tp, 1, (long long)Tp, 0, 1, (long long)Tp, 0, 1, mot_sp));
-        SOLA_TRY(out_proj(l, 1, x_obj, 1));
-        SOLA_TRY(gn(lp, 1, x_mot, nullptr, 1, B * N, 1, Tp, 0, 1, Tp));
+        SOLA_TRY(b.out_proj(l, 1, M, x_obj));
+        SOLA_TRY(gn(l, 1, x_mot, nullptr, 1, B * N, 1, Tp, 0, 1, Tp));
         // (iii) object -> language cross attention: module.py:46-50
-        SOLA_TRY(linear3(x_mot, nullptr, nullptr, l, 2, 1, M, q, nullptr, nullptr, 0, o2l_sp));
-        SOLA_TRY(linear3(lang_in, lang_in, nullptr, l, 2, 2, (int)lang_rows, buf("lk"), buf("lv"), nullptr, 1, o2l_sp, c->scal_pair(1) + 1));
+        SOLA_TRY(b.linear3(x_mot, nullptr, nullptr, l, 2, 1, M, q, nullptr, nullptr, 0, o2l_sp));
+        SOLA_TRY(b.linear3(lang_in, lang_in, nullptr, l, 2, 2, lang_rows, buf("lk"), buf("lv"), nullptr, 1, o2l_sp, b.lang_inv_scale()));
         if (shared_neg) SOLA_TRY(attention(q, buf("lk"), buf("lv"), B, N * Tp, Wn, 1, (long long)N * Tp, 0, 1, (long long)L, 0, 1, o2l_sp, L, (long long)B * L));
         else SOLA_TRY(attention(q, buf("lk"), buf("lv"), B, N * Tp, Wn, 1, (long long)N * Tp, 0, 1, (long long)Wn, 0, 1, o2l_sp));
-        SOLA_TRY(out_proj(l, 2, x_mot, 1));
-        SOLA_TRY(gn(lp, 2, x_o2l, nullptr, last ? 0 : 1, B, 1, (long long)N * Tp, 0, 1, N * Tp));  // the score head reads f32
+        SOLA_TRY(b.out_proj(l, 2, M, x_mot));
+        SOLA_TRY(gn(l, 2, x_o2l, nullptr, last ? 0 : 1, B, 1, (long long)N * Tp, 0, 1, N * Tp));  // the score head reads f32
         xin = x_o2l;
-        xres = x_o2l;
-        xres_sp = 1;
     }
 
     // ---- score head (module/module.py:152-160)
@@ -379,5 +466,203 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
     SOLA_TRY(launch_score_head(hd, s));
     c->last = p;
     c->last_obj = nullptr;
+    return SOLA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// ragged batch (sola_forward_ragged): many (video, expression) samples of DIFFERENT shapes in one pass.
+//
+// The reference scores one sample per call (configs/mevis/default.yaml:37,42,47 batch_size 1; inference.py:44-58,
+// evaluator.py:88-112): per-sample N tracks, T frames, L text tokens.  At one sample per launch the GPU runs 0.5-1.3 ms
+// per call at a few percent of its rate; here the token rows of all samples are concatenated, the dense contractions run
+// as ONE GEMM over all rows, and everything whose extent depends on the sample (conv windows along T, GroupNorm statistics,
+// the three attentions, the score head) takes per-unit descriptors built on the device from the (N, T, L) arrays (ragged.hip) -
+// no padding, so no statistic or softmax ever sees a token that is not the sample's own.
+//
+// Two levels:
+//   videos  (object sets): N_v tracks x T_v frames of object tokens;
+//   samples (video, expression): index of a video + L_i text tokens.
+// Everything that does not depend on the text is computed once per VIDEO and shared by its expressions
+// (inference.py:44-58 re-runs it per expression): the motion encoder and layer 0's inter-object and motion sub-blocks,
+// 9.3 of the 16.4 GFLOP per sample at the headline shape.  The text enters at layer 0's object->language attention
+// (module/module.py:46-50); from there on the rows are per sample (a row gather repeats the video's activations).
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct RagPlan {
+    std::unordered_map<std::string, size_t> off;
+    size_t total = 0;
+    size_t add(const std::string& name, size_t bytes) {
+        const size_t o = total;
+        off[name] = o;
+        total += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+constexpr size_t kRagSplitkBytes = (size_t)8192 * 4096 * sizeof(float);
+
+RagPlan rag_plan(const SolaCtx* c, const RagShape& r, int precision) {  // `precision`: the arithmetic the plan is sized for (the ctx's, or 0 for the guard's exact-f32 repeat)
+    RagPlan p;
+    const size_t D = c->cfg.lang_token_dim, f = sizeof(float);
+    const bool sp = precision >= 1;  // split-f16 or plain-f16 copies of the caller's tensors
+    p.add("tables", rag_tables_bytes(r, false));
+    for (int i = 0; i < 6; ++i) {
+        p.add("conv" + std::to_string(i), (size_t)r.rows[i + 1] * c->conv[i].cout * f);
+        if (i < 5) p.add("act" + std::to_string(i), (size_t)r.rows[i + 1] * c->conv[i].cout * f);
+    }
+    if (sp) p.add("obj_sp", (size_t)r.rows[0] * c->cfg.object_token_dim * f);
+    const size_t Mmax = (size_t)std::max(r.Mv, r.Ms);
+    if (Mmax <= 8192) p.add("splitk", kRagSplitkBytes);
+    p.add("pe", (size_t)r.maxT[6] * D * f);
+    p.add("gn_slots", rag_gn_slots_bytes(r));  // sliced GroupNorm shape: 8 B per (unit, slice)
+    p.add("lang", (size_t)r.LW * D * f);
+    if (sp) p.add("lang_sp", (size_t)r.LW * D * f);
+    p.add("lbar", (size_t)r.S * D * f);
+    p.add("lk", (size_t)r.LW * D * f);
+    p.add("lv", (size_t)r.LW * D * f);
+    for (const char* nm : {"q", "k", "v", "attn", "res"}) p.add(nm, Mmax * D * f);
+    p.add("v_obj", (size_t)r.Mv * D * f);
+    p.add("v_xpe", (size_t)r.Mv * D * f);
+    p.add("v_motion", (size_t)r.Mv * D * f);
+    if (!r.identity) p.add("s_motion0", (size_t)r.Ms * D * f);
+    p.add("s0_o2l", (size_t)r.Ms * D * f);
+    for (int l = 1; l < c->cfg.n_layers; ++l) {
+        const std::string ls = "s" + std::to_string(l);
+        p.add(ls + "_obj", (size_t)r.Ms * D * f);
+        p.add(ls + "_xpe", (size_t)r.Ms * D * f);
+        p.add(ls + "_motion", (size_t)r.Ms * D * f);
+        p.add(ls + "_o2l", (size_t)r.Ms * D * f);
+    }
+    return p;
+}
+
+}  // namespace
+
+size_t sola_ragged_workspace_bytes_impl(const SolaCtx* c, const SolaRaggedBatch* b, int precision) {
+    RagShape r;
+    if (!c || rag_shape(c, b, r) != SOLA_OK) return 0;
+    return rag_plan(c, r, precision).total;
+}
+
+int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, const SolaRaggedBatch* batch, float* score_map,
+                             float* score_tokens, void* workspace, size_t ws_bytes, hipStream_t s) {
+    SOLA_ARG(c && obj && lang && batch && score_map && score_tokens && workspace, "forward_ragged: null argument");
+    InferBuilder b(c, s);
+    SOLA_TRY(b.check_mode());
+    const bool sp = b.sp;
+    RagShape r;
+    SOLA_TRY(rag_shape(c, batch, r));
+    const RagPlan p = rag_plan(c, r, c->precision);
+    SOLA_TRY(sola_check_forward_args(c, "forward_ragged", p.total, workspace, ws_bytes));
+    char* base = static_cast<char*>(workspace);
+    auto raw = [&](const std::string& name) { return base + p.off.at(name); };
+    auto buf = [&](const std::string& name) { return reinterpret_cast<float*>(raw(name)); };
+    b.use_workspace(p.off.count("splitk") ? buf("splitk") : nullptr, kRagSplitkBytes, raw("gn_slots"), rag_gn_slots_bytes(r), buf("pe"), buf("attn"),
+                    buf("res"));
+    const int D = b.D, DH = b.DH, S = r.S;
+
+    // ---- descriptors -> device, unit tables
+    RagTables rt;
+    SOLA_TRY(rag_build_tables(c, r, raw("tables"), false, &rt, s));
+
+    SOLA_TRY(b.prepare_weights());
+
+    // ---- encoder over the videos' tracks (module/module.py:74-96,137-140)
+    const float* x = obj;
+    if (b.op16) {
+        SOLA_TRY(b.cast_obj(obj, buf("obj_sp"), r.rows[0]));
+        x = buf("obj_sp");
+    }
+    for (int i = 0; i < 6; ++i) {
+        const std::string is = std::to_string(i);
+        // conv5 is written in the mode's operand format into its own buffer
+        GemmDesc gd = b.conv_gemm(i, x, buf("conv" + is), r.rows[i + 1]);
+        gd.T_in = 1; gd.T_out = 1;
+        if (gd.conv) gd.rowmap = rt.rowmap[i];
+        SOLA_TRY(launch_gemm(gd, s));
+        if (i < 5) {
+            GroupNormDesc nd = b.encoder_norm(i, buf("conv" + is), buf("act" + is));
+            nd.n_inst = r.NT; nd.inner = 1; nd.tok_stride = 1; nd.units = rt.u_lvl[i + 1]; nd.ntok = r.maxT[i + 1];
+            SOLA_TRY(launch_group_norm(nd, s));
+            x = buf("act" + is);
+        }
+    }
+    const int maxTp = r.maxT[6];
+    SOLA_TRY(launch_pos_encoding(b.W("positional_encoding_gaussian_matrix"), D, maxTp, c->cfg.max_temporal_length, buf("pe"), s));
+    SOLA_TRY(launch_lang_concat_ragged(lang, b.W("negative_token.weight"), buf("lang"), buf("lbar"), S, rt.u_lang, c->cfg.n_negative, D, s));
+    const float* lang_in = buf("lang");
+    if (b.op16) {
+        SOLA_TRY(b.cast_lang(buf("lang"), buf("lang_sp"), r.LW));
+        lang_in = buf("lang_sp");
+    }
+
+    auto attention = [&](const float* q, const float* k, const float* v, int G, const int4* qu, const int4* ku, int maxSq, int maxSk,
+                         int in_sp16) -> int {
+        AttnDesc ad = b.attention(q, k, v, in_sp16);
+        ad.G = G; ad.Sq = maxSq; ad.Sk = maxSk; ad.inner = 1; ad.q_rs = 1; ad.k_rs = 1;
+        ad.q_units = qu; ad.k_units = ku;
+        return b.launch(ad);
+    };
+    auto gn = [&](int layer, int idx, float* y, float* y2, int out16, const int4* units, int n_inst, int max_tok) -> int {
+        GroupNormDesc nd = b.layer_norm(layer, idx, y, y2, out16);
+        nd.n_inst = n_inst; nd.inner = 1; nd.tok_stride = 1; nd.units = units; nd.ntok = max_tok;
+        return launch_group_norm(nd, s);
+    };
+    // q/k/v leave the projection already split where the attention runs the split-f16 MFMA shape (units of more than
+    // g_attn_split_min_keys keys; never the packed short-sequence shape)
+    const int obj_in_sp = (sp && r.maxN > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;
+    const int mot_in_sp = (sp && maxTp > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;
+    const int o2l_in_sp = (sp && r.maxW > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;
+    float *q = buf("q"), *k = buf("k"), *v = buf("v");
+
+    // ---- layer 0, text-independent half, once per VIDEO (module/module.py:31-43)
+    {
+        const float* xin = buf("conv5");
+        const long long M = r.Mv;
+        SOLA_TRY(b.linear3(xin, xin, xin, 0, 0, 3, M, q, k, v, 0, obj_in_sp));
+        SOLA_TRY(attention(q, k, v, r.sumTpV, rt.u_vt, nullptr, r.maxN, r.maxN, obj_in_sp));
+        SOLA_TRY(b.out_proj(0, 0, M, xin));
+        SOLA_TRY(gn(0, 0, buf("v_obj"), buf("v_xpe"), 1, rt.u_vt, r.sumTpV, r.maxN));
+        SOLA_TRY(b.linear3(buf("v_xpe"), buf("v_xpe"), buf("v_obj"), 0, 1, 3, M, q, k, v, 0, mot_in_sp));
+        SOLA_TRY(attention(q, k, v, r.NT, rt.u_lvl[6], nullptr, maxTp, maxTp, mot_in_sp));
+        SOLA_TRY(b.out_proj(0, 1, M, buf("v_obj")));
+        SOLA_TRY(gn(0, 1, buf("v_motion"), nullptr, 1, rt.u_lvl[6], r.NT, maxTp));
+    }
+    // ---- from here on rows are per SAMPLE: repeat the video's activations for each of its expressions
+    const float* x_mot = buf("v_motion");
+    if (!r.identity) {
+        SOLA_TRY(launch_gather_rows(buf("v_motion"), buf("s_motion0"), rt.u_gather, S, b.h16 ? D / 2 : D, r.Ms, s));  // f16 rows: D halfs
+        x_mot = buf("s_motion0");
+    }
+    const long long M = r.Ms;
+    const float* xin = nullptr;
+    for (int l = 0; l < c->cfg.n_layers; ++l) {
+        const std::string ls = "s" + std::to_string(l);
+        const bool last = l + 1 == c->cfg.n_layers;
+        if (l > 0) {
+            float* x_obj = buf(ls + "_obj");
+            float* x_pe = buf(ls + "_xpe");
+            SOLA_TRY(b.linear3(xin, xin, xin, l, 0, 3, M, q, k, v, 0, obj_in_sp));
+            SOLA_TRY(attention(q, k, v, r.sumTpS, rt.u_st, nullptr, r.maxN, r.maxN, obj_in_sp));
+            SOLA_TRY(b.out_proj(l, 0, M, xin));
+            SOLA_TRY(gn(l, 0, x_obj, x_pe, 1, rt.u_st, r.sumTpS, r.maxN));
+            SOLA_TRY(b.linear3(x_pe, x_pe, x_obj, l, 1, 3, M, q, k, v, 0, mot_in_sp));
+            SOLA_TRY(attention(q, k, v, r.sumNS, rt.u_strk, nullptr, maxTp, maxTp, mot_in_sp));
+            SOLA_TRY(b.out_proj(l, 1, M, x_obj));
+            SOLA_TRY(gn(l, 1, buf(ls + "_motion"), nullptr, 1, rt.u_strk, r.sumNS, maxTp));
+            x_mot = buf(ls + "_motion");
+        }
+        // object -> language attention (module/module.py:46-50)
+        float* x_o2l = buf(ls + "_o2l");
+        SOLA_TRY(b.linear3(x_mot, nullptr, nullptr, l, 2, 1, M, q, nullptr, nullptr, 0, o2l_in_sp));
+        SOLA_TRY(b.linear3(lang_in, lang_in, nullptr, l, 2, 2, r.LW, buf("lk"), buf("lv"), nullptr, 1, o2l_in_sp, b.lang_inv_scale()));
+        SOLA_TRY(attention(q, buf("lk"), buf("lv"), S, rt.u_smp, rt.u_langk, r.maxRowsSample, r.maxW, o2l_in_sp));
+        SOLA_TRY(b.out_proj(l, 2, M, x_mot));
+        SOLA_TRY(gn(l, 2, x_o2l, nullptr, last ? 0 : 1, rt.u_smp, S, r.maxRowsSample));  // the score head reads f32
+        xin = x_o2l;
+    }
+    HeadDesc hd{xin, buf("lbar"), score_map, score_tokens, 1, r.sumNS, maxTp, D};
+    hd.units = rt.u_strk;
+    SOLA_TRY(launch_score_head(hd, s));
     return SOLA_OK;
 }

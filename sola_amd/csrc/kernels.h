@@ -224,6 +224,7 @@ struct AttnDesc {
     bool* o_cast_done = nullptr;
 };
 int launch_attention(const AttnDesc& d, hipStream_t s);
+int launch_attention_f16(const AttnDesc& d, hipStream_t s);  // the 16-bit storage mode's kernels (attn_f16.hip): q / k / v / o are _Float16 rows
 bool attention_in_bf16_supported(const AttnDesc& d);   // attn_simple.hip's f32-MFMA kernel on bfloat16 rows
 bool attention_bf16_mfma_supported(const AttnDesc& d);  // attn_f16.hip's bf16-MFMA training kernel (the default where it applies)
 bool attention_shared_keys_supported(const AttnDesc& d);  // d.k_private / k_shared_row can be honoured (the launch then takes attn_res.hip's shape)

@@ -1,6 +1,6 @@
 // Ragged batches (samples of different N tracks x T frames x L text tokens in one pass): host-side shape bookkeeping and the
-// device tables every shape-dependent kernel reads.  Shared by the ragged inference forward (forward_ragged.hip) and the
-// ragged training step (forward.hip / backward.hip with a RagTables argument).
+// device tables every shape-dependent kernel reads (ragged.hip).  Shared by the ragged inference forward (forward_infer.hip) and
+// the ragged training step (forward.hip / backward.hip with a RagTables argument).
 //
 // The reference handles one sample per call (configs/mevis/default.yaml:37,42,47 batch_size 1; train.py:62-137,
 // inference.py:44-58); here the token rows of all samples are concatenated and what depends on a sample's extent is
