@@ -573,6 +573,35 @@ int sola_png_deflate_sizes(const void* dev_masks, int elem_type, int n, int h, i
 int sola_png_deflate_write(const void* dev_masks, int elem_type, int n, int h, int w, const int64_t* dev_byte_off,
                            const uint32_t* dev_adler, uint8_t* dev_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* Connected components of the set pixels of n independent frames [n,h,w] (row-major), and the fused rewrite of the small
+ * ones: what SAM2's fill_holes_in_mask_scores needs in front of the `> 0` threshold.  connectivity 8 or 4; n*h*w < 2^31
+ * and at most 2^24 - 1 tiles of SOLA_CC_TILE_W x SOLA_CC_TILE_H in one call.  elem_type: 0 = uint8 != 0, 1 = float32 != 0,
+ * 2 = float32 logits > 0, 3 = background of float32 scores: x <= 0 (-0.0 is set, NaN is not), 4 = uint8 == 0 and
+ * 5 = float32 == 0: the complement of kinds 0 / 1, taken on read (hole filling).
+ *   sola_mask_components: labels, areas int32 [n,h,w].  labels = 0 on clear pixels, else 1 + (y*w + x) of the component's
+ *     first pixel in raster order within its own frame; areas = 0 on clear pixels, else the pixel count of the pixel's
+ *     component.  Pure functions of the input (integer atomics only): identical from run to run and on any stream.
+ *   sola_mask_fill_small: out (the element type of in; may alias in) = in, except on the pixels of set components of at
+ *     most max_area pixels.  Kind 3: those become fill_value, and every other float passes through bit for bit (NaN and
+ *     both zeros included).  Kinds 0, 1, 2: they become 0 (island removal).  Kinds 4, 5: they become 1 (hole filling).
+ *     fill_value is read for kind 3 only.  Labels and areas are never materialised for the caller.
+ *   sola_mask_fill_small_profile: the same call, then a wait for the stream; launch_us [4] (host) = the time of its four
+ *     launches (tile labelling, tile borders, flatten + counts, rewrite) between HIP events.  Bench tools only.
+ * dev_scratch: >= sola_mask_components_scratch_bytes(n,h,w) = 8*n*h*w rounded up to 256 bytes (0 for empty or refused
+ * sizes; host-only), 4-byte aligned.  It is written before it is read: nothing depends on what it held.  Asynchronous on
+ * the stream.  Refused before any launch: connectivity other than 4 / 8, max_area < 0, a short scratch, n*h*w >= 2^31.  Any
+ * of n, h, w equal to 0 is a successful no-op. */
+#define SOLA_CC_TILE_W 64
+#define SOLA_CC_TILE_H 16
+size_t sola_mask_components_scratch_bytes(int n, int h, int w);
+int sola_mask_components(const void* dev_masks, int elem_type, int n, int h, int w, int connectivity, int32_t* dev_labels,
+                         int32_t* dev_areas, void* dev_scratch, size_t scratch_bytes, void* stream);
+int sola_mask_fill_small(const void* dev_in, int elem_type, int n, int h, int w, int connectivity, int64_t max_area,
+                         float fill_value, void* dev_out, void* dev_scratch, size_t scratch_bytes, void* stream);
+int sola_mask_fill_small_profile(const void* dev_in, int elem_type, int n, int h, int w, int connectivity, int64_t max_area,
+                                 float fill_value, void* dev_out, void* dev_scratch, size_t scratch_bytes, void* stream,
+                                 float* launch_us);
+
 /* ---- in-library kernel timing (HIP events on the launch stream; used by bench.py's roofline object) ------------ */
 enum { SOLA_PROF_GEMM = 0,      /* gemm_nt_f32_kernel<128,128> */
        SOLA_PROF_ATTN = 1,      /* attn_fwd_f32_kernel */

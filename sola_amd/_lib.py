@@ -141,6 +141,10 @@ SIGNATURES = {
     "sola_png_deflate_scratch_bytes": (_sz, [_i, _i, _i]),
     "sola_png_deflate_sizes": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sola_png_deflate_write": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sola_mask_components_scratch_bytes": (_sz, [_i, _i, _i]),
+    "sola_mask_components": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "sola_mask_fill_small": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _f, _vp, _vp, _sz, _vp]),
+    "sola_mask_fill_small_profile": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _f, _vp, _vp, _sz, _vp, C.POINTER(_f)]),
     "sola_mask_iou_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "sola_mask_iou_matrix": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sola_grad_sqnorms_scratch_bytes": (_sz, [_i, _vp]),

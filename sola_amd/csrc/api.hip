@@ -1170,6 +1170,28 @@ extern "C" int sola_png_deflate_write(const void* masks, int elem_type, int n, i
                                     scratch_bytes, as_stream(stream_));
 }
 
+// connected components / small-component rewrite (components.hip)
+extern "C" size_t sola_mask_components_scratch_bytes(int n, int h, int w) { return components_scratch_bytes(n, h, w); }
+
+extern "C" int sola_mask_components(const void* masks, int elem_type, int n, int h, int w, int connectivity, int32_t* labels,
+                                    int32_t* areas, void* scratch, size_t scratch_bytes, void* stream_) {
+    return launch_mask_components(masks, elem_type, n, h, w, connectivity, labels, areas, scratch, scratch_bytes, as_stream(stream_));
+}
+
+extern "C" int sola_mask_fill_small(const void* in, int elem_type, int n, int h, int w, int connectivity, int64_t max_area,
+                                    float fill_value, void* out, void* scratch, size_t scratch_bytes, void* stream_) {
+    return launch_mask_fill_small(in, elem_type, n, h, w, connectivity, max_area, fill_value, out, scratch, scratch_bytes,
+                                  as_stream(stream_), nullptr);
+}
+
+extern "C" int sola_mask_fill_small_profile(const void* in, int elem_type, int n, int h, int w, int connectivity, int64_t max_area,
+                                            float fill_value, void* out, void* scratch, size_t scratch_bytes, void* stream_,
+                                            float* launch_us) {
+    SOLA_ARG(launch_us, "mask_fill_small_profile: null launch_us");
+    return launch_mask_fill_small(in, elem_type, n, h, w, connectivity, max_area, fill_value, out, scratch, scratch_bytes,
+                                  as_stream(stream_), launch_us);
+}
+
 // Host helper (no GPU work): COCO compressed run-length string -> inclusive prefix sums of the run lengths, the form
 // sola_rle_fill_or consumes.  pycocotools rleFrString: 5 data bits + continuation bit per char (offset 48), sign
 // extension from bit 4 of the last char, runs from the 4th on stored as a delta to the run two places back.

@@ -494,3 +494,11 @@ int launch_png_deflate_sizes(const void* masks, int elem_type, int n, int h, int
                              void* scratch, size_t scratch_bytes, hipStream_t s);
 int launch_png_deflate_write(const void* masks, int elem_type, int n, int h, int w, const long long* byte_off,
                              const uint32_t* adler, uint8_t* bytes, void* scratch, size_t scratch_bytes, hipStream_t s);
+
+// ---- connected components of masks, small-component rewrite (components.hip) --------------------------------------
+size_t components_scratch_bytes(int n, int h, int w);
+int launch_mask_components(const void* masks, int elem_type, int n, int h, int w, int connectivity, int32_t* labels, int32_t* areas,
+                           void* scratch, size_t scratch_bytes, hipStream_t s);
+// launch_us: nullptr, or 4 host floats = the time of each launch (the call then waits for the stream)
+int launch_mask_fill_small(const void* in, int elem_type, int n, int h, int w, int connectivity, long long max_area, float fill_value,
+                           void* out, void* scratch, size_t scratch_bytes, hipStream_t s, float* launch_us);

@@ -743,3 +743,94 @@ def encode_png_masklets(masklets, logits=False):
         out.append(flat[f:f + m.shape[0]])
         f += m.shape[0]
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# connected components, SAM2's fill_holes_in_mask_scores, small-region removal (components.hip)
+# ----------------------------------------------------------------------------------------------------------------
+CC_TILE = (16, 64)  # (rows, columns) of the labelling kernel's tile: include/sola_hip.h SOLA_CC_TILE_H / _W
+_CC_SCRATCH = {}
+
+
+def _cc_frames(t, what):
+    """[N,1,H,W] (SAM2's layout) or [N,H,W] -> contiguous [N,H,W] on the GPU and the caller's shape."""
+    shape = tuple(t.shape)
+    if not (t.dim() == 3 or (t.dim() == 4 and shape[1] == 1)):
+        raise SolaError(f"{what}: masks must be (N,1,H,W) or (N,H,W), got {shape}")
+    t = _prep(t)
+    return t.reshape(shape[0], shape[-2], shape[-1]), shape
+
+
+def _cc_scratch(dev, n, h, w, scratch):
+    nb = lib().sola_mask_components_scratch_bytes(n, h, w)
+    if scratch is not None:  # the caller's own (tests): a contiguous uint8 device tensor
+        return scratch, scratch.numel()
+    # reused from call to call like the IoU scratch: calls on one stream are ordered
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    scratch = _CC_SCRATCH.get(key)
+    if scratch is None or scratch.numel() < nb:
+        scratch = _CC_SCRATCH[key] = torch.empty(max(nb, 256), device=dev, dtype=torch.uint8)
+    return scratch, scratch.numel()
+
+
+@torch.no_grad()
+def connected_components(mask, connectivity=8, logits=False, scratch=None):
+    """The binding for ``sam2.utils.misc.get_connected_components``: mask (N,1,H,W) or (N,H,W) on the GPU, uint8 / bool /
+    float32 (set where != 0) -> ``(labels, areas)``, int32 tensors of the input's shape.  ``labels`` is 0 on clear pixels and,
+    on set pixels, 1 + (y*W + x) of the component's first pixel in raster order within its own frame; ``areas`` is 0 on
+    clear pixels and the pixel count of the pixel's component elsewhere.  The N frames are labelled independently in one
+    library call; ``connectivity`` is 8 (SAM2's) or 4; ``logits=True`` counts float32 ``> 0``."""
+    m, shape = _cc_frames(mask, "connected_components")
+    if logits and m.dtype != torch.float32:
+        raise SolaError("logits must be float32")
+    et = 2 if logits else _elem_type(m)
+    n, h, w = m.shape
+    dev = m.device
+    out = torch.empty((2, n, h, w), device=dev, dtype=torch.int32)
+    scratch, nb = _cc_scratch(dev, n, h, w, scratch)
+    check(lib().sola_mask_components(ptr(m), et, n, h, w, int(connectivity), ptr(out[0]), ptr(out[1]), ptr(scratch), nb,
+                                     current_stream(dev)), "sola_mask_components")
+    return out[0].reshape(shape), out[1].reshape(shape)
+
+
+def _fill_small(m, et, connectivity, max_area, fill_value, out, scratch):
+    n, h, w = m.shape
+    dev = m.device
+    scratch, nb = _cc_scratch(dev, n, h, w, scratch)
+    check(lib().sola_mask_fill_small(ptr(m), et, n, h, w, int(connectivity), int(max_area), float(fill_value), ptr(out), ptr(scratch),
+                                     nb, current_stream(dev)), "sola_mask_fill_small")
+    return out
+
+
+@torch.no_grad()
+def fill_holes_in_mask_scores(mask, max_area, fill_value=0.1, connectivity=8, out=None, scratch=None):
+    """The binding for ``sam2.utils.misc.fill_holes_in_mask_scores``: float32 mask scores (N,1,H,W) or (N,H,W) -> a new
+    tensor of the same shape in which every background component (scores <= 0, 8-connected) of at most ``max_area`` pixels
+    holds ``fill_value``; every other score passes through bit for bit.  ``out``: the tensor to write instead of a new one;
+    ``out=mask`` (contiguous) rewrites in place.  There is no fallback and no warning path."""
+    if max_area <= 0:
+        raise SolaError(f"fill_holes_in_mask_scores: max_area must be positive, got {max_area}")
+    if mask.dtype != torch.float32:
+        raise SolaError(f"fill_holes_in_mask_scores: scores must be float32, got {mask.dtype}")
+    m, shape = _cc_frames(mask, "fill_holes_in_mask_scores")
+    if out is None:
+        out = torch.empty_like(m)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == m.numel()):
+        raise SolaError("fill_holes_in_mask_scores: out must be a contiguous float32 device tensor of the input's size")
+    return _fill_small(m, 3, connectivity, max_area, fill_value, out, scratch).reshape(shape)
+
+
+@torch.no_grad()
+def remove_small_regions(masks, max_area, mode, connectivity=8, scratch=None):
+    """{0,1} masks (N,1,H,W) or (N,H,W), uint8 / bool / float32 -> a new tensor of the same shape and dtype.
+    ``mode="islands"``: set components of at most ``max_area`` pixels are cleared.  ``mode="holes"``: clear components of
+    at most ``max_area`` pixels are set to 1, those cut by the image border included; the complement is taken on read in
+    the kernel.  These semantics are this library's own."""
+    if mode not in ("holes", "islands"):
+        raise SolaError(f"remove_small_regions: mode must be 'holes' or 'islands', got {mode!r}")
+    if max_area < 0:
+        raise SolaError(f"remove_small_regions: max_area must not be negative, got {max_area}")
+    m, shape = _cc_frames(masks, "remove_small_regions")
+    et = _elem_type(m) + (4 if mode == "holes" else 0)
+    out = _fill_small(m, et, connectivity, max_area, 0.0, torch.empty_like(m), scratch).reshape(shape)
+    return out.view(torch.bool) if masks.dtype == torch.bool else out
