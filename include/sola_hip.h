@@ -602,6 +602,44 @@ int sola_mask_fill_small_profile(const void* dev_in, int elem_type, int n, int h
                                  float fill_value, void* dev_out, void* dev_scratch, size_t scratch_bytes, void* stream,
                                  float* launch_us);
 
+/* ---- the grid-prompt stage: what SAM2's automatic mask generator computes per mask and per box (track_generation/
+ * generate_prompts_grid.py:67,100; the stability score of prompt_generator.py:169-185) --------------------------------------
+ * sola_mask_logit_stats: n maps [n,h,w] (row-major) -> dev_stats int64 [n,7] = (n_hi, n_lo, area, x0, y0, x1, y1), from ONE
+ *   read of the maps (16-byte loads wherever the address allows, any w, any alignment of the element type).
+ *   elem_type 2 = float32 logits: a pixel counts for a threshold t when x > t (strict; NaN never counts, -0.0 does not
+ *   count at t = 0); n_hi, n_lo and area are the counts at thr_hi, thr_lo and thr.  elem_type 0 / 1 = uint8 / float32 masks,
+ *   set where != 0: all three counts are the area and the thresholds are not read.  (x0, y0, x1, y1) is the INCLUSIVE
+ *   bounding box of the pixels that count for thr; a map with none has (0, 0, 0, 0), batched_mask_to_box's convention.
+ *   SAM2's stability score is n_hi / n_lo with thr_hi = mask_threshold + offset, thr_lo = mask_threshold - offset.
+ *   Partial results meet in 64-bit integer atomics after a memset of the table on the stream (no workspace): exact in any
+ *   order, identical from run to run.  Refused before any launch: negative sizes, elem_type outside 0..2, h*w >= 2^31 (a
+ *   map is indexed in int32; n*h*w then fits 2^62), more than 2^31 - 1 pieces of 64 KiB in one call, masks not aligned to
+ *   their element.  n == 0 is a successful no-op; with n > 0 and h*w == 0 the rows are written as zeros.  Asynchronous.
+ * sola_box_nms: greedy non-maximum suppression of n boxes [n,4] float32 (x0, y0, x1, y1), 16-byte aligned.  dev_order [n]
+ *   int64 is the visiting order, a permutation of 0..n-1 (an entry outside that range is read as 0, never outside the
+ *   arrays); dev_idxs [n] int64 gives every box a category, NULL = one category.  Box order[a] is kept unless a KEPT box
+ *   order[b], b < a, of the same category has iou > iou_threshold; categories never interact (torchvision's per-category
+ *   batched_nms exactly, and its coordinate-offset form without that form's rounding).  dev_keep receives the kept original
+ *   indices in visiting order, dev_n_keep [1] their number; dev_keep beyond that is not written.  The IoU is float32, every
+ *   operation rounded on its own, in this order: area = (x1 - x0) * (y1 - y0); iw = max(0, min(x1a, x1b) - max(x0a, x0b)),
+ *   ih likewise; inter = iw * ih; iou = inter / ((area_a + area_b) - inter), a correctly rounded division.  0/0 is NaN and
+ *   does not suppress: two identical zero-area boxes both survive.  The decision equals a float32 restatement on any finite input.
+ *   Two launches: the upper triangle of the suppression bit matrix (64 boxes per word), then one workgroup that settles the
+ *   order 64 rows at a time.  dev_scratch: >= sola_box_nms_scratch_bytes(n) = n * ceil(n/64) * 8 rounded up to 256 bytes (0
+ *   for n <= 0 or n > SOLA_BOX_NMS_MAX_N; host-only), 8-byte aligned; written before it is read.  n > SOLA_BOX_NMS_MAX_N, a
+ *   negative n, a short scratch and null arguments are refused before any launch; n == 0 only writes dev_n_keep = 0.
+ *   sola_box_nms_profile: the same call, then a wait for the stream; launch_us [2] (host) = the time of the matrix and the
+ *   resolve launch between HIP events.  Bench tools only. */
+#define SOLA_BOX_NMS_MAX_N 16384
+int sola_mask_logit_stats(const void* dev_masks, int elem_type, int n, int h, int w, float thr, float thr_hi, float thr_lo,
+                          int64_t* dev_stats, void* stream);
+size_t sola_box_nms_scratch_bytes(int n);
+int sola_box_nms(const float* dev_boxes, const int64_t* dev_order, const int64_t* dev_idxs, int n, float iou_threshold,
+                 int64_t* dev_keep, int64_t* dev_n_keep, void* dev_scratch, size_t scratch_bytes, void* stream);
+int sola_box_nms_profile(const float* dev_boxes, const int64_t* dev_order, const int64_t* dev_idxs, int n, float iou_threshold,
+                         int64_t* dev_keep, int64_t* dev_n_keep, void* dev_scratch, size_t scratch_bytes, void* stream,
+                         float* launch_us);
+
 /* ---- in-library kernel timing (HIP events on the launch stream; used by bench.py's roofline object) ------------ */
 enum { SOLA_PROF_GEMM = 0,      /* gemm_nt_f32_kernel<128,128> */
        SOLA_PROF_ATTN = 1,      /* attn_fwd_f32_kernel */

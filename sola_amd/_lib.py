@@ -145,6 +145,10 @@ SIGNATURES = {
     "sola_mask_components": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sola_mask_fill_small": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _f, _vp, _vp, _sz, _vp]),
     "sola_mask_fill_small_profile": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _f, _vp, _vp, _sz, _vp, C.POINTER(_f)]),
+    "sola_mask_logit_stats": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    "sola_box_nms_scratch_bytes": (_sz, [_i]),
+    "sola_box_nms": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "sola_box_nms_profile": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp, C.POINTER(_f)]),
     "sola_mask_iou_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "sola_mask_iou_matrix": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sola_grad_sqnorms_scratch_bytes": (_sz, [_i, _vp]),

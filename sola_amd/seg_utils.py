@@ -834,3 +834,151 @@ def remove_small_regions(masks, max_area, mode, connectivity=8, scratch=None):
     et = _elem_type(m) + (4 if mode == "holes" else 0)
     out = _fill_small(m, et, connectivity, max_area, 0.0, torch.empty_like(m), scratch).reshape(shape)
     return out.view(torch.bool) if masks.dtype == torch.bool else out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the grid-prompt stage (generate_prompts_grid.py; SAM2's automatic mask generator): per-mask statistics from one read of
+# the logits, box NMS, the part filter, uncompressed RLE (amg.hip; the part filter and the RLE ride on kernels above)
+# ----------------------------------------------------------------------------------------------------------------
+NMS_MAX_BOXES = 16384  # include/sola_hip.h SOLA_BOX_NMS_MAX_N
+_NMS_SCRATCH = {}
+
+
+def _f32(x):
+    """A Python double rounded once to float32: what ``tensor_f32 > python_float`` compares against in torch and numpy."""
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
+
+
+@torch.no_grad()
+def mask_logit_stats(masks, mask_threshold=0.0, threshold_offset=1.0, logits=True):
+    """(N,H,W) or (N,1,H,W) on the GPU -> int64 [N,7] device tensor (n_hi, n_lo, area, x0, y0, x1, y1) from ONE read of the
+    masks (sola_mask_logit_stats).  ``logits=True``: float32 mask logits; the three counts are the pixels strictly above
+    mask_threshold + threshold_offset, mask_threshold - threshold_offset and mask_threshold (each sum formed in Python double
+    and rounded once to float32), NaN never counting.  ``logits=False``: uint8 / bool / float32 masks set where != 0; all
+    three counts are the area.  (x0, y0, x1, y1) is the inclusive box of the pixels counted in ``area``, (0, 0, 0, 0) for an
+    empty mask."""
+    if logits and masks.dtype != torch.float32:
+        raise SolaError(f"mask_logit_stats: logits must be float32, got {masks.dtype}")
+    et = 2 if logits else _elem_type(masks)
+    m, _ = _cc_frames(masks, "mask_logit_stats")
+    n, h, w = m.shape
+    stats = torch.empty((n, 7), device=m.device, dtype=torch.int64)
+    check(lib().sola_mask_logit_stats(ptr(m), et, n, h, w, _f32(mask_threshold), _f32(mask_threshold + threshold_offset),
+                                      _f32(mask_threshold - threshold_offset), ptr(stats), current_stream(m.device)),
+          "sola_mask_logit_stats")
+    return stats
+
+
+def calculate_stability_score(masks, mask_threshold, threshold_offset):
+    """The binding for ``sam2.utils.amg.calculate_stability_score`` (and prompt_generator.get_stability_score without its host
+    copy): float32 logits (N,H,W) / (N,1,H,W) -> float32 [N] on the device = |x > thr + off| / |x > thr - off|; 0/0 is nan,
+    as in SAM2."""
+    stats = mask_logit_stats(masks, mask_threshold, threshold_offset)
+    return stats[:, 0].float() / stats[:, 1].float()
+
+
+def batched_mask_to_box(masks):
+    """The binding for ``sam2.utils.amg.batched_mask_to_box``: bool / uint8 masks (N,H,W) or (N,1,H,W) -> int64 [N,4] XYXY
+    (inclusive corners), (0, 0, 0, 0) for an empty mask."""
+    if masks.dtype not in (torch.bool, torch.uint8):
+        raise SolaError(f"batched_mask_to_box: masks must be bool or uint8, got {masks.dtype}")
+    return mask_logit_stats(masks, logits=False)[:, 3:7]
+
+
+def box_area(boxes):
+    """torchvision.ops.boxes.box_area: [N,4] XYXY -> [N]."""
+    return (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1])
+
+
+@torch.no_grad()
+def batched_nms(boxes, scores, idxs, iou_threshold, scratch=None):
+    """torchvision.ops.boxes.batched_nms on libsola_hip.so: boxes float32 [N,4] XYXY, scores [N], idxs [N] integer categories
+    (None = one category) -> int64 indices of the kept boxes by decreasing score.  A box is dropped when a kept box of its
+    own category with a higher score overlaps it by IoU > iou_threshold (float32, include/sola_hip.h gives the order of the
+    operations); categories never interact.  The visiting order is ``torch.sort(scores, descending=True, stable=True)`` on the
+    device: boxes of equal score are visited lower index first.  That tie rule is this library's own choice; torchvision
+    leaves ties unspecified.  One host read (the number kept) per call; at most NMS_MAX_BOXES boxes."""
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise SolaError(f"nms: boxes must be [N,4], got {tuple(boxes.shape)}")
+    if boxes.dtype != torch.float32:
+        raise SolaError(f"nms: boxes must be float32, got {boxes.dtype}")
+    n = boxes.shape[0]
+    if scores.dim() != 1 or scores.shape[0] != n:
+        raise SolaError(f"nms: scores must be [{n}], got {tuple(scores.shape)}")
+    if idxs is not None:
+        if idxs.dim() != 1 or idxs.shape[0] != n:
+            raise SolaError(f"nms: idxs must be [{n}], got {tuple(idxs.shape)}")
+        if idxs.dtype.is_floating_point or idxs.dtype == torch.bool:
+            raise SolaError(f"nms: idxs must be integers, got {idxs.dtype}")
+    require_cuda(boxes, scores, idxs)
+    if idxs is not None:
+        idxs = idxs.to(torch.int64).contiguous()
+    if n > NMS_MAX_BOXES:
+        raise SolaError(f"nms: {n} boxes, at most {NMS_MAX_BOXES} in one call")
+    dev = boxes.device
+    boxes = boxes.contiguous()
+    order = torch.sort(scores, descending=True, stable=True).indices.contiguous()
+    out = torch.empty((n + 1,), device=dev, dtype=torch.int64)  # n_keep, then the kept indices
+    nb = lib().sola_box_nms_scratch_bytes(n)
+    if scratch is None:  # reused from call to call like the IoU scratch: calls on one stream are ordered
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        scratch = _NMS_SCRATCH.get(key)
+        if scratch is None or scratch.numel() * 8 < nb:
+            scratch = _NMS_SCRATCH[key] = torch.empty(max(nb // 8, 32), device=dev, dtype=torch.int64)
+    check(lib().sola_box_nms(ptr(boxes), ptr(order), ptr(idxs), n, float(iou_threshold), ptr(out[1:]), ptr(out), ptr(scratch),
+                             scratch.numel() * scratch.element_size(), current_stream(dev)), "sola_box_nms")
+    return out[1:1 + int(out[0])]  # the host read
+
+
+def nms(boxes, scores, iou_threshold):
+    """torchvision.ops.nms: batched_nms with one category."""
+    return batched_nms(boxes, scores, None, iou_threshold)
+
+
+@torch.no_grad()
+def filter_part_masks(masks, thresh=0.7):
+    """The part filter of generate_prompts_grid.py:105-116: masks (N,H,W) {0,1} on the GPU, sorted by area descending by the
+    caller -> bool [N] CPU tensor ``is_part``, element for element what the reference's loop of N-1 ``compute_P`` calls leaves.
+    All N x N intersections come from one pack launch, one pair launch and one copy (the areas are the diagonal); the
+    order-dependent loop runs on the host over the integers, with the reference's float32 ratio and comparison."""
+    import numpy as np
+    if masks.dim() != 3:
+        raise SolaError(f"filter_part_masks: masks must be (N,H,W), got {tuple(masks.shape)}")
+    _elem_type(masks)
+    masks = _prep(masks)
+    n = masks.shape[0]
+    is_part = np.zeros(n, bool)
+    if n < 2:
+        return torch.from_numpy(is_part)
+    bits, area = pack_masks(masks)
+    inter, _ = pair_counts(bits, area, bits, area)
+    inter = inter.cpu().numpy()  # inter[p, f] = |mask p & mask f|
+    area = np.diagonal(inter).astype(np.float32)
+    t = np.float32(thresh)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for full in range(n - 1):
+            if is_part[full]:
+                continue
+            P = inter[:, full].astype(np.float32) / area  # 0/0 = nan: never marked
+            is_part[P > t] = True
+            is_part[full] = False
+    return torch.from_numpy(is_part)
+
+
+@torch.no_grad()
+def mask_to_rle_uncompressed(masks, logits=False):
+    """``sam2.utils.amg.mask_to_rle_pytorch``: (N,h,w) masks on the GPU -> list of ``{"size": [h, w], "counts": [int, ...]}``,
+    the runs of the column-major flattening starting with a (possibly empty) run of zeros.  Built from
+    encode_rle_masklet(..., return_cum=True): one copy of the prefix sums and offsets, differences on the host."""
+    import numpy as np
+    cum, run_off = encode_rle_masklet(masks, logits, return_cum=True)
+    n, h, w = masks.shape
+    if n == 0:
+        return []
+    both = torch.cat([run_off, cum.to(torch.int64) & 0xFFFFFFFF]).cpu().numpy()  # (cum holds uint32 in int32)
+    off, c = both[:n + 1], both[n + 1:]
+    out = []
+    for i in range(n):
+        ends = c[off[i]:off[i + 1]]  # ends with h*w: the last run closes the frame
+        out.append({"size": [h, w], "counts": np.diff(ends, prepend=0).tolist()})
+    return out
