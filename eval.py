@@ -22,9 +22,13 @@ F: every entry gains ``F_boundary`` (mean over frames of the DAVIS contour F-mea
 ground truth, each matched against the other dilated by a disk of ``boundary_th`` of the image diagonal; no void pixels)
 and ``JF_boundary`` = (J + F_boundary) / 2, track_metrics.json and the printed line ``mean_F_boundary`` /
 ``mean_JF_boundary`` / ``boundary_th``, from one more launch on the planes the J pass decoded
-(sola_mask_select_boundary_counts).  J&F needs mask ground truth: MeViS with a ``mask_dict.json``.  Without it
-(synthetic data, the MeViS ``valid`` test split, Ref-DAVIS, whose reference GT loader gives every object the last object's
-masks) or with ``--jf false`` one line says why J&F was skipped and the outputs are the loss / track metrics alone.
+(sola_mask_select_boundary_counts).  J&F needs mask ground truth: MeViS with a ``mask_dict.json`` (COCO RLE), or Ref-DAVIS
+with its ``Annotations/<video>/`` folders of palette PNGs, whose index maps are uploaded once per video and turned into the
+same planes on the GPU (sola_index_pack; object k's ground truth is ``maps == k``, not the reference loader's, which gives
+every object the last object's masks).  A video whose tracks and annotation differ in their number of frames raises a
+RuntimeError naming the video and both counts.  Without ground truth (synthetic data, the MeViS ``valid`` test split,
+Ref-YouTube-VOS, whose valid split has no public annotation) or with ``--jf false`` one line says why J&F was skipped and
+the outputs are the loss / track metrics alone.
 
 BCE convention: ``bce`` / ``total`` follow train.py:98-113 (BCE-with-logits on the LOGITS, what the
 network is trained and validated with).  The reference's evaluator applies binary_cross_entropy_with_logits to the
@@ -52,10 +56,8 @@ def jf_skip_reason(cfg, ds):
         return "--jf false"
     if cfg.get("synthetic", False):
         return "synthetic tracks have no masks"
-    if getattr(ds, "data_name", None) == "ref-davis":
-        return "Ref-DAVIS mask ground truth is not supported"
     if not getattr(ds, "has_mask_gt", False):
-        return f"no mask ground truth (mask_dict.json) for {getattr(ds, 'data_type', 'this split')}"
+        return f"no mask ground truth (mask_dict.json / Annotations) for {getattr(ds, 'data_type', 'this split')}"
     return None
 
 
@@ -99,7 +101,11 @@ def jf_entries(ds, rows, device, boundary=None):
                 raise RuntimeError(f"{vid}/{eid}: {len(tracks)} track files but {len(sel)} predictions")
             ids = [idx(t) for t in tracks]
             pred_sets.append([ids[j] for j in np.flatnonzero(sel)])
-            gt_sets.append([idx(g) for g in ds.gt_rles(vid, eid)])
+            gts = ds.gt_masklets(vid, eid, device)
+            for g in gts:  # (an RLE list from mask_dict.json and an annotation folder are checked alike)
+                if tracks and len(tracks[0]) != len(g):
+                    raise RuntimeError(f"{vid}: the tracks have {len(tracks[0])} frames but the annotation has {len(g)}")
+            gt_sets.append([idx(g) for g in gts])
             no_tracks.append(not tracks)
         keys = ("J", "F", "JF") if boundary is None else ("J", "F", "JF", "F_boundary", "JF_boundary")
         scores = (seg_utils.compute_JF_batch(masklets, pred_sets, gt_sets, device, boundary=boundary) if masklets

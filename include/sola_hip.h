@@ -640,6 +640,35 @@ int sola_box_nms_profile(const float* dev_boxes, const int64_t* dev_order, const
                          int64_t* dev_keep, int64_t* dev_n_keep, void* dev_scratch, size_t scratch_bytes, void* stream,
                          float* launch_us);
 
+/* ---- index maps -> bit planes: the palette-PNG ground truth of Ref-DAVIS / Ref-YouTube-VOS (dataloader.py:260-276
+ * load_gt_masklet; track_generation/seg_utils.py:29-49 get_masklets_ytbvos) -----------------------------------------------
+ * dev_idx: T maps [T,h,w] of uint8 (row-major), the value of a pixel is its object id; any w, any alignment of the base.
+ * sola_index_hist: dev_counts int64 [T,256] = the pixels of every value in every frame, from ONE read of the maps (16-byte
+ *   loads wherever the address allows).  Per-block LDS histograms meet in 64-bit integer atomics after a memset of the table
+ *   on the stream (no workspace): exact in any order, identical from run to run, also when a frame holds a single value.
+ *   T == 0 is a successful no-op; with T > 0 and h*w == 0 the table is written as zeros.
+ * sola_index_pack: plane (dev_first_plane ? dev_first_plane[k] : k*T) + t of dev_bits [planes, words_stride] receives
+ *   (idx[t] == dev_ids[k]) for every k < K, t < T; the maps are read once for all K ids (the ids are taken
+ *   SOLA_INDEX_ID_CHUNK at a time; a longer list loops inside the launch).  dev_ids / dev_first_plane: int32 [K] on the
+ *   device.  An id outside 0..255 gives empty planes; 0 and 255 are ordinary values; ids may repeat.  dev_first_plane lets
+ *   the planes fall into rows of a buffer whose other rows sola_rle_pack_cm fills: the ranges [first, first + T) must be
+ *   disjoint and inside the buffer (a negative entry writes nothing).  Every word of every addressed plane up to
+ *   words_stride is written, tail and pad bits as zeros, by exactly one thread (no atomics, no memset of the planes); rows
+ *   not addressed are not touched.
+ *     layout 0: row-major, the format of sola_mask_pack / sola_mask_pair_counts: bit j of word i is pixel 32*i + j of the
+ *       raster; words_stride >= sola_mask_words(h, w).
+ *     layout 1: column-major, the format of sola_rle_pack_cm / sola_mask_select_counts: position = x*h + y; words_stride a
+ *       multiple of 4 and >= sola_jf_plane_words(h, w), planes 16-byte aligned; h <= SOLA_INDEX_MAX_H (frames of more than
+ *       1259 rows take narrower column strips, a slower path with the same result).
+ *   dev_area (optional, int64, indexed by plane like dev_bits): the popcount of every addressed plane, either layout.
+ *   Refused before any launch: negative sizes, a layout other than 0 / 1, h*w >= 2^31, a short or (layout 1) odd
+ *   words_stride, misaligned planes, null ids / bits.  T == 0 or K == 0 is a successful no-op.  Asynchronous. */
+#define SOLA_INDEX_ID_CHUNK 8
+#define SOLA_INDEX_MAX_H 16384
+int sola_index_hist(const uint8_t* dev_idx, int T, int h, int w, int64_t* dev_counts, void* stream);
+int sola_index_pack(const uint8_t* dev_idx, int T, int h, int w, const int32_t* dev_ids, int K, const int32_t* dev_first_plane,
+                    int layout, int64_t words_stride, uint32_t* dev_bits, int64_t* dev_area, void* stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream; used by bench.py's roofline object) ------------ */
 enum { SOLA_PROF_GEMM = 0,      /* gemm_nt_f32_kernel<128,128> */
        SOLA_PROF_ATTN = 1,      /* attn_fwd_f32_kernel */

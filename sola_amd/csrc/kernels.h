@@ -502,3 +502,5 @@ int launch_mask_components(const void* masks, int elem_type, int n, int h, int w
 // launch_us: nullptr, or 4 host floats = the time of each launch (the call then waits for the stream)
 int launch_mask_fill_small(const void* in, int elem_type, int n, int h, int w, int connectivity, long long max_area, float fill_value,
                            void* out, void* scratch, size_t scratch_bytes, hipStream_t s, float* launch_us);
+
+// ---- index maps -> bit planes (index_planes.hip): sola_index_hist / sola_index_pack are the whole interface (sola_hip.h) ----

@@ -212,12 +212,68 @@ class TrackDataset(torch.utils.data.Dataset):
     def _mask_dict_path(self):
         return os.path.join(self.data_root, self.data_name, self.data_type, "mask_dict.json")
 
+    def _annotations_dir(self):
+        return os.path.join(self.data_root, self.data_name, self.data_type, "Annotations")
+
     @property
     def has_mask_gt(self):
         """True when the split has mask ground truth for J&F: MeViS with a ``mask_dict.json`` (the ``valid`` test split has
-        none).  Ref-DAVIS is not supported: the reference's loader (dataloader.py:262-276) stores one shared array under every
-        object id, so every object would get the last object's masks."""
-        return self.data_name == "mevis" and os.path.isfile(self._mask_dict_path())
+        none), Ref-DAVIS with an ``Annotations`` directory of palette PNGs (one folder per video, gt_index_maps)."""
+        if self.data_name == "mevis":
+            return os.path.isfile(self._mask_dict_path())
+        return self.data_name == "ref-davis" and os.path.isdir(self._annotations_dir())
+
+    def gt_index_maps(self, video_id):
+        """The annotation frames of a Ref-DAVIS video as one uint8 [T,h,w] array of object ids: the files of
+        ``Annotations/<video_id>/`` in sorted name order, read with PIL.  Mode ``P`` and ``L`` images are read as indices
+        without conversion; any other mode raises ValueError naming the file (the reference's ``.convert("P")``,
+        dataloader.py:262-264, would quantise its colours into a new palette).  Frames of different sizes raise ValueError.
+        The array of the last video read is kept."""
+        cached = self.__dict__.get("_index_cache")
+        if cached is not None and cached[0] == video_id:
+            return cached[1]
+        if self.data_name != "ref-davis" or not self.has_mask_gt:
+            raise ValueError(f"{self.data_name}/{self.data_type} has no annotation frames")
+        from PIL import Image
+        vdir = os.path.join(self._annotations_dir(), video_id)
+        frames = []
+        for name in sorted(os.listdir(vdir)):
+            path = os.path.join(vdir, name)
+            with Image.open(path) as im:
+                if im.mode not in ("P", "L"):
+                    raise ValueError(f"{path}: mode {im.mode!r}, an annotation frame must be a palette (P) or greyscale (L) image")
+                frame = np.array(im, dtype=np.uint8)
+            if frames and frame.shape != frames[0].shape:
+                raise ValueError(f"{path}: frame size {frame.shape} != {frames[0].shape} of {video_id}'s first frame")
+            frames.append(frame)
+        if not frames:
+            raise ValueError(f"{vdir}: no annotation frames")
+        maps = np.stack(frames, axis=0)
+        self._index_cache = (video_id, maps)
+        return maps
+
+    def gt_masklets(self, video_id, expression_id, device):
+        """The expression's ground-truth masklets for seg_utils.compute_JF_batch (their OR is the ground truth).  MeViS: gt_rles
+        unchanged.  Ref-DAVIS: ``[IndexMasklet(maps, obj_id)]`` for the expression's ``obj_id``, with the video's index maps
+        (gt_index_maps) uploaded to ``device`` once per video and ONE object per (video, obj_id), so that repeated ids are
+        the same list element to a caller that de-duplicates by ``id()``.  Object k's masklet is ``maps == k``, the intended
+        meaning: the reference's load_gt_masklet (dataloader.py:260-276) allocates one array outside its object loop and stores
+        it under every id, so there every object ends up with the LAST object's masks.  An expression without an object id
+        gets an empty list, an all-zero ground truth."""
+        if self.data_name != "ref-davis":
+            return self.gt_rles(video_id, expression_id)
+        from . import seg_utils
+        dev = torch.device(device)
+        cached = self.__dict__.get("_index_dev_cache")
+        if cached is None or cached[0] != (video_id, str(dev)):
+            cached = self._index_dev_cache = ((video_id, str(dev)), torch.from_numpy(self.gt_index_maps(video_id)).to(dev), {})
+        _, maps, objects = cached
+        obj_id = int(self.meta["videos"][video_id]["expressions"][expression_id].get("obj_id", NO_OBJECT_ID))
+        if obj_id < 0:
+            return []
+        if obj_id not in objects:
+            objects[obj_id] = seg_utils.IndexMasklet(maps, obj_id)
+        return [objects[obj_id]]
 
     def gt_rles(self, video_id, expression_id):
         """The RLE masklets of the expression's ``anno_id`` objects from MeViS ``mask_dict.json`` (read once, on first use;

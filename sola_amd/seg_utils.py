@@ -447,19 +447,18 @@ def rle_strings_to_cum(strings, limit=-1):
 
 
 def _masklet_geometry(masklets):
-    """(T, (h, w) or None) shared by every masklet; SolaError when they differ."""
+    """(T, (h, w) or None) shared by every masklet (lists of RLE dicts and IndexMasklets alike); SolaError when they differ."""
     T = len(masklets[0])
     size = None
     for m in masklets:
         if len(m) != T:
             raise SolaError(f"masklet_select_counts: masklets have {len(m)} and {T} frames")
-        for r in m:
-            if isinstance(r, dict):
-                s = tuple(r["size"])
-                if size is None:
-                    size = s
-                elif s != size:
-                    raise SolaError(f"masklet_select_counts: frame size {s} != {size}")
+        sizes = [m.size] if isinstance(m, IndexMasklet) else [tuple(r["size"]) for r in m if isinstance(r, dict)]
+        for s in sizes:
+            if size is None:
+                size = s
+            elif s != size:
+                raise SolaError(f"masklet_select_counts: frame size {s} != {size}")
     return T, size
 
 
@@ -499,8 +498,9 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
     host, where expression e's prediction is the OR of ``masklets[i]`` for i in ``pred_sets[e]`` and its ground truth the OR
     over ``gt_sets[e]`` (dataloader.py:251-351 get_gt_masklet / get_sam2_masklet, evaluator.py:227-247).
 
-    ``masklets``: M RLE masklets, each a list of T per-frame COCO dicts (a non-dict is a missing frame = zeros), all of one
-    T and (h, w).  Only the masks some list references are decoded, once each, into column-major bit planes (sola_rle_pack_cm)
+    ``masklets``: M masklets of one T and (h, w), each a list of T per-frame COCO RLE dicts (a non-dict is a missing frame =
+    zeros) or an IndexMasklet (``index_maps == obj_id``; those of one index-map tensor are compared by one sola_index_pack
+    launch into their rows of the RLE masklets' plane buffer).  Only the masks some list references are decoded, once each, into column-major bit planes (sola_rle_pack_cm)
     and every (expression, frame) is counted by one launch (sola_mask_select_counts): one host parse, one decode launch, one
     count launch and one copy.  The planes of one launch are capped at ``max_plane_bytes``: expressions are grouped in order
     under that budget (an expression that alone exceeds it runs by itself).  An empty list is an all-zero masklet.  Counts
@@ -544,6 +544,15 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
     outs, bouts = [], []
     for grp in groups:
         ids = sorted(set(int(i) for e in grp for i in list(pred_sets[e]) + list(gt_sets[e])))
+        # RLE masklets come first in the buffer (one decode launch over their rows), then the index masklets, those of one
+        # index-map tensor next to each other (one compare launch per tensor into its objects' rows)
+        by_maps = {}
+        for m in ids:
+            if isinstance(masklets[m], IndexMasklet):
+                by_maps.setdefault(id(masklets[m].index_maps), []).append(m)
+        if by_maps:
+            ids = [m for m in ids if not isinstance(masklets[m], IndexMasklet)] + [m for ms in by_maps.values() for m in ms]
+        n_rle = len(ids) - sum(len(ms) for ms in by_maps.values())
         local = {m: k for k, m in enumerate(ids)}
         csr = []
         for sets in (pred_sets, gt_sets):
@@ -559,11 +568,17 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
         d_pidx, d_gidx = ints[2 * Eg + 2:2 * Eg + 2 + len(pidx)], ints[2 * Eg + 2 + len(pidx):]
         counts = torch.empty((Eg, T, 3), device=dev, dtype=torch.int64)
         if ids:
-            cum, off = _planes_cum(masklets, ids, T, h * w)
-            cum_t = torch.from_numpy((cum if len(cum) else np.zeros(1, np.uint32)).view(np.int32)).to(dev)
-            off_t = torch.from_numpy(off).to(dev)
             bits = torch.empty((len(ids) * T, stride), device=dev, dtype=torch.int32)
-            check(L.sola_rle_pack_cm(ptr(cum_t), ptr(off_t), len(ids) * T, h, w, stride, ptr(bits), stream), "sola_rle_pack_cm")
+            if n_rle:
+                cum, off = _planes_cum(masklets, ids[:n_rle], T, h * w)
+                cum_t = torch.from_numpy((cum if len(cum) else np.zeros(1, np.uint32)).view(np.int32)).to(dev)
+                off_t = torch.from_numpy(off).to(dev)
+                check(L.sola_rle_pack_cm(ptr(cum_t), ptr(off_t), n_rle * T, h, w, stride, ptr(bits), stream), "sola_rle_pack_cm")
+            for ms in by_maps.values():
+                maps = masklets[ms[0]].index_maps
+                if maps.device.type != dev.type or (dev.index is not None and maps.device.index != dev.index):
+                    raise SolaError(f"masklet_select_counts: index maps on {maps.device}, counting on {dev}")
+                pack_index_masklets(maps, [masklets[m].obj_id for m in ms], "cm", out=bits, first_plane=[local[m] * T for m in ms])
         else:  # no expression of the group references a mask: every count is 0
             bits = torch.zeros((1, 4), device=dev, dtype=torch.int32)
         check(L.sola_mask_select_counts(ptr(bits), stride if ids else 4, len(ids), T, ptr(d_poff), ptr(d_pidx), ptr(d_goff),
@@ -982,3 +997,137 @@ def mask_to_rle_uncompressed(masks, logits=False):
         ends = c[off[i]:off[i + 1]]  # ends with h*w: the last run closes the frame
         out.append({"size": [h, w], "counts": np.diff(ends, prepend=0).tolist()})
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# index maps (the palette-PNG ground truth of Ref-DAVIS / Ref-YouTube-VOS: one byte per pixel = the object id) -> masklets
+# ----------------------------------------------------------------------------------------------------------------
+INDEX_ID_CHUNK = 8          # SOLA_INDEX_ID_CHUNK: the ids sola_index_pack compares in one pass over a staged piece
+_INDEX_LAYOUTS = {"row": 0, "cm": 1}
+
+
+def _index_maps(index_maps):
+    require_cuda(index_maps)
+    if index_maps.dtype != torch.uint8 or index_maps.dim() != 3:
+        raise SolaError(f"index maps must be uint8 [T,h,w], got {index_maps.dtype} {tuple(index_maps.shape)}")
+    return index_maps.contiguous()
+
+
+@torch.no_grad()
+def index_hist(index_maps):
+    """uint8 [T,h,w] on the GPU -> int64 [T,256] on the device: the pixels of every value in every frame, from one read of
+    the maps (sola_index_hist)."""
+    maps = _index_maps(index_maps)
+    T, h, w = maps.shape
+    counts = torch.empty((T, 256), device=maps.device, dtype=torch.int64)
+    check(lib().sola_index_hist(ptr(maps), T, h, w, ptr(counts), current_stream(maps.device)), "sola_index_hist")
+    return counts
+
+
+def object_ids_from_hist(hist, rule):
+    """The object ids of a video from its [T,256] histogram (any array-like, on the host).  ``rule="davis"``: the values
+    present in frame 0, minus 0 and 255 (dataloader.py:266-267, np.unique of the first annotation).  ``rule="ytbvos"``: the
+    values 1..255 with a pixel in any frame (track_generation/seg_utils.py:37-48)."""
+    import numpy as np
+    hist = np.asarray(hist)
+    if hist.ndim != 2 or hist.shape[1] != 256:
+        raise ValueError(f"histogram must be [T,256], got {hist.shape}")
+    if rule == "davis":
+        return [v for v in range(1, 255) if len(hist) and hist[0, v] > 0]
+    if rule == "ytbvos":
+        total = hist.sum(axis=0)
+        return [v for v in range(1, 256) if total[v] > 0]
+    raise ValueError(f"unknown rule {rule!r}: 'davis' or 'ytbvos'")
+
+
+def index_object_ids(index_maps, rule):
+    """Host list of the object ids in ``index_maps`` under ``rule`` (object_ids_from_hist): one index_hist and one copy."""
+    return object_ids_from_hist(index_hist(index_maps).cpu().numpy(), rule)
+
+
+@torch.no_grad()
+def pack_index_masklets(index_maps, ids, layout="row", out=None, first_plane=None):
+    """(bits int32 [planes, words], area int64 [planes] or None): plane ``k*T + t`` (``first_plane[k] + t`` when given) is
+    ``index_maps[t] == ids[k]``, every id from one read of the maps (sola_index_pack).  ``layout="row"`` is the pack_masks /
+    pair_counts format and also returns the planes' areas; ``"cm"`` is the column-major format of masklet_select_counts
+    (area None).  ``out``: an int32 [rows, words] buffer to write into (the rows not addressed keep their content);
+    ``first_plane``: a host list of K first rows, whose ranges of T rows must be disjoint and inside ``out``.  ``ids``: a host
+    list or an int32 device tensor; a value outside 0..255 gives empty planes."""
+    if layout not in _INDEX_LAYOUTS:
+        raise SolaError(f"layout {layout!r}: 'row' or 'cm'")
+    maps = _index_maps(index_maps)
+    T, h, w = maps.shape
+    dev = maps.device
+    L = lib()
+    if torch.is_tensor(ids):
+        require_cuda(ids)
+        d_ids = ids.to(torch.int32).contiguous()
+    else:
+        d_ids = torch.tensor([int(i) for i in ids], dtype=torch.int32).to(dev)
+    K = d_ids.numel()
+    words = L.sola_mask_words(h, w) if layout == "row" else L.sola_jf_plane_words(h, w)
+    if out is None:
+        if first_plane is not None:
+            raise SolaError("pack_index_masklets: first_plane needs out")
+        out = torch.empty((K * T, words), device=dev, dtype=torch.int32)
+    else:
+        require_cuda(out)
+        if out.dtype != torch.int32 or out.dim() != 2 or not out.is_contiguous() or out.shape[1] < words:
+            raise SolaError(f"pack_index_masklets: out must be a contiguous int32 [rows, >= {words}] tensor")
+    d_first = None
+    if first_plane is not None:
+        first = [int(p) for p in first_plane]
+        rows = sorted(first)
+        if len(first) != K or any(p < 0 or p + T > out.shape[0] for p in first) or any(b - a < T for a, b in zip(rows, rows[1:])):
+            raise SolaError("pack_index_masklets: first_plane must give K disjoint ranges of T rows inside out")
+        d_first = torch.tensor(first, dtype=torch.int32).to(dev)
+    elif K * T > out.shape[0]:
+        raise SolaError(f"pack_index_masklets: out has {out.shape[0]} rows, {K * T} needed")
+    area = torch.zeros((out.shape[0],), device=dev, dtype=torch.int64) if layout == "row" else None
+    check(L.sola_index_pack(ptr(maps), T, h, w, ptr(d_ids), K, ptr(d_first), _INDEX_LAYOUTS[layout], out.shape[1], ptr(out),
+                            ptr(area), current_stream(dev)), "sola_index_pack")
+    return out, area
+
+
+@torch.no_grad()
+def index_masklets(index_maps, ids=None, reshape=False, target_shape=None):
+    """``get_masklets_ytbvos`` (track_generation/seg_utils.py:29-49) on the GPU: ``{str(id): float32 {0,1} [T,H,W]}`` of the
+    objects in uint8 index maps [T,h,w]; objects that are empty over the whole video are dropped.  ``ids=None``: the values
+    1..255 that occur (index_object_ids' "ytbvos" rule).  One histogram pass finds the objects, one pack launch compares
+    every id (row-major planes), unpack_masks writes the images.  ``reshape=True``: each masklet goes through
+    pack_masklet_bilinear, so the result is reshape_masklet's on ``(index_maps == id)`` bit for bit."""
+    maps = _index_maps(index_maps)
+    T, h, w = maps.shape
+    total = index_hist(maps).sum(dim=0).cpu().numpy()
+    ids = [v for v in range(1, 256) if total[v] > 0] if ids is None else [int(i) for i in ids]
+    keep = list(dict.fromkeys(i for i in ids if 0 <= i <= 255 and total[i] > 0))
+    if not keep or T == 0:
+        return {}
+    bits, _ = pack_index_masklets(maps, keep, "row")
+    out = {}
+    if not reshape:
+        images = unpack_masks(bits, h, w, torch.float32).view(len(keep), T, h, w)
+        for k, i in enumerate(keep):
+            out[str(i)] = images[k]
+        return out
+    images = unpack_masks(bits, h, w, torch.uint8).view(len(keep), T, h, w)
+    for k, i in enumerate(keep):
+        out[str(i)] = reshape_masklet(images[k], target_shape)
+    return out
+
+
+class IndexMasklet:
+    """A masklet given as ``index_maps == obj_id`` (uint8 [T,h,w] on the GPU, e.g. the frames of a Ref-DAVIS annotation
+    folder): masklet_select_counts / compute_JF_batch take it as an element of ``masklets`` in place of a list of RLE dicts.
+    IndexMasklets that share one ``index_maps`` tensor are compared in one sola_index_pack launch."""
+
+    def __init__(self, index_maps, obj_id):
+        self.index_maps = _index_maps(index_maps)
+        self.obj_id = int(obj_id)
+
+    def __len__(self):
+        return int(self.index_maps.shape[0])
+
+    @property
+    def size(self):
+        return (int(self.index_maps.shape[1]), int(self.index_maps.shape[2]))
