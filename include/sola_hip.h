@@ -510,6 +510,23 @@ int sola_mask_select_counts(const uint32_t* dev_bits, int64_t words_stride, int 
 int64_t sola_rle_strings_to_cum_batch(const char* chars, const int64_t* str_off, int64_t n, uint32_t* host_cum, int64_t cap,
                                       int64_t limit, int64_t* run_off);
 
+/* ---- J&F at K nested selections (a sweep of the selection threshold) from one counting pass ------------------------------
+ * Planes, stride, alignment and id rules of sola_mask_select_counts.  dev_pred_idx[dev_pred_off[e] .. dev_pred_off[e+1]) is
+ * expression e's ORDERED candidate list, len_e long: the selection of level k is its prefix of end(e, k) entries, with
+ * end(e, -1) = 0 and end(e, k) = min(max(dev_level_end[e*K + k], end(e, k-1)), len_e): a decreasing or too-long entry is
+ * clamped and nothing is read out of range; entries behind end(e, K-1) are never read.  p_k = OR of the planes of that prefix,
+ * g = OR of the GT list -> dev_counts [E, K, T, 3] int64 = (popc(p_k & g), popc(p_k), popc(g)), exact; dev_counts[e, k] is
+ * the [T, 3] table sola_mask_select_counts gives for the prefix as a prediction list.  One block per (e, t) carries p over the
+ * levels and ORs in only the planes that enter at each, so every plane of the largest selection and of the GT list is read
+ * once per (e, t) and SOLA_NESTED_MAX_LEVELS levels; K above that bound costs ceil(K / 16) launches, each of which reads the
+ * prefix of its first level again.  Every entry is written by exactly one thread (no atomics, no memset; the result does not
+ * depend on any order).  K, E, T > 0, n_masks >= 0, E*T < 2^31, words_stride a positive multiple of 4 below 2^26, planes
+ * 16-byte aligned, no null pointer.  Asynchronous on the stream. */
+#define SOLA_NESTED_MAX_LEVELS 16
+int sola_mask_nested_counts(const uint32_t* dev_bits, int64_t words_stride, int n_masks, int T, const int32_t* dev_pred_off,
+                            const int32_t* dev_pred_idx, const int32_t* dev_level_end, int K, const int32_t* dev_gt_off,
+                            const int32_t* dev_gt_idx, int E, int64_t* dev_counts, void* stream);
+
 /* ---- DAVIS boundary (contour) F on the same planes and id lists (no void pixels, both masks of one size) ----------------
  * For every expression e < E and frame t < T, fg / gt = the ORs sola_mask_select_counts forms.  The boundary map B(m) is 1
  * where m differs from an in-image neighbour among east (y, x+1), south (y+1, x) and south-east (y+1, x+1); dil(B) is B

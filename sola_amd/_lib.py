@@ -131,6 +131,7 @@ SIGNATURES = {
     "sola_jf_plane_words": (_i64, [_i, _i]),
     "sola_rle_pack_cm": (_i, [_vp, _vp, _i64, _i, _i, _i64, _vp, _vp]),
     "sola_mask_select_counts": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "sola_mask_nested_counts": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "sola_mask_select_boundary_counts": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "sola_boundary_counts_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sola_rle_strings_to_cum_batch": (_i64, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),

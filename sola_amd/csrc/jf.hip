@@ -13,6 +13,12 @@
 //   mask_select_counts_kernel  one block per (expression e, frame t): OR of e's selected track planes into p and of its GT
 //                              planes into g, 16 bytes per lane and load, popc(p & g), popc(p), popc(g) reduced over the
 //                              block and stored as int64 counts[e, t, 0..2].  No atomics, no memset, order-independent.
+//   mask_nested_counts_kernel  the same block per (e, t) for up to SOLA_NESTED_MAX_LEVELS nested selections at once: e's
+//                              candidate list is ordered so that the selection of level k is a prefix of it; g is formed once
+//                              per quad, p is carried over the levels in registers and each level ORs in only the planes that
+//                              enter there, then adds popc(p & g), popc(p) to that level's per-lane counters (2*16 + 1 VGPRs,
+//                              the level loop unrolled to the compile-time bound).  Every plane of the largest selection and
+//                              of the GT list is read once per (e, t), whatever the number of levels.
 //   sola_rle_strings_to_cum_batch  host: every compressed string of a video -> prefix sums + run offsets in one call, with
 //                              the parser of sola_rle_string_to_cum (api.hip).
 #include <string.h>
@@ -103,6 +109,83 @@ __global__ __launch_bounds__(256) void mask_select_counts_kernel(const uint4* __
     }
 }
 
+// Levels k0 .. k0 + nl - 1 of the K prefix ends of every expression (nl <= SOLA_NESTED_MAX_LEVELS): the first level of the launch
+// ORs the whole prefix [0, end(e, k0)), the later ones what enters with them.  end(e, k) = min(max(level_end[e, k], end(e, k - 1)),
+// len_e) is formed here, so a decreasing or too-long entry reads nothing outside e's list.  All list and level reads are
+// block-uniform (scalar loads); the counters are indexed by unrolled constants only, so they stay in VGPRs.
+__global__ __launch_bounds__(256) void mask_nested_counts_kernel(const uint4* __restrict__ planes, long long quads, int M, int T,
+                                                                 const int* __restrict__ pred_off, const int* __restrict__ pred_idx,
+                                                                 const int* __restrict__ level_end, int K, int k0, int nl,
+                                                                 const int* __restrict__ gt_off, const int* __restrict__ gt_idx,
+                                                                 long long* __restrict__ counts) {
+    constexpr int NL = SOLA_NESTED_MAX_LEVELS;
+    __shared__ unsigned red[4][2 * NL + 1];
+    const long long b = blockIdx.x;
+    const int e = (int)(b / T), t = (int)(b - (long long)e * T);
+    const int p0 = pred_off[e], len = max(pred_off[e + 1] - p0, 0), g0 = gt_off[e], g1 = gt_off[e + 1];
+    const int* le = level_end + (long long)e * K;
+    int prev = 0;
+    for (int k = 0; k < k0; ++k) prev = min(max(le[k], prev), len);
+    int ends[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        if (l < nl) prev = min(max(le[k0 + l], prev), len);
+        ends[l] = p0 + prev;
+    }
+    unsigned ci[NL], cp[NL], cg = 0;  // per lane at most 128 * ceil(quads / 256) < 2^24 pixels
+#pragma unroll
+    for (int l = 0; l < NL; ++l) ci[l] = cp[l] = 0;
+    for (long long q = threadIdx.x; q < quads; q += 256) {
+        uint4 p = make_uint4(0, 0, 0, 0), g = make_uint4(0, 0, 0, 0);
+#pragma unroll 4
+        for (int k = g0; k < g1; ++k) {
+            const int m = gt_idx[k];
+            if ((unsigned)m >= (unsigned)M) continue;
+            const uint4 v = planes[((long long)m * T + t) * quads + q];
+            g.x |= v.x; g.y |= v.y; g.z |= v.z; g.w |= v.w;
+        }
+        cg += __popc(g.x) + __popc(g.y) + __popc(g.z) + __popc(g.w);
+        int k = p0;
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            if (l < nl) {
+                for (; k < ends[l]; ++k) {
+                    const int m = pred_idx[k];
+                    if ((unsigned)m >= (unsigned)M) continue;
+                    const uint4 v = planes[((long long)m * T + t) * quads + q];
+                    p.x |= v.x; p.y |= v.y; p.z |= v.z; p.w |= v.w;
+                }
+                ci[l] += __popc(p.x & g.x) + __popc(p.y & g.y) + __popc(p.z & g.z) + __popc(p.w & g.w);
+                cp[l] += __popc(p.x) + __popc(p.y) + __popc(p.z) + __popc(p.w);
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            ci[l] += __shfl_xor(ci[l], o, 64);
+            cp[l] += __shfl_xor(cp[l], o, 64);
+        }
+        cg += __shfl_xor(cg, o, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            red[wave][2 * l] = ci[l];
+            red[wave][2 * l + 1] = cp[l];
+        }
+        red[wave][2 * NL] = cg;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 3 * nl) {  // one thread per entry of counts[e, k0 .. k0 + nl, t, 0..2]
+        const int l = threadIdx.x / 3, c = threadIdx.x - 3 * l;
+        const int j = c == 2 ? 2 * NL : 2 * l + c;
+        counts[(((long long)e * K + k0 + l) * T + t) * 3 + c] =
+            (long long)red[0][j] + (long long)red[1][j] + (long long)red[2][j] + (long long)red[3][j];
+    }
+}
+
 }  // namespace
 
 extern "C" int64_t sola_jf_plane_words(int h, int w) {
@@ -149,6 +232,28 @@ extern "C" int sola_mask_select_counts(const uint32_t* bits, int64_t words_strid
                        reinterpret_cast<const uint4*>(bits), (long long)(words_stride / 4), n_masks, T, pred_off, pred_idx, gt_off,
                        gt_idx, reinterpret_cast<long long*>(counts));
     SOLA_LAUNCH_CHECK();
+    return SOLA_OK;
+}
+
+extern "C" int sola_mask_nested_counts(const uint32_t* bits, int64_t words_stride, int n_masks, int T, const int32_t* pred_off,
+                                       const int32_t* pred_idx, const int32_t* level_end, int K, const int32_t* gt_off,
+                                       const int32_t* gt_idx, int E, int64_t* counts, void* stream_) {
+    SOLA_ARG(bits && pred_off && pred_idx && level_end && gt_off && gt_idx && counts, "mask_nested_counts: null argument");
+    SOLA_ARG(K > 0 && T > 0 && E > 0 && n_masks >= 0, "mask_nested_counts: bad sizes (n_masks %d, T %d, E %d, K %d)", n_masks, T, E, K);
+    SOLA_ARG(words_stride > 0 && words_stride % 4 == 0, "mask_nested_counts: words_stride %lld is not a positive multiple of 4",
+             (long long)words_stride);
+    SOLA_ARG(words_stride < (1ll << 26), "mask_nested_counts: planes too large");
+    SOLA_ARG((reinterpret_cast<uintptr_t>(bits) & 15) == 0, "mask_nested_counts: planes must be 16-byte aligned");
+    SOLA_ARG((long long)E * T < (1ll << 31), "mask_nested_counts: E*T too large");
+    hipStream_t s = as_stream(stream_);
+    // as sola_mask_select_counts: the plane reads depend on the lists on the device, only the counts are in the profile's bytes
+    SolaProfScope prof(SOLA_PROF_IOU_PACK, s, 0, 24.0 * (double)E * K * T);
+    for (int k0 = 0; k0 < K; k0 += SOLA_NESTED_MAX_LEVELS) {  // a launch per 16 levels; its first level ORs the whole prefix again
+        hipLaunchKernelGGL(mask_nested_counts_kernel, dim3((unsigned)((long long)E * T)), dim3(256), 0, s,
+                           reinterpret_cast<const uint4*>(bits), (long long)(words_stride / 4), n_masks, T, pred_off, pred_idx, level_end,
+                           K, k0, std::min(SOLA_NESTED_MAX_LEVELS, K - k0), gt_off, gt_idx, reinterpret_cast<long long*>(counts));
+        SOLA_LAUNCH_CHECK();
+    }
     return SOLA_OK;
 }
 

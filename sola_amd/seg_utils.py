@@ -492,6 +492,55 @@ def _planes_cum(masklets, ids, T, hw):
     return cum, off
 
 
+def _plane_groups(masklets, refs, T, h, w, stride, dev, max_plane_bytes):
+    """The plane-building half of masklet_select_counts / masklet_sweep_counts.  ``refs[e]`` lists the masklets expression e
+    reads.  Expressions are grouped in order so that the planes of one group stay under ``max_plane_bytes`` (an expression
+    that alone exceeds it runs by itself); for every group the masks it references are decoded once (one parse and one
+    sola_rle_pack_cm launch for the RLE masklets, one sola_index_pack launch per index-map tensor) and
+    ``(expressions, {masklet: row of the group's buffer}, bits [rows * T, stride], rows)`` is yielded.  A group that references
+    no mask gets one dummy plane of 4 words and 0 rows."""
+    import numpy as np
+    L = lib()
+    stream = current_stream(dev)
+    mask_bytes = T * stride * 4
+    groups, cur, cur_ids = [], [], set()
+    for e, ref in enumerate(refs):
+        ids = set(ref)
+        if cur and len(cur_ids | ids) * mask_bytes > max_plane_bytes:
+            groups.append(cur)
+            cur, cur_ids = [], set()
+        cur.append(e)
+        cur_ids |= ids
+    groups.append(cur)
+    for grp in groups:
+        ids = sorted(set(i for e in grp for i in refs[e]))
+        # RLE masklets come first in the buffer (one decode launch over their rows), then the index masklets, those of one
+        # index-map tensor next to each other (one compare launch per tensor into its objects' rows)
+        by_maps = {}
+        for m in ids:
+            if isinstance(masklets[m], IndexMasklet):
+                by_maps.setdefault(id(masklets[m].index_maps), []).append(m)
+        if by_maps:
+            ids = [m for m in ids if not isinstance(masklets[m], IndexMasklet)] + [m for ms in by_maps.values() for m in ms]
+        n_rle = len(ids) - sum(len(ms) for ms in by_maps.values())
+        local = {m: k for k, m in enumerate(ids)}
+        if ids:
+            bits = torch.empty((len(ids) * T, stride), device=dev, dtype=torch.int32)
+            if n_rle:
+                cum, off = _planes_cum(masklets, ids[:n_rle], T, h * w)
+                cum_t = torch.from_numpy((cum if len(cum) else np.zeros(1, np.uint32)).view(np.int32)).to(dev)
+                off_t = torch.from_numpy(off).to(dev)
+                check(L.sola_rle_pack_cm(ptr(cum_t), ptr(off_t), n_rle * T, h, w, stride, ptr(bits), stream), "sola_rle_pack_cm")
+            for ms in by_maps.values():
+                maps = masklets[ms[0]].index_maps
+                if maps.device.type != dev.type or (dev.index is not None and maps.device.index != dev.index):
+                    raise SolaError(f"masklet_select_counts: index maps on {maps.device}, counting on {dev}")
+                pack_index_masklets(maps, [masklets[m].obj_id for m in ms], "cm", out=bits, first_plane=[local[m] * T for m in ms])
+        else:  # no expression of the group references a mask: every count is 0
+            bits = torch.zeros((1, 4), device=dev, dtype=torch.int32)
+        yield grp, local, bits, len(ids)
+
+
 @torch.no_grad()
 def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=2 << 30, boundary=None):
     """Every expression of a video against its ground truth, per frame: int64 [E, T, 3] (intersection, n_pred, n_gt) on the
@@ -529,31 +578,11 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
     L = lib()
     radius = None if boundary is None else boundary_radius(h, w, _boundary_th(boundary))
     stride = L.sola_jf_plane_words(h, w)
-    mask_bytes = T * stride * 4
-    groups, cur, cur_ids = [], [], set()
-    for e in range(E):
-        ids = set(int(i) for i in pred_sets[e]) | set(int(i) for i in gt_sets[e])
-        if cur and len(cur_ids | ids) * mask_bytes > max_plane_bytes:
-            groups.append(cur)
-            cur, cur_ids = [], set()
-        cur.append(e)
-        cur_ids |= ids
-    groups.append(cur)
     dev = torch.device(device)
     stream = current_stream(dev)
+    refs = [[int(i) for i in pred_sets[e]] + [int(i) for i in gt_sets[e]] for e in range(E)]
     outs, bouts = [], []
-    for grp in groups:
-        ids = sorted(set(int(i) for e in grp for i in list(pred_sets[e]) + list(gt_sets[e])))
-        # RLE masklets come first in the buffer (one decode launch over their rows), then the index masklets, those of one
-        # index-map tensor next to each other (one compare launch per tensor into its objects' rows)
-        by_maps = {}
-        for m in ids:
-            if isinstance(masklets[m], IndexMasklet):
-                by_maps.setdefault(id(masklets[m].index_maps), []).append(m)
-        if by_maps:
-            ids = [m for m in ids if not isinstance(masklets[m], IndexMasklet)] + [m for ms in by_maps.values() for m in ms]
-        n_rle = len(ids) - sum(len(ms) for ms in by_maps.values())
-        local = {m: k for k, m in enumerate(ids)}
+    for grp, local, bits, n_ids in _plane_groups(masklets, refs, T, h, w, stride, dev, max_plane_bytes):
         csr = []
         for sets in (pred_sets, gt_sets):
             off, idx = [0], []
@@ -567,27 +596,13 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
         d_poff, d_goff = ints[:Eg + 1], ints[Eg + 1:2 * Eg + 2]
         d_pidx, d_gidx = ints[2 * Eg + 2:2 * Eg + 2 + len(pidx)], ints[2 * Eg + 2 + len(pidx):]
         counts = torch.empty((Eg, T, 3), device=dev, dtype=torch.int64)
-        if ids:
-            bits = torch.empty((len(ids) * T, stride), device=dev, dtype=torch.int32)
-            if n_rle:
-                cum, off = _planes_cum(masklets, ids[:n_rle], T, h * w)
-                cum_t = torch.from_numpy((cum if len(cum) else np.zeros(1, np.uint32)).view(np.int32)).to(dev)
-                off_t = torch.from_numpy(off).to(dev)
-                check(L.sola_rle_pack_cm(ptr(cum_t), ptr(off_t), n_rle * T, h, w, stride, ptr(bits), stream), "sola_rle_pack_cm")
-            for ms in by_maps.values():
-                maps = masklets[ms[0]].index_maps
-                if maps.device.type != dev.type or (dev.index is not None and maps.device.index != dev.index):
-                    raise SolaError(f"masklet_select_counts: index maps on {maps.device}, counting on {dev}")
-                pack_index_masklets(maps, [masklets[m].obj_id for m in ms], "cm", out=bits, first_plane=[local[m] * T for m in ms])
-        else:  # no expression of the group references a mask: every count is 0
-            bits = torch.zeros((1, 4), device=dev, dtype=torch.int32)
-        check(L.sola_mask_select_counts(ptr(bits), stride if ids else 4, len(ids), T, ptr(d_poff), ptr(d_pidx), ptr(d_goff),
+        check(L.sola_mask_select_counts(ptr(bits), stride if n_ids else 4, n_ids, T, ptr(d_poff), ptr(d_pidx), ptr(d_goff),
                                         ptr(d_gidx), Eg, ptr(counts), stream), "sola_mask_select_counts")
         outs.append(counts)
         if radius is not None:
             bcounts = torch.empty((Eg, T, 4), device=dev, dtype=torch.int64)
             # (without ids no plane is read: the stride is the frame's over the dummy plane)
-            check(L.sola_mask_select_boundary_counts(ptr(bits), stride, len(ids), T, h, w, radius, ptr(d_poff), ptr(d_pidx),
+            check(L.sola_mask_select_boundary_counts(ptr(bits), stride, n_ids, T, h, w, radius, ptr(d_poff), ptr(d_pidx),
                                                      ptr(d_goff), ptr(d_gidx), Eg, ptr(bcounts), None, 0, stream),
                   "sola_mask_select_boundary_counts")
             bouts.append(bcounts)
@@ -615,6 +630,138 @@ def compute_JF_batch(masklets, pred_sets, gt_sets, device, boundary=None, **kw):
         else:
             Fb = float(F_boundary_from_counts(bcounts[e]))
             out.append((J, F, (J + F) / 2, Fb, (J + Fb) / 2))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# J&F at every selection threshold of a sweep (inference.py:104,141 / eval.py --eval_pred_threshold): the selections at
+# descending thresholds are nested, so one counting pass over the largest one gives every level (sola_mask_nested_counts)
+# ----------------------------------------------------------------------------------------------------------------
+def sweep_levels(probs, thresholds):
+    """One expression's float32 scores [n] and K thresholds (any order, duplicates allowed) -> ``(order, level_end, perm)``.
+    A track is selected at a threshold when ``np.float32(prob) > np.float32(threshold)``, strict: the entry points' own
+    ``prob > pred_threshold`` on float32 tensors.  With the thresholds stably sorted descending (the levels), ``order`` holds
+    the indices of the tracks selected at the lowest one, stably sorted by the first level that selects them, and
+    ``level_end`` (int32 [K]) the number of them selected at each level: level k's selection is ``order[:level_end[k]]``.
+    ``perm`` (int64 [K]) maps the levels back: the caller's threshold j is level ``perm[j]``.  Host only."""
+    import numpy as np
+    p = np.asarray(probs, dtype=np.float32).reshape(-1)
+    th = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    K = len(th)
+    desc = np.argsort(-th, kind="stable")
+    perm = np.empty(K, np.int64)
+    perm[desc] = np.arange(K)
+    first = K - (p[:, None] > th[desc][None, :]).sum(1) if K else np.zeros(len(p), np.int64)  # nested: the levels that select a track are a suffix
+    keep = np.flatnonzero(first < K)
+    order = keep[np.argsort(first[keep], kind="stable")].astype(np.int64)
+    level_end = np.searchsorted(first[order], np.arange(K), side="right").astype(np.int32)
+    return order, level_end, perm
+
+
+@torch.no_grad()
+def masklet_sweep_counts(masklets, cand_sets, probs, thresholds, gt_sets, device, max_plane_bytes=2 << 30, boundary=None):
+    """masklet_select_counts at every threshold of a sweep from one decode and one counting pass: int64 [E, K, T, 3] on the
+    host, ``[e, j]`` the (intersection, n_pred, n_gt) table of the prediction {``cand_sets[e][i]`` : ``probs[e][i]`` >
+    ``thresholds[j]``} (the rule of sweep_levels) against the OR over ``gt_sets[e]``, levels in the caller's threshold order.
+
+    ``cand_sets[e]`` holds the masklet indices of expression e's tracks, ``probs[e]`` their float32 scores.  The host work is
+    masklet_select_counts': the masks referenced are the selection at the lowest threshold plus the ground truth, decoded once
+    per group of expressions under ``max_plane_bytes``; then one sola_mask_nested_counts call, in which every plane is read
+    once per (expression, frame) whatever K, and one copy.  With ``boundary`` (the DAVIS bound_th, ``True`` = 0.008) returns
+    ``(counts, bcounts)``, bcounts int64 [E, K, T, 4] as masklet_select_counts gives it: the K prefix lists of every
+    expression go as E*K pseudo-expressions through one sola_mask_select_boundary_counts launch on the same planes."""
+    import numpy as np
+    E, K = len(cand_sets), len(thresholds)
+    if K == 0:
+        raise SolaError("masklet_sweep_counts: no thresholds")
+    if len(gt_sets) != E or len(probs) != E:
+        raise SolaError(f"masklet_sweep_counts: {E} candidate sets but {len(probs)} score vectors and {len(gt_sets)} GT sets")
+    M = len(masklets)
+    if M == 0:
+        raise SolaError("masklet_sweep_counts: no masklets")
+    for s in list(cand_sets) + list(gt_sets):
+        for i in s:
+            if not 0 <= int(i) < M:
+                raise SolaError(f"masklet_sweep_counts: index {i} outside the {M} masklets")
+    ordered, ends, perm = [], [], np.arange(K)
+    for e in range(E):
+        if len(probs[e]) != len(cand_sets[e]):
+            raise SolaError(f"masklet_sweep_counts: expression {e} has {len(cand_sets[e])} tracks but {len(probs[e])} scores")
+        order, level_end, perm = sweep_levels(probs[e], thresholds)
+        ordered.append([int(cand_sets[e][i]) for i in order])
+        ends.append(level_end.tolist())
+    T, size = _masklet_geometry(masklets)
+    if E == 0 or size is None or T == 0:
+        counts = torch.zeros((E, K, T, 3), dtype=torch.int64)
+        return counts if boundary is None else (counts, torch.zeros((E, K, T, 4), dtype=torch.int64))
+    h, w = size
+    L = lib()
+    radius = None if boundary is None else boundary_radius(h, w, _boundary_th(boundary))
+    stride = L.sola_jf_plane_words(h, w)
+    dev = torch.device(device)
+    stream = current_stream(dev)
+    refs = [ordered[e] + [int(i) for i in gt_sets[e]] for e in range(E)]
+    outs, bouts = [], []
+    for grp, local, bits, n_ids in _plane_groups(masklets, refs, T, h, w, stride, dev, max_plane_bytes):
+        Eg = len(grp)
+        poff, pidx, goff, gidx, lend = [0], [], [0], [], []
+        for e in grp:
+            pidx += [local[i] for i in ordered[e]]
+            poff.append(len(pidx))
+            gidx += [local[int(i)] for i in gt_sets[e]]
+            goff.append(len(gidx))
+            lend += ends[e]
+        parts = [poff, goff, lend, pidx + [0], gidx + [0]]  # (the pad entries keep the pointers of empty lists non-null)
+        if radius is not None:  # level k of expression e as pseudo-expression e*K + k of the boundary launch
+            boff, bidx, bgoff, bgidx = [0], [], [0], []
+            for j, e in enumerate(grp):
+                for k in range(K):
+                    bidx += pidx[poff[j]:poff[j] + ends[e][k]]
+                    boff.append(len(bidx))
+                    bgidx += gidx[goff[j]:goff[j + 1]]
+                    bgoff.append(len(bgidx))
+            parts += [boff, bgoff, bidx + [0], bgidx + [0]]
+        ints = torch.tensor([x for part in parts for x in part], dtype=torch.int32).to(dev)  # one copy for every list
+        d, o = [], 0
+        for part in parts:
+            d.append(ints[o:o + len(part)])
+            o += len(part)
+        counts = torch.empty((Eg, K, T, 3), device=dev, dtype=torch.int64)
+        check(L.sola_mask_nested_counts(ptr(bits), stride if n_ids else 4, n_ids, T, ptr(d[0]), ptr(d[3]), ptr(d[2]), K, ptr(d[1]),
+                                        ptr(d[4]), Eg, ptr(counts), stream), "sola_mask_nested_counts")
+        outs.append(counts)
+        if radius is not None:
+            bcounts = torch.empty((Eg, K, T, 4), device=dev, dtype=torch.int64)
+            check(L.sola_mask_select_boundary_counts(ptr(bits), stride, n_ids, T, h, w, radius, ptr(d[5]), ptr(d[7]), ptr(d[6]),
+                                                     ptr(d[8]), Eg * K, ptr(bcounts), None, 0, stream),
+                  "sola_mask_select_boundary_counts")
+            bouts.append(bcounts)
+    perm = torch.from_numpy(perm)
+    counts = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu()[:, perm].contiguous()
+    if radius is None:
+        return counts
+    return counts, (bouts[0] if len(bouts) == 1 else torch.cat(bouts)).cpu()[:, perm].contiguous()
+
+
+def compute_JF_sweep(masklets, cand_sets, probs, thresholds, gt_sets, device, boundary=None, **kw):
+    """compute_JF_batch at every threshold of a sweep, from masklet_sweep_counts: per expression a list over ``thresholds`` (the
+    caller's order) of the tuples compute_JF_batch returns for that threshold's selection, (J, F, JF) or, with ``boundary``,
+    (J, F, JF, F_boundary, JF_boundary)."""
+    counts = masklet_sweep_counts(masklets, cand_sets, probs, thresholds, gt_sets, device, boundary=boundary, **kw)
+    bcounts = None
+    if boundary is not None:
+        counts, bcounts = counts
+    out = []
+    for e, ce in enumerate(counts):
+        row = []
+        for k, c in enumerate(ce):
+            J, F = float(J_from_counts(c)), float(F_from_counts(c))
+            if bcounts is None:
+                row.append((J, F, (J + F) / 2))
+            else:
+                Fb = float(F_boundary_from_counts(bcounts[e, k]))
+                row.append((J, F, (J + F) / 2, Fb, (J + Fb) / 2))
+        out.append(row)
     return out
 
 

@@ -123,12 +123,13 @@ def run_train_ragged(module, text, batches, tcfg, device, optimizer, world=1):
 
 
 @torch.no_grad()
-def run_split_ragged(module, text, batches, tcfg, device, world=1, on_batch=None):
+def run_split_ragged(module, text, batches, tcfg, device, world=1, on_batch=None, on_prob=None):
     """Validation / evaluation over ragged batches (sola_forward_ragged + sola_loss_ragged): the same per-sample numbers as
     ``run_split(train=False)`` - each sample's losses are means over its own tracks, as at the reference's batch size of 1
     (train.py:147-216, evaluator.py:88-112) - at up to ``ragged_max_samples`` samples per launch, the expressions of one
     video sharing the text-independent half of the network.  ``on_batch(batch, pred)``, if given, receives every batch and
-    its device selection vector (float {0,1}, the samples' tracks back to back)."""
+    its device selection vector (float {0,1}, the samples' tracks back to back); ``on_prob(batch, prob)`` the float32
+    probabilities that vector was thresholded from, in the same layout."""
     pw, temp, aw = tcfg["positive_weight"], tcfg["temperature"], tcfg["alignment_weight"]
     module.eval()
     sums = torch.zeros(3, device=device)
@@ -147,6 +148,8 @@ def run_split_ragged(module, text, batches, tcfg, device, world=1, on_batch=None
         pred = (prob > tcfg["pred_threshold"]).float()
         if on_batch is not None:
             on_batch(batch, pred)
+        if on_prob is not None:
+            on_prob(batch, prob)
         counts4 += torch.stack([(pred * labels).sum(), (pred * (1 - labels)).sum(), ((1 - pred) * labels).sum(),
                                 ((1 - pred) * (1 - labels)).sum()])
         # the reference's evaluator feeds the SIGMOID-ed scores to binary_cross_entropy_with_logits (evaluator.py:101,107-111;
