@@ -10,15 +10,15 @@
 //                              sums at 32*i (its parity is the value there, rle_value() of masklet.hip), then a walk over
 //                              the run ends inside the word.  One search per 32 pixels where rle_fill_or_kernel does one per
 //                              pixel.  Runs that cover fewer than h*w pixels follow rle_fill_or_kernel's parity rule.
-//   mask_select_counts_kernel  one block per (expression e, frame t): OR of e's selected track planes into p and of its GT
-//                              planes into g, 16 bytes per lane and load, popc(p & g), popc(p), popc(g) reduced over the
-//                              block and stored as int64 counts[e, t, 0..2].  No atomics, no memset, order-independent.
-//   mask_nested_counts_kernel  the same block per (e, t) for up to SOLA_NESTED_MAX_LEVELS nested selections at once: e's
-//                              candidate list is ordered so that the selection of level k is a prefix of it; g is formed once
-//                              per quad, p is carried over the levels in registers and each level ORs in only the planes that
-//                              enter there, then adds popc(p & g), popc(p) to that level's per-lane counters (2*16 + 1 VGPRs,
-//                              the level loop unrolled to the compile-time bound).  Every plane of the largest selection and
-//                              of the GT list is read once per (e, t), whatever the number of levels.
+//   mask_nested_counts_kernel<NL>  one block per (expression e, frame t) for up to NL nested selections at once: e's candidate
+//                              list is ordered so that the selection of level k is a prefix of it.  OR of e's GT planes into g once
+//                              per quad (16 bytes per lane and load); p is carried over the levels in registers, each level ORs in
+//                              only the planes that enter there, then adds popc(p & g), popc(p) to that level's per-lane counters;
+//                              popc(g) once.  Reduced over the block and stored as int64 counts[e, k, t, 0..2]: no atomics, no
+//                              memset, order-independent.  <1> is the plain selection of sola_mask_select_counts (one level that
+//                              ends at the list's end), <SOLA_NESTED_MAX_LEVELS> the sweep (2*16 + 1 VGPRs of counters, the level
+//                              loop unrolled to the compile-time bound): every plane of the largest selection and of the GT list
+//                              is read once per (e, t), whatever the number of levels.
 //   sola_rle_strings_to_cum_batch  host: every compressed string of a video -> prefix sums + run offsets in one call, with
 //                              the parser of sola_rle_string_to_cum (api.hip).
 #include <string.h>
@@ -63,73 +63,28 @@ __global__ __launch_bounds__(256) void rle_pack_cm_kernel(const uint32_t* __rest
     bits[p * stride + i] = word;
 }
 
-__global__ __launch_bounds__(256) void mask_select_counts_kernel(const uint4* __restrict__ planes, long long quads, int M, int T,
-                                                                 const int* __restrict__ pred_off, const int* __restrict__ pred_idx,
-                                                                 const int* __restrict__ gt_off, const int* __restrict__ gt_idx,
-                                                                 long long* __restrict__ counts) {
-    __shared__ unsigned red[3][4];
-    const long long b = blockIdx.x;
-    const int e = (int)(b / T), t = (int)(b - (long long)e * T);
-    const int p0 = pred_off[e], p1 = pred_off[e + 1], g0 = gt_off[e], g1 = gt_off[e + 1];
-    unsigned ci = 0, cp = 0, cg = 0;  // per lane at most 128 * ceil(quads / 256) < 2^24 pixels
-    for (long long q = threadIdx.x; q < quads; q += 256) {
-        uint4 p = make_uint4(0, 0, 0, 0), g = make_uint4(0, 0, 0, 0);
-#pragma unroll 4
-        for (int k = p0; k < p1; ++k) {
-            const int m = pred_idx[k];
-            if ((unsigned)m >= (unsigned)M) continue;
-            const uint4 v = planes[((long long)m * T + t) * quads + q];
-            p.x |= v.x; p.y |= v.y; p.z |= v.z; p.w |= v.w;
-        }
-#pragma unroll 4
-        for (int k = g0; k < g1; ++k) {
-            const int m = gt_idx[k];
-            if ((unsigned)m >= (unsigned)M) continue;
-            const uint4 v = planes[((long long)m * T + t) * quads + q];
-            g.x |= v.x; g.y |= v.y; g.z |= v.z; g.w |= v.w;
-        }
-        ci += __popc(p.x & g.x) + __popc(p.y & g.y) + __popc(p.z & g.z) + __popc(p.w & g.w);
-        cp += __popc(p.x) + __popc(p.y) + __popc(p.z) + __popc(p.w);
-        cg += __popc(g.x) + __popc(g.y) + __popc(g.z) + __popc(g.w);
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        ci += __shfl_xor(ci, o, 64);
-        cp += __shfl_xor(cp, o, 64);
-        cg += __shfl_xor(cg, o, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = ci; red[1][wave] = cp; red[2][wave] = cg;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long* c = counts + b * 3;
-        for (int j = 0; j < 3; ++j)
-            c[j] = (long long)red[j][0] + (long long)red[j][1] + (long long)red[j][2] + (long long)red[j][3];
-    }
-}
-
-// Levels k0 .. k0 + nl - 1 of the K prefix ends of every expression (nl <= SOLA_NESTED_MAX_LEVELS): the first level of the launch
-// ORs the whole prefix [0, end(e, k0)), the later ones what enters with them.  end(e, k) = min(max(level_end[e, k], end(e, k - 1)),
-// len_e) is formed here, so a decreasing or too-long entry reads nothing outside e's list.  All list and level reads are
-// block-uniform (scalar loads); the counters are indexed by unrolled constants only, so they stay in VGPRs.
+// One block per (expression e, frame t) for levels k0 .. k0 + nl - 1 of the K prefix ends of e's ordered list (nl <= NL): the first
+// level of the launch ORs the whole prefix [0, end(e, k0)), the later ones what enters with them.  end(e, k) = min(max(level_end[e, k],
+// end(e, k - 1)), len_e) is formed here, so a decreasing or too-long entry reads nothing outside e's list; a null level_end ends
+// every level at len_e.  NL = 1 is the plain selection (sola_mask_select_counts), NL = SOLA_NESTED_MAX_LEVELS the sweep.  All list
+// and level reads are block-uniform (scalar loads); the counters are indexed by unrolled constants only, so they stay in VGPRs.
+template <int NL>
 __global__ __launch_bounds__(256) void mask_nested_counts_kernel(const uint4* __restrict__ planes, long long quads, int M, int T,
                                                                  const int* __restrict__ pred_off, const int* __restrict__ pred_idx,
                                                                  const int* __restrict__ level_end, int K, int k0, int nl,
                                                                  const int* __restrict__ gt_off, const int* __restrict__ gt_idx,
                                                                  long long* __restrict__ counts) {
-    constexpr int NL = SOLA_NESTED_MAX_LEVELS;
     __shared__ unsigned red[4][2 * NL + 1];
     const long long b = blockIdx.x;
     const int e = (int)(b / T), t = (int)(b - (long long)e * T);
     const int p0 = pred_off[e], len = max(pred_off[e + 1] - p0, 0), g0 = gt_off[e], g1 = gt_off[e + 1];
     const int* le = level_end + (long long)e * K;
-    int prev = 0;
-    for (int k = 0; k < k0; ++k) prev = min(max(le[k], prev), len);
+    int prev = level_end ? 0 : len;
+    for (int k = 0; level_end && k < k0; ++k) prev = min(max(le[k], prev), len);
     int ends[NL];
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
-        if (l < nl) prev = min(max(le[k0 + l], prev), len);
+        if (level_end && l < nl) prev = min(max(le[k0 + l], prev), len);
         ends[l] = p0 + prev;
     }
     unsigned ci[NL], cp[NL], cg = 0;  // per lane at most 128 * ceil(quads / 256) < 2^24 pixels
@@ -149,6 +104,7 @@ __global__ __launch_bounds__(256) void mask_nested_counts_kernel(const uint4* __
 #pragma unroll
         for (int l = 0; l < NL; ++l) {
             if (l < nl) {
+#pragma unroll NL == 1 ? 4 : 1  // (more would spill SGPRs in the 16-level instance)
                 for (; k < ends[l]; ++k) {
                     const int m = pred_idx[k];
                     if ((unsigned)m >= (unsigned)M) continue;
@@ -215,24 +171,36 @@ extern "C" int sola_rle_pack_cm(const uint32_t* cum, const int64_t* off, int64_t
     return SOLA_OK;
 }
 
+// The checks sola_mask_select_counts and sola_mask_nested_counts share (`who` is the name in front of the message), then the launches:
+// one level (a null level_end included) runs the <1> instance, more levels the <SOLA_NESTED_MAX_LEVELS> one in chunks of 16.
+static int nested_counts_launch(const char* who, const uint32_t* bits, int64_t words_stride, int n_masks, int T, const int32_t* pred_off,
+                                const int32_t* pred_idx, const int32_t* level_end, int K, const int32_t* gt_off, const int32_t* gt_idx,
+                                int E, int64_t* counts, void* stream_) {
+    SOLA_ARG(words_stride < (1ll << 26), "%s: planes too large", who);
+    SOLA_ARG((reinterpret_cast<uintptr_t>(bits) & 15) == 0, "%s: planes must be 16-byte aligned", who);
+    SOLA_ARG((long long)E * T < (1ll << 31), "%s: E*T too large", who);
+    hipStream_t s = as_stream(stream_);
+    // the plane reads depend on the id lists, which live on the device: only the counts are in the profile's bytes
+    SolaProfScope prof(SOLA_PROF_IOU_PACK, s, 0, 24.0 * (double)E * K * T);
+    const auto kernel = K == 1 ? mask_nested_counts_kernel<1> : mask_nested_counts_kernel<SOLA_NESTED_MAX_LEVELS>;
+    for (int k0 = 0; k0 < K; k0 += SOLA_NESTED_MAX_LEVELS) {  // a launch per 16 levels; its first level ORs the whole prefix again
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)E * T)), dim3(256), 0, s, reinterpret_cast<const uint4*>(bits),
+                           (long long)(words_stride / 4), n_masks, T, pred_off, pred_idx, level_end, K, k0,
+                           std::min(SOLA_NESTED_MAX_LEVELS, K - k0), gt_off, gt_idx, reinterpret_cast<long long*>(counts));
+        SOLA_LAUNCH_CHECK();
+    }
+    return SOLA_OK;
+}
+
 extern "C" int sola_mask_select_counts(const uint32_t* bits, int64_t words_stride, int n_masks, int T, const int32_t* pred_off,
                                        const int32_t* pred_idx, const int32_t* gt_off, const int32_t* gt_idx, int E,
                                        int64_t* counts, void* stream_) {
-    SOLA_ARG(bits && pred_off && gt_off && counts, "mask_select_counts: null argument");
+    SOLA_ARG(bits && pred_off && gt_off && counts, "mask_select_counts: null argument");  // (null index lists: every list is empty)
     SOLA_ARG(n_masks >= 0 && T > 0 && E > 0, "mask_select_counts: bad sizes (n_masks %d, T %d, E %d)", n_masks, T, E);
     SOLA_ARG(words_stride > 0 && words_stride % 4 == 0, "mask_select_counts: words_stride %lld is not a multiple of 4",
              (long long)words_stride);
-    SOLA_ARG(words_stride < (1ll << 26), "mask_select_counts: planes too large");
-    SOLA_ARG((reinterpret_cast<uintptr_t>(bits) & 15) == 0, "mask_select_counts: planes must be 16-byte aligned");
-    SOLA_ARG((long long)E * T < (1ll << 31), "mask_select_counts: E*T too large");
-    hipStream_t s = as_stream(stream_);
-    // the plane reads depend on the id lists, which live on the device: only the counts are in the profile's bytes
-    SolaProfScope prof(SOLA_PROF_IOU_PACK, s, 0, 24.0 * (double)E * T);
-    hipLaunchKernelGGL(mask_select_counts_kernel, dim3((unsigned)((long long)E * T)), dim3(256), 0, s,
-                       reinterpret_cast<const uint4*>(bits), (long long)(words_stride / 4), n_masks, T, pred_off, pred_idx, gt_off,
-                       gt_idx, reinterpret_cast<long long*>(counts));
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
+    return nested_counts_launch("mask_select_counts", bits, words_stride, n_masks, T, pred_off, pred_idx, nullptr, 1, gt_off, gt_idx, E,
+                                counts, stream_);
 }
 
 extern "C" int sola_mask_nested_counts(const uint32_t* bits, int64_t words_stride, int n_masks, int T, const int32_t* pred_off,
@@ -242,19 +210,8 @@ extern "C" int sola_mask_nested_counts(const uint32_t* bits, int64_t words_strid
     SOLA_ARG(K > 0 && T > 0 && E > 0 && n_masks >= 0, "mask_nested_counts: bad sizes (n_masks %d, T %d, E %d, K %d)", n_masks, T, E, K);
     SOLA_ARG(words_stride > 0 && words_stride % 4 == 0, "mask_nested_counts: words_stride %lld is not a positive multiple of 4",
              (long long)words_stride);
-    SOLA_ARG(words_stride < (1ll << 26), "mask_nested_counts: planes too large");
-    SOLA_ARG((reinterpret_cast<uintptr_t>(bits) & 15) == 0, "mask_nested_counts: planes must be 16-byte aligned");
-    SOLA_ARG((long long)E * T < (1ll << 31), "mask_nested_counts: E*T too large");
-    hipStream_t s = as_stream(stream_);
-    // as sola_mask_select_counts: the plane reads depend on the lists on the device, only the counts are in the profile's bytes
-    SolaProfScope prof(SOLA_PROF_IOU_PACK, s, 0, 24.0 * (double)E * K * T);
-    for (int k0 = 0; k0 < K; k0 += SOLA_NESTED_MAX_LEVELS) {  // a launch per 16 levels; its first level ORs the whole prefix again
-        hipLaunchKernelGGL(mask_nested_counts_kernel, dim3((unsigned)((long long)E * T)), dim3(256), 0, s,
-                           reinterpret_cast<const uint4*>(bits), (long long)(words_stride / 4), n_masks, T, pred_off, pred_idx, level_end,
-                           K, k0, std::min(SOLA_NESTED_MAX_LEVELS, K - k0), gt_off, gt_idx, reinterpret_cast<long long*>(counts));
-        SOLA_LAUNCH_CHECK();
-    }
-    return SOLA_OK;
+    return nested_counts_launch("mask_nested_counts", bits, words_stride, n_masks, T, pred_off, pred_idx, level_end, K, gt_off, gt_idx, E,
+                                counts, stream_);
 }
 
 extern "C" int64_t sola_rle_strings_to_cum_batch(const char* chars, const int64_t* str_off, int64_t n, uint32_t* cum, int64_t cap,

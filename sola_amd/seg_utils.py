@@ -21,6 +21,26 @@ def _elem_type(t):
     raise SolaError(f"masks must be uint8/bool or float32, got {t.dtype}")
 
 
+def _mask_kind(t, logits, who=None):
+    """The library's element kind of mask tensor ``t``: 0 uint8 / bool, 1 float32 (set where != 0), 2 float32 logits (set where > 0)."""
+    if logits and t.dtype != torch.float32:
+        raise SolaError("logits must be float32" if who is None else f"{who}: logits must be float32, got {t.dtype}")
+    return 2 if logits else _elem_type(t)
+
+
+_SCRATCH = {}
+
+
+def _stream_scratch(name, dev, nbytes, dtype=torch.uint8, floor=0):
+    """Kernel ``name``'s scratch of at least ``nbytes`` bytes (and ``floor`` elements of ``dtype``), reused from call to call per
+    device and stream: calls on one stream are ordered, and an allocation can cost as much as the kernel it serves."""
+    key = (name, dev, torch.cuda.current_stream(dev).cuda_stream)
+    buf = _SCRATCH.get(key)
+    if buf is None or buf.numel() * buf.element_size() < nbytes:
+        buf = _SCRATCH[key] = torch.empty(max(-(-nbytes // dtype.itemsize), floor), device=dev, dtype=dtype)
+    return buf
+
+
 def _prep(t):
     require_cuda(t)
     if t.dtype == torch.bool:
@@ -60,9 +80,6 @@ def pair_counts(a_bits, a_area, b_bits, b_area, T=1, a_frame=None):
     return inter, union
 
 
-_IOU_SCRATCH = {}
-
-
 def mask_iou_matrix(A, B):
     """A [P,H,W], B [R,h,w] (resampled to H x W) -> (inter, union) int64 [P,R] in one library call."""
     A, B = _prep(A), _prep(B)
@@ -74,12 +91,8 @@ def mask_iou_matrix(A, B):
     out = torch.empty((2, P, R), device=dev, dtype=torch.int64)  # one allocation for both count matrices
     inter, union = out[0], out[1]
     nb = lib().sola_mask_iou_scratch_bytes(P, R, H, W)
-    # the scratch is reused from call to call (same stream: the calls are ordered): the de-dup loop calls this once per SAM2
-    # iteration with 10-35 MB of masks, where an allocation costs as much as the kernel
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    scratch = _IOU_SCRATCH.get(key)
-    if scratch is None or scratch.numel() < nb:
-        scratch = _IOU_SCRATCH[key] = torch.empty(nb, device=dev, dtype=torch.uint8)
+    # reused from call to call: the de-dup loop calls this once per SAM2 iteration with 10-35 MB of masks
+    scratch = _stream_scratch("iou", dev, nb)
     check(lib().sola_mask_iou_matrix(ptr(A), ptr(B), _elem_type(A), P, R, H, W, h, w, ptr(inter), ptr(union),
                                      ptr(scratch), scratch.numel(), current_stream(dev)), "sola_mask_iou_matrix")
     return inter, union
@@ -169,14 +182,13 @@ def pack_masklet_bilinear(masklet, target_shape=None, logits=False):
     pass over the source (seg_utils.py:145-160 without the fp32 [N,H,W] intermediate).  ``logits=True``: the input is
     the tracker's float32 mask logits and `(logits > 0).float()` (generate_tokens_grid.py:215-222) is applied on read."""
     masklet = _prep(masklet)
-    if logits and masklet.dtype != torch.float32:
-        raise SolaError("logits must be float32")
+    et = _mask_kind(masklet, logits)
     n, h, w = masklet.shape
     H, W = default_target_shape(h, w) if target_shape is None else target_shape
     words = lib().sola_mask_words(H, W)
     bits = torch.empty((n, words), device=masklet.device, dtype=torch.int32)
     area = torch.empty((n,), device=masklet.device, dtype=torch.int64)
-    check(lib().sola_mask_bilinear_pack(ptr(masklet), 2 if logits else _elem_type(masklet), n, h, w, H, W, ptr(bits), ptr(area),
+    check(lib().sola_mask_bilinear_pack(ptr(masklet), et, n, h, w, H, W, ptr(bits), ptr(area),
                                         current_stream(masklet.device)), "sola_mask_bilinear_pack")
     return bits, area, (H, W)
 
@@ -361,6 +373,15 @@ def compute_P(part_masks, full_mask):
     return inter[:, 0].to(torch.float32) / a_area.to(torch.float32)
 
 
+def _run_list_cum(counts, limit, who):
+    """Inclusive prefix sums (uint32) of an uncompressed run list, which must be non-negative and cover at most ``limit`` pixels."""
+    import numpy as np
+    c = np.cumsum(np.asarray(counts, dtype=np.int64))
+    if len(c) and (c[-1] > limit or np.any(np.diff(c) < 0) or c[0] < 0):
+        raise SolaError(f"{who}: runs are negative or exceed the image")
+    return c.astype(np.uint32)
+
+
 def _rle_cum(rle, limit):
     """Inclusive prefix sums (uint32) of one RLE dict's run lengths; compressed strings are parsed by the library's
     host helper (sola_rle_string_to_cum), uncompressed lists by numpy."""
@@ -375,10 +396,7 @@ def _rle_cum(rle, limit):
         if n < 0:
             check(int(n), "sola_rle_string_to_cum")
         return buf[:n]
-    c = np.cumsum(np.asarray(counts, dtype=np.int64))
-    if len(c) and (c[-1] > limit or np.any(np.diff(c) < 0) or c[0] < 0):
-        raise SolaError("rle_merge_or: runs are negative or exceed the image")
-    return c.astype(np.uint32)
+    return _run_list_cum(counts, limit, "rle_merge_or")
 
 
 @torch.no_grad()
@@ -479,13 +497,7 @@ def _planes_cum(masklets, ids, T, hw):
     if lists:
         pieces = []
         for p in range(len(frames)):
-            if p in lists:
-                c = np.cumsum(np.asarray(lists[p], dtype=np.int64))
-                if len(c) and (c[-1] > hw or np.any(np.diff(c) < 0) or c[0] < 0):
-                    raise SolaError("masklet_select_counts: runs are negative or exceed the image")
-                pieces.append(c.astype(np.uint32))
-            else:
-                pieces.append(cum[off[p]:off[p + 1]])
+            pieces.append(_run_list_cum(lists[p], hw, "masklet_select_counts") if p in lists else cum[off[p]:off[p + 1]])
         off = np.zeros(len(frames) + 1, np.int64)
         np.cumsum([len(x) for x in pieces], out=off[1:])
         cum = np.concatenate(pieces) if pieces else cum[:0]
@@ -541,6 +553,70 @@ def _plane_groups(masklets, refs, T, h, w, stride, dev, max_plane_bytes):
         yield grp, local, bits, len(ids)
 
 
+def _level_counts(who, masklets, lists, ends, K, gt_sets, device, max_plane_bytes, boundary):
+    """The counting path under masklet_select_counts and masklet_sweep_counts (``who``: the caller's name in the messages):
+    ``(counts, bcounts)`` on the host, counts int64 [E, K, T, 3] with ``[e, k]`` the (intersection, n_pred, n_gt) table of the
+    prediction OR over ``lists[e][:ends[e][k]]`` against the OR over ``gt_sets[e]``; ``ends[e]`` holds K non-decreasing prefix
+    lengths.  bcounts is None, or with ``boundary`` int64 [E, K, T, 4].  Per group of _plane_groups: one int32 upload of every
+    list, one sola_mask_nested_counts call, and the K prefix lists of every expression as E*K pseudo-expressions through one
+    sola_mask_select_boundary_counts launch on the same planes (with K = 1 those are the prediction lists themselves)."""
+    E, M = len(lists), len(masklets)
+    if M == 0:
+        raise SolaError(f"{who}: no masklets")
+    for s in list(lists) + list(gt_sets):
+        for i in s:
+            if not 0 <= int(i) < M:
+                raise SolaError(f"{who}: index {i} outside the {M} masklets")
+    T, size = _masklet_geometry(masklets)
+    if E == 0 or size is None or T == 0:  # (no size: every frame of every masklet is missing, all masks are empty)
+        return torch.zeros((E, K, T, 3), dtype=torch.int64), None if boundary is None else torch.zeros((E, K, T, 4), dtype=torch.int64)
+    h, w = size
+    L = lib()
+    radius = None if boundary is None else boundary_radius(h, w, _boundary_th(boundary))
+    stride = L.sola_jf_plane_words(h, w)
+    dev = torch.device(device)
+    stream = current_stream(dev)
+    preds = [[int(i) for i in lists[e][:ends[e][-1]]] for e in range(E)]  # what the largest level selects
+    gts = [[int(i) for i in s] for s in gt_sets]
+    outs, bouts = [], []
+    for grp, local, bits, n_ids in _plane_groups(masklets, [p + g for p, g in zip(preds, gts)], T, h, w, stride, dev, max_plane_bytes):
+        Eg = len(grp)
+        poff, pidx, goff, gidx, lend = [0], [], [0], [], []
+        for e in grp:
+            pidx += [local[i] for i in preds[e]]
+            poff.append(len(pidx))
+            gidx += [local[i] for i in gts[e]]
+            goff.append(len(gidx))
+            lend += ends[e]
+        parts = [lend, poff, pidx + [0], goff, gidx + [0]]  # (the pad entries keep the pointers of empty lists non-null)
+        if radius is not None and K > 1:  # level k of expression e as pseudo-expression e*K + k of the boundary launch
+            boff, bidx, bgoff, bgidx = [0], [], [0], []
+            for j, e in enumerate(grp):
+                for k in range(K):
+                    bidx += pidx[poff[j]:poff[j] + ends[e][k]]
+                    boff.append(len(bidx))
+                    bgidx += gidx[goff[j]:goff[j + 1]]
+                    bgoff.append(len(bgidx))
+            parts += [boff, bidx + [0], bgoff, bgidx + [0]]
+        ints = torch.tensor([x for part in parts for x in part], dtype=torch.int32).to(dev)  # one copy for every list
+        d, o = [], 0
+        for part in parts:
+            d.append(ptr(ints[o:o + len(part)]))
+            o += len(part)
+        counts = torch.empty((Eg, K, T, 3), device=dev, dtype=torch.int64)
+        check(L.sola_mask_nested_counts(ptr(bits), stride if n_ids else 4, n_ids, T, d[1], d[2], d[0], K, d[3], d[4], Eg, ptr(counts),
+                                        stream), "sola_mask_nested_counts")
+        outs.append(counts)
+        if radius is not None:
+            bcounts = torch.empty((Eg, K, T, 4), device=dev, dtype=torch.int64)
+            # (without ids no plane is read: the stride is the frame's over the dummy plane)
+            check(L.sola_mask_select_boundary_counts(ptr(bits), stride, n_ids, T, h, w, radius, *d[-4:], Eg * K, ptr(bcounts), None, 0,
+                                                     stream), "sola_mask_select_boundary_counts")
+            bouts.append(bcounts)
+    counts = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu()
+    return counts, None if radius is None else (bouts[0] if len(bouts) == 1 else torch.cat(bouts)).cpu()
+
+
 @torch.no_grad()
 def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=2 << 30, boundary=None):
     """Every expression of a video against its ground truth, per frame: int64 [E, T, 3] (intersection, n_pred, n_gt) on the
@@ -549,67 +625,31 @@ def masklet_select_counts(masklets, pred_sets, gt_sets, device, max_plane_bytes=
 
     ``masklets``: M masklets of one T and (h, w), each a list of T per-frame COCO RLE dicts (a non-dict is a missing frame =
     zeros) or an IndexMasklet (``index_maps == obj_id``; those of one index-map tensor are compared by one sola_index_pack
-    launch into their rows of the RLE masklets' plane buffer).  Only the masks some list references are decoded, once each, into column-major bit planes (sola_rle_pack_cm)
-    and every (expression, frame) is counted by one launch (sola_mask_select_counts): one host parse, one decode launch, one
-    count launch and one copy.  The planes of one launch are capped at ``max_plane_bytes``: expressions are grouped in order
-    under that budget (an expression that alone exceeds it runs by itself).  An empty list is an all-zero masklet.  Counts
-    are exact int64; the reference sums float32 tensors, which is exact while every count is below 2^24.
+    launch into their rows of the RLE masklets' plane buffer).  Only the masks some list references are decoded, once each,
+    into column-major bit planes (sola_rle_pack_cm) and every (expression, frame) is counted by one launch (_level_counts with
+    one level per expression, the whole list): one host parse, one decode launch, one count launch and one copy.  The planes
+    of one launch are capped at ``max_plane_bytes``: expressions are grouped in order under that budget (an expression that
+    alone exceeds it runs by itself).  An empty list is an all-zero masklet.  Counts are exact int64; the reference sums
+    float32 tensors, which is exact while every count is below 2^24.
 
     ``boundary`` = the DAVIS ``bound_th`` (``True`` = 0.008): returns ``(counts, bcounts)`` with bcounts int64 [E, T, 4] =
     (n_fg, n_gt, fg_match, gt_match), the boundary pixels of prediction and ground truth and those within the disk of
     boundary_radius(h, w, bound_th) of the other's (sola_mask_select_boundary_counts on the planes of the same decode
     launch; F_boundary_from_counts turns a [T,4] table into the benchmark's F)."""
-    import numpy as np
-    E = len(pred_sets)
-    if len(gt_sets) != E:
-        raise SolaError(f"masklet_select_counts: {E} prediction sets but {len(gt_sets)} GT sets")
-    M = len(masklets)
-    if M == 0:
-        raise SolaError("masklet_select_counts: no masklets")
-    for s in list(pred_sets) + list(gt_sets):
-        for i in s:
-            if not 0 <= int(i) < M:
-                raise SolaError(f"masklet_select_counts: index {i} outside the {M} masklets")
-    T, size = _masklet_geometry(masklets)
-    if E == 0 or size is None or T == 0:  # (no size: every frame of every masklet is missing, all masks are empty)
-        counts = torch.zeros((E, T, 3), dtype=torch.int64)
-        return counts if boundary is None else (counts, torch.zeros((E, T, 4), dtype=torch.int64))
-    h, w = size
-    L = lib()
-    radius = None if boundary is None else boundary_radius(h, w, _boundary_th(boundary))
-    stride = L.sola_jf_plane_words(h, w)
-    dev = torch.device(device)
-    stream = current_stream(dev)
-    refs = [[int(i) for i in pred_sets[e]] + [int(i) for i in gt_sets[e]] for e in range(E)]
-    outs, bouts = [], []
-    for grp, local, bits, n_ids in _plane_groups(masklets, refs, T, h, w, stride, dev, max_plane_bytes):
-        csr = []
-        for sets in (pred_sets, gt_sets):
-            off, idx = [0], []
-            for e in grp:
-                idx += [local[int(i)] for i in sets[e]]
-                off.append(len(idx))
-            csr.append((off, idx))
-        (poff, pidx), (goff, gidx) = csr
-        ints = torch.tensor(poff + goff + pidx + gidx + [0], dtype=torch.int32).to(dev)  # one copy for the four lists
-        Eg = len(grp)
-        d_poff, d_goff = ints[:Eg + 1], ints[Eg + 1:2 * Eg + 2]
-        d_pidx, d_gidx = ints[2 * Eg + 2:2 * Eg + 2 + len(pidx)], ints[2 * Eg + 2 + len(pidx):]
-        counts = torch.empty((Eg, T, 3), device=dev, dtype=torch.int64)
-        check(L.sola_mask_select_counts(ptr(bits), stride if n_ids else 4, n_ids, T, ptr(d_poff), ptr(d_pidx), ptr(d_goff),
-                                        ptr(d_gidx), Eg, ptr(counts), stream), "sola_mask_select_counts")
-        outs.append(counts)
-        if radius is not None:
-            bcounts = torch.empty((Eg, T, 4), device=dev, dtype=torch.int64)
-            # (without ids no plane is read: the stride is the frame's over the dummy plane)
-            check(L.sola_mask_select_boundary_counts(ptr(bits), stride, n_ids, T, h, w, radius, ptr(d_poff), ptr(d_pidx),
-                                                     ptr(d_goff), ptr(d_gidx), Eg, ptr(bcounts), None, 0, stream),
-                  "sola_mask_select_boundary_counts")
-            bouts.append(bcounts)
-    counts = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu()
-    if radius is None:
-        return counts
-    return counts, (bouts[0] if len(bouts) == 1 else torch.cat(bouts)).cpu()
+    if len(gt_sets) != len(pred_sets):
+        raise SolaError(f"masklet_select_counts: {len(pred_sets)} prediction sets but {len(gt_sets)} GT sets")
+    counts, bcounts = _level_counts("masklet_select_counts", masklets, pred_sets, [[len(s)] for s in pred_sets], 1, gt_sets, device,
+                                    max_plane_bytes, boundary)
+    return counts[:, 0] if boundary is None else (counts[:, 0], bcounts[:, 0])
+
+
+def _jf_scores(counts, bcounts=None):
+    """One expression's [T,3] table (and [T,4] boundary table) -> (J, F, JF) or (J, F, JF, F_boundary, JF_boundary)."""
+    J, F = float(J_from_counts(counts)), float(F_from_counts(counts))
+    if bcounts is None:
+        return J, F, (J + F) / 2
+    Fb = float(F_boundary_from_counts(bcounts))
+    return J, F, (J + F) / 2, Fb, (J + Fb) / 2
 
 
 def compute_JF_batch(masklets, pred_sets, gt_sets, device, boundary=None, **kw):
@@ -619,18 +659,9 @@ def compute_JF_batch(masklets, pred_sets, gt_sets, device, boundary=None, **kw):
     ``boundary`` = its ``bound_th`` (``True`` = 0.008): every entry is then (J, F, JF, F_boundary, JF_boundary), F_boundary
     the mean over frames of the contour F-measure and JF_boundary = (J + F_boundary) / 2, the benchmark's J&F."""
     counts = masklet_select_counts(masklets, pred_sets, gt_sets, device, boundary=boundary, **kw)
-    bcounts = None
-    if boundary is not None:
-        counts, bcounts = counts
-    out = []
-    for e, c in enumerate(counts):
-        J, F = float(J_from_counts(c)), float(F_from_counts(c))
-        if bcounts is None:
-            out.append((J, F, (J + F) / 2))
-        else:
-            Fb = float(F_boundary_from_counts(bcounts[e]))
-            out.append((J, F, (J + F) / 2, Fb, (J + Fb) / 2))
-    return out
+    if boundary is None:
+        return [_jf_scores(c) for c in counts]
+    return [_jf_scores(c, b) for c, b in zip(*counts)]
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -665,82 +696,28 @@ def masklet_sweep_counts(masklets, cand_sets, probs, thresholds, gt_sets, device
     ``thresholds[j]``} (the rule of sweep_levels) against the OR over ``gt_sets[e]``, levels in the caller's threshold order.
 
     ``cand_sets[e]`` holds the masklet indices of expression e's tracks, ``probs[e]`` their float32 scores.  The host work is
-    masklet_select_counts': the masks referenced are the selection at the lowest threshold plus the ground truth, decoded once
-    per group of expressions under ``max_plane_bytes``; then one sola_mask_nested_counts call, in which every plane is read
-    once per (expression, frame) whatever K, and one copy.  With ``boundary`` (the DAVIS bound_th, ``True`` = 0.008) returns
-    ``(counts, bcounts)``, bcounts int64 [E, K, T, 4] as masklet_select_counts gives it: the K prefix lists of every
-    expression go as E*K pseudo-expressions through one sola_mask_select_boundary_counts launch on the same planes."""
+    masklet_select_counts' (_level_counts): the masks referenced are the selection at the lowest threshold plus the ground
+    truth, decoded once per group of expressions under ``max_plane_bytes``; then one sola_mask_nested_counts call, in which
+    every plane is read once per (expression, frame) whatever K, and one copy.  With ``boundary`` (the DAVIS bound_th,
+    ``True`` = 0.008) returns ``(counts, bcounts)``, bcounts int64 [E, K, T, 4] as masklet_select_counts gives it."""
     import numpy as np
     E, K = len(cand_sets), len(thresholds)
     if K == 0:
         raise SolaError("masklet_sweep_counts: no thresholds")
     if len(gt_sets) != E or len(probs) != E:
         raise SolaError(f"masklet_sweep_counts: {E} candidate sets but {len(probs)} score vectors and {len(gt_sets)} GT sets")
-    M = len(masklets)
-    if M == 0:
-        raise SolaError("masklet_sweep_counts: no masklets")
-    for s in list(cand_sets) + list(gt_sets):
-        for i in s:
-            if not 0 <= int(i) < M:
-                raise SolaError(f"masklet_sweep_counts: index {i} outside the {M} masklets")
     ordered, ends, perm = [], [], np.arange(K)
     for e in range(E):
         if len(probs[e]) != len(cand_sets[e]):
             raise SolaError(f"masklet_sweep_counts: expression {e} has {len(cand_sets[e])} tracks but {len(probs[e])} scores")
         order, level_end, perm = sweep_levels(probs[e], thresholds)
-        ordered.append([int(cand_sets[e][i]) for i in order])
+        rest = np.setdiff1d(np.arange(len(probs[e])), order)  # never selected: range-checked with the others, never read
+        ordered.append([cand_sets[e][i] for i in order] + [cand_sets[e][i] for i in rest])
         ends.append(level_end.tolist())
-    T, size = _masklet_geometry(masklets)
-    if E == 0 or size is None or T == 0:
-        counts = torch.zeros((E, K, T, 3), dtype=torch.int64)
-        return counts if boundary is None else (counts, torch.zeros((E, K, T, 4), dtype=torch.int64))
-    h, w = size
-    L = lib()
-    radius = None if boundary is None else boundary_radius(h, w, _boundary_th(boundary))
-    stride = L.sola_jf_plane_words(h, w)
-    dev = torch.device(device)
-    stream = current_stream(dev)
-    refs = [ordered[e] + [int(i) for i in gt_sets[e]] for e in range(E)]
-    outs, bouts = [], []
-    for grp, local, bits, n_ids in _plane_groups(masklets, refs, T, h, w, stride, dev, max_plane_bytes):
-        Eg = len(grp)
-        poff, pidx, goff, gidx, lend = [0], [], [0], [], []
-        for e in grp:
-            pidx += [local[i] for i in ordered[e]]
-            poff.append(len(pidx))
-            gidx += [local[int(i)] for i in gt_sets[e]]
-            goff.append(len(gidx))
-            lend += ends[e]
-        parts = [poff, goff, lend, pidx + [0], gidx + [0]]  # (the pad entries keep the pointers of empty lists non-null)
-        if radius is not None:  # level k of expression e as pseudo-expression e*K + k of the boundary launch
-            boff, bidx, bgoff, bgidx = [0], [], [0], []
-            for j, e in enumerate(grp):
-                for k in range(K):
-                    bidx += pidx[poff[j]:poff[j] + ends[e][k]]
-                    boff.append(len(bidx))
-                    bgidx += gidx[goff[j]:goff[j + 1]]
-                    bgoff.append(len(bgidx))
-            parts += [boff, bgoff, bidx + [0], bgidx + [0]]
-        ints = torch.tensor([x for part in parts for x in part], dtype=torch.int32).to(dev)  # one copy for every list
-        d, o = [], 0
-        for part in parts:
-            d.append(ints[o:o + len(part)])
-            o += len(part)
-        counts = torch.empty((Eg, K, T, 3), device=dev, dtype=torch.int64)
-        check(L.sola_mask_nested_counts(ptr(bits), stride if n_ids else 4, n_ids, T, ptr(d[0]), ptr(d[3]), ptr(d[2]), K, ptr(d[1]),
-                                        ptr(d[4]), Eg, ptr(counts), stream), "sola_mask_nested_counts")
-        outs.append(counts)
-        if radius is not None:
-            bcounts = torch.empty((Eg, K, T, 4), device=dev, dtype=torch.int64)
-            check(L.sola_mask_select_boundary_counts(ptr(bits), stride, n_ids, T, h, w, radius, ptr(d[5]), ptr(d[7]), ptr(d[6]),
-                                                     ptr(d[8]), Eg * K, ptr(bcounts), None, 0, stream),
-                  "sola_mask_select_boundary_counts")
-            bouts.append(bcounts)
+    counts, bcounts = _level_counts("masklet_sweep_counts", masklets, ordered, ends, K, gt_sets, device, max_plane_bytes, boundary)
     perm = torch.from_numpy(perm)
-    counts = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu()[:, perm].contiguous()
-    if radius is None:
-        return counts
-    return counts, (bouts[0] if len(bouts) == 1 else torch.cat(bouts)).cpu()[:, perm].contiguous()
+    counts = counts[:, perm].contiguous()
+    return counts if boundary is None else (counts, bcounts[:, perm].contiguous())
 
 
 def compute_JF_sweep(masklets, cand_sets, probs, thresholds, gt_sets, device, boundary=None, **kw):
@@ -748,21 +725,9 @@ def compute_JF_sweep(masklets, cand_sets, probs, thresholds, gt_sets, device, bo
     caller's order) of the tuples compute_JF_batch returns for that threshold's selection, (J, F, JF) or, with ``boundary``,
     (J, F, JF, F_boundary, JF_boundary)."""
     counts = masklet_sweep_counts(masklets, cand_sets, probs, thresholds, gt_sets, device, boundary=boundary, **kw)
-    bcounts = None
-    if boundary is not None:
-        counts, bcounts = counts
-    out = []
-    for e, ce in enumerate(counts):
-        row = []
-        for k, c in enumerate(ce):
-            J, F = float(J_from_counts(c)), float(F_from_counts(c))
-            if bcounts is None:
-                row.append((J, F, (J + F) / 2))
-            else:
-                Fb = float(F_boundary_from_counts(bcounts[e, k]))
-                row.append((J, F, (J + F) / 2, Fb, (J + Fb) / 2))
-        out.append(row)
-    return out
+    if boundary is None:
+        return [[_jf_scores(c) for c in ce] for ce in counts]
+    return [[_jf_scores(c, b) for c, b in zip(ce, be)] for ce, be in zip(*counts)]
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -780,9 +745,7 @@ def encode_rle_masklet(masks, logits=False, return_cum=False):
     masks = _prep(masks)
     if masks.dim() != 3:
         raise SolaError(f"encode_rle_masklet: masks must be (T,h,w), got {tuple(masks.shape)}")
-    if logits and masks.dtype != torch.float32:
-        raise SolaError("logits must be float32")
-    et = 2 if logits else _elem_type(masks)
+    et = _mask_kind(masks, logits)
     n, h, w = masks.shape
     dev = masks.device
     offs = torch.zeros((2, n + 1), device=dev, dtype=torch.int64)  # run_off, char_off
@@ -816,18 +779,22 @@ def encode_rle_mask(mask, logits=False):
     return encode_rle_masklet(mask.unsqueeze(0), logits)[0]
 
 
+def _split_frames(flat, masklets):
+    """The per-frame list of an encode over masklets concatenated along frames -> one list per masklet."""
+    out, f = [], 0
+    for m in masklets:
+        out.append(flat[f:f + m.shape[0]])
+        f += m.shape[0]
+    return out
+
+
 @torch.no_grad()
 def encode_rle_masklets(masklets, logits=False):
     """Every track of a SAM2 batch (list of (T_i,h,w) masklets of one size and dtype) -> list of per-track RLE lists,
     from ONE encode over the masklets concatenated along frames."""
     if len(masklets) == 0:
         return []
-    flat = encode_rle_masklet(torch.cat([_prep(m) for m in masklets]), logits)
-    out, f = [], 0
-    for m in masklets:
-        out.append(flat[f:f + m.shape[0]])
-        f += m.shape[0]
-    return out
+    return _split_frames(encode_rle_masklet(torch.cat([_prep(m) for m in masklets]), logits), masklets)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -843,9 +810,7 @@ def png_deflate_masklet(masks, logits=False, out=None):
     masks = _prep(masks)
     if masks.dim() != 3:
         raise SolaError(f"png_deflate_masklet: masks must be (T,h,w), got {tuple(masks.shape)}")
-    if logits and masks.dtype != torch.float32:
-        raise SolaError("logits must be float32")
-    et = 2 if logits else _elem_type(masks)
+    et = _mask_kind(masks, logits)
     n, h, w = masks.shape
     if n == 0:
         return b"", [0]
@@ -899,19 +864,13 @@ def encode_png_masklets(masklets, logits=False):
     concatenated along frames."""
     if len(masklets) == 0:
         return []
-    flat = encode_png_masklet(torch.cat([_prep(m) for m in masklets]), logits)
-    out, f = [], 0
-    for m in masklets:
-        out.append(flat[f:f + m.shape[0]])
-        f += m.shape[0]
-    return out
+    return _split_frames(encode_png_masklet(torch.cat([_prep(m) for m in masklets]), logits), masklets)
 
 
 # ----------------------------------------------------------------------------------------------------------------
 # connected components, SAM2's fill_holes_in_mask_scores, small-region removal (components.hip)
 # ----------------------------------------------------------------------------------------------------------------
 CC_TILE = (16, 64)  # (rows, columns) of the labelling kernel's tile: include/sola_hip.h SOLA_CC_TILE_H / _W
-_CC_SCRATCH = {}
 
 
 def _cc_frames(t, what):
@@ -927,11 +886,7 @@ def _cc_scratch(dev, n, h, w, scratch):
     nb = lib().sola_mask_components_scratch_bytes(n, h, w)
     if scratch is not None:  # the caller's own (tests): a contiguous uint8 device tensor
         return scratch, scratch.numel()
-    # reused from call to call like the IoU scratch: calls on one stream are ordered
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    scratch = _CC_SCRATCH.get(key)
-    if scratch is None or scratch.numel() < nb:
-        scratch = _CC_SCRATCH[key] = torch.empty(max(nb, 256), device=dev, dtype=torch.uint8)
+    scratch = _stream_scratch("cc", dev, nb, floor=256)
     return scratch, scratch.numel()
 
 
@@ -943,9 +898,7 @@ def connected_components(mask, connectivity=8, logits=False, scratch=None):
     clear pixels and the pixel count of the pixel's component elsewhere.  The N frames are labelled independently in one
     library call; ``connectivity`` is 8 (SAM2's) or 4; ``logits=True`` counts float32 ``> 0``."""
     m, shape = _cc_frames(mask, "connected_components")
-    if logits and m.dtype != torch.float32:
-        raise SolaError("logits must be float32")
-    et = 2 if logits else _elem_type(m)
+    et = _mask_kind(m, logits)
     n, h, w = m.shape
     dev = m.device
     out = torch.empty((2, n, h, w), device=dev, dtype=torch.int32)
@@ -1003,7 +956,6 @@ def remove_small_regions(masks, max_area, mode, connectivity=8, scratch=None):
 # the logits, box NMS, the part filter, uncompressed RLE (amg.hip; the part filter and the RLE ride on kernels above)
 # ----------------------------------------------------------------------------------------------------------------
 NMS_MAX_BOXES = 16384  # include/sola_hip.h SOLA_BOX_NMS_MAX_N
-_NMS_SCRATCH = {}
 
 
 def _f32(x):
@@ -1019,9 +971,7 @@ def mask_logit_stats(masks, mask_threshold=0.0, threshold_offset=1.0, logits=Tru
     and rounded once to float32), NaN never counting.  ``logits=False``: uint8 / bool / float32 masks set where != 0; all
     three counts are the area.  (x0, y0, x1, y1) is the inclusive box of the pixels counted in ``area``, (0, 0, 0, 0) for an
     empty mask."""
-    if logits and masks.dtype != torch.float32:
-        raise SolaError(f"mask_logit_stats: logits must be float32, got {masks.dtype}")
-    et = 2 if logits else _elem_type(masks)
+    et = _mask_kind(masks, logits, "mask_logit_stats")
     m, _ = _cc_frames(masks, "mask_logit_stats")
     n, h, w = m.shape
     stats = torch.empty((n, 7), device=m.device, dtype=torch.int64)
@@ -1082,11 +1032,8 @@ def batched_nms(boxes, scores, idxs, iou_threshold, scratch=None):
     order = torch.sort(scores, descending=True, stable=True).indices.contiguous()
     out = torch.empty((n + 1,), device=dev, dtype=torch.int64)  # n_keep, then the kept indices
     nb = lib().sola_box_nms_scratch_bytes(n)
-    if scratch is None:  # reused from call to call like the IoU scratch: calls on one stream are ordered
-        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-        scratch = _NMS_SCRATCH.get(key)
-        if scratch is None or scratch.numel() * 8 < nb:
-            scratch = _NMS_SCRATCH[key] = torch.empty(max(nb // 8, 32), device=dev, dtype=torch.int64)
+    if scratch is None:
+        scratch = _stream_scratch("nms", dev, nb, torch.int64, floor=32)
     check(lib().sola_box_nms(ptr(boxes), ptr(order), ptr(idxs), n, float(iou_threshold), ptr(out[1:]), ptr(out), ptr(scratch),
                              scratch.numel() * scratch.element_size(), current_stream(dev)), "sola_box_nms")
     return out[1:1 + int(out[0])]  # the host read

@@ -134,7 +134,7 @@ def numpy_counts(planes, T, pred_sets, gt_sets):
     return out
 
 
-@pytest.mark.parametrize("M,T,stride,E", [(9, 5, 44, 12), (40, 3, 4, 300), (3, 250, 4, 300)])
+@pytest.mark.parametrize("M,T,stride,E", [(9, 5, 44, 12), (40, 3, 4, 300), (3, 250, 4, 300), (3, 2, 1032, 5)])
 def test_select_counts_match_numpy(M, T, stride, E):
     rng = np.random.default_rng(M * 31 + E)
     planes = rng.integers(0, 1 << 32, size=(M * T, stride), dtype=np.uint64).astype(np.uint32)
@@ -145,8 +145,20 @@ def test_select_counts_match_numpy(M, T, stride, E):
     pred_sets[2], gt_sets[2] = [1, 1, M - 1], [M - 1, 1]  # duplicates, the same masks in both lists
     pred_sets[3], gt_sets[3] = [], []
     bits = torch.from_numpy(planes.view(np.int32)).cuda()
-    got = select_counts(bits, stride, M, T, pred_sets, gt_sets)  # (3, 250, 4, 300): E*T = 75000 blocks
+    got = select_counts(bits, stride, M, T, pred_sets, gt_sets)  # (3, 250, 4, 300): E*T = 75000 blocks; 1032 words: 258 quads, lanes 0 and 1 loop twice
     np.testing.assert_array_equal(got, numpy_counts(planes, T, pred_sets, gt_sets))
+
+
+def test_select_counts_skip_indices_outside_the_masks():
+    """A list entry >= n_masks is skipped: the counts are those of the lists without it."""
+    M, T, stride = 4, 3, 12
+    rng = np.random.default_rng(5)
+    planes = rng.integers(0, 1 << 32, size=(M * T, stride), dtype=np.uint64).astype(np.uint32)
+    pred_sets = [[0, M, 2], [M + 7], [M, 1, M], [3]]
+    gt_sets = [[1], [2, M], [M], [M + 1, 3, 0]]
+    inside = lambda sets: [[i for i in s if i < M] for s in sets]  # noqa: E731
+    got = select_counts(torch.from_numpy(planes.view(np.int32)).cuda(), stride, M, T, pred_sets, gt_sets)
+    np.testing.assert_array_equal(got, numpy_counts(planes, T, inside(pred_sets), inside(gt_sets)))
 
 
 def oracle_jf(masklets, pred_sets, gt_sets):
@@ -188,6 +200,23 @@ def test_compute_JF_batch_equals_the_oracle():
     with pytest.raises(_lib.SolaError):
         other = jc.rle_list(mc.blob_masklet(T, h + 1, w, 1))
         seg_utils.masklet_select_counts(masklets + [other], [[0]], [[1]], "cuda")  # (h, w) differs
+
+
+def test_masklet_select_counts_with_no_prediction_or_no_gt_index_at_all():
+    """Groups that have planes while every prediction list, or every GT list, is empty (the uploaded index list is then only
+    its pad entry), one expression with both lists empty among them: the counts of the numpy restatement on the same planes."""
+    T, h, w = 3, 13, 21
+    masklets = [jc.rle_list(mc.blob_masklet(T, h, w, 70 + k)) for k in range(3)]
+    stride = _lib.lib().sola_jf_plane_words(h, w)
+    planes = cm_planes(np.concatenate([mo.masklet_decode(m) for m in masklets]), stride)
+    for pred_sets, gt_sets in [([[], [], []], [[0], [], [1, 2]]), ([[0], [], [1, 2]], [[], [], []])]:
+        want = numpy_counts(planes, T, pred_sets, gt_sets)
+        assert want.any() and not want[1].any()
+        got = seg_utils.masklet_select_counts(masklets, pred_sets, gt_sets, "cuda")
+        np.testing.assert_array_equal(got.numpy(), want)
+        got, bgot = seg_utils.masklet_select_counts(masklets, pred_sets, gt_sets, "cuda", boundary=True)
+        np.testing.assert_array_equal(got.numpy(), want)
+        assert tuple(bgot.shape) == (3, T, 4) and not bgot[1].any()  # nothing on either side: no boundary pixel
 
 
 # ------------------------------------------------------------------------------------------------ eval.py end to end

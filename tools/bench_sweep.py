@@ -5,7 +5,7 @@ tools/bench_jf.py (40 SAM2-like blob masklets = 36 tracks + 4 GT objects, 16 exp
 
   a  sola_mask_nested_counts: every level's counts from one pass over the planes of the largest selection (two launches at
      K = 19), median HIP-event time on the stream;
-  b  the same numbers on the existing kernel: sola_mask_select_counts with every (expression, level) as a pseudo-expression,
+  b  the same numbers from the one-level launch: sola_mask_select_counts with every (expression, level) as a pseudo-expression,
      which reads the planes of each level's prefix again; median HIP-event time;
   c  K separate seg_utils.masklet_select_counts calls (parse, decode, count, copy per threshold), wall;
   d  one seg_utils.masklet_sweep_counts call, wall;
