@@ -30,6 +30,7 @@
 //      kept original indices written in visiting order.
 // The scratch is the matrix alone, n * ceil(n/64) words of 64 bits; every word that is read was written by launch 1.
 #include "kernels.h"
+#include "mask_elems.h"
 
 // The NMS decision is specified as separately rounded float32 operations: no a*b+c may become one fma in this file (the
 // Makefile also passes -ffp-contract=off for it).
@@ -57,11 +58,6 @@ struct StatsArgs {
     float thr, thr_hi, thr_lo;
 };
 
-__device__ __forceinline__ uint32_t amg_byte_bits(uint32_t d) {  // bytes != 0 of one dword -> 4 bits
-    const uint32_t nz = ((((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d) & 0x80808080u);
-    return ((nz >> 7) & 1u) | ((nz >> 14) & 2u) | ((nz >> 21) & 4u) | ((nz >> 28) & 8u);
-}
-
 struct StatsAcc {
     uint32_t n_hi = 0, n_lo = 0, area = 0;  // a thread sees at most AMG_CHUNK_BYTES / AMG_THREADS + 15 pixels
     int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
@@ -71,24 +67,20 @@ struct StatsAcc {
     }
 };
 
-// KIND 0: uint8 != 0, 1: float32 != 0, 2: float32 logits against the three thresholds (strict >, NaN never counts)
+// kind 2 is read against the three thresholds; masks (kinds 0, 1) are the same bits for all three
 template <int KIND>
 __device__ __forceinline__ void amg_one(const void* masks, long long at, int x, int y, const StatsArgs& a, StatsAcc& s) {
-    bool on, hi, lo;
-    if constexpr (KIND == 0) {
-        on = hi = lo = static_cast<const uint8_t*>(masks)[at] != 0;
-    } else {
-        const float v = static_cast<const float*>(masks)[at];
-        if constexpr (KIND == 1) on = hi = lo = v != 0.f;
-        else { on = v > a.thr; hi = v > a.thr_hi; lo = v > a.thr_lo; }
-    }
+    const auto v = static_cast<const typename mask_elem<KIND>::type*>(masks)[at];
+    const bool on = mask_is_set<KIND>(v, a.thr);
+    bool hi = on, lo = on;
+    if constexpr (KIND == MASK_LOGIT) { hi = mask_is_set<KIND>(v, a.thr_hi); lo = mask_is_set<KIND>(v, a.thr_lo); }
     s.n_hi += hi; s.n_lo += lo;
     if (on) { s.area += 1; s.pixel(x, y); }
 }
 
 template <int KIND>
 __global__ __launch_bounds__(AMG_THREADS) void amg_stats_kernel(const StatsArgs a) {
-    constexpr int V = KIND == 0 ? 16 : 4;           // pixels per 16-byte vector
+    constexpr int V = 16 / mask_elem<KIND>::size;    // pixels per 16-byte vector
     constexpr int CHUNK = AMG_CHUNK_BYTES / 16 * V;  // pixels per block
     __shared__ u64 red[7][AMG_THREADS / 64];
     const int tid = threadIdx.x;
@@ -98,18 +90,12 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_stats_kernel(const StatsArgs 
     const int w = a.w;
     const int lo = c * CHUNK;                                             // < hw < 2^31
     const int hi = (int)min((long long)lo + CHUNK, a.hw);
-    // [v_lo, v_hi): the part of [lo, hi) that is whole 16-byte-aligned vectors
-    const int mis_lo = (int)(((long long)a.base_mod + first % V + lo) % V);
-    const int mis_hi = (int)(((long long)a.base_mod + first % V + hi) % V);
-    const int v_lo = min(hi, lo + (V - mis_lo) % V);
-    const int v_hi = max(v_lo, hi - mis_hi);
-    const int n_vec = (v_hi - v_lo) / V;
+    const MaskPiece pc = mask_piece<V>(a.base_mod, first, lo, hi);
+    const int v_lo = pc.v_lo, n_vec = pc.n_vec;
     StatsAcc s;
 
-    // the pixels in front of and behind the vectors, at most 2 (V - 1)
-    const int n_head = v_lo - lo, n_edge = n_head + (hi - v_hi);
-    if (tid < n_edge) {
-        const int p = tid < n_head ? lo + tid : v_hi + (tid - n_head);
+    if (tid < pc.n_edge) {
+        const int p = tid < pc.n_head ? lo + tid : pc.v_hi + (tid - pc.n_head);
         const int y = p / w;
         amg_one<KIND>(a.masks, first + p, p - y * w, y, a, s);
     }
@@ -117,33 +103,20 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_stats_kernel(const StatsArgs 
     if (tid < n_vec) {
         const int p0 = v_lo + tid * V;
         int y = p0 / w, x = p0 - y * w;
-        const uint4* src = reinterpret_cast<const uint4*>(static_cast<const char*>(a.masks) + (first + p0) * (KIND == 0 ? 1 : 4));
+        using Vec = typename mask_elem<KIND>::vec;
+        const Vec* src = reinterpret_cast<const Vec*>(static_cast<const char*>(a.masks) + (first + p0) * mask_elem<KIND>::size);
         for (int k0 = 0; k0 < AMG_VECS && k0 * AMG_THREADS < n_vec; k0 += AMG_BATCH) {
             // AMG_BATCH loads in flight per lane; a vector past the end re-reads the piece's last one and is not counted
-            uint4 data[AMG_BATCH];
+            Vec data[AMG_BATCH];
 #pragma unroll
             for (int j = 0; j < AMG_BATCH; ++j) data[j] = src[(size_t)min((k0 + j) * AMG_THREADS, n_vec - 1 - tid)];
 #pragma unroll
             for (int j = 0; j < AMG_BATCH; ++j) {
                 if (tid + (k0 + j) * AMG_THREADS < n_vec) {
-                    const uint4 d = data[j];
-                    uint32_t b_on, b_hi, b_lo;
-                    if constexpr (KIND == 0) {
-                        b_on = amg_byte_bits(d.x) | amg_byte_bits(d.y) << 4 | amg_byte_bits(d.z) << 8 | amg_byte_bits(d.w) << 12;
-                        b_hi = b_lo = b_on;
-                    } else {
-                        const float f0 = __uint_as_float(d.x), f1 = __uint_as_float(d.y), f2 = __uint_as_float(d.z), f3 = __uint_as_float(d.w);
-                        if constexpr (KIND == 1) {
-                            b_on = (uint32_t)(f0 != 0.f) | (uint32_t)(f1 != 0.f) << 1 | (uint32_t)(f2 != 0.f) << 2 | (uint32_t)(f3 != 0.f) << 3;
-                            b_hi = b_lo = b_on;
-                        } else {
-                            b_on = (uint32_t)(f0 > a.thr) | (uint32_t)(f1 > a.thr) << 1 | (uint32_t)(f2 > a.thr) << 2 | (uint32_t)(f3 > a.thr) << 3;
-                            b_hi = (uint32_t)(f0 > a.thr_hi) | (uint32_t)(f1 > a.thr_hi) << 1 | (uint32_t)(f2 > a.thr_hi) << 2 |
-                                   (uint32_t)(f3 > a.thr_hi) << 3;
-                            b_lo = (uint32_t)(f0 > a.thr_lo) | (uint32_t)(f1 > a.thr_lo) << 1 | (uint32_t)(f2 > a.thr_lo) << 2 |
-                                   (uint32_t)(f3 > a.thr_lo) << 3;
-                        }
-                    }
+                    const Vec d = data[j];
+                    const uint32_t b_on = vec_bits<KIND>(d, a.thr);
+                    uint32_t b_hi = b_on, b_lo = b_on;
+                    if constexpr (KIND == MASK_LOGIT) { b_hi = vec_bits<KIND>(d, a.thr_hi); b_lo = vec_bits<KIND>(d, a.thr_lo); }
                     s.n_hi += __popc(b_hi);
                     s.n_lo += __popc(b_lo);
                     s.area += __popc(b_on);
@@ -208,11 +181,6 @@ __global__ __launch_bounds__(256) void amg_stats_finish_kernel(u64* stats, int n
     if (row[2] == 0) return;
     row[3] = (u64)w - row[3];
     row[4] = (u64)h - row[4];
-}
-
-template <int KIND>
-void amg_launch_stats(const StatsArgs& a, unsigned blocks, hipStream_t s) {
-    hipLaunchKernelGGL(amg_stats_kernel<KIND>, dim3(blocks), dim3(AMG_THREADS), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ NMS
@@ -403,11 +371,9 @@ extern "C" int sola_mask_logit_stats(const void* masks, int elem_type, int n, in
     a.step_y = (AMG_THREADS * V) / w;
     a.step_x = (AMG_THREADS * V) % w;
     a.thr = thr; a.thr_hi = thr_hi; a.thr_lo = thr_lo;
-    switch (elem_type) {
-        case 0: amg_launch_stats<0>(a, (unsigned)blocks, s); break;
-        case 1: amg_launch_stats<1>(a, (unsigned)blocks, s); break;
-        default: amg_launch_stats<2>(a, (unsigned)blocks, s); break;
-    }
+    with_mask_kind<MASK_LOGIT>(elem_type, [&](auto kind) {
+        hipLaunchKernelGGL(amg_stats_kernel<decltype(kind)::value>, dim3((unsigned)blocks), dim3(AMG_THREADS), 0, s, a);
+    });
     SOLA_LAUNCH_CHECK();
     hipLaunchKernelGGL(amg_stats_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a.stats, n, h, w);
     SOLA_LAUNCH_CHECK();

@@ -22,6 +22,7 @@
 //      inside its frame, areas = count[root]; or the fused rewrite of sola_mask_fill_small, which re-reads the input and
 //      stores only what the contract changes when `out` aliases `in`.
 #include "kernels.h"
+#include "mask_elems.h"
 
 namespace {
 
@@ -33,16 +34,9 @@ static_assert(CC_TW == 64 && CC_TH % (CC_THREADS / 64) == 0, "a wave is one tile
 
 typedef unsigned long long u64;
 
-// element kinds: 0 uint8 != 0, 1 float32 != 0, 2 float32 > 0, 3 float32 <= 0 (-0.0 set, NaN not), 4 uint8 == 0, 5 float32 == 0
-template <int KIND>
+template <int KIND>  // element kinds 0 to 5: mask_elems.h
 __device__ __forceinline__ bool cc_is_set(const void* p, long long i) {
-    if constexpr (KIND == 0) return static_cast<const uint8_t*>(p)[i] != 0;
-    if constexpr (KIND == 4) return static_cast<const uint8_t*>(p)[i] == 0;
-    const float v = static_cast<const float*>(p)[i];
-    if constexpr (KIND == 1) return v != 0.f;
-    if constexpr (KIND == 2) return v > 0.f;
-    if constexpr (KIND == 3) return v <= 0.f;
-    return v == 0.f;
+    return mask_is_set<KIND>(static_cast<const typename mask_elem<KIND>::type*>(p)[i]);
 }
 
 __device__ __forceinline__ u64 bits_upto(int b) { return ~0ull >> (63 - b); }  // bits 0..b, b in 0..63
@@ -254,7 +248,7 @@ __global__ __launch_bounds__(256) void cc_emit_fill_kernel(const void* in, void*
                                                            const int* __restrict__ count, long long max_area, uint32_t fill, int total) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
-    constexpr bool BYTES = KIND == 0 || KIND == 4;
+    constexpr bool BYTES = mask_elem<KIND>::size == 1;
     uint32_t v;  // the element's bits: floats pass through as integers, NaN payloads included
     if constexpr (BYTES) v = static_cast<const uint8_t*>(in)[i];
     else v = static_cast<const uint32_t*>(in)[i];
@@ -265,16 +259,6 @@ __global__ __launch_bounds__(256) void cc_emit_fill_kernel(const void* in, void*
     if (change) v = fill;
     if constexpr (BYTES) static_cast<uint8_t*>(out)[i] = (uint8_t)v;
     else static_cast<uint32_t*>(out)[i] = v;
-}
-
-template <int KIND>
-void cc_launch_tile(const void* in, const CcDims& d, int* parent, int* count, unsigned blocks, hipStream_t s) {
-    hipLaunchKernelGGL(cc_tile_kernel<KIND>, dim3(blocks), dim3(CC_THREADS), 0, s, in, d, parent, count);
-}
-template <int KIND>
-void cc_launch_fill(const void* in, void* out, const int* parent, const int* count, long long max_area, uint32_t fill, int total,
-                    unsigned blocks, hipStream_t s) {
-    hipLaunchKernelGGL(cc_emit_fill_kernel<KIND>, dim3(blocks), dim3(256), 0, s, in, out, parent, count, max_area, fill, total);
 }
 
 struct CcEvents {  // optional: the four launches between five events (sola_mask_fill_small_profile)
@@ -315,14 +299,9 @@ int cc_run(bool fused, const void* in, int elem_type, int n, int h, int w, int c
     auto mark = [&](int i) { return launch_us ? hipEventRecord(E.ev[i], s) : hipSuccess; };
 
     SOLA_HIP(mark(0));
-    switch (elem_type) {
-        case 0: cc_launch_tile<0>(in, d, parent, count, tiles, s); break;
-        case 1: cc_launch_tile<1>(in, d, parent, count, tiles, s); break;
-        case 2: cc_launch_tile<2>(in, d, parent, count, tiles, s); break;
-        case 3: cc_launch_tile<3>(in, d, parent, count, tiles, s); break;
-        case 4: cc_launch_tile<4>(in, d, parent, count, tiles, s); break;
-        default: cc_launch_tile<5>(in, d, parent, count, tiles, s); break;
-    }
+    with_mask_kind<MASK_F32_CLEAR>(elem_type, [&](auto kind) {
+        hipLaunchKernelGGL(cc_tile_kernel<decltype(kind)::value>, dim3(tiles), dim3(CC_THREADS), 0, s, in, d, parent, count);
+    });
     SOLA_LAUNCH_CHECK();
     SOLA_HIP(mark(1));
     const long long edges = (long long)n * ((long long)(d.tiles_y - 1) * w + (long long)(d.tiles_x - 1) * h);
@@ -337,15 +316,15 @@ int cc_run(bool fused, const void* in, int elem_type, int n, int h, int w, int c
     if (!fused) {
         hipLaunchKernelGGL(cc_emit_labels_kernel, dim3(px_blocks), dim3(256), 0, s, parent, count, h * w, labels, areas, (int)total);
     } else {
-        const uint32_t one_f = 0x3f800000u;
-        switch (elem_type) {  // what a small component becomes
-            case 0: cc_launch_fill<0>(in, out, parent, count, max_area, 0u, (int)total, px_blocks, s); break;
-            case 1: cc_launch_fill<1>(in, out, parent, count, max_area, 0u, (int)total, px_blocks, s); break;
-            case 2: cc_launch_fill<2>(in, out, parent, count, max_area, 0u, (int)total, px_blocks, s); break;
-            case 3: cc_launch_fill<3>(in, out, parent, count, max_area, __builtin_bit_cast(uint32_t, fill_value), (int)total, px_blocks, s); break;
-            case 4: cc_launch_fill<4>(in, out, parent, count, max_area, 1u, (int)total, px_blocks, s); break;
-            default: cc_launch_fill<5>(in, out, parent, count, max_area, one_f, (int)total, px_blocks, s); break;
-        }
+        // what a small component becomes: kinds 0 to 2 are cleared; 3 takes fill_value, 4 and 5 a one of their type
+        const uint32_t fill = elem_type == MASK_LOGIT_CLEAR ? __builtin_bit_cast(uint32_t, fill_value)
+                              : elem_type == MASK_U8_CLEAR  ? 1u
+                              : elem_type == MASK_F32_CLEAR ? 0x3f800000u
+                                                            : 0u;
+        with_mask_kind<MASK_F32_CLEAR>(elem_type, [&](auto kind) {
+            hipLaunchKernelGGL(cc_emit_fill_kernel<decltype(kind)::value>, dim3(px_blocks), dim3(256), 0, s, in, out, parent, count, max_area,
+                               fill, (int)total);
+        });
     }
     SOLA_LAUNCH_CHECK();
     SOLA_HIP(mark(4));

@@ -4,7 +4,7 @@
 //
 // sola_index_hist: idx [T,h,w] uint8 -> counts int64 [T,256].  hipMemsetAsync of the table, then index_hist_kernel: one block
 //   of 256 threads per IH_CHUNK_BYTES (64 KiB) piece of ONE frame.  16-byte loads wherever the absolute ADDRESS is 16-byte
-//   aligned (any w, any base: only the < 16 bytes at either end of a piece are read byte by byte, amg_stats_kernel's rule).  A
+//   aligned (any w, any base: only the < 16 bytes at either end of a piece are read byte by byte, mask_elems.h's mask_piece).  A
 //   lane counts RUNS of equal bytes and carries the open run from vector to vector, so a frame of one value costs a lane one
 //   LDS atomic, not one per pixel.  One LDS histogram per wave (4 x 256 uint32; a block sees at most 65536 pixels), folded by
 //   thread b = bin b into the table with one 64-bit integer atomicAdd per non-zero bin.
@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "mask_elems.h"
 
 namespace {
 
@@ -68,17 +69,12 @@ __global__ __launch_bounds__(IH_THREADS) void index_hist_kernel(const uint8_t* _
     const long long first = (long long)m * hw;
     const int lo = c * IH_CHUNK_BYTES;  // < hw < 2^31
     const int hi = (int)min((long long)lo + IH_CHUNK_BYTES, hw);
-    // [v_lo, v_hi): the part of [lo, hi) that is whole 16-byte-aligned vectors
-    const int mis_lo = (int)(((long long)base_mod + first % 16 + lo) % 16);
-    const int mis_hi = (int)(((long long)base_mod + first % 16 + hi) % 16);
-    const int v_lo = min(hi, lo + (16 - mis_lo) % 16);
-    const int v_hi = max(v_lo, hi - mis_hi);
-    const int n_vec = (v_hi - v_lo) / 16;
+    const MaskPiece pc = mask_piece<16>(base_mod, first, lo, hi);
+    const int v_lo = pc.v_lo, n_vec = pc.n_vec;
     uint32_t* mine = hist[wave];
     HistRun run;
 
-    const int n_head = v_lo - lo, n_edge = n_head + (hi - v_hi);  // at most 30 bytes
-    if (tid < n_edge) run.byte(idx[first + (tid < n_head ? lo + tid : v_hi + (tid - n_head))], mine);
+    if (tid < pc.n_edge) run.byte(idx[first + (tid < pc.n_head ? lo + tid : pc.v_hi + (tid - pc.n_head))], mine);
 
     if (tid < n_vec) {
         const uint4* src = reinterpret_cast<const uint4*>(idx + first + v_lo) + tid;
@@ -126,7 +122,8 @@ struct PackArgs {
     int cw, extra;                  // layout 1: columns a strip owns, columns after them it may need
 };
 
-// flags of the bytes of x that are ZERO, as 4 bits
+// flags of the bytes of x that are ZERO, as 4 bits: the complement of mask_elems.h's nz_byte_bits, kept apart because
+// nz_byte_bits(x) ^ 15 here makes the pack kernels 8 to 13 % longer (profiles/mask_elems_isa.txt)
 __device__ __forceinline__ uint32_t ip_zero_bytes(uint32_t x) {
     uint32_t z = ~((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x)) & 0x80808080u;  // bit 7 of every zero byte
     z >>= 7;        // bits 0, 8, 16, 24

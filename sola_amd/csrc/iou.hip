@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "mask_elems.h"
 
 namespace {
 
@@ -30,12 +31,22 @@ struct PackArgs {
     unsigned long long* area2;
 };
 
-template <typename T>
-__device__ __forceinline__ bool is_set(T v) { return v != (T)0; }
+// 16 uint8 pixels -> 16 bits: vec_bits<MASK_U8> with the four byte flags of a dword gathered into a nibble by one multiply (no
+// carries reach bits 24-27) where nz_byte_bits takes shifts.  Kept for this file's kernels, which pack up to 48 vectors per
+// lane: with the shift gather mask_iou_onepass_kernel<1> compiles to 1660 instructions and 107 VGPRs, with this one to 1247
+// and 97 (profiles/mask_elems_isa.txt).
+__device__ __forceinline__ unsigned pack16(const uint4 v) {
+    const unsigned wv[4] = {v.x, v.y, v.z, v.w};
+    unsigned bits = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bits |= ((nz_byte_flags(wv[j]) * 0x01020408u) >> 24 & 0xfu) << (4 * j);
+    return bits;
+}
 
 // One lane packs 16 consecutive destination pixels; lane pairs are OR-combined into one 32-bit word.
-template <typename T>
+template <int KIND>
 __global__ __launch_bounds__(256) void mask_pack_kernel(const PackArgs a) {
+    using T = typename mask_elem<KIND>::type;
     __shared__ int red[4];
     const int n = blockIdx.y;
     const long long run = (long long)blockIdx.x * 256 + threadIdx.x;  // 16-pixel run index inside this mask
@@ -45,24 +56,11 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const PackArgs a) {
     if (p0 < a.HW) {
         if (a.identity && p0 + 16 <= a.HW && (a.hw_src * (long long)sizeof(T)) % 16 == 0 &&
             (reinterpret_cast<uintptr_t>(a.src) & 15) == 0) {
-            if constexpr (sizeof(T) == 1) {
-                const uint4 v = *reinterpret_cast<const uint4*>(src + p0);
-                const unsigned wv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    // word-parallel "byte != 0" -> one bit per byte: high bit of each non-zero byte, moved to bit 0 of its
-                    // byte, then the four byte flags are gathered into a nibble by one multiply (no carries reach bits 24-27)
-                    const unsigned w = wv[j];
-                    const unsigned nz = ((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u) >> 7;
-                    bits |= ((nz * 0x01020408u) >> 24 & 0xfu) << (4 * j);
-                }
+            if constexpr (KIND == MASK_U8) {
+                bits |= pack16(*reinterpret_cast<const uint4*>(src + p0));
             } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float4 v = *reinterpret_cast<const float4*>(src + p0 + 4 * j);
-                    bits |= (v.x != 0.f ? 1u : 0u) << (4 * j) | (v.y != 0.f ? 1u : 0u) << (4 * j + 1) |
-                            (v.z != 0.f ? 1u : 0u) << (4 * j + 2) | (v.w != 0.f ? 1u : 0u) << (4 * j + 3);
-                }
+                for (int j = 0; j < 4; ++j) bits |= vec_bits<KIND>(reinterpret_cast<const float4*>(src + p0)[j]) << (4 * j);
             }
         } else {
             int y = (int)(p0 / a.W);
@@ -75,7 +73,7 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const PackArgs a) {
                     sy = a.h == a.H ? y : min((int)floorf((float)y * a.sy), a.h - 1);
                     sx = a.w == a.W ? x : min((int)floorf((float)x * a.sx), a.w - 1);
                 }
-                bits |= (is_set(src[(long long)sy * a.w + sx]) ? 1u : 0u) << i;
+                bits |= (mask_is_set<KIND>(src[(long long)sy * a.w + sx]) ? 1u : 0u) << i;
                 if (++x == a.W) { x = 0; ++y; }
             }
         }
@@ -106,9 +104,9 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const PackArgs a) {
 //      as the gather from HBM), the column rule and the bit select run in registers.
 // Needs W % 32 == 0 and a horizontal scale of at most 3 (a word's 32 pixels then span < 128 source pixels).
 constexpr int RS_RPB = 8, RS_MAXW = 4096, RS_WORDS = RS_MAXW / 32 + 4;
-__device__ __forceinline__ unsigned pack16(const uint4 v);
-template <typename T>
+template <int KIND>
 __global__ __launch_bounds__(256) void mask_pack_resample_kernel(const PackArgs a) {
+    using T = typename mask_elem<KIND>::type;
     __shared__ unsigned sbits[RS_RPB][RS_WORDS];
     __shared__ int red[4];
     const int n = blockIdx.y;
@@ -135,22 +133,19 @@ __global__ __launch_bounds__(256) void mask_pack_resample_kernel(const PackArgs 
             const int sy = a.h == a.H ? y : min((int)floorf((float)y * a.sy), a.h - 1);  // ATen nearest, fp32 product
             const T* p = src + (long long)sy * a.w + jw * 32;
             if (vec) {
-                if constexpr (sizeof(T) == 1) {
+                if constexpr (KIND == MASK_U8) {
                     const uint4 lo = reinterpret_cast<const uint4*>(p)[0], hi = reinterpret_cast<const uint4*>(p)[1];
                     word[q] = pack16(lo) | (pack16(hi) << 16);
                 } else {
                     unsigned wv = 0;
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const float4 v = reinterpret_cast<const float4*>(p)[k];
-                        wv |= ((v.x != 0.f ? 1u : 0u) | (v.y != 0.f ? 2u : 0u) | (v.z != 0.f ? 4u : 0u) | (v.w != 0.f ? 8u : 0u)) << (4 * k);
-                    }
+                    for (int k = 0; k < 8; ++k) wv |= vec_bits<KIND>(reinterpret_cast<const float4*>(p)[k]) << (4 * k);
                     word[q] = wv;
                 }
             } else {
                 unsigned wv = 0;
                 const int lim = min(32, a.w - jw * 32);
-                for (int k = 0; k < lim; ++k) wv |= (is_set(p[k]) ? 1u : 0u) << k;
+                for (int k = 0; k < lim; ++k) wv |= (mask_is_set<KIND>(p[k]) ? 1u : 0u) << k;
                 word[q] = wv;
             }
         }
@@ -199,18 +194,6 @@ __global__ __launch_bounds__(256) void mask_pack_resample_kernel(const PackArgs 
 // Streaming fast path for the common case (uint8 masks already at the comparison resolution, 32-byte aligned rows of
 // H*W % 32 == 0 pixels): a lane packs one whole 32-bit word from 32 bytes, four words per lane with all eight 16-byte
 // loads in flight before the first use, one area atomic per 32 KiB of mask.
-__device__ __forceinline__ unsigned pack16(const uint4 v) {
-    const unsigned wv[4] = {v.x, v.y, v.z, v.w};
-    unsigned bits = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const unsigned w = wv[j];
-        const unsigned nz = ((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u) >> 7;
-        bits |= ((nz * 0x01020408u) >> 24 & 0xfu) << (4 * j);
-    }
-    return bits;
-}
-
 __global__ __launch_bounds__(256) void mask_pack_u8_stream_kernel(const PackArgs a) {
     __shared__ int red[4];
     constexpr int IT = 4;
@@ -609,14 +592,14 @@ int launch_mask_pack(const void* masks, int elem_type, int n, int h, int w, int 
     SolaProfScope prof(SOLA_PROF_IOU_PACK, s, 0, src_bytes + (double)n * a.words * 4);
     if (elem_type == 0 && a.identity && a.HW % 32 == 0 && (reinterpret_cast<uintptr_t>(masks) & 15) == 0)
         hipLaunchKernelGGL(mask_pack_u8_stream_kernel, dim3((unsigned)((a.words + 1023) / 1024), n), dim3(256), 0, s, a);
-    else if (!a.identity && resample_lds_ok(masks, elem_type, h, w, W) && elem_type == 0)
-        hipLaunchKernelGGL(mask_pack_resample_kernel<uint8_t>, dim3(resample_blocks(H, n), n), dim3(256), 0, s, a);
-    else if (!a.identity && resample_lds_ok(masks, elem_type, h, w, W) && elem_type == 1)
-        hipLaunchKernelGGL(mask_pack_resample_kernel<float>, dim3(resample_blocks(H, n), n), dim3(256), 0, s, a);
-    else if (elem_type == 0)
-        hipLaunchKernelGGL(mask_pack_kernel<uint8_t>, dim3(blocks, n), dim3(256), 0, s, a);
+    else if (!a.identity && resample_lds_ok(masks, elem_type, h, w, W))
+        with_mask_kind<MASK_F32>(elem_type, [&](auto kind) {
+            hipLaunchKernelGGL(mask_pack_resample_kernel<decltype(kind)::value>, dim3(resample_blocks(H, n), n), dim3(256), 0, s, a);
+        });
     else
-        hipLaunchKernelGGL(mask_pack_kernel<float>, dim3(blocks, n), dim3(256), 0, s, a);
+        with_mask_kind<MASK_F32>(elem_type, [&](auto kind) {
+            hipLaunchKernelGGL(mask_pack_kernel<decltype(kind)::value>, dim3(blocks, n), dim3(256), 0, s, a);
+        });
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
 }

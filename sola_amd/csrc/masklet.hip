@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "mask_elems.h"
 
 namespace {
 
@@ -40,13 +41,12 @@ __device__ __forceinline__ void source_index(float scale, int dst, int in, int o
     l1 = fminf(fmaxf(__fsub_rn(s, (float)i0), 0.f), 1.f);
 }
 
-// MODE 0: uint8, non-zero -> 1.0;  1: float32 value as is;  2: float32 tracker logits, (v > 0) -> 1.0
-// (generate_tokens_grid.py:215-222 `(out_mask_logits > 0.0).float()` folded into the read).
-template <typename T, int MODE>
-__device__ __forceinline__ float mask_value(T v) {
-    if constexpr (MODE == 0) return v ? 1.f : 0.f;
-    else if constexpr (MODE == 1) return v;
-    else return v > 0.f ? 1.f : 0.f;
+// The value a tap contributes: kinds 0 and 2 (generate_tokens_grid.py:215-222 `(out_mask_logits > 0.0).float()` folded
+// into the read) are binarised by the predicate; a plain float32 image (kind 1) is resampled as it is.
+template <int KIND>
+__device__ __forceinline__ float mask_value(typename mask_elem<KIND>::type v) {
+    if constexpr (KIND == MASK_F32) return v;
+    else return mask_is_set<KIND>(v) ? 1.f : 0.f;
 }
 
 // A block packs `rows_per_block` destination rows of one mask.  The per-column source index and weight are the same
@@ -58,10 +58,11 @@ __device__ __forceinline__ float mask_value(T v) {
 // STAGED (w % 4 == 0): the source rows the block's destination rows touch are first streamed into LDS with 16-byte
 // (4-byte for u8) loads, binarised to one byte per pixel on the way, and the four taps come from LDS - the scattered
 // per-pixel dword loads of the direct version were bound by the L1/TA rate (~12 cycles per wave-load), not by HBM.
-// Plain float32 masks (MODE 1) are staged too: a block that meets a value other than 0 or 1 while staging falls back
+// Plain float32 masks (kind 1) are staged too: a block that meets a value other than 0 or 1 while staging falls back
 // to the direct float taps for its rows, so arbitrary float images keep ATen's arithmetic.
-template <typename T, int MODE, bool ALIGNED, bool STAGED>
+template <int KIND, bool ALIGNED, bool STAGED>
 __global__ __launch_bounds__(256) void mask_bilinear_pack_kernel(const BilinearArgs a) {
+    using T = typename mask_elem<KIND>::type;
     extern __shared__ int2 xtab[];  // [W] (i0, bits of l1), then the staged rows
     __shared__ int red[4];
     const int n = blockIdx.y;
@@ -93,13 +94,13 @@ __global__ __launch_bounds__(256) void mask_bilinear_pack_kernel(const BilinearA
             uint32_t packed;
             if constexpr (sizeof(T) == 4) {
                 const float4 v = reinterpret_cast<const float4*>(src + (long long)(ys0 + r) * a.w)[c];
-                if (MODE == 1)
+                if (KIND == MASK_F32)
                     not_binary |= (v.x != 0.f && v.x != 1.f) | (v.y != 0.f && v.y != 1.f) | (v.z != 0.f && v.z != 1.f) | (v.w != 0.f && v.w != 1.f);
-                packed = (uint32_t)(mask_value<float, MODE>(v.x) != 0.f) | (uint32_t)(mask_value<float, MODE>(v.y) != 0.f) << 8 |
-                         (uint32_t)(mask_value<float, MODE>(v.z) != 0.f) << 16 | (uint32_t)(mask_value<float, MODE>(v.w) != 0.f) << 24;
+                packed = (uint32_t)mask_is_set<KIND>(v.x) | (uint32_t)mask_is_set<KIND>(v.y) << 8 | (uint32_t)mask_is_set<KIND>(v.z) << 16 |
+                         (uint32_t)mask_is_set<KIND>(v.w) << 24;
             } else {
                 const uint32_t wv = reinterpret_cast<const uint32_t*>(src + (long long)(ys0 + r) * a.w)[c];
-                packed = ((((wv & 0x7f7f7f7fu) + 0x7f7f7f7fu) | wv) & 0x80808080u) >> 7;  // byte != 0 -> 1
+                packed = nz_byte_flags(wv);
             }
             rows32[idx] = packed;
         }
@@ -126,8 +127,8 @@ __global__ __launch_bounds__(256) void mask_bilinear_pack_kernel(const BilinearA
             if (from_lds) {
                 v00 = (float)s0[i0]; v01 = (float)s0[i1]; v10 = (float)s1[i0]; v11 = (float)s1[i1];
             } else {
-                v00 = mask_value<T, MODE>(r0[i0]); v01 = mask_value<T, MODE>(r0[i1]);
-                v10 = mask_value<T, MODE>(r1[i0]); v11 = mask_value<T, MODE>(r1[i1]);
+                v00 = mask_value<KIND>(r0[i0]); v01 = mask_value<KIND>(r0[i1]);
+                v10 = mask_value<KIND>(r1[i0]); v11 = mask_value<KIND>(r1[i1]);
             }
             const float t = __fmaf_rn(lx0, v00, __fmul_rn(lx1, v01));
             const float u = __fmaf_rn(lx0, v10, __fmul_rn(lx1, v11));
@@ -240,16 +241,16 @@ __global__ __launch_bounds__(256) void rle_fill_or_kernel(const RleArgs a) {
 
 }  // namespace
 
-template <typename T, int MODE>
+template <int KIND>
 static void launch_bilinear(const BilinearArgs& a, int n, bool aligned, size_t staged_bytes, hipStream_t s) {
     const dim3 grid((a.H + a.rows_per_block - 1) / a.rows_per_block, n), block(256);
     const size_t lds = (size_t)a.W * sizeof(int2) + staged_bytes;
     if (staged_bytes) {
-        if (aligned) hipLaunchKernelGGL((mask_bilinear_pack_kernel<T, MODE, true, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((mask_bilinear_pack_kernel<T, MODE, false, true>), grid, block, lds, s, a);
+        if (aligned) hipLaunchKernelGGL((mask_bilinear_pack_kernel<KIND, true, true>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((mask_bilinear_pack_kernel<KIND, false, true>), grid, block, lds, s, a);
     } else {
-        if (aligned) hipLaunchKernelGGL((mask_bilinear_pack_kernel<T, MODE, true, false>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((mask_bilinear_pack_kernel<T, MODE, false, false>), grid, block, lds, s, a);
+        if (aligned) hipLaunchKernelGGL((mask_bilinear_pack_kernel<KIND, true, false>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((mask_bilinear_pack_kernel<KIND, false, false>), grid, block, lds, s, a);
     }
 }
 
@@ -288,9 +289,7 @@ int launch_mask_bilinear_pack(const void* masks, int elem_type, int n, int h, in
     const bool aligned = W % 32 == 0;
     if (!aligned) SOLA_HIP(hipMemsetAsync(bits, 0, sizeof(uint32_t) * (size_t)n * a.words, s));
     SolaProfScope prof(SOLA_PROF_IOU_PACK, s, 0, (double)n * h * w * esz + (double)n * a.words * 4);
-    if (elem_type == 0) launch_bilinear<uint8_t, 0>(a, n, aligned, staged_bytes, s);
-    else if (elem_type == 1) launch_bilinear<float, 1>(a, n, aligned, staged_bytes, s);
-    else launch_bilinear<float, 2>(a, n, aligned, staged_bytes, s);
+    with_mask_kind<MASK_LOGIT>(elem_type, [&](auto kind) { launch_bilinear<decltype(kind)::value>(a, n, aligned, staged_bytes, s); });
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
 }

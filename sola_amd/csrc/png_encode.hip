@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "mask_elems.h"
 
 namespace {
 
@@ -56,48 +57,28 @@ struct PngArgs {
     uint8_t* out;
 };
 
-template <typename T, int MODE>
-__device__ __forceinline__ uint32_t pix_set(T v) {  // MODE 0: uint8 != 0; 1: float32 != 0; 2: float32 > 0
-    if constexpr (MODE == 0) return v != 0;
-    else if constexpr (MODE == 1) return v != 0.f;
-    else return v > 0.f;
-}
-
-__device__ __forceinline__ uint32_t nz_bytes(uint32_t d) {  // bytes != 0 of one dword -> 4 bits
-    const uint32_t nz = ((((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d) & 0x80808080u);
-    return ((nz >> 7) & 1u) | ((nz >> 14) & 2u) | ((nz >> 21) & 4u) | ((nz >> 28) & 8u);
-}
-
 // Pixels [c*CP, c*CP + CP) of the whole tensor -> CP bits; CP = pixels per 16 bytes.  The vector load is taken when the
 // chunk lies inside the tensor and the tensor is 16-byte aligned, else guarded scalar loads.
-template <typename T, int MODE>
-__device__ __forceinline__ uint32_t chunk_bits(const T* base, long long c, long long npix, bool vec) {
-    constexpr int CP = 16 / (int)sizeof(T);
-    if (vec && (c + 1) * CP <= npix) {
-        if constexpr (sizeof(T) == 1) {
-            const uint4 v = *reinterpret_cast<const uint4*>(base + c * CP);
-            return nz_bytes(v.x) | nz_bytes(v.y) << 4 | nz_bytes(v.z) << 8 | nz_bytes(v.w) << 12;
-        } else {
-            const float4 v = *reinterpret_cast<const float4*>(base + c * CP);
-            return pix_set<float, MODE>(v.x) | pix_set<float, MODE>(v.y) << 1 | pix_set<float, MODE>(v.z) << 2 | pix_set<float, MODE>(v.w) << 3;
-        }
-    }
+template <int KIND>
+__device__ __forceinline__ uint32_t chunk_bits(const typename mask_elem<KIND>::type* base, long long c, long long npix, bool vec) {
+    constexpr int CP = 16 / mask_elem<KIND>::size;
+    if (vec && (c + 1) * CP <= npix) return vec_bits<KIND>(*reinterpret_cast<const typename mask_elem<KIND>::vec*>(base + c * CP));
     uint32_t b = 0;
 #pragma unroll
     for (int i = 0; i < CP; ++i)
-        if (c * CP + i < npix) b |= pix_set<T, MODE>(base[c * CP + i]) << i;
+        if (c * CP + i < npix) b |= (uint32_t)mask_is_set<KIND>(base[c * CP + i]) << i;
     return b;
 }
 
 // `len` (1..64) consecutive pixels from `start` -> bits
-template <typename T, int MODE>
-__device__ __forceinline__ u64 fetch_bits(const T* base, long long start, int len, long long npix, bool vec) {
-    constexpr int CP = 16 / (int)sizeof(T);
+template <int KIND>
+__device__ __forceinline__ u64 fetch_bits(const typename mask_elem<KIND>::type* base, long long start, int len, long long npix, bool vec) {
+    constexpr int CP = 16 / mask_elem<KIND>::size;
     long long c = start / CP;
     const int o = (int)(start - c * CP);
     u64 acc = 0;
     for (int got = -o; got < len; got += CP, ++c) {
-        const u64 b = chunk_bits<T, MODE>(base, c, npix, vec);
+        const u64 b = chunk_bits<KIND>(base, c, npix, vec);
         acc |= got < 0 ? b >> o : b << got;
     }
     return len < 64 ? acc & ((1ull << len) - 1ull) : acc;
@@ -150,8 +131,9 @@ __device__ __forceinline__ uint32_t last_start(u64 B, uint32_t prevbit, uint32_t
 }
 
 // ---- phase 1 ------------------------------------------------------------------------------------------------------------
-template <typename T, int MODE>
+template <int KIND>
 __global__ __launch_bounds__(256) void png_bitmap_kernel(const PngArgs a) {
+    using T = typename mask_elem<KIND>::type;
     __shared__ uint32_t top[256];
     __shared__ uint32_t r32[4];
     __shared__ u64 r64[4];
@@ -172,7 +154,7 @@ __global__ __launch_bounds__(256) void png_bitmap_kernel(const PngArgs a) {
                 continue;
             }
             const uint32_t len = min(nv - filled, row - c);
-            B |= fetch_bits<T, MODE>(base, fpix + (long long)y * a.w + (c - 1), (int)len, a.npix, a.vec != 0) << filled;
+            B |= fetch_bits<KIND>(base, fpix + (long long)y * a.w + (c - 1), (int)len, a.npix, a.vec != 0) << filled;
             filled += len;
             c += len;
             if (c == row) {
@@ -188,7 +170,7 @@ __global__ __launch_bounds__(256) void png_bitmap_kernel(const PngArgs a) {
     if (threadIdx.x) prevbit = top[threadIdx.x - 1];
     else if (k > 0 && k < a.W) {  // the raw byte before this workgroup's first
         const uint32_t p = p0 - 1u, y = p / row, c = p - y * row;
-        if (c) prevbit = pix_set<T, MODE>(base[fpix + (long long)y * a.w + (c - 1)]);
+        if (c) prevbit = mask_is_set<KIND>(base[fpix + (long long)y * a.w + (c - 1)]);
     }
     u64 tr;
     const uint32_t lt = last_start(B, prevbit, k, p0, nv, tr);
@@ -499,8 +481,7 @@ Layout layout(int n, int h, int w) {
 }
 
 int check_sizes(const char* what, int elem_type, int n, int h, int w, size_t scratch_bytes) {
-    SOLA_ARG(n > 0 && h > 0 && w > 0, "%s: bad sizes n=%d h=%d w=%d", what, n, h, w);
-    SOLA_ARG(elem_type >= 0 && elem_type <= 2, "%s: elem_type %d (0=u8, 1=f32, 2=f32 logits)", what, elem_type);
+    SOLA_TRY(check_mask_sizes(what, elem_type, n, h, w));
     SOLA_ARG((long long)h * ((long long)w + 1) < (1ll << 31), "%s: image too large (h*(w+1) must be < 2^31)", what);
     const size_t need = png_deflate_scratch_bytes(n, h, w);
     SOLA_ARG(need > 0, "%s: sizes overflow n=%d h=%d w=%d", what, n, h, w);
@@ -545,9 +526,9 @@ int launch_png_deflate_sizes(const void* masks, int elem_type, int n, int h, int
         a.frame0 = f0;
         const unsigned nf = (unsigned)std::min(PNG_FRAMES, n - f0);
         const dim3 grid(a.NB, nf), block(256);
-        if (elem_type == 0) hipLaunchKernelGGL((png_bitmap_kernel<uint8_t, 0>), grid, block, 0, s, a);
-        else if (elem_type == 1) hipLaunchKernelGGL((png_bitmap_kernel<float, 1>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((png_bitmap_kernel<float, 2>), grid, block, 0, s, a);
+        with_mask_kind<MASK_LOGIT>(elem_type, [&](auto kind) {
+            hipLaunchKernelGGL(png_bitmap_kernel<decltype(kind)::value>, grid, block, 0, s, a);
+        });
         SOLA_LAUNCH_CHECK();
         hipLaunchKernelGGL(png_count_kernel, grid, block, 0, s, a);
         SOLA_LAUNCH_CHECK();

@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "mask_elems.h"
 
 namespace {
 
@@ -39,39 +40,24 @@ struct RowsArgs {
     int frame0;
 };
 
-// VEC consecutive pixels of one row -> bit c = pixel c is set.  MODE 0: uint8 != 0; 1: float32 != 0; 2: float32 > 0.
-template <typename T, int MODE>
-__device__ __forceinline__ uint32_t fg(T v) {
-    if constexpr (MODE == 0) return v != 0;
-    else if constexpr (MODE == 1) return v != 0.f;
-    else return v > 0.f;
-}
-
-__device__ __forceinline__ uint32_t byte_bits(uint32_t d) {  // bytes != 0 of one dword -> 4 bits
-    const uint32_t nz = ((((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d) & 0x80808080u);
-    return ((nz >> 7) & 1u) | ((nz >> 14) & 2u) | ((nz >> 21) & 4u) | ((nz >> 28) & 8u);
-}
-
-template <typename T, int MODE, int VEC>
-__device__ __forceinline__ uint32_t load_bits(const T* p) {
-    if constexpr (sizeof(T) == 1 && VEC == 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        return byte_bits(v.x) | byte_bits(v.y) << 4 | byte_bits(v.z) << 8 | byte_bits(v.w) << 12;
-    } else if constexpr (sizeof(T) == 1 && VEC == 4) {
-        return byte_bits(*reinterpret_cast<const uint32_t*>(p));
-    } else if constexpr (sizeof(T) == 4 && VEC == 4) {
-        const float4 v = *reinterpret_cast<const float4*>(p);
-        return fg<float, MODE>(v.x) | fg<float, MODE>(v.y) << 1 | fg<float, MODE>(v.z) << 2 | fg<float, MODE>(v.w) << 3;
+// VEC consecutive pixels of one row -> bit c = pixel c is set
+template <int KIND, int VEC>
+__device__ __forceinline__ uint32_t load_bits(const typename mask_elem<KIND>::type* p) {
+    if constexpr (VEC * mask_elem<KIND>::size == 16) {
+        return vec_bits<KIND>(*reinterpret_cast<const typename mask_elem<KIND>::vec*>(p));
+    } else if constexpr (KIND == MASK_U8 && VEC == 4) {
+        return nz_byte_bits(*reinterpret_cast<const uint32_t*>(p));
     } else {
         static_assert(VEC == 1, "unsupported vector width");
-        return fg<T, MODE>(*p);
+        return mask_is_set<KIND>(*p);
     }
 }
 
 // One lane = VEC columns x0.. of one band of one frame.  EMIT=false: write the band's transition count of each column to
 // seg; EMIT=true: write the transitions' positions into cum at the offsets seg now holds.
-template <typename T, int MODE, int VEC, bool EMIT>
+template <int KIND, int VEC, bool EMIT>
 __global__ __launch_bounds__(256) void rle_rows_kernel(const RowsArgs a) {
+    using T = typename mask_elem<KIND>::type;
     const int f = a.frame0 + blockIdx.y;
     const long long S = (long long)a.w * a.B;
     if (EMIT && blockIdx.x == 0 && threadIdx.x == 0) a.cum[a.run_off[f + 1] - 1] = (uint32_t)a.h * (uint32_t)a.w;
@@ -82,11 +68,11 @@ __global__ __launch_bounds__(256) void rle_rows_kernel(const RowsArgs a) {
     const T* img = reinterpret_cast<const T*>(a.masks) + (long long)f * a.h * a.w + x0;
     uint32_t prev;
     if (y0 > 0) {
-        prev = load_bits<T, MODE, VEC>(img + (long long)(y0 - 1) * a.w);
+        prev = load_bits<KIND, VEC>(img + (long long)(y0 - 1) * a.w);
     } else {  // column x0+c follows (h-1, x0+c-1); column 0 follows the implicit 0
         const T* last = img + (long long)(a.h - 1) * a.w;
-        prev = (load_bits<T, MODE, VEC>(last) << 1) & ((1u << VEC) - 1u);
-        if (x0 > 0) prev |= fg<T, MODE>(last[-1]);
+        prev = (load_bits<KIND, VEC>(last) << 1) & ((1u << VEC) - 1u);
+        if (x0 > 0) prev |= mask_is_set<KIND>(last[-1]);
     }
     uint32_t* seg = a.seg + (long long)f * S + (long long)x0 * a.B + b;  // column x0+c: seg[c * B]
     uint32_t cnt[VEC];
@@ -106,7 +92,7 @@ __global__ __launch_bounds__(256) void rle_rows_kernel(const RowsArgs a) {
     for (; y + 4 <= y1; y += 4, row += 4 * (long long)a.w) {  // four rows' loads in flight per lane
         uint32_t m[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) m[r] = load_bits<T, MODE, VEC>(row + (long long)r * a.w);
+        for (int r = 0; r < 4; ++r) m[r] = load_bits<KIND, VEC>(row + (long long)r * a.w);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const uint32_t tr = m[r] ^ prev;
@@ -124,7 +110,7 @@ __global__ __launch_bounds__(256) void rle_rows_kernel(const RowsArgs a) {
         }
     }
     for (; y < y1; ++y, row += a.w) {
-        const uint32_t m = load_bits<T, MODE, VEC>(row);
+        const uint32_t m = load_bits<KIND, VEC>(row);
         const uint32_t tr = m ^ prev;
         prev = m;
         if constexpr (EMIT) {
@@ -305,25 +291,20 @@ int launch_rows(const RowsArgs& base, int elem_type, int n, hipStream_t s) {
     for (int f0 = 0; f0 < n; f0 += RLE_FRAMES) {
         a.frame0 = f0;
         const dim3 grid(gx, (unsigned)std::min(RLE_FRAMES, n - f0)), block(256);
-        if (elem_type == 0) {
-            if (vec == 16) hipLaunchKernelGGL((rle_rows_kernel<uint8_t, 0, 16, EMIT>), grid, block, 0, s, a);
-            else if (vec == 4) hipLaunchKernelGGL((rle_rows_kernel<uint8_t, 0, 4, EMIT>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((rle_rows_kernel<uint8_t, 0, 1, EMIT>), grid, block, 0, s, a);
-        } else if (elem_type == 1) {
-            if (vec == 4) hipLaunchKernelGGL((rle_rows_kernel<float, 1, 4, EMIT>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((rle_rows_kernel<float, 1, 1, EMIT>), grid, block, 0, s, a);
-        } else {
-            if (vec == 4) hipLaunchKernelGGL((rle_rows_kernel<float, 2, 4, EMIT>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((rle_rows_kernel<float, 2, 1, EMIT>), grid, block, 0, s, a);
-        }
+        with_mask_kind<MASK_LOGIT>(elem_type, [&](auto kind) {
+            constexpr int KIND = decltype(kind)::value;
+            constexpr int WIDE = 16 / mask_elem<KIND>::size;  // rows_vec gives 16 for uint8 alone
+            if (vec == WIDE) hipLaunchKernelGGL((rle_rows_kernel<KIND, WIDE, EMIT>), grid, block, 0, s, a);
+            else if (KIND == MASK_U8 && vec == 4) hipLaunchKernelGGL((rle_rows_kernel<MASK_U8, 4, EMIT>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((rle_rows_kernel<KIND, 1, EMIT>), grid, block, 0, s, a);
+        });
         SOLA_LAUNCH_CHECK();
     }
     return SOLA_OK;
 }
 
 int check_sizes(const char* what, int elem_type, int n, int h, int w, size_t scratch_bytes) {
-    SOLA_ARG(n > 0 && h > 0 && w > 0, "%s: bad sizes n=%d h=%d w=%d", what, n, h, w);
-    SOLA_ARG(elem_type >= 0 && elem_type <= 2, "%s: elem_type %d (0=u8, 1=f32, 2=f32 logits)", what, elem_type);
+    SOLA_TRY(check_mask_sizes(what, elem_type, n, h, w));
     SOLA_ARG((long long)h * w < (1ll << 31), "%s: image too large (h*w must be < 2^31)", what);
     const size_t need = rle_encode_scratch_bytes(n, h, w);
     SOLA_ARG(scratch_bytes >= need, "%s: scratch %zu bytes < required %zu", what, scratch_bytes, need);
