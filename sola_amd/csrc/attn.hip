@@ -20,7 +20,7 @@
 //   packed : sequences of <= 16 steps (motion attention over T').  16 / pow2(T') independent (group, head) units share
 //            ONE 16x16 MFMA tile as a block-diagonal problem (cross-unit scores masked to -inf), so a T'=4 launch
 //            issues a quarter of the waves and MFMAs and each wave moves 4x the bytes per tile.
-#include "kernels.h"
+#include "attn_common.h"
 
 namespace {
 
@@ -49,59 +49,10 @@ struct AttnArgs {
     int tile_rows;    // shared, restaged (multi-tile) path: keys per K/V tile, 64 or 32
 };
 
-// Geometry of one group: first rows, row strides and lengths of its query and key sequences.  With unit tables the values
-// are loaded per group (and made wave-uniform by hand: the compiler cannot know a table entry is the same for all lanes).
-struct AttnGeo { long long q0, k0, q_rs, k_rs; int Sq, Sk; };
-__device__ __forceinline__ AttnGeo attn_geo(const AttnArgs& a, int grp) {
-    AttnGeo g;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        g.q0 = qu.x; g.q_rs = qu.y; g.Sq = qu.z;
-        g.k0 = ku.x; g.k_rs = ku.y; g.Sk = ku.z;
-    } else {
-        g.q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        g.k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        g.q_rs = a.q_rs; g.k_rs = a.k_rs; g.Sq = a.Sq; g.Sk = a.Sk;
-    }
-    return g;
-}
-__device__ __forceinline__ AttnGeo attn_geo_uniform(const AttnArgs& a, int grp) {  // grp is wave-uniform
-    AttnGeo g = attn_geo(a, grp);
-    if (a.q_units) {
-        g.q0 = __builtin_amdgcn_readfirstlane((int)g.q0); g.k0 = __builtin_amdgcn_readfirstlane((int)g.k0);
-        g.q_rs = __builtin_amdgcn_readfirstlane((int)g.q_rs); g.k_rs = __builtin_amdgcn_readfirstlane((int)g.k_rs);
-        g.Sq = __builtin_amdgcn_readfirstlane(g.Sq); g.Sk = __builtin_amdgcn_readfirstlane(g.Sk);
-    }
-    return g;
-}
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-
-// SPLIT shape of the shared mode (inference fast path): q, k, v arrive as split-f16 rows straight from the projection
-// GEMM's epilogue (every 8 values = 32 bytes [hi8 | lo8], cast.hip), so nothing is converted here; every product runs as
-// lo*hi + hi*lo + hi*hi on v_mfma_f32_16x16x16_f16 with f32 accumulation (~22-bit products, as in gemm_glds.hip).  The
-// exact-f32 v_mfma_f32_16x16x4_f32 has 1/16 of that rate and made the kernel co-bound by the matrix pipe (218 us of MFMA
-// against 215 us of HBM at N = 128).  A lane's 4 consecutive head dims are (hi4, lo4) = two 8-byte pieces of one block.
-struct HL4 { half4v hi, lo; };
-__device__ __forceinline__ HL4 split4(float x, float y, float z, float w) {
-    HL4 r;
-    const float in[4] = {x, y, z, w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        _Float16 h1, l1;
-        split_f16(in[j], h1, l1);
-        r.hi[j] = h1; r.lo[j] = l1;
-    }
-    return r;
-}
-__device__ __forceinline__ f32x4 mfma3(const HL4& a, const HL4& b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x16f16(a.lo, b.hi, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x16f16(a.hi, b.lo, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a.hi, b.hi, c, 0, 0, 0);
-}
-
-// Store one query row's output tile.  op points at o[row][h*DH]; this lane holds d = 16c + 4*g4 + {0..3} of every chunk c.
+// attn_store_tile (attn_common.h), but with all four products of a chunk in front of its first split_f16, whose register pin orders
+// what surrounds it.  A kept copy for this file's kernels: with the shared form the shared mode at head_dim 128 (256 VGPRs, spilling)
+// comes out as a different kernel (vgpr 256 -> 242, scratch 24 -> 0, sgpr spills 132 -> 98, 105 instructions fewer) and every other
+// instantiation moves a few instructions; with this one all twenty are what they were before attn_common.h, line for line (profiles/attn_common_isa.txt).
 template <int NC>
 __device__ __forceinline__ void store_o(float* op, int g4, const f32x4 (&oacc)[NC], float inv, int sp16, int* guard) {
     if (!sp16) {
@@ -111,9 +62,6 @@ __device__ __forceinline__ void store_o(float* op, int g4, const f32x4 (&oacc)[N
                 make_float4(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv);
         return;
     }
-    // split-f16: an 8-wide block [hi8 | lo8] is held by the lane pair (g4, g4 ^ 1); each lane writes the hi and the lo halves
-    // of its OWN four values as two 8-byte stores (block offset 8 * (g4 & 1), lo 16 bytes behind) - no cross-lane traffic
-    // (the lanes of a pair are 16 apart, a shuffle between them goes through the LDS crossbar)
     float m = 0.f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -130,9 +78,14 @@ __device__ __forceinline__ void store_o(float* op, int g4, const f32x4 (&oacc)[N
         *reinterpret_cast<half4v*>(dst) = hi;
         *reinterpret_cast<half4v*>(dst + 16) = lo;
     }
-    if (guard && !(m < 65000.f)) atomicOr(guard, 1);  // NaN fails the comparison too
+    attn_range_guard(guard, m);
 }
 
+// SPLIT shape of the shared mode (inference fast path): q, k, v arrive as split-f16 rows straight from the projection
+// GEMM's epilogue (every 8 values = 32 bytes [hi8 | lo8], cast.hip), so nothing is converted here; every product runs as
+// mfma3 (attn_common.h) with f32 accumulation.  The exact-f32 v_mfma_f32_16x16x4_f32 has 1/16 of that rate and made the
+// kernel co-bound by the matrix pipe (218 us of MFMA against 215 us of HBM at N = 128).  A lane's 4 consecutive head dims
+// are (hi4, lo4) = two 8-byte pieces of one block.
 // NW = waves per block of the shared mode (4: 64-query blocks, K/V tiles of up to 64 rows, two blocks per CU; 8: 128-query
 // blocks and a resident K/V tile of up to 128 rows for units of 65..128 keys, one block per CU).  The packed mode uses 4.
 template <int DH, bool PACKED, int NW, bool SPLIT, int MINB = 2>
@@ -165,7 +118,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
         };
         int grp, h, jq;
         const bool unit_ok = row_unit(c16, grp, h, jq);
-        const AttnGeo gq = attn_geo(a, grp);  // this lane's query row's unit
+        const AttnUnit gq = attn_unit<false>(a, grp);  // this lane's query row's unit (the rows of a tile belong to different units)
         const bool q_ok = unit_ok && jq < gq.Sq;
         const long long qrow = gq.q0 + (long long)jq * gq.q_rs;
         float4 qf[NC];
@@ -182,7 +135,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
             const int r = idx / F4, c4 = idx - r * F4;
             int kg, kh, kj;
             const bool uok = row_unit(r, kg, kh, kj);
-            const AttnGeo gk = attn_geo(a, kg);
+            const AttnUnit gk = attn_unit<false>(a, kg);
             const bool ok = uok && kj < gk.Sk;
             float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
             if (ok) {
@@ -223,8 +176,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
             sc[r] = vis ? (a0[r] + a1[r]) : -INFINITY;
             mx = fmaxf(mx, sc[r]);
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        mx = xor16_32_max(mx);
         if (mx == -INFINITY) mx = 0.f;  // rows of absent units: keep exp() finite, nothing is stored for them
         float rs = 0.f;
 #pragma unroll
@@ -232,8 +184,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
             sc[r] = __expf(sc[r] - mx);
             rs += sc[r];
         }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
+        rs = xor16_32_sum(rs);
         if (a.drop.enabled) {
             const unsigned long long rbase = ((unsigned long long)(grp * a.H + h) * gq.Sq + jq) * gq.Sk;
 #pragma unroll
@@ -268,7 +219,15 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
             u /= a.qsplit;
             c.h = (int)(u % a.H);
             c.grp = (int)(u / a.H);
-            const AttnGeo g = attn_geo_uniform(a, c.grp);
+            // A block serves one unit at a time, so attn_unit's rule asks for the scalarised form; this kernel keeps its earlier two
+            // steps (table values, then readfirstlane on the narrowed values under a second test): with attn_unit<true> all sixteen
+            // instantiations change their register rows (head_dim 64: vgpr 187 -> 171, sgpr spills 101 -> 136; profiles/attn_common_isa.txt)
+            AttnUnit g = attn_unit<false>(a, c.grp);
+            if (a.q_units) {
+                g.q0 = __builtin_amdgcn_readfirstlane((int)g.q0); g.k0 = __builtin_amdgcn_readfirstlane((int)g.k0);
+                g.q_rs = __builtin_amdgcn_readfirstlane((int)g.q_rs); g.k_rs = __builtin_amdgcn_readfirstlane((int)g.k_rs);
+                g.Sq = __builtin_amdgcn_readfirstlane(g.Sq); g.Sk = __builtin_amdgcn_readfirstlane(g.Sk);
+            }
             c.qrow0 = g.q0; c.krow0 = g.k0; c.q_rs = g.q_rs; c.k_rs = g.k_rs; c.Sq = g.Sq; c.Sk = g.Sk;
             c.nqb = a.q_units ? (g.Sq + NW * 16 - 1) / (NW * 16) : a.nqb;
             return c;
@@ -434,8 +393,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
                 for (int t = 0; t < 4; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[t][r]);
-                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                mx = xor16_32_max(mx);
                 const float m_new = fmaxf(m_run, mx);
                 const float alpha = __expf(m_run - m_new);  // exp(-inf) = 0 on the first tile
                 float rs = 0.f;
@@ -446,8 +404,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
                         sc[t][r] = __expf(sc[t][r] - m_new);
                         rs += sc[t][r];
                     }
-                rs += __shfl_xor(rs, 16, 64);
-                rs += __shfl_xor(rs, 32, 64);
+                rs = xor16_32_sum(rs);
                 l_run = l_run * alpha + rs;
                 m_run = m_new;
 #pragma unroll
@@ -573,7 +530,7 @@ int launch_dh(const AttnArgs& a0, hipStream_t s) {
         }
         a.qsplit = qsplit;
         long long blocks = gh * qsplit;  // units; the grid is capped at the resident block count, blocks walk the rest
-        SOLA_ARG(blocks < (1ll << 31), "attention: grid too large");
+        SOLA_TRY(attn_grid_ok(blocks, "attention"));
         const long long resident = wide ? g_attn_resident_blocks / 2 : g_attn_resident_blocks;
         if (g_attn_variant != 0 && blocks > resident) blocks = resident;
         a.tile_rows = 64;
@@ -594,28 +551,6 @@ int launch_dh(const AttnArgs& a0, hipStream_t s) {
 
 int g_attn_splitm = 0;  // sola_tune "attn_splitm": 1 = f16-MFMA triples on f32 inputs in the split precision mode (measured slower:
                         // 1.49 vs 1.39 ms of attention per 256-sample step - every wave re-converts the K/V fragments it reads)
-
-bool attention_simple_supported(const AttnDesc& d);
-int launch_attention_simple(const AttnDesc& d, hipStream_t s);
-bool attention_small_supported(const AttnDesc& d);
-int launch_attention_small(const AttnDesc& d, hipStream_t s);
-bool attention_splitm_supported(const AttnDesc& d);
-int launch_attention_splitm(const AttnDesc& d, hipStream_t s);
-bool attention_reg_supported(const AttnDesc& d);
-int launch_attention_reg(const AttnDesc& d, hipStream_t s);
-bool attention_res_supported(const AttnDesc& d);
-int launch_attention_res(const AttnDesc& d, hipStream_t s);
-extern int g_attn_splitm;
-
-bool attention_bf16_mfma_supported(const AttnDesc& d);
-int launch_attention_bf16_train(const AttnDesc& d, hipStream_t s);
-bool attention_spin_supported(const AttnDesc& d);
-int launch_attention_spin(const AttnDesc& d, hipStream_t s);
-#ifdef SOLA_EXPERIMENTS  // closed experiment (lab/attn_ring.hip): EXPERIMENTS=1 builds with sola_tune "attn_ring" only
-bool attention_ring_supported(const AttnDesc& d);
-int launch_attention_ring(const AttnDesc& d, hipStream_t s);
-extern int g_attn_ring;
-#endif
 
 int launch_attention(const AttnDesc& d, hipStream_t s) {
     SOLA_ARG(d.G > 0 && d.H > 0 && d.Sq > 0 && d.Sk > 0 && d.inner > 0, "attention: bad sizes");
@@ -657,25 +592,11 @@ int launch_attention(const AttnDesc& d, hipStream_t s) {
         return launch_attention_simple(d, s);
     AttnArgs a;
     a.q = d.q; a.k = d.k; a.v = d.v; a.o = d.o;
-    a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
-    a.G = d.G; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk; a.inner = d.inner; a.nqb = 1;
-    a.q_outer = d.q_outer; a.q_inner = d.q_inner; a.q_rs = d.q_rs;
-    a.k_outer = d.k_outer; a.k_inner = d.k_inner; a.k_rs = d.k_rs;
-    a.scale = d.scale;
+    attn_fill_common(a, d);
     a.lse = d.lse;
     a.drop = d.drop;
-    a.o_sp16 = d.o_sp16;
     a.in_sp16 = d.in_sp16;
-    a.guard = d.o_sp16 ? d.guard : nullptr;
-    a.q_units = d.q_units; a.k_units = d.q_units ? (d.k_units ? d.k_units : d.q_units) : nullptr;
-    a.kv_rows = 64; a.qsplit = 1; a.sp_log2 = 4; a.tile_rows = 64;
-    const double elems = (double)d.G * d.H * d.DH;
-    SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, 4.0 * elems * (2.0 * d.Sq + 2.0 * d.Sk));
-    switch (d.DH) {
-        case 128: return launch_dh<128>(a, s);
-        case 64: return launch_dh<64>(a, s);
-        case 32: return launch_dh<32>(a, s);
-        case 16: return launch_dh<16>(a, s);
-        default: sola_set_error("attention: head_dim %d unsupported (16/32/64/128)", d.DH); return SOLA_ERR_ARG;
-    }
+    a.nqb = 1; a.kv_rows = 64; a.qsplit = 1; a.sp_log2 = 4; a.tile_rows = 64;
+    const SolaProfScope prof = attn_prof_scope(d, s);
+    return attn_dispatch_dh(d.DH, "attention: head_dim %d unsupported (16/32/64/128)", [&](auto dh) { return launch_dh<decltype(dh)::value>(a, s); });
 }

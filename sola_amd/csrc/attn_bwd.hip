@@ -8,8 +8,8 @@
 // softmax statistics sits in the 16-lane column (pass 1) or is fetched per register slot (pass 2), so - as in the
 // forward kernel - probabilities never move across lanes.  Every wave stages the streamed side through its own LDS
 // slice (16 rows at a time); all waves of a launch run the same trip count, so block barriers are uniform.
-// Addressing is the forward kernel's (outer / inner / row strides), so no permuted copies exist in the backward either.
-#include "kernels.h"
+// Addressing is the forward kernels' (attn_unit, attn_common.h), so no permuted copies exist in the backward either.
+#include "attn_common.h"
 
 namespace {
 
@@ -48,32 +48,10 @@ struct AttnBwdArgs {
     int g16;
     int o16;  // ... and o too (pitch ldo in values): the forward kept only the bfloat16 rows the out-projection reads (with g16)
 };
-__device__ __forceinline__ float4 bf16x4_to_f32(uint2 w) {
-    return make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                       __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
-}
-__device__ __forceinline__ uint2 f32x4_to_bf16(float x, float y, float z, float w) {
-    typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-    bf4 b;
-    b[0] = (__bf16)x; b[1] = (__bf16)y; b[2] = (__bf16)z; b[3] = (__bf16)w;
-    return __builtin_bit_cast(uint2, b);
-}
 
-struct BwdGeo { long long q0, k0, q_rs, k_rs; int Sq, Sk; };
-__device__ __forceinline__ BwdGeo bwd_geo(const AttnBwdArgs& a, int grp) {
-    BwdGeo g;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        g.q0 = qu.x; g.q_rs = qu.y; g.Sq = qu.z;
-        g.k0 = ku.x; g.k_rs = ku.y; g.Sk = ku.z;
-    } else {
-        g.q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        g.k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        g.q_rs = a.q_rs; g.k_rs = a.k_rs; g.Sq = a.Sq; g.Sk = a.Sk;
-    }
-    return g;
-}
-
+// Every kernel here takes attn_unit<false>: the waves of the per-wave kernels serve different units and the one-pass kernels read the
+// table once per block, where the scalarised form bought nothing (attn_bwd_fused_kernel's four-wave bf16 shape has no scalar register
+// to spare: tests/test_host_cpu.py).
 // RAG (ragged batches): every wave stages its unit through its OWN LDS slice, so nothing is shared between the waves of a block:
 // the block barriers become wave barriers (a wave's LDS instructions execute in order), a wave whose query tile lies past its
 // unit's length leaves at once, and the key / query loops run to the unit's OWN length instead of the batch's largest.
@@ -102,7 +80,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnBwdArgs a) {
     const int qt = unit_ok ? (int)(unit % a.ntile) : 0;
     const long long gh = unit_ok ? unit / a.ntile : 0;
     const int h = (int)(gh % a.H), grp = (int)(gh / a.H);
-    const BwdGeo geo = bwd_geo(a, grp);
+    const AttnUnit geo = attn_unit<false>(a, grp);
     const long long qrow0 = geo.q0, krow0 = geo.k0;
     const int qi = qt * 16 + c16;
     const bool q_ok = unit_ok && qi < geo.Sq;
@@ -129,8 +107,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnBwdArgs a) {
             dsum += (ov.x * gv.x + ov.y * gv.y) + (ov.z * gv.z + ov.w * gv.w);
         }
     }
-    dsum += __shfl_xor(dsum, 16, 64);
-    dsum += __shfl_xor(dsum, 32, 64);  // D[q] for the lane's column
+    dsum += __shfl_xor(dsum, 16, 64);  // xor16_32_sum (attn_common.h) written out: through it the dQ kernels of head_dim 64 / 128
+    dsum += __shfl_xor(dsum, 32, 64);  // come out with other register names (profiles/attn_common_isa.txt).  D[q] for the lane's column
     const float lse_q = q_ok ? a.lse[qrow * a.H + h] : 0.f;
     if (q_ok && g4 == 0) a.dvec[qrow * a.H + h] = dsum;
 
@@ -225,7 +203,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdArgs a) 
     const int kt = unit_ok ? (int)(unit % a.ntile) : 0;
     const long long gh = unit_ok ? unit / a.ntile : 0;
     const int h = (int)(gh % a.H), grp = (int)(gh / a.H);
-    const BwdGeo geo = bwd_geo(a, grp);
+    const AttnUnit geo = attn_unit<false>(a, grp);
     const long long qrow0 = geo.q0, krow0 = geo.k0;
     const int kj = kt * 16 + c16;
     const bool k_ok = unit_ok && kj < geo.Sk;
@@ -357,7 +335,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_blk_kernel(const AttnBwdArgs 
     const long long gh = blockIdx.x / nqc;
     const int qc = (int)(blockIdx.x - gh * nqc);
     const int h = (int)(gh % a.H), grp = (int)(gh / a.H);
-    const BwdGeo geo = bwd_geo(a, grp);
+    const AttnUnit geo = attn_unit<false>(a, grp);
     if (qc * 64 >= geo.Sq) return;  // ragged: the grid follows the longest unit (the whole block leaves together)
     const long long qrow0 = geo.q0, krow0 = geo.k0;
     const int qi = qc * 64 + wave * 16 + c16;
@@ -381,8 +359,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_blk_kernel(const AttnBwdArgs 
             dsum += (ov.x * gv.x + ov.y * gv.y) + (ov.z * gv.z + ov.w * gv.w);
         }
     }
-    dsum += __shfl_xor(dsum, 16, 64);
-    dsum += __shfl_xor(dsum, 32, 64);  // D[q] for the lane's column
+    dsum += __shfl_xor(dsum, 16, 64);  // xor16_32_sum (attn_common.h) written out: through it the dQ kernels of head_dim 64 / 128
+    dsum += __shfl_xor(dsum, 32, 64);  // come out with other register names (profiles/attn_common_isa.txt).  D[q] for the lane's column
     const float lse_q = q_ok ? a.lse[qrow * a.H + h] : 0.f;
     if (q_ok && g4 == 0) a.dvec[qrow * a.H + h] = dsum;
 
@@ -476,7 +454,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_blk_kernel(const AttnBwdA
     const long long gh = blockIdx.x / nkc;
     const int kc = (int)(blockIdx.x - gh * nkc);
     const int h = (int)(gh % a.H), grp = (int)(gh / a.H);
-    const BwdGeo geo = bwd_geo(a, grp);
+    const AttnUnit geo = attn_unit<false>(a, grp);
     if (kc * 64 >= geo.Sk) return;  // ragged: the grid follows the longest unit
     const long long qrow0 = geo.q0, krow0 = geo.k0;
     const int kj = kc * 64 + wave * 16 + c16;
@@ -610,7 +588,7 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(const AttnBwdArgs a
     const bool live = unit < n_units;
     const long long uu = live ? unit : 0;
     const int grp = (int)(uu / a.H), h = (int)(uu - (long long)grp * a.H);
-    const BwdGeo geo = bwd_geo(a, grp);
+    const AttnUnit geo = attn_unit<false>(a, grp);
     const long long q0 = geo.q0, k0 = geo.k0;
     const int Sq = live ? geo.Sq : 0, Sk = live ? geo.Sk : 0;
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -760,7 +738,7 @@ __global__ __launch_bounds__(64 * NWU, 2) void attn_bwd_fused_kernel(const AttnB
     float* const lsh = dsh + NBUF * 16;                   // [NBUF][16] their log-sum-exp
 
     const int h = (int)(blockIdx.x % a.H), grp = (int)(blockIdx.x / a.H);
-    const BwdGeo geo = bwd_geo(a, grp);
+    const AttnUnit geo = attn_unit<false>(a, grp);
     const int nkt = (geo.Sk + 15) >> 4, nqt_all = (geo.Sq + 15) >> 4;
     const int qt_begin = a.qc_tiles ? (int)blockIdx.y * a.qc_tiles : 0;
     const int nqt = a.qc_tiles ? min(nqt_all, qt_begin + a.qc_tiles) : nqt_all;  // this block's tiles: [qt_begin, nqt)
@@ -1195,7 +1173,7 @@ __global__ __launch_bounds__(64 * NWU, 2) void attn_bwd_fused_kernel(const AttnB
 __global__ __launch_bounds__(256) void attn_bwd_part_reduce_kernel(const AttnBwdArgs a, int kp) {
     constexpr int DH = 128;
     const int h = (int)(blockIdx.x % a.H), grp = (int)(blockIdx.x / a.H);
-    const BwdGeo geo = bwd_geo(a, grp);
+    const AttnUnit geo = attn_unit<false>(a, grp);
     const int nch = ((geo.Sq + 15) / 16 + a.qc_tiles - 1) / a.qc_tiles;
     const long long slot0 = geo.q0 / (16 * a.qc_tiles) + grp;
     // blockIdx.y: 256 of the unit's Sk * 64 float4 each (one sample per step has eight (unit, head) pairs: eight blocks walked twelve
@@ -1349,12 +1327,12 @@ int launch_bwd_dh(const AttnBwdArgs& a0, hipStream_t s) {
         }
         a.ntile = (a.Sq + 15) / 16;
         long long u = (long long)a.G * a.H * a.ntile;
-        SOLA_ARG((u + 3) / 4 < (1ll << 31), "attention backward: grid too large");
+        SOLA_TRY(attn_grid_ok((u + 3) / 4, "attention backward"));
         hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, true>), dim3((unsigned)((u + 3) / 4)), dim3(256), lds, s, a);
         SOLA_LAUNCH_CHECK();
         a.ntile = (a.Sk + 15) / 16;
         u = (long long)a.G * a.H * a.ntile;
-        SOLA_ARG((u + 3) / 4 < (1ll << 31), "attention backward: grid too large");
+        SOLA_TRY(attn_grid_ok((u + 3) / 4, "attention backward"));
         hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH, true>), dim3((unsigned)((u + 3) / 4)), dim3(256), lds, s, a);
         SOLA_LAUNCH_CHECK();
         return SOLA_OK;
@@ -1388,13 +1366,13 @@ int launch_bwd_dh(const AttnBwdArgs& a0, hipStream_t s) {
     if (!done_dq) {
         a.ntile = (a.Sq + 15) / 16;
         units = (long long)a.G * a.H * a.ntile;
-        SOLA_ARG((units + 3) / 4 < (1ll << 31), "attention backward: grid too large");
+        SOLA_TRY(attn_grid_ok((units + 3) / 4, "attention backward"));
         hipLaunchKernelGGL((attn_bwd_dq_kernel<DH>), dim3((unsigned)((units + 3) / 4)), dim3(256), lds, s, a);
         SOLA_LAUNCH_CHECK();
     }
     a.ntile = (a.Sk + 15) / 16;
     units = (long long)a.G * a.H * a.ntile;
-    SOLA_ARG((units + 3) / 4 < (1ll << 31), "attention backward: grid too large");
+    SOLA_TRY(attn_grid_ok((units + 3) / 4, "attention backward"));
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH>), dim3((unsigned)((units + 3) / 4)), dim3(256), lds, s, a);
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
@@ -1424,14 +1402,10 @@ int launch_attention_bwd(const AttnBwdDesc& d, hipStream_t s) {
     AttnBwdArgs a;
     a.q = d.q; a.k = d.k; a.v = d.v; a.o = d.o; a.dout = d.dout; a.lse = d.lse;
     a.dq = d.dq; a.dk = d.dk; a.dv = d.dv; a.dvec = d.dvec;
-    a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
+    attn_fill_common(a, d);
     a.ld_dq = d.ld_dq; a.ld_dk = d.ld_dk; a.ld_dv = d.ld_dv;
-    a.G = d.G; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk; a.inner = d.inner; a.ntile = 1;
-    a.q_outer = d.q_outer; a.q_inner = d.q_inner; a.q_rs = d.q_rs;
-    a.k_outer = d.k_outer; a.k_inner = d.k_inner; a.k_rs = d.k_rs;
-    a.scale = d.scale;
+    a.ntile = 1;
     a.drop = d.drop;
-    a.q_units = d.q_units; a.k_units = d.q_units ? (d.k_units ? d.k_units : d.q_units) : nullptr;
     a.io16 = d.io_bf16 ? 1 : 0;
     a.g16 = d.dout_bf16 ? 1 : 0;
     a.o16 = d.o_bf16 ? 1 : 0;
@@ -1450,11 +1424,5 @@ int launch_attention_bwd(const AttnBwdDesc& d, hipStream_t s) {
     const bool can_chunk = d.part && d.Sk <= 64 && d.part_floats >= attention_bwd_part_floats(d.part_rows, d.G, d.H, d.Sk) &&
                            (d.q_units || (d.q_rs == 1 && d.inner == 1));
     if (bwd_fused_supported(a, d.DH, can_chunk)) return launch_bwd_fused(a, can_chunk, d.part_rows, s);
-    switch (d.DH) {
-        case 128: return launch_bwd_dh<128>(a, s);
-        case 64: return launch_bwd_dh<64>(a, s);
-        case 32: return launch_bwd_dh<32>(a, s);
-        case 16: return launch_bwd_dh<16>(a, s);
-        default: sola_set_error("attention backward: head_dim %d unsupported", d.DH); return SOLA_ERR_ARG;
-    }
+    return attn_dispatch_dh(d.DH, "attention backward: head_dim %d unsupported", [&](auto dh) { return launch_bwd_dh<decltype(dh)::value>(a, s); });
 }

@@ -2,7 +2,7 @@
 // matrices (2 bytes per element: half the HBM traffic of the f32 / split-f16 kernels of attn.hip, which this kernel is
 // otherwise a restatement of), products run on v_mfma_f32_16x16x16_f16 with f32 accumulation, softmax in f32.
 //
-// Same single [B, N, T', D] layout and the same (outer, inner, row) / unit-table addressing as attn.hip.  One wave owns a
+// Same single [B, N, T', D] layout and the (outer, inner, row) / unit-table addressing of attn_common.h.  One wave owns a
 // 16-query tile:
 //   S^T = K Q^T : A = K rows, B = Q (registers); lane (c16, g4) ends with the scores of query c16 against keys 4*g4 + {0..3} of
 //                 the tile: a softmax row lives in one 16-lane column.  Round 5: the head dimension is taken in PAIRS of 16-wide
@@ -17,12 +17,9 @@
 // per block at head_dim 128, so four 4-wave blocks share a CU and cover each other's memory latency; longer key sequences
 // take further tiles with an online softmax.  Sequences of at most 16 steps (motion attention over T') use one wave per
 // (group, head) unit with a private 16-row tile, four units per block, no block-level synchronisation.
-#include "kernels.h"
+#include "attn_common.h"
 
 namespace {
-
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
 
 struct AttnHArgs {
     const _Float16 *q, *k, *v;
@@ -59,21 +56,6 @@ int g_attn_f16_small = 1;
 int g_attn_f16_qpb = 4;  // sola_tune "attn_f16_qpb": q-blocks per block against <= 64 keys, at most (1 = every q-block stages the unit's K / V itself; < 0: exactly -v, tests)  // sola_tune "attn_f16_small": 0 = the MFMA shape for sequences of <= 4 steps too (A/B)
 namespace {
 
-struct GeoH { long long q0, k0, q_rs, k_rs; int Sq, Sk; };
-__device__ __forceinline__ GeoH geo_h(const AttnHArgs& a, int grp) {
-    GeoH g;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        g.q0 = __builtin_amdgcn_readfirstlane(qu.x); g.q_rs = __builtin_amdgcn_readfirstlane(qu.y); g.Sq = __builtin_amdgcn_readfirstlane(qu.z);
-        g.k0 = __builtin_amdgcn_readfirstlane(ku.x); g.k_rs = __builtin_amdgcn_readfirstlane(ku.y); g.Sk = __builtin_amdgcn_readfirstlane(ku.z);
-    } else {
-        g.q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        g.k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        g.q_rs = a.q_rs; g.k_rs = a.k_rs; g.Sq = a.Sq; g.Sk = a.Sk;
-    }
-    return g;
-}
-
 // WPU = wave per unit (sequences of <= 16 steps): the block's four waves serve four different (group, head) units
 // (Round 5, measured and removed: two 32-key LDS stages with the next tile's rows prefetched in registers, attn_fwd_f32_simple_kernel's DB
 // shape - 161 vs 151 us at the 128-key inter-object site, equal at 64 keys: at four blocks per CU the other blocks already cover a tile's load.)
@@ -101,7 +83,7 @@ __global__ __launch_bounds__(256, WPU ? 2 : 4) void attn_fwd_f16_kernel(const At
         qb = (blockIdx.x - (int)unit * nqg) * a.qpb;
     }
     const int grp = (int)(unit / a.H), h = (int)(unit - (long long)grp * a.H);
-    const GeoH g = geo_h(a, grp);
+    const AttnUnit g = attn_unit<true>(a, grp);  // a block (WPU: a wave) serves one unit
     _Float16* Ks = smem_h + (WPU ? wave * 2 * TROWS * LD : 0);
     _Float16* Vs = Ks + TROWS * LD;
 
@@ -200,8 +182,7 @@ __global__ __launch_bounds__(256, WPU ? 2 : 4) void attn_fwd_f16_kernel(const At
             for (int t = 0; t < TROWS / 16; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[t][r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            mx = xor16_32_max(mx);
             const float m_new = fmaxf(m_run, mx);
             const float alpha = __expf(m_run - m_new);  // exp(-inf) = 0 on the first tile
             float rs = 0.f;
@@ -212,8 +193,7 @@ __global__ __launch_bounds__(256, WPU ? 2 : 4) void attn_fwd_f16_kernel(const At
                     sc[t][r] = __expf(sc[t][r] - m_new);
                     rs += sc[t][r];
                 }
-            rs += __shfl_xor(rs, 16, 64);
-            rs += __shfl_xor(rs, 32, 64);
+            rs = xor16_32_sum(rs);
             l_run = l_run * alpha + rs;
             m_run = m_new;
 #pragma unroll
@@ -320,7 +300,7 @@ __global__ __launch_bounds__(256, WPU ? 2 : 4) void attn_fwd_f16_kernel(const At
                     *reinterpret_cast<half4v*>(op + cp * 32 + 4) = half4v{o8[4], o8[5], o8[6], o8[7]};
                 }
             }
-            if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+            attn_range_guard(a.guard, m);
         }
     }
 }
@@ -348,16 +328,9 @@ __global__ __launch_bounds__(256) void attn_fwd_small_f16_kernel(const AttnHArgs
     const bool live = unit < n_units;
     const long long uu = live ? unit : 0;
     const int grp = (int)(uu / a.H), h = (int)(uu - (long long)grp * a.H);
-    long long q0, k0, q_rs, k_rs;
-    int Sq, Sk;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        q0 = qu.x; q_rs = qu.y; Sq = qu.z; k0 = ku.x; k_rs = ku.y; Sk = ku.z;
-    } else {
-        q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        q_rs = a.q_rs; k_rs = a.k_rs; Sq = a.Sq; Sk = a.Sk;
-    }
+    const AttnUnit u = attn_unit<false>(a, grp);  // the four quarters of a wave serve different units
+    const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
+    int Sq = u.Sq, Sk = u.Sk;
     if (!live) { Sq = 0; Sk = 0; }
     float qv[TT][8], kv[TT][8], vv[TT][8];
     // rows past the unit's length: a CLAMPED row is loaded and the VALUE zeroed (attn_simple.hip: a select of pointers goes through
@@ -413,15 +386,17 @@ __global__ __launch_bounds__(256) void attn_fwd_small_f16_kernel(const AttnHArgs
         }
         *reinterpret_cast<half8v*>(a.o + (q0 + (long long)i * q_rs) * a.ldo + h * DH + 8 * c) = o8;
     }
-    if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+    attn_range_guard(a.guard, m);
 }
 
-template <int DH>
+// TRAIN: the training forward on bfloat16 q / k / v (head_dim 128 / 64; the BF + TR instantiations): one wave per unit for sequences
+// of <= 16 steps, else 64-query blocks.  The streaming kernel of <= 4 steps and the forced qpb of the tests are inference only.
+template <int DH, bool TRAIN>
 int launch_h(const AttnHArgs& a0, hipStream_t s) {
     AttnHArgs a = a0;
     constexpr int LD = DH + 8;
     const long long units = (long long)a.G * a.H;
-    if (DH == 128 && a.Sq <= 4 && a.Sk <= 4 && g_attn_f16_small && a.ldo % 8 == 0) {
+    if (!TRAIN && DH == 128 && a.Sq <= 4 && a.Sk <= 4 && g_attn_f16_small && a.ldo % 8 == 0) {
         const unsigned blocks = (unsigned)((units + 15) / 16);
         const int need = a.Sq > a.Sk ? a.Sq : a.Sk;
         if (need <= 1) hipLaunchKernelGGL((attn_fwd_small_f16_kernel<1>), dim3(blocks), dim3(256), 0, s, a);
@@ -430,44 +405,20 @@ int launch_h(const AttnHArgs& a0, hipStream_t s) {
     } else if (a.Sq <= 16 && a.Sk <= 16) {
         a.nqb = 1; a.qpb = 1;
         const size_t lds = (size_t)4 * 2 * 16 * LD * sizeof(_Float16);
-        hipLaunchKernelGGL((attn_fwd_f16_kernel<DH, true>), dim3((unsigned)((units + 3) / 4)), dim3(256), lds, s, a);
+        hipLaunchKernelGGL((attn_fwd_f16_kernel<DH, true, TRAIN, TRAIN>), dim3((unsigned)((units + 3) / 4)), dim3(256), lds, s, a);
     } else {
         a.nqb = (a.Sq + 63) / 64;
         // many queries against at most one tile of keys (object -> language): a block walks qpb q-blocks of its unit over the staged K / V
         // as long as the grid still fills the chip several times over
         a.qpb = 1;
-        if (a.Sk <= 64 && g_attn_f16_qpb < 0)  // tests: forced, whatever the grid
+        if (!TRAIN && a.Sk <= 64 && g_attn_f16_qpb < 0)  // tests: forced, whatever the grid
             a.qpb = std::min(-g_attn_f16_qpb, a.nqb);
         else if (a.Sk <= 64 && g_attn_f16_qpb > 1)
             while (a.qpb < g_attn_f16_qpb && a.qpb * 2 <= a.nqb && units * ((a.nqb + 2 * a.qpb - 1) / (2 * a.qpb)) >= 8ll * sola_cu_count()) a.qpb *= 2;
         const long long blocks = units * ((a.nqb + a.qpb - 1) / a.qpb);
-        SOLA_ARG(blocks < (1ll << 31), "attention (f16): grid too large");
+        SOLA_TRY(attn_grid_ok(blocks, TRAIN ? "attention (bf16)" : "attention (f16)"));
         const size_t lds = (size_t)2 * 64 * LD * sizeof(_Float16);
-        hipLaunchKernelGGL((attn_fwd_f16_kernel<DH, false>), dim3((unsigned)blocks), dim3(256), lds, s, a);
-    }
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-
-// training forward on bfloat16 q / k / v (head_dim 128 / 64): one wave per unit for sequences of <= 16 steps, else 64-query blocks
-template <int DH>
-int launch_h_bf16_train(const AttnHArgs& a0, hipStream_t s) {
-    AttnHArgs a = a0;
-    constexpr int LD = DH + 8;
-    const long long units = (long long)a.G * a.H;
-    if (a.Sq <= 16 && a.Sk <= 16) {
-        a.nqb = 1; a.qpb = 1;
-        const size_t lds = (size_t)4 * 2 * 16 * LD * sizeof(_Float16);
-        hipLaunchKernelGGL((attn_fwd_f16_kernel<DH, true, true, true>), dim3((unsigned)((units + 3) / 4)), dim3(256), lds, s, a);
-    } else {
-        a.nqb = (a.Sq + 63) / 64;
-        a.qpb = 1;
-        if (a.Sk <= 64 && g_attn_f16_qpb > 1)
-            while (a.qpb < g_attn_f16_qpb && a.qpb * 2 <= a.nqb && units * ((a.nqb + 2 * a.qpb - 1) / (2 * a.qpb)) >= 8ll * sola_cu_count()) a.qpb *= 2;
-        const long long blocks = units * ((a.nqb + a.qpb - 1) / a.qpb);
-        SOLA_ARG(blocks < (1ll << 31), "attention (bf16): grid too large");
-        const size_t lds = (size_t)2 * 64 * LD * sizeof(_Float16);
-        hipLaunchKernelGGL((attn_fwd_f16_kernel<DH, false, true, true>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+        hipLaunchKernelGGL((attn_fwd_f16_kernel<DH, false, TRAIN, TRAIN>), dim3((unsigned)blocks), dim3(256), lds, s, a);
     }
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
@@ -487,16 +438,12 @@ int launch_attention_bf16_train(const AttnDesc& d, hipStream_t s) {
     a.q = reinterpret_cast<const _Float16*>(d.q); a.k = reinterpret_cast<const _Float16*>(d.k);
     a.v = reinterpret_cast<const _Float16*>(d.v); a.o = reinterpret_cast<_Float16*>(d.o_cast);
     a.o32 = d.o; a.lse = d.lse; a.drop = d.drop;
-    a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
-    a.G = d.G; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk; a.inner = d.inner; a.nqb = 1;
-    a.q_outer = d.q_outer; a.q_inner = d.q_inner; a.q_rs = d.q_rs;
-    a.k_outer = d.k_outer; a.k_inner = d.k_inner; a.k_rs = d.k_rs;
-    a.scale = d.scale; a.guard = nullptr; a.qpb = 1;
-    a.q_units = d.q_units; a.k_units = d.q_units ? (d.k_units ? d.k_units : d.q_units) : nullptr;
+    attn_fill_common(a, d);
+    a.nqb = 1; a.qpb = 1; a.guard = nullptr;
     if (d.o_cast && d.o_cast_done) *d.o_cast_done = true;
     const double elems = (double)d.G * d.H * d.DH;
     SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, elems * (2.0 * (d.Sq + 2.0 * d.Sk) + (d.o ? 4.0 : 0.0) * d.Sq + (d.o_cast ? 2.0 : 0.0) * d.Sq));
-    return d.DH == 128 ? launch_h_bf16_train<128>(a, s) : launch_h_bf16_train<64>(a, s);
+    return d.DH == 128 ? launch_h<128, true>(a, s) : launch_h<64, true>(a, s);
 }
 
 void sola_attn_set_f16_qpb(int v) { g_attn_f16_qpb = v == 0 ? 1 : v; }
@@ -509,20 +456,9 @@ int launch_attention_f16(const AttnDesc& d, hipStream_t s) {
     AttnHArgs a;
     a.q = reinterpret_cast<const _Float16*>(d.q); a.k = reinterpret_cast<const _Float16*>(d.k);
     a.v = reinterpret_cast<const _Float16*>(d.v); a.o = reinterpret_cast<_Float16*>(d.o);
-    a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
-    a.G = d.G; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk; a.inner = d.inner; a.nqb = 1;
-    a.q_outer = d.q_outer; a.q_inner = d.q_inner; a.q_rs = d.q_rs;
-    a.k_outer = d.k_outer; a.k_inner = d.k_inner; a.k_rs = d.k_rs;
-    a.scale = d.scale; a.guard = d.guard; a.qpb = 1;
+    attn_fill_common(a, d);
+    a.nqb = 1; a.qpb = 1; a.guard = d.guard;  // every output of this mode is 16-bit: the guard word is always looked at
     a.o32 = nullptr; a.lse = nullptr; a.drop = DropoutCfg{};
-    a.q_units = d.q_units; a.k_units = d.q_units ? (d.k_units ? d.k_units : d.q_units) : nullptr;
-    const double elems = (double)d.G * d.H * d.DH;
-    SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, 2.0 * elems * (2.0 * d.Sq + 2.0 * d.Sk));
-    switch (d.DH) {
-        case 128: return launch_h<128>(a, s);
-        case 64: return launch_h<64>(a, s);
-        case 32: return launch_h<32>(a, s);
-        case 16: return launch_h<16>(a, s);
-        default: sola_set_error("attention (f16): head_dim %d unsupported (16/32/64/128)", d.DH); return SOLA_ERR_ARG;
-    }
+    const SolaProfScope prof = attn_prof_scope(d, s, 2.0);
+    return attn_dispatch_dh(d.DH, "attention (f16): head_dim %d unsupported (16/32/64/128)", [&](auto dh) { return launch_h<decltype(dh)::value, false>(a, s); });
 }

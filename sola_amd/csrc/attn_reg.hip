@@ -16,11 +16,9 @@
 // q + k + v + o.  Keys are taken 64 at a time with the online softmax, so any Sk works; units of up to 64 keys take one pass.
 // Exact f32 (v_mfma_f32_16x16x4_f32), strided groups or unit tables, optional log-sum-exp, f32 or split-f16 output.
 // head_dim 128.  tools/attention.py:66-72.
-#include "kernels.h"
+#include "attn_common.h"
 
 namespace {
-
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 
 struct AttnRArgs {
     const float *q, *k, *v;
@@ -36,15 +34,6 @@ struct AttnRArgs {
     int* guard;
     const int4 *q_units, *k_units;
 };
-
-__device__ __forceinline__ float xor16_32_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float xor16_32_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
 
 // One pass over up to 64 keys (NT tiles of 16) of a unit.  Two float4[8] buffers carry the K tiles and then the V tiles: the
 // loads of tile t + 1 are issued before the MFMAs of tile t (sched_barrier keeps the compiler from sinking them to their
@@ -159,17 +148,9 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_f32_reg_kernel(const AttnR
     const long long unit = task / a.nqt;
     const int qt = (int)(task - unit * a.nqt);
     const int grp = (int)(unit / a.H), h = (int)(unit - (long long)grp * a.H);
-    long long q0, k0, q_rs, k_rs;
-    int Sq, Sk;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        q0 = __builtin_amdgcn_readfirstlane(qu.x); q_rs = __builtin_amdgcn_readfirstlane(qu.y); Sq = __builtin_amdgcn_readfirstlane(qu.z);
-        k0 = __builtin_amdgcn_readfirstlane(ku.x); k_rs = __builtin_amdgcn_readfirstlane(ku.y); Sk = __builtin_amdgcn_readfirstlane(ku.z);
-    } else {
-        q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        q_rs = a.q_rs; k_rs = a.k_rs; Sq = a.Sq; Sk = a.Sk;
-    }
+    const AttnUnit u = attn_unit<true>(a, grp);  // a wave serves one unit
+    const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
+    const int Sq = u.Sq, Sk = u.Sk;
     if (qt * 16 >= Sq || Sk <= 0) return;
     const int qi = qt * 16 + x;
     const bool q_ok = qi < Sq;
@@ -218,8 +199,9 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_f32_reg_kernel(const AttnR
                     make_float4(oacc[hf][0][r] * inv, oacc[hf][1][r] * inv, oacc[hf][2][r] * inv, oacc[hf][3][r] * inv);
         return;
     }
-    // split-f16: the 8-wide block [hi8 | lo8] is shared by the lane pair (g4, g4 ^ 1); each lane writes the hi and the lo
-    // halves of its own four values (block offset 8 * (g4 & 1), lo 16 bytes behind), as store_o in attn.hip
+    // split-f16: attn_store_tile's pairs (attn_common.h) written out for this kernel's TRANSPOSED accumulators (chunk 4 hf + r, value c).
+    // Gathered into chunk order and handed to the shared store, the spilling experiment instantiations change their spills (<4>: 200 ->
+    // 209 VGPRs spilled) and <2> swaps two address instructions; written out all three are unchanged (profiles/attn_common_isa.txt)
     float m = 0.f;
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf)
@@ -238,7 +220,7 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_f32_reg_kernel(const AttnR
             *reinterpret_cast<half4v*>(dst) = hi;
             *reinterpret_cast<half4v*>(dst + 16) = lo;
         }
-    if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+    attn_range_guard(a.guard, m);
 }
 
 }  // namespace
@@ -266,18 +248,12 @@ bool attention_reg_supported(const AttnDesc& d) {
 int launch_attention_reg(const AttnDesc& d, hipStream_t s) {
     AttnRArgs a;
     a.q = d.q; a.k = d.k; a.v = d.v; a.o = d.o; a.lse = d.lse;
-    a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
-    a.G = d.G; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk; a.inner = d.inner;
-    a.q_outer = d.q_outer; a.q_inner = d.q_inner; a.q_rs = d.q_rs;
-    a.k_outer = d.k_outer; a.k_inner = d.k_inner; a.k_rs = d.k_rs;
-    a.scale = d.scale; a.o_sp16 = d.o_sp16; a.guard = d.o_sp16 ? d.guard : nullptr;
-    a.q_units = d.q_units; a.k_units = d.q_units ? (d.k_units ? d.k_units : d.q_units) : nullptr;
+    attn_fill_common(a, d);
     a.nqt = (d.Sq + 15) / 16;
     a.n_tasks = (long long)d.G * d.H * a.nqt;
     const long long blocks = ((a.n_tasks + 3) / 4 + 7) / 8 * 8;
-    SOLA_ARG(blocks < (1ll << 31), "attention: grid too large");
-    const double elems = (double)d.G * d.H * d.DH;
-    SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, 4.0 * elems * (2.0 * d.Sq + 2.0 * d.Sk));
+    SOLA_TRY(attn_grid_ok(blocks, "attention"));
+    const SolaProfScope prof = attn_prof_scope(d, s);
 #ifdef SOLA_EXPERIMENTS  // the register budgets that spill (A/B record: 1.3x / 2.4x slower)
     if (g_attn_reg_minw >= 4) hipLaunchKernelGGL((attn_fwd_f32_reg_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, s, a);
     else if (g_attn_reg_minw == 3) hipLaunchKernelGGL((attn_fwd_f32_reg_kernel<3>), dim3((unsigned)blocks), dim3(256), 0, s, a);

@@ -8,11 +8,9 @@
 // K/V through registers) at two 4-wave blocks per CU: 212 us per launch, 38 % of the HBM peak.
 // Same register layout as attn.hip (S^T = K Q^T, O^T = V^T P^T, v_mfma_f32_16x16x4_f32), strided groups or unit tables,
 // f32 or split-f16 output, optional log-sum-exp.  head_dim 128, at most 64 keys.  tools/attention.py:66-72.
-#include "kernels.h"
+#include "attn_common.h"
 
 namespace {
-
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 
 struct AttnQArgs {
     const float *q, *k, *v;
@@ -86,30 +84,7 @@ __device__ __forceinline__ void res_tile(const AttnQArgs& a, const float* Ks, co
         }
     if (!q_ok) return;
     if (lsep && g4 == 0) *lsep = mx + logf(rs);
-    const float inv = 1.f / rs;
-    if (!a.o_sp16) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            *reinterpret_cast<float4*>(op + 16 * c + 4 * g4) = make_float4(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv);
-        return;
-    }
-    float m = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        half4v hi, lo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float v = oacc[c][j] * inv;
-            _Float16 h1, l1;
-            split_f16(v, h1, l1);
-            hi[j] = h1; lo[j] = l1;
-            m = fmaxf(m, fabsf(v));
-        }
-        char* dst = reinterpret_cast<char*>(op + 16 * c + 8 * (g4 >> 1)) + 8 * (g4 & 1);
-        *reinterpret_cast<half4v*>(dst) = hi;
-        *reinterpret_cast<half4v*>(dst + 16) = lo;
-    }
-    if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+    attn_store_tile<8>(op, g4, oacc, 1.f / rs, a.o_sp16, a.guard);
 }
 
 // ---- the same shape in the split precision mode's arithmetic (AttnDesc::split_math) -----------------------------------------
@@ -120,34 +95,15 @@ __device__ __forceinline__ void res_tile(const AttnQArgs& a, const float* Ks, co
 // ([dh][key], so both MFMA A-fragments are 8-byte LDS reads); per 16-query tile Q (32 values per lane) and P (12) are split
 // in registers.  3 x v_mfma_f32_16x16x16_f16 per 16-deep product step: 144 MFMAs of 8 cycles per tile instead of 192 of 32.
 // (attn_simple.hip's first attempt converted K/V per 64-query block and every wave re-split the fragments it read: slower.)
-typedef _Float16 half4r __attribute__((ext_vector_type(4)));
-struct HL4r { half4r hi, lo; };
-__device__ __forceinline__ HL4r split4r(float x, float y, float z, float w, float& amax) {
-    HL4r r;
-    const float in[4] = {x, y, z, w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        _Float16 h1, l1;
-        split_f16(in[j], h1, l1);
-        r.hi[j] = h1; r.lo[j] = l1;
-        amax = fmaxf(amax, fabsf(in[j]));
-    }
-    return r;
-}
-__device__ __forceinline__ f32x4 mfma3r(const HL4r& a, const HL4r& b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x16f16(a.lo, b.hi, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x16f16(a.hi, b.lo, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a.hi, b.hi, c, 0, 0, 0);
-}
 constexpr int SM_KP = 136;  // K row pitch in halfs: 272 B = 16 B past a bank row, the 8-byte fragment reads of 16 keys x 2 k-groups tile the banks
 constexpr int SM_VP = 72;   // V^T row pitch in halfs: 144 B = 9 x 16 B (odd), up to 64 keys per row
 
 template <int NT>
 __device__ __forceinline__ void sm_tile(const AttnQArgs& a, const _Float16* Kh, const _Float16* Kl, const _Float16* Vh, const _Float16* Vl,
                                         const float4 (&qf)[8], float* op, float* lsep, int Sk, int x, int g4, bool q_ok, float& amax) {
-    HL4r q[8];
+    HL4 q[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) q[i] = split4r(qf[i].x, qf[i].y, qf[i].z, qf[i].w, amax);
+    for (int i = 0; i < 8; ++i) q[i] = split4(qf[i].x, qf[i].y, qf[i].z, qf[i].w, amax);
     f32x4 sc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -155,11 +111,11 @@ __device__ __forceinline__ void sm_tile(const AttnQArgs& a, const _Float16* Kh, 
         f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < 8; i += 2) {
-            HL4r k0, k1;
-            k0.hi = *reinterpret_cast<const half4r*>(Kh + ko + 16 * i); k0.lo = *reinterpret_cast<const half4r*>(Kl + ko + 16 * i);
-            k1.hi = *reinterpret_cast<const half4r*>(Kh + ko + 16 * i + 16); k1.lo = *reinterpret_cast<const half4r*>(Kl + ko + 16 * i + 16);
-            a0 = mfma3r(k0, q[i], a0);
-            a1 = mfma3r(k1, q[i + 1], a1);
+            HL4 k0, k1;
+            k0.hi = *reinterpret_cast<const half4v*>(Kh + ko + 16 * i); k0.lo = *reinterpret_cast<const half4v*>(Kl + ko + 16 * i);
+            k1.hi = *reinterpret_cast<const half4v*>(Kh + ko + 16 * i + 16); k1.lo = *reinterpret_cast<const half4v*>(Kl + ko + 16 * i + 16);
+            a0 = mfma3(k0, q[i], a0);
+            a1 = mfma3(k1, q[i + 1], a1);
         }
         const int key0 = 16 * t + 4 * g4;
 #pragma unroll
@@ -172,8 +128,7 @@ __device__ __forceinline__ void sm_tile(const AttnQArgs& a, const _Float16* Kh, 
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[t][r]);
     mx = max_xor32(max_xor16(mx));
     float rs = 0.f;
-    HL4r p[NT];
-    float dummy = 0.f;
+    HL4 p[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -181,7 +136,7 @@ __device__ __forceinline__ void sm_tile(const AttnQArgs& a, const _Float16* Kh, 
             sc[t][r] = __expf(sc[t][r] - mx);
             rs += sc[t][r];
         }
-        p[t] = split4r(sc[t][0], sc[t][1], sc[t][2], sc[t][3], dummy);
+        p[t] = split4(sc[t][0], sc[t][1], sc[t][2], sc[t][3]);
     }
     rs = sum_xor32(sum_xor16(rs));
     f32x4 oacc[8];
@@ -192,25 +147,24 @@ __device__ __forceinline__ void sm_tile(const AttnQArgs& a, const _Float16* Kh, 
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const int vo = (16 * c + x) * SM_VP + 16 * t + 4 * g4;
-            HL4r v;
-            v.hi = *reinterpret_cast<const half4r*>(Vh + vo); v.lo = *reinterpret_cast<const half4r*>(Vl + vo);
-            oacc[c] = mfma3r(v, p[t], oacc[c]);
+            HL4 v;
+            v.hi = *reinterpret_cast<const half4v*>(Vh + vo); v.lo = *reinterpret_cast<const half4v*>(Vl + vo);
+            oacc[c] = mfma3(v, p[t], oacc[c]);
         }
     if (!q_ok) return;
     if (lsep && g4 == 0) *lsep = mx + logf(rs);
     const float inv = 1.f / rs;
     if (!a.o_sp16) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            *reinterpret_cast<float4*>(op + 16 * c + 4 * g4) = make_float4(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv);
+        attn_store_tile<8>(op, g4, oacc, inv, 0, nullptr);
         return;
     }
+    // split pairs: the shared store's layout, but the magnitudes join this kernel's own amax (one guard test per block, below)
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        const HL4r o = split4r(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv, amax);
+        const HL4 o = split4(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv, amax);
         char* dst = reinterpret_cast<char*>(op + 16 * c + 8 * (g4 >> 1)) + 8 * (g4 & 1);
-        *reinterpret_cast<half4r*>(dst) = o.hi;
-        *reinterpret_cast<half4r*>(dst + 16) = o.lo;
+        *reinterpret_cast<half4v*>(dst) = o.hi;
+        *reinterpret_cast<half4v*>(dst + 16) = o.lo;
     }
 }
 
@@ -225,17 +179,9 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_sm_res_kernel(const AttnQArgs
     if (unit >= (long long)a.G * a.H) return;
     const int chunk = (int)(lb - unit * a.nchunk);
     const int grp = (int)(unit / a.H), h = (int)(unit - (long long)grp * a.H);
-    long long q0, k0, q_rs, k_rs;
-    int Sq, Sk;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        q0 = __builtin_amdgcn_readfirstlane(qu.x); q_rs = __builtin_amdgcn_readfirstlane(qu.y); Sq = __builtin_amdgcn_readfirstlane(qu.z);
-        k0 = __builtin_amdgcn_readfirstlane(ku.x); k_rs = __builtin_amdgcn_readfirstlane(ku.y); Sk = __builtin_amdgcn_readfirstlane(ku.z);
-    } else {
-        q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        q_rs = a.q_rs; k_rs = a.k_rs; Sq = a.Sq; Sk = a.Sk;
-    }
+    const AttnUnit u = attn_unit<true>(a, grp);  // a block serves one unit
+    const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
+    const int Sq = u.Sq, Sk = u.Sk;
     const int qchunk = NW * 16 * a.tiles_per_wave;
     const int qbeg = chunk * qchunk;
     if (qbeg >= Sq || Sk <= 0) return;  // block-uniform
@@ -254,9 +200,9 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_sm_res_kernel(const AttnQArgs
             kv = *reinterpret_cast<const float4*>(a.k + row * a.ldk + h * DH + 4 * c);
             vv = *reinterpret_cast<const float4*>(a.v + row * a.ldv + h * DH + 4 * c);
         }
-        const HL4r kk = split4r(kv.x, kv.y, kv.z, kv.w, amax), vs = split4r(vv.x, vv.y, vv.z, vv.w, amax);
-        *reinterpret_cast<half4r*>(Kh + r * SM_KP + 4 * c) = kk.hi;
-        *reinterpret_cast<half4r*>(Kl + r * SM_KP + 4 * c) = kk.lo;
+        const HL4 kk = split4(kv.x, kv.y, kv.z, kv.w, amax), vs = split4(vv.x, vv.y, vv.z, vv.w, amax);
+        *reinterpret_cast<half4v*>(Kh + r * SM_KP + 4 * c) = kk.hi;
+        *reinterpret_cast<half4v*>(Kl + r * SM_KP + 4 * c) = kk.lo;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             Vh[(4 * c + j) * SM_VP + r] = vs.hi[j];
@@ -283,7 +229,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_sm_res_kernel(const AttnQArgs
         else sm_tile<1>(a, Kh, Kl, Vh, Vl, qf, op, lsep, Sk, x, g4, q_ok, amax);
     }
     // anything that left the f16 range (q, k, v or the output pairs; NaN fails the comparison too): the forward repeats in f32
-    if (a.guard && !(amax < 65000.f)) atomicOr(a.guard, 1);
+    attn_range_guard(a.guard, amax);
 }
 #endif
 
@@ -301,17 +247,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_f32_res_kernel(const A
     if (unit >= (long long)a.G * a.H) return;
     const int chunk = (int)(lb - unit * a.nchunk);
     const int grp = (int)(unit / a.H), h = (int)(unit - (long long)grp * a.H);
-    long long q0, k0, q_rs, k_rs;
-    int Sq, Sk;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        q0 = __builtin_amdgcn_readfirstlane(qu.x); q_rs = __builtin_amdgcn_readfirstlane(qu.y); Sq = __builtin_amdgcn_readfirstlane(qu.z);
-        k0 = __builtin_amdgcn_readfirstlane(ku.x); k_rs = __builtin_amdgcn_readfirstlane(ku.y); Sk = __builtin_amdgcn_readfirstlane(ku.z);
-    } else {
-        q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        q_rs = a.q_rs; k_rs = a.k_rs; Sq = a.Sq; Sk = a.Sk;
-    }
+    const AttnUnit u = attn_unit<true>(a, grp);  // a block serves one unit
+    const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
+    const int Sq = u.Sq, Sk = u.Sk;
     const int qchunk = NW * 16 * a.tiles_per_wave;
     const int qbeg = chunk * qchunk;
     if (qbeg >= Sq || Sk <= 0) return;  // block-uniform
@@ -404,7 +342,7 @@ static int launch_res(AttnQArgs a, const AttnDesc& d, hipStream_t s) {
     const int qchunk = NW * 16 * a.tiles_per_wave;
     a.nchunk = (d.Sq + qchunk - 1) / qchunk;
     const long long blocks = ((long long)d.G * d.H * a.nchunk + 7) / 8 * 8;
-    SOLA_ARG(blocks < (1ll << 31), "attention: grid too large");
+    SOLA_TRY(attn_grid_ok(blocks, "attention"));
     const size_t lds = (size_t)2 * ((d.Sk + 15) & ~15) * RES_LD * sizeof(float);
     static DeviceOnce once;
     int dev;
@@ -421,17 +359,11 @@ static int launch_res(AttnQArgs a, const AttnDesc& d, hipStream_t s) {
 int launch_attention_res(const AttnDesc& d, hipStream_t s) {
     AttnQArgs a;
     a.q = d.q; a.k = d.k; a.v = d.v; a.o = d.o; a.lse = d.lse;
-    a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
-    a.G = d.G; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk; a.inner = d.inner;
-    a.q_outer = d.q_outer; a.q_inner = d.q_inner; a.q_rs = d.q_rs;
-    a.k_outer = d.k_outer; a.k_inner = d.k_inner; a.k_rs = d.k_rs;
-    a.scale = d.scale; a.o_sp16 = d.o_sp16; a.guard = d.o_sp16 ? d.guard : nullptr;
-    a.q_units = d.q_units; a.k_units = d.q_units ? (d.k_units ? d.k_units : d.q_units) : nullptr;
+    attn_fill_common(a, d);
     a.tiles_per_wave = 1; a.nchunk = 1;
     a.k_priv = d.k_private > 0 ? d.k_private : 0x7fffffff;
     a.k_shared = d.k_shared_row;
-    const double elems = (double)d.G * d.H * d.DH;
-    SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, 4.0 * elems * (2.0 * d.Sq + 2.0 * d.Sk));
+    const SolaProfScope prof = attn_prof_scope(d, s);
     // measured at 256 samples (256 queries x 48 keys per unit, tools/attn_probe3.py): 8 waves without prefetch 180-183 us, three
     // 4-wave blocks per CU with the next tile's Q prefetched (pinned in front of the MFMAs by sched_barrier) 191-193 us,
     // attn.hip's resident loop 205 us.  Also measured without effect: staggered block starts (0-8 us), f16-MFMA triples (175 us:
@@ -453,7 +385,7 @@ int launch_attention_res(const AttnDesc& d, hipStream_t s) {
         const int qchunk = 8 * 16 * a.tiles_per_wave;
         a.nchunk = (d.Sq + qchunk - 1) / qchunk;
         const long long blocks = ((long long)d.G * d.H * a.nchunk + 7) / 8 * 8;
-        SOLA_ARG(blocks < (1ll << 31), "attention: grid too large");
+        SOLA_TRY(attn_grid_ok(blocks, "attention"));
         const int rows = (d.Sk + 15) & ~15;
         const size_t lds = ((size_t)2 * rows * SM_KP + (size_t)2 * 128 * SM_VP) * sizeof(_Float16);
         static DeviceOnce once;

@@ -7,11 +7,9 @@
 // VGPRs, so four to five blocks share a CU and cover each other's latency; longer key sequences take further tiles with
 // the online softmax.  Same arithmetic (v_mfma_f32_16x16x4_f32, S^T = K Q^T / O^T = V^T P^T register layout), same
 // addressing (strided groups or unit tables), f32 or split-f16 output.
-#include "kernels.h"
+#include "attn_common.h"
 
 namespace {
-
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 
 struct AttnSArgs {
     const float *q, *k, *v;
@@ -33,12 +31,6 @@ struct AttnSArgs {
     int o_cast_fmt;
     int o_skip_f32;   // TR + IN16: the f32 output is not written (the bf16 o_cast is the only copy: AttnDesc::in_bf16 with o == nullptr)
 };
-
-// four / eight bfloat16 values of one 8- / 16-byte load as floats (a bf16 is the upper half of an f32)
-__device__ __forceinline__ float4 bf16x4_f32(uint2 w) {
-    return make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                       __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
-}
 
 // DB: two LDS stages of TK keys; the next tile's K/V rows travel in registers while the current tile is multiplied and there
 // is ONE barrier per tile (the shape that took the attention backward from 460 to 299 us, attn_bwd.hip).
@@ -64,17 +56,9 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_f32_simple_kernel(const AttnS
     const long long unit = lb / a.nqb;
     const int qb = (int)(lb - unit * a.nqb);
     const int grp = (int)(unit / a.H), h = (int)(unit - (long long)grp * a.H);
-    long long q0, k0, q_rs, k_rs;
-    int Sq, Sk;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        q0 = __builtin_amdgcn_readfirstlane(qu.x); q_rs = __builtin_amdgcn_readfirstlane(qu.y); Sq = __builtin_amdgcn_readfirstlane(qu.z);
-        k0 = __builtin_amdgcn_readfirstlane(ku.x); k_rs = __builtin_amdgcn_readfirstlane(ku.y); Sk = __builtin_amdgcn_readfirstlane(ku.z);
-    } else {
-        q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        q_rs = a.q_rs; k_rs = a.k_rs; Sq = a.Sq; Sk = a.Sk;
-    }
+    const AttnUnit u = attn_unit<true>(a, grp);  // a block serves one unit
+    const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
+    const int Sq = u.Sq, Sk = u.Sk;
     if (qb * 64 >= Sq) return;  // ragged: fewer q-blocks than the largest unit (block-uniform)
     const int qi = qb * 64 + wave * 16 + c16;
     const bool q_ok = qi < Sq;
@@ -83,7 +67,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_f32_simple_kernel(const AttnS
         const unsigned short* qp = reinterpret_cast<const unsigned short*>(a.q) + (q0 + (long long)(q_ok ? qi : 0) * q_rs) * a.ldq + h * DH + 4 * g4;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const float4 v = bf16x4_f32(*reinterpret_cast<const uint2*>(qp + c * 16));
+            const float4 v = bf16x4_to_f32(*reinterpret_cast<const uint2*>(qp + c * 16));
             qf[c] = q_ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     } else {
@@ -142,8 +126,8 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_f32_simple_kernel(const AttnS
                 float* dst = &(which ? Vs : Ks)[r * LDK + cp * VPP];
                 if constexpr (IN16) {
                     const uint4 w = __builtin_bit_cast(uint4, st[j]);
-                    *reinterpret_cast<float4*>(dst) = bf16x4_f32(make_uint2(w.x, w.y));
-                    *reinterpret_cast<float4*>(dst + 4) = bf16x4_f32(make_uint2(w.z, w.w));
+                    *reinterpret_cast<float4*>(dst) = bf16x4_to_f32(make_uint2(w.x, w.y));
+                    *reinterpret_cast<float4*>(dst + 4) = bf16x4_to_f32(make_uint2(w.z, w.w));
                 } else {
                     *reinterpret_cast<float4*>(dst) = st[j];
                 }
@@ -247,13 +231,9 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_f32_simple_kernel(const AttnS
         if (a.lse && g4 == 0) a.lse[(q0 + (long long)qi * q_rs) * a.H + h] = m_run + logf(l_run);
     }
     float* op = a.o + (q0 + (long long)qi * q_rs) * a.ldo + h * DH;
-    if (!a.o_sp16) {
-        if (!(TR && a.o_skip_f32)) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-                *reinterpret_cast<float4*>(op + 4 * g4 + c * 16) = make_float4(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv);
-        }
-        if constexpr (TR) {
+    if constexpr (TR) {  // the f32 output may be skipped, and the out-projection's operand cast is written next to it
+        if (!a.o_sp16) {
+            if (!a.o_skip_f32) attn_store_tile<NC>(op, g4, oacc, inv, 0, nullptr);
             if (a.o_cast) {  // the out-projection's operand cast of the same values (uniform branch)
                 const long long eo = (q0 + (long long)qi * q_rs) * a.ldo + h * DH;  // element offset of this row's head slice
                 if (a.o_cast_fmt == 1) {
@@ -292,26 +272,10 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_f32_simple_kernel(const AttnS
                     }
                 }
             }
+            return;
         }
-        return;
     }
-    float m = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        half4v hi, lo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float v = oacc[c][j] * inv;
-            _Float16 h1, l1;
-            split_f16(v, h1, l1);
-            hi[j] = h1; lo[j] = l1;
-            m = fmaxf(m, fabsf(v));
-        }
-        char* dst = reinterpret_cast<char*>(op + c * 16 + 8 * (g4 >> 1)) + 8 * (g4 & 1);
-        *reinterpret_cast<half4v*>(dst) = hi;
-        *reinterpret_cast<half4v*>(dst + 16) = lo;
-    }
-    if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+    attn_store_tile<NC>(op, g4, oacc, inv, a.o_sp16, a.guard);
 }
 
 // ---- sequences of at most 4 steps (motion attention over T' = ceil(T/8): 4 at the headline shape) -----------------------
@@ -331,16 +295,9 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(const AttnSArgs a) 
     const bool live = unit < n_units;
     const long long uu = live ? unit : 0;
     const int grp = (int)(uu / a.H), h = (int)(uu - (long long)grp * a.H);
-    long long q0, k0, q_rs, k_rs;
-    int Sq, Sk;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        q0 = qu.x; q_rs = qu.y; Sq = qu.z; k0 = ku.x; k_rs = ku.y; Sk = ku.z;
-    } else {
-        q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        q_rs = a.q_rs; k_rs = a.k_rs; Sq = a.Sq; Sk = a.Sk;
-    }
+    const AttnUnit u = attn_unit<false>(a, grp);  // the two halves of a wave serve different units
+    const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
+    int Sq = u.Sq, Sk = u.Sk;
     if (!live) { Sq = 0; Sk = 0; }
     float4 qv[TT], kv[TT], vv[TT];
     // Rows past the unit's length: load a CLAMPED row and zero the VALUE.  `t < Sq ? *p : z` made the compiler select between the
@@ -411,7 +368,7 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(const AttnSArgs a) 
             // even lane: [my hi4 | partner's hi4] at block + 0;  odd lane: [partner's lo4 | my lo4] at block + 16
             const int4 piece = odd ? make_int4(rx, ry, lw2.x, lw2.y) : make_int4(hw2.x, hw2.y, rx, ry);
             *reinterpret_cast<int4*>(reinterpret_cast<char*>(op + 8 * (c >> 1)) + (odd ? 16 : 0)) = piece;
-            if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+            attn_range_guard(a.guard, m);
         }
     }
 }
@@ -424,21 +381,6 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(const AttnSArgs a) 
 // converted to (hi, lo) halfs while it is staged - K row-major, V TRANSPOSED ([d][key]) so that both MFMA A-fragments are
 // single 8-byte LDS reads - Q and P are split in registers, and a product costs 3 x 8 cycles instead of 4 x 32.  The halved
 // tile (38 KB for 32 keys) keeps four blocks per CU.  Same block decomposition, addressing and online softmax as above.
-__device__ __forceinline__ void split4h(const float4 v, half4v& hi, half4v& lo) {
-    const float in[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        _Float16 h1, l1;
-        split_f16(in[j], h1, l1);
-        hi[j] = h1; lo[j] = l1;
-    }
-}
-__device__ __forceinline__ f32x4 mfma3h(const half4v ah, const half4v al, const half4v bh, const half4v bl, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x16f16(al, bh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x16f16(ah, bl, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(ah, bh, c, 0, 0, 0);
-}
-
 template <int DH, int TK>
 __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs a) {
     constexpr int NC = DH / 16;
@@ -455,27 +397,19 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs
     const long long unit = blockIdx.x / a.nqb;
     const int qb = blockIdx.x - (int)unit * a.nqb;
     const int grp = (int)(unit / a.H), h = (int)(unit - (long long)grp * a.H);
-    long long q0, k0, q_rs, k_rs;
-    int Sq, Sk;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        q0 = __builtin_amdgcn_readfirstlane(qu.x); q_rs = __builtin_amdgcn_readfirstlane(qu.y); Sq = __builtin_amdgcn_readfirstlane(qu.z);
-        k0 = __builtin_amdgcn_readfirstlane(ku.x); k_rs = __builtin_amdgcn_readfirstlane(ku.y); Sk = __builtin_amdgcn_readfirstlane(ku.z);
-    } else {
-        q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        q_rs = a.q_rs; k_rs = a.k_rs; Sq = a.Sq; Sk = a.Sk;
-    }
+    const AttnUnit u = attn_unit<true>(a, grp);  // a block serves one unit
+    const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
+    const int Sq = u.Sq, Sk = u.Sk;
     if (qb * 64 >= Sq) return;
     const int qi = qb * 64 + wave * 16 + c16;
     const bool q_ok = qi < Sq;
-    half4v qh[NC], ql[NC];
+    HL4 qs[NC];
     {
         const float* qp = a.q + (q0 + (long long)qi * q_rs) * a.ldq + h * DH + 4 * g4;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const float4 v = q_ok ? *reinterpret_cast<const float4*>(qp + c * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-            split4h(v, qh[c], ql[c]);
+            qs[c] = split4(v.x, v.y, v.z, v.w);
         }
     }
     f32x4 oacc[NC];
@@ -494,15 +428,13 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs
                 kv = *reinterpret_cast<const float4*>(a.k + row * a.ldk + h * DH + c4 * 4);
                 vv = *reinterpret_cast<const float4*>(a.v + row * a.ldv + h * DH + c4 * 4);
             }
-            half4v hi, lo;
-            split4h(kv, hi, lo);
-            *reinterpret_cast<half4v*>(&Kh[r * LDK + c4 * 4]) = hi;
-            *reinterpret_cast<half4v*>(&Kl[r * LDK + c4 * 4]) = lo;
-            split4h(vv, hi, lo);
+            const HL4 ks = split4(kv.x, kv.y, kv.z, kv.w), vs = split4(vv.x, vv.y, vv.z, vv.w);
+            *reinterpret_cast<half4v*>(&Kh[r * LDK + c4 * 4]) = ks.hi;
+            *reinterpret_cast<half4v*>(&Kl[r * LDK + c4 * 4]) = ks.lo;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                Vh[(c4 * 4 + j) * LDT + r] = hi[j];
-                Vl[(c4 * 4 + j) * LDT + r] = lo[j];
+                Vh[(c4 * 4 + j) * LDT + r] = vs.hi[j];
+                Vl[(c4 * 4 + j) * LDT + r] = vs.lo[j];
             }
         }
         __syncthreads();
@@ -515,10 +447,9 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs
                 const int ko = (t * 16 + c16) * LDK + 4 * g4;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    const half4v kh = *reinterpret_cast<const half4v*>(&Kh[ko + c * 16]);
-                    const half4v kl = *reinterpret_cast<const half4v*>(&Kl[ko + c * 16]);
-                    if (c & 1) a1 = mfma3h(kh, kl, qh[c], ql[c], a1);
-                    else a0 = mfma3h(kh, kl, qh[c], ql[c], a0);
+                    const HL4 kf = {*reinterpret_cast<const half4v*>(&Kh[ko + c * 16]), *reinterpret_cast<const half4v*>(&Kl[ko + c * 16])};
+                    if (c & 1) a1 = mfma3(kf, qs[c], a1);
+                    else a0 = mfma3(kf, qs[c], a0);
                 }
                 const int key0 = kt0 + t * 16 + 4 * g4;
 #pragma unroll
@@ -551,39 +482,19 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs
 #pragma unroll
         for (int t = 0; t < TK / 16; ++t) {
             if (t < ntile) {
-                half4v ph, pl;
-                split4h(make_float4(sc[t][0], sc[t][1], sc[t][2], sc[t][3]), ph, pl);
+                const HL4 ps = split4(sc[t][0], sc[t][1], sc[t][2], sc[t][3]);
                 const int vo = c16 * LDT + t * 16 + 4 * g4;  // V^T row d = 16c + c16, keys 16t + 4*g4 .. +3
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    const half4v vh = *reinterpret_cast<const half4v*>(&Vh[vo + c * 16 * LDT]);
-                    const half4v vl = *reinterpret_cast<const half4v*>(&Vl[vo + c * 16 * LDT]);
-                    oacc[c] = mfma3h(vh, vl, ph, pl, oacc[c]);
+                    const HL4 vf = {*reinterpret_cast<const half4v*>(&Vh[vo + c * 16 * LDT]), *reinterpret_cast<const half4v*>(&Vl[vo + c * 16 * LDT])};
+                    oacc[c] = mfma3(vf, ps, oacc[c]);
                 }
             }
         }
     }
     if (!q_ok) return;
     const float inv = 1.f / l_run;
-    float* op = a.o + (q0 + (long long)qi * q_rs) * a.ldo + h * DH;
-    if (!a.o_sp16) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            *reinterpret_cast<float4*>(op + 4 * g4 + c * 16) = make_float4(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv);
-        return;
-    }
-    float m = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        half4v hi, lo;
-        const float4 v = make_float4(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv);
-        split4h(v, hi, lo);
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-        char* dst = reinterpret_cast<char*>(op + c * 16 + 8 * (g4 >> 1)) + 8 * (g4 & 1);
-        *reinterpret_cast<half4v*>(dst) = hi;
-        *reinterpret_cast<half4v*>(dst + 16) = lo;
-    }
-    if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+    attn_store_tile<NC>(a.o + (q0 + (long long)qi * q_rs) * a.ldo + h * DH, g4, oacc, inv, a.o_sp16, a.guard);
 }
 
 // ---- split-f16 q / k / v (written as split pairs by the projection GEMMs, GemmDesc::c_sp16), high-occupancy shape (round 3) -----
@@ -615,23 +526,15 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
     const long long unit = blockIdx.x / a.nqb;
     const int qb = blockIdx.x - (int)unit * a.nqb;
     const int grp = (int)(unit / a.H), h = (int)(unit - (long long)grp * a.H);
-    long long q0, k0, q_rs, k_rs;
-    int Sq, Sk;
-    if (a.q_units) {
-        const int4 qu = a.q_units[grp], ku = a.k_units[grp];
-        q0 = __builtin_amdgcn_readfirstlane(qu.x); q_rs = __builtin_amdgcn_readfirstlane(qu.y); Sq = __builtin_amdgcn_readfirstlane(qu.z);
-        k0 = __builtin_amdgcn_readfirstlane(ku.x); k_rs = __builtin_amdgcn_readfirstlane(ku.y); Sk = __builtin_amdgcn_readfirstlane(ku.z);
-    } else {
-        q0 = (long long)(grp / a.inner) * a.q_outer + (long long)(grp % a.inner) * a.q_inner;
-        k0 = (long long)(grp / a.inner) * a.k_outer + (long long)(grp % a.inner) * a.k_inner;
-        q_rs = a.q_rs; k_rs = a.k_rs; Sq = a.Sq; Sk = a.Sk;
-    }
+    const AttnUnit u = attn_unit<true>(a, grp);  // a block serves one unit
+    const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
+    const int Sq = u.Sq, Sk = u.Sk;
     if (qb * 64 >= Sq) return;
     const int qi = qb * 64 + wave * 16 + c16;
     const bool q_ok = qi < Sq;
     // byte offset, inside a split row, of the hi4 this lane's 4 head dims of chunk 0 (16c + 4*g4 .. +3); lo4 sits 16 bytes on
     const int frag = (g4 >> 1) * 32 + (g4 & 1) * 8;
-    half4v qh[NC], ql[NC];
+    HL4 qs[NC];
     {
         const char* qp = reinterpret_cast<const char*>(a.q + (q0 + (long long)(q_ok ? qi : 0) * q_rs) * a.ldq + h * DH) + frag;
 #pragma unroll
@@ -640,8 +543,8 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
             const half4v lv = *reinterpret_cast<const half4v*>(qp + c * 64 + 16);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                qh[c][j] = q_ok ? hv[j] : (_Float16)0.f;
-                ql[c][j] = q_ok ? lv[j] : (_Float16)0.f;
+                qs[c].hi[j] = q_ok ? hv[j] : (_Float16)0.f;
+                qs[c].lo[j] = q_ok ? lv[j] : (_Float16)0.f;
             }
         }
     }
@@ -705,10 +608,9 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
                 const char* kp = Ks + (t * 16 + c16) * RB + frag;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    const half4v kh = *reinterpret_cast<const half4v*>(kp + c * 64);
-                    const half4v kl = *reinterpret_cast<const half4v*>(kp + c * 64 + 16);
-                    if (c & 1) a1 = mfma3h(kh, kl, qh[c], ql[c], a1);
-                    else a0 = mfma3h(kh, kl, qh[c], ql[c], a0);
+                    const HL4 kf = {*reinterpret_cast<const half4v*>(kp + c * 64), *reinterpret_cast<const half4v*>(kp + c * 64 + 16)};
+                    if (c & 1) a1 = mfma3(kf, qs[c], a1);
+                    else a0 = mfma3(kf, qs[c], a0);
                 }
                 const int key0 = kt0 + t * 16 + 4 * g4;
 #pragma unroll
@@ -741,40 +643,21 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
 #pragma unroll
         for (int t = 0; t < TK / 16; ++t) {
             if (t < ntile) {
-                half4v ph, pl;
-                split4h(make_float4(sc[t][0], sc[t][1], sc[t][2], sc[t][3]), ph, pl);
+                const HL4 ps = split4(sc[t][0], sc[t][1], sc[t][2], sc[t][3]);
                 const char* vp = Vs + t * 16 * RB + vfrag;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
                     typedef __attribute__((address_space(3))) short4v lds_s4;
                     const short4v vh4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(vp + c * 64));
                     const short4v vl4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(vp + c * 64 + 16));
-                    oacc[c] = mfma3h(__builtin_bit_cast(half4v, vh4), __builtin_bit_cast(half4v, vl4), ph, pl, oacc[c]);
+                    oacc[c] = mfma3(HL4{__builtin_bit_cast(half4v, vh4), __builtin_bit_cast(half4v, vl4)}, ps, oacc[c]);
                 }
             }
         }
     }
     if (!q_ok) return;
     const float inv = 1.f / l_run;
-    float* op = a.o + (q0 + (long long)qi * q_rs) * a.ldo + h * DH;
-    if (!a.o_sp16) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            *reinterpret_cast<float4*>(op + 4 * g4 + c * 16) = make_float4(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv);
-        return;
-    }
-    float m = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        half4v hi, lo;
-        const float4 v = make_float4(oacc[c][0] * inv, oacc[c][1] * inv, oacc[c][2] * inv, oacc[c][3] * inv);
-        split4h(v, hi, lo);
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-        char* dst = reinterpret_cast<char*>(op + c * 16 + 8 * (g4 >> 1)) + 8 * (g4 & 1);
-        *reinterpret_cast<half4v*>(dst) = hi;
-        *reinterpret_cast<half4v*>(dst + 16) = lo;
-    }
-    if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+    attn_store_tile<NC>(a.o + (q0 + (long long)qi * q_rs) * a.ldo + h * DH, g4, oacc, inv, a.o_sp16, a.guard);
 }
 
 }  // namespace: sola_tune switches are extern (tune.h)
@@ -785,7 +668,7 @@ int launch_spin(const AttnSArgs& a0, hipStream_t s) {
     constexpr int TK = 32;
     a.nqb = (a.Sq + 63) / 64;
     const long long blocks = (long long)a.G * a.H * a.nqb;
-    SOLA_ARG(blocks < (1ll << 31), "attention: grid too large");
+    SOLA_TRY(attn_grid_ok(blocks, "attention"));
     if (g_attn_spin_db) {  // two stages of 16 keys (the same 35.8 KB), next tile prefetched in registers
         hipLaunchKernelGGL((attn_fwd_spin_kernel<16, true>), dim3((unsigned)blocks), dim3(256), (size_t)2 * 2 * 16 * 560, s, a);
         SOLA_LAUNCH_CHECK();
@@ -802,7 +685,7 @@ int launch_splitm(const AttnSArgs& a0, hipStream_t s) {
     constexpr int DH = 128, TK = 32;
     a.nqb = (a.Sq + 63) / 64;
     const long long blocks = (long long)a.G * a.H * a.nqb;
-    SOLA_ARG(blocks < (1ll << 31), "attention: grid too large");
+    SOLA_TRY(attn_grid_ok(blocks, "attention"));
     const size_t lds = ((size_t)2 * TK * (DH + 8) + (size_t)2 * DH * (TK + 8)) * sizeof(_Float16);
     hipLaunchKernelGGL((attn_fwd_splitm_kernel<DH, TK>), dim3((unsigned)blocks), dim3(256), lds, s, a);
     SOLA_LAUNCH_CHECK();
@@ -820,28 +703,19 @@ int launch_s(const AttnSArgs& a0, hipStream_t s) {
     constexpr int TK = 32;
     a.nqb = (a.Sq + 63) / 64;
     const long long blocks = (long long)a.G * a.H * a.nqb;
-    SOLA_ARG(blocks < (1ll << 31), "attention: grid too large");
+    SOLA_TRY(attn_grid_ok(blocks, "attention"));
     a.xcd_remap = (g_attn_simple_remap && blocks % 8 == 0) ? 1 : 0;
-    if (a.in_bf16) {  // training forward on bf16 q / k / v
-        const size_t lds2 = (size_t)2 * 2 * 16 * (DH + 4) * sizeof(float);
-        hipLaunchKernelGGL((attn_fwd_f32_simple_kernel<DH, 16, true, true, true>), dim3((unsigned)blocks), dim3(256), lds2, s, a);
-        SOLA_LAUNCH_CHECK();
-        return SOLA_OK;
-    }
-    if (a.lse || a.drop.enabled) {  // training forward
-        const size_t lds2 = (size_t)2 * 2 * 16 * (DH + 4) * sizeof(float);
-        hipLaunchKernelGGL((attn_fwd_f32_simple_kernel<DH, 16, true, true>), dim3((unsigned)blocks), dim3(256), lds2, s, a);
-        SOLA_LAUNCH_CHECK();
-        return SOLA_OK;
-    }
-    if (g_attn_simple_db) {  // two stages of 16 keys: the same LDS footprint (34 KB), next tile prefetched in registers
-        const size_t lds2 = (size_t)2 * 2 * 16 * (DH + 4) * sizeof(float);
-        hipLaunchKernelGGL((attn_fwd_f32_simple_kernel<DH, 16, true>), dim3((unsigned)blocks), dim3(256), lds2, s, a);
-        SOLA_LAUNCH_CHECK();
-        return SOLA_OK;
-    }
-    const size_t lds = (size_t)2 * TK * (DH + 4) * sizeof(float);
-    hipLaunchKernelGGL((attn_fwd_f32_simple_kernel<DH, TK>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+    // two stages of 16 keys: the LDS footprint of one 32-key stage (34 KB), the next tile prefetched in registers
+    const size_t lds_db = (size_t)2 * 2 * 16 * (DH + 4) * sizeof(float);
+    const dim3 grid((unsigned)blocks), block(256);
+    if (a.in_bf16)  // training forward on bf16 q / k / v
+        hipLaunchKernelGGL((attn_fwd_f32_simple_kernel<DH, 16, true, true, true>), grid, block, lds_db, s, a);
+    else if (a.lse || a.drop.enabled)  // training forward
+        hipLaunchKernelGGL((attn_fwd_f32_simple_kernel<DH, 16, true, true>), grid, block, lds_db, s, a);
+    else if (g_attn_simple_db)
+        hipLaunchKernelGGL((attn_fwd_f32_simple_kernel<DH, 16, true>), grid, block, lds_db, s, a);
+    else
+        hipLaunchKernelGGL((attn_fwd_f32_simple_kernel<DH, TK>), grid, block, (size_t)2 * TK * (DH + 4) * sizeof(float), s, a);
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
 }
@@ -857,13 +731,8 @@ bool attention_small_supported(const AttnDesc& d) {
 static AttnSArgs make_sargs(const AttnDesc& d) {
     AttnSArgs a;
     a.q = d.q; a.k = d.k; a.v = d.v; a.o = d.o;
-    a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
-    a.G = d.G; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk; a.inner = d.inner; a.nqb = 1;
-    a.q_outer = d.q_outer; a.q_inner = d.q_inner; a.q_rs = d.q_rs;
-    a.k_outer = d.k_outer; a.k_inner = d.k_inner; a.k_rs = d.k_rs;
-    a.scale = d.scale; a.o_sp16 = d.o_sp16; a.guard = d.o_sp16 ? d.guard : nullptr;
-    a.q_units = d.q_units; a.k_units = d.q_units ? (d.k_units ? d.k_units : d.q_units) : nullptr;
-    a.xcd_remap = 0;
+    attn_fill_common(a, d);
+    a.nqb = 1; a.xcd_remap = 0;
     a.lse = d.lse;
     a.drop = d.drop;
     a.o_cast = nullptr; a.o_side = nullptr; a.o_cast_fmt = 0;  // launch_attention_simple's training instantiation takes them
@@ -873,8 +742,7 @@ static AttnSArgs make_sargs(const AttnDesc& d) {
 
 int launch_attention_small(const AttnDesc& d, hipStream_t s) {
     const AttnSArgs a = make_sargs(d);
-    const double elems = (double)d.G * d.H * d.DH;
-    SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, 4.0 * elems * (2.0 * d.Sq + 2.0 * d.Sk));
+    const SolaProfScope prof = attn_prof_scope(d, s);
     const long long units = (long long)d.G * d.H;
     const unsigned blocks = (unsigned)((units + 7) / 8);
     const int need = d.Sq > d.Sk ? d.Sq : d.Sk;
@@ -909,8 +777,7 @@ int launch_attention_simple(const AttnDesc& d, hipStream_t s) {
         a.o_skip_f32 = d.o == nullptr;
         SOLA_ARG(d.o || a.o_cast, "attention: no output");
     }
-    const double elems = (double)d.G * d.H * d.DH;
-    SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, 4.0 * elems * (2.0 * d.Sq + 2.0 * d.Sk));
+    const SolaProfScope prof = attn_prof_scope(d, s);
     return d.DH == 128 ? launch_s<128>(a, s) : launch_s<64>(a, s);
 }
 
@@ -925,8 +792,7 @@ bool attention_spin_supported(const AttnDesc& d) {
 }
 int launch_attention_spin(const AttnDesc& d, hipStream_t s) {
     const AttnSArgs a = make_sargs(d);
-    const double elems = (double)d.G * d.H * d.DH;
-    SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, 4.0 * elems * (2.0 * d.Sq + 2.0 * d.Sk));
+    const SolaProfScope prof = attn_prof_scope(d, s);
     return launch_spin(a, s);
 }
 
@@ -936,7 +802,6 @@ bool attention_splitm_supported(const AttnDesc& d) {
 }
 int launch_attention_splitm(const AttnDesc& d, hipStream_t s) {
     const AttnSArgs a = make_sargs(d);
-    const double elems = (double)d.G * d.H * d.DH;
-    SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, 4.0 * elems * (2.0 * d.Sq + 2.0 * d.Sk));
+    const SolaProfScope prof = attn_prof_scope(d, s);
     return launch_splitm(a, s);
 }

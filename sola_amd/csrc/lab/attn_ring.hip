@@ -27,13 +27,12 @@
 // softmax per 16-key tile): the outputs are bit-identical to that kernel's.
 #include <type_traits>
 
-#include "../kernels.h"
+#include "../attn_common.h"
 
 #ifdef SOLA_EXPERIMENTS
 namespace {
 
 typedef __attribute__((address_space(3))) void* lptr_t;
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4s __attribute__((ext_vector_type(4)));
 
@@ -85,7 +84,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_ring_kernel(const AttnRAr
         it.grp = unit / a.H;
         it.h = unit - it.grp * a.H;
         if (a.q_units) {
-            // scalar loads by hand: a compiler-visible vector load would be waited for with vmcnt(0) - the whole ring drained per item
+            // attn_unit's table read as scalar loads by hand: a compiler-visible vector load would be waited for with vmcnt(0) - the whole
+            // ring drained per item
             i32x4s qu, ku;
             asm volatile("s_load_dwordx4 %0, %2, 0x0\n\ts_load_dwordx4 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
                          : "=&s"(qu), "=&s"(ku)
@@ -94,9 +94,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_ring_kernel(const AttnRAr
             it.q0 = qu[0]; it.q_rs = qu[1]; it.Sq = qu[2];
             it.k0 = ku[0]; it.k_rs = ku[1]; it.Sk = ku[2];
         } else {
-            it.q0 = (long long)(it.grp / a.inner) * a.q_outer + (long long)(it.grp % a.inner) * a.q_inner;
-            it.k0 = (long long)(it.grp / a.inner) * a.k_outer + (long long)(it.grp % a.inner) * a.k_inner;
-            it.q_rs = (int)a.q_rs; it.k_rs = (int)a.k_rs; it.Sq = a.Sq; it.Sk = a.Sk;
+            const AttnUnit u = attn_unit_strided(a, it.grp);
+            it.q0 = u.q0; it.k0 = u.k0; it.q_rs = (int)u.q_rs; it.k_rs = (int)u.k_rs; it.Sq = u.Sq; it.Sk = u.Sk;
         }
         return it.qb * 64 < it.Sq;  // ragged: fewer q-blocks than the largest unit
     };
@@ -310,6 +309,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_ring_kernel(const AttnRAr
         const int qi = cur.qb * 64 + wave * 16 + c16;
         if (cur.qb * 64 + wave * 16 < cur.Sq) {  // wave-uniform: the stores are issued (and counted) or not
             if (qi < cur.Sq) {
+                // attn_store_tile (attn_common.h) written out: as a call it moves the register allocation of the whole kernel (vgpr 163 -> 165 in
+                // the no-DMA ablation), and this instrument stays the kernel profiles/r05_attention_ring.txt timed (profiles/attn_common_isa.txt)
                 const float inv = 1.f / l_run;
                 float* op = a.o + (cur.q0 + (long long)qi * cur.q_rs) * a.ldo + cur.h * RDH;
                 if (!a.o_sp16) {
@@ -333,7 +334,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_ring_kernel(const AttnRAr
                         *reinterpret_cast<half4v*>(dst) = h4;
                         *reinterpret_cast<half4v*>(dst + 16) = l4;
                     }
-                    if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+                    attn_range_guard(a.guard, m);
                 }
             }
             issued += a.o_sp16 ? 16 : 8;
@@ -384,18 +385,12 @@ bool attention_ring_supported(const AttnDesc& d) {
 int launch_attention_ring(const AttnDesc& d, hipStream_t s) {
     AttnRArgs a;
     a.q = d.q; a.k = d.k; a.v = d.v; a.o = d.o;
-    a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
-    a.G = d.G; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk; a.inner = d.inner;
+    attn_fill_common(a, d);
     a.nqb = (d.Sq + 63) / 64;
-    a.q_outer = d.q_outer; a.q_inner = d.q_inner; a.q_rs = d.q_rs;
-    a.k_outer = d.k_outer; a.k_inner = d.k_inner; a.k_rs = d.k_rs;
-    a.scale = d.scale; a.o_sp16 = d.o_sp16; a.guard = d.o_sp16 ? d.guard : nullptr;
-    a.q_units = d.q_units; a.k_units = d.q_units ? (d.k_units ? d.k_units : d.q_units) : nullptr;
     const long long items = (long long)d.G * d.H * a.nqb;
-    SOLA_ARG(items < (1ll << 31), "attention: grid too large");
+    SOLA_TRY(attn_grid_ok(items, "attention"));
     a.n_items = (int)items;
-    const double elems = (double)d.G * d.H * d.DH;
-    SolaProfScope prof(SOLA_PROF_ATTN, s, 4.0 * elems * d.Sq * d.Sk, 4.0 * elems * (2.0 * d.Sq + 2.0 * d.Sk));
+    const SolaProfScope prof = attn_prof_scope(d, s);
     const long long want = (long long)g_attn_ring_blocks * sola_cu_count();
     const int grid = (int)std::min(want, items);
     a.xcd_remap = (grid % 8 == 0 && g_attn_ring_remap) ? 1 : 0;
