@@ -686,6 +686,34 @@ int sola_index_hist(const uint8_t* dev_idx, int T, int h, int w, int64_t* dev_co
 int sola_index_pack(const uint8_t* dev_idx, int T, int h, int w, const int32_t* dev_ids, int K, const int32_t* dev_first_plane,
                     int layout, int64_t words_stride, uint32_t* dev_bits, int64_t* dev_area, void* stream);
 
+/* ---- multi-scale deformable attention, forward (Deformable-DETR; GroundingDINO's one custom operator,
+ * groundingdino._C.ms_deform_attn_forward; Mask2Former's pixel decoder).  Upstream details are from its public source. -------
+ * All float32, contiguous:
+ *   dev_value [N,S,M,D]: batch, S = sum_l H_l*W_l rows in level order, heads, channels per head;
+ *   dev_spatial_shapes int64 [L,2] = (H_l, W_l) and dev_level_start int64 [L], both ON THE DEVICE (never read by the host);
+ *   dev_sampling_loc [N,Lq,M,L,P,2], normalised, last axis (x, y);  dev_attn_weight [N,Lq,M,L,P];  dev_out [N,Lq,M*D].
+ * For query q, head m, level l, point p: x = fma(loc_x, W_l, -0.5), y = fma(loc_y, H_l, -0.5) (one rounding each); x0 = floor(x),
+ * y0 = floor(y), lx = x - x0, ly = y - y0; the corners (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1) carry (1-ly)(1-lx),
+ * (1-ly)lx, ly(1-lx), ly*lx; a corner outside [0,H_l) x [0,W_l) contributes nothing, one inside reads row
+ * level_start[l] + yy*W_l + xx of value[n,:,m,:];  out[n,q,m*D:(m+1)*D] = sum_{l,p} attn_weight[n,q,m,l,p] * bilinear sample,
+ * summed in float32 in the fixed order (l, p, corner), every step a fused multiply-add.  This is F.grid_sample(level map,
+ * 2*loc - 1, "bilinear", "zeros", align_corners=False) per level, weighted and summed.
+ * The table is not trusted: a corner whose row is not in [0,S) contributes nothing; so does a level with H_l or W_l outside
+ * 1 .. 2^30 or a start outside (-2^62, S) (sides float32 cannot address to a pixel; starts from which no 64-bit row sum overflows).  No
+ * table and no location, NaN and infinities included, makes the kernel read outside dev_value or write outside dev_out (rows
+ * are fetched through a range-checked buffer descriptor of one batch element; what a non-finite location contributes is
+ * unspecified).  One launch, no atomics, no workspace, no memset: every output element is written by exactly one thread, the
+ * bits are the same from run to run and on any stream.  Asynchronous on the stream.
+ * Refused before any launch: N, S, M or Lq < 1; D other than 16, 32, 64; L outside 1 .. SOLA_MSDA_MAX_LEVELS; P outside
+ * 1 .. SOLA_MSDA_MAX_POINTS; null arguments; S*M*D*4 >= 2^31 bytes (32-bit row offsets), or N*S*M*D, N*Lq*M*L*P*2 or
+ * N*Lq*M*D >= 2^31 elements; value, sampling_loc or out not 16-byte aligned (attn_weight: 4 bytes, and 16 for the P = 4
+ * fast path - otherwise the any-P kernel runs, same bits; tables: 8).  Forward only: no backward exists. */
+#define SOLA_MSDA_MAX_LEVELS 8
+#define SOLA_MSDA_MAX_POINTS 8
+int sola_ms_deform_attn(const float* dev_value, const int64_t* dev_spatial_shapes, const int64_t* dev_level_start,
+                        const float* dev_sampling_loc, const float* dev_attn_weight, int N, int S, int M, int D, int Lq, int L, int P,
+                        float* dev_out, void* stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream; used by bench.py's roofline object) ------------ */
 enum { SOLA_PROF_GEMM = 0,      /* gemm_nt_f32_kernel<128,128> */
        SOLA_PROF_ATTN = 1,      /* attn_fwd_f32_kernel */

@@ -1192,6 +1192,11 @@ extern "C" int sola_mask_fill_small_profile(const void* in, int elem_type, int n
                                   as_stream(stream_), launch_us);
 }
 
+extern "C" int sola_ms_deform_attn(const float* value, const int64_t* spatial_shapes, const int64_t* level_start, const float* sampling_loc,
+                                   const float* attn_weight, int N, int S, int M, int D, int Lq, int L, int P, float* out, void* stream_) {
+    return launch_ms_deform_attn(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, Lq, L, P, out, as_stream(stream_));
+}
+
 // Host helper (no GPU work): COCO compressed run-length string -> inclusive prefix sums of the run lengths, the form
 // sola_rle_fill_or consumes.  pycocotools rleFrString: 5 data bits + continuation bit per char (offset 48), sign
 // extension from bit 4 of the last char, runs from the 4th on stored as a delta to the run two places back.

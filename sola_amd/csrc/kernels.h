@@ -504,3 +504,7 @@ int launch_mask_fill_small(const void* in, int elem_type, int n, int h, int w, i
                            void* out, void* scratch, size_t scratch_bytes, hipStream_t s, float* launch_us);
 
 // ---- index maps -> bit planes (index_planes.hip): sola_index_hist / sola_index_pack are the whole interface (sola_hip.h) ----
+
+// ---- multi-scale deformable attention, forward (msda.hip): every argument check of sola_ms_deform_attn is in the launcher ----
+int launch_ms_deform_attn(const float* value, const int64_t* shapes, const int64_t* start, const float* loc, const float* weight, int N,
+                          int S, int M, int D, int Lq, int L, int P, float* out, hipStream_t s);

@@ -302,3 +302,66 @@ def select(score_map, threshold=0.5):
     pred = torch.empty_like(s)
     check(lib().sola_select(ptr(s), s.numel(), threshold, ptr(prob), ptr(pred), current_stream(s.device)), "sola_select")
     return prob, pred
+
+
+MSDA_HEAD_DIMS = (16, 32, 64)  # channels per head of sola_ms_deform_attn
+MSDA_MAX_LEVELS = 8            # SOLA_MSDA_MAX_LEVELS
+MSDA_MAX_POINTS = 8            # SOLA_MSDA_MAX_POINTS
+
+
+def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations, attention_weights):
+    """Multi-scale deformable attention, forward (sola_ms_deform_attn in the header has the contract): value [N,S,M,D],
+    spatial_shapes int64 [L,2] = (H_l, W_l), level_start_index int64 [L], sampling_locations [N,Lq,M,L,P,2] normalised (x, y),
+    attention_weights [N,Lq,M,L,P] -> [N,Lq,M*D].  float32 only; the level tables stay on the device (never copied to the
+    host, so S is not compared with them: a row outside value contributes nothing).  Inference only."""
+    v, loc, w, shp, lsi = value, sampling_locations, attention_weights, spatial_shapes, level_start_index
+    for name, t in (("value", v), ("sampling_locations", loc), ("attention_weights", w)):
+        if t.dtype in (torch.float16, torch.bfloat16):
+            raise _lib.SolaError(f"ms_deform_attn: {name} is {t.dtype}; the operator is float32 only (GroundingDINO itself casts with "
+                                 ".float() before the call)")
+        if t.dtype != torch.float32:
+            raise _lib.SolaError(f"ms_deform_attn: {name} must be float32, got {t.dtype}")
+    if v.dim() != 4 or loc.dim() != 6 or w.dim() != 5 or loc.shape[-1] != 2:
+        raise _lib.SolaError(f"ms_deform_attn: expected value [N,S,M,D], sampling_locations [N,Lq,M,L,P,2], attention_weights "
+                             f"[N,Lq,M,L,P], got {tuple(v.shape)}, {tuple(loc.shape)}, {tuple(w.shape)}")
+    N, S, M, D = v.shape
+    Lq, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
+    if tuple(loc.shape) != (N, Lq, M, L, P, 2) or tuple(w.shape) != (N, Lq, M, L, P):
+        raise _lib.SolaError(f"ms_deform_attn: shapes disagree: value {tuple(v.shape)} = [N,S,M,D], sampling_locations "
+                             f"{tuple(loc.shape)} = [N,Lq,M,L,P,2], attention_weights {tuple(w.shape)} = [N,Lq,M,L,P]")
+    for name, t, shape in (("spatial_shapes", shp, (L, 2)), ("level_start_index", lsi, (L,))):
+        if t.dtype != torch.int64 or tuple(t.shape) != shape:
+            raise _lib.SolaError(f"ms_deform_attn: {name} must be int64 {list(shape)} (L = {L} levels in sampling_locations), got "
+                                 f"{t.dtype} {list(t.shape)}")
+    if D not in MSDA_HEAD_DIMS:
+        raise _lib.SolaError(f"ms_deform_attn: D = {D} channels per head, supported are {MSDA_HEAD_DIMS}")
+    if not 1 <= L <= MSDA_MAX_LEVELS:
+        raise _lib.SolaError(f"ms_deform_attn: L = {L} levels, supported are 1 to {MSDA_MAX_LEVELS}")
+    if not 1 <= P <= MSDA_MAX_POINTS:
+        raise _lib.SolaError(f"ms_deform_attn: P = {P} points, supported are 1 to {MSDA_MAX_POINTS}")
+    if min(N, S, M, Lq) < 1:
+        raise _lib.SolaError(f"ms_deform_attn: N {N}, S {S}, M {M}, Lq {Lq} must all be >= 1")
+    require_cuda(v, shp, lsi, loc, w)
+    v, loc, w, shp, lsi = v.contiguous(), loc.contiguous(), w.contiguous(), shp.contiguous(), lsi.contiguous()
+    out = torch.empty((N, Lq, M * D), device=v.device, dtype=torch.float32)
+    check(lib().sola_ms_deform_attn(ptr(v), ptr(shp), ptr(lsi), ptr(loc), ptr(w), N, S, M, D, Lq, L, P, ptr(out),
+                                    current_stream(v.device)), "sola_ms_deform_attn")
+    return out
+
+
+class _GdinoExt:
+    """Stand-in for GroundingDINO's CUDA extension module ``groundingdino._C`` (the two names ms_deform_attn.py calls;
+    INTEGRATION.md 2 shows where it is bound)."""
+
+    @staticmethod
+    def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step):
+        """``im2col_step`` (the extension's batch tile) is accepted and ignored: the kernel takes any N."""
+        return ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations, attention_weights)
+
+    @staticmethod
+    def ms_deform_attn_backward(*args, **kwargs):
+        raise _lib.SolaError("ms_deform_attn_backward: inference only (sola_ms_deform_attn has no backward; run the model under "
+                             "torch.no_grad())")
+
+
+gdino_ext = _GdinoExt()
