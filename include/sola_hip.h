@@ -707,12 +707,38 @@ int sola_index_pack(const uint8_t* dev_idx, int T, int h, int w, const int32_t* 
  * Refused before any launch: N, S, M or Lq < 1; D other than 16, 32, 64; L outside 1 .. SOLA_MSDA_MAX_LEVELS; P outside
  * 1 .. SOLA_MSDA_MAX_POINTS; null arguments; S*M*D*4 >= 2^31 bytes (32-bit row offsets), or N*S*M*D, N*Lq*M*L*P*2 or
  * N*Lq*M*D >= 2^31 elements; value, sampling_loc or out not 16-byte aligned (attn_weight: 4 bytes, and 16 for the P = 4
- * fast path - otherwise the any-P kernel runs, same bits; tables: 8).  Forward only: no backward exists. */
+ * fast path - otherwise the any-P kernel runs, same bits; tables: 8).  The backward is sola_ms_deform_attn_backward below. */
 #define SOLA_MSDA_MAX_LEVELS 8
 #define SOLA_MSDA_MAX_POINTS 8
 int sola_ms_deform_attn(const float* dev_value, const int64_t* dev_spatial_shapes, const int64_t* dev_level_start,
                         const float* dev_sampling_loc, const float* dev_attn_weight, int N, int S, int M, int D, int Lq, int L, int P,
                         float* dev_out, void* stream);
+
+/* ---- multi-scale deformable attention, backward: the three gradients of sola_ms_deform_attn for dev_grad_out [N,Lq,M*D] (float32,
+ * contiguous); the other inputs, their layout and the notation are the forward's.  With c_k the coefficient of corner k, v_k its row
+ * of value[n,:,m,:] (zeros where the corner does not count), w = attn_weight[n,q,m,l,p] and g = grad_out[n,q,m*D:(m+1)*D]:
+ *   dev_grad_weight [N,Lq,M,L,P]   = sum_d g_d * sum_k c_k v_k[d];
+ *   dev_grad_loc    [N,Lq,M,L,P,2] = (W_l * w * sum_d g_d * ((1-ly)(v_01 - v_00) + ly (v_11 - v_10)),
+ *                                     H_l * w * sum_d g_d * ((1-lx)(v_10 - v_00) + lx (v_11 - v_01)));
+ *   dev_grad_value  [N,S,M,D]:       row_k of (n, m) receives w * c_k * g for every corner that counts.
+ * This is the derivative on the cell [x0, x0+1) x [y0, y0+1), the one F.grid_sample's backward takes.
+ * Each of the three outputs may be null: it is then not wanted and not computed; at least one must be given.  Every element of
+ * every requested output is written by the call: dev_grad_value is zeroed by the entry point itself on the stream (the caller
+ * need not), the entries of a level that does not count are written as zeros.
+ * The table is distrusted exactly as in the forward: a corner that does not count issues no add and reads as zero, and no table and
+ * no location, NaN and infinities included, makes the kernel read outside dev_value or write outside the three outputs.
+ * dev_grad_loc and dev_grad_weight: one unit of D lanes owns each element, sums the channels in a fixed order and stores it
+ * once - the bits are the same from run to run, on any stream, and with or without the other outputs.
+ * dev_grad_value is a scatter accumulated with float32 atomic adds in the order the hardware delivers them: its last bits are
+ * NOT repeatable from run to run (the only output of this library that is not; no ordered variant exists).  It must be ordinary
+ * device memory (hipMalloc, what torch allocates): float atomics into host-coherent (fine-grained) memory are not supported.
+ * One memset and one launch, no workspace.  Asynchronous on the stream.
+ * Refused before any launch: everything the forward refuses (dev_grad_out in the place of dev_out, except that it needs 4-byte
+ * alignment only), all three outputs null, dev_grad_value or dev_grad_weight not 4-byte aligned, dev_grad_loc not 8-byte. */
+int sola_ms_deform_attn_backward(const float* dev_value, const int64_t* dev_spatial_shapes, const int64_t* dev_level_start,
+                                 const float* dev_sampling_loc, const float* dev_attn_weight, const float* dev_grad_out,
+                                 int N, int S, int M, int D, int Lq, int L, int P,
+                                 float* dev_grad_value, float* dev_grad_loc, float* dev_grad_weight, void* stream);
 
 /* ---- in-library kernel timing (HIP events on the launch stream; used by bench.py's roofline object) ------------ */
 enum { SOLA_PROF_GEMM = 0,      /* gemm_nt_f32_kernel<128,128> */

@@ -153,6 +153,7 @@ SIGNATURES = {
     "sola_index_hist": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "sola_index_pack": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp]),
     "sola_ms_deform_attn": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sola_ms_deform_attn_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sola_mask_iou_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "sola_mask_iou_matrix": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sola_grad_sqnorms_scratch_bytes": (_sz, [_i, _vp]),

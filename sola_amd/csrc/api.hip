@@ -1197,6 +1197,13 @@ extern "C" int sola_ms_deform_attn(const float* value, const int64_t* spatial_sh
     return launch_ms_deform_attn(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, Lq, L, P, out, as_stream(stream_));
 }
 
+extern "C" int sola_ms_deform_attn_backward(const float* value, const int64_t* spatial_shapes, const int64_t* level_start,
+                                            const float* sampling_loc, const float* attn_weight, const float* grad_out, int N, int S, int M, int D,
+                                            int Lq, int L, int P, float* grad_value, float* grad_loc, float* grad_weight, void* stream_) {
+    return launch_ms_deform_attn_backward(value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_out, N, S, M, D, Lq, L, P, grad_value,
+                                          grad_loc, grad_weight, as_stream(stream_));
+}
+
 // Host helper (no GPU work): COCO compressed run-length string -> inclusive prefix sums of the run lengths, the form
 // sola_rle_fill_or consumes.  pycocotools rleFrString: 5 data bits + continuation bit per char (offset 48), sign
 // extension from bit 4 of the last char, runs from the 4th on stored as a delta to the run two places back.

@@ -505,6 +505,10 @@ int launch_mask_fill_small(const void* in, int elem_type, int n, int h, int w, i
 
 // ---- index maps -> bit planes (index_planes.hip): sola_index_hist / sola_index_pack are the whole interface (sola_hip.h) ----
 
-// ---- multi-scale deformable attention, forward (msda.hip): every argument check of sola_ms_deform_attn is in the launcher ----
+// ---- multi-scale deformable attention, forward and backward (msda.hip): every argument check of sola_ms_deform_attn and of
+// sola_ms_deform_attn_backward is in the launcher; the backward's launcher zeroes grad_value on the stream ----
 int launch_ms_deform_attn(const float* value, const int64_t* shapes, const int64_t* start, const float* loc, const float* weight, int N,
                           int S, int M, int D, int Lq, int L, int P, float* out, hipStream_t s);
+int launch_ms_deform_attn_backward(const float* value, const int64_t* shapes, const int64_t* start, const float* loc, const float* weight,
+                                   const float* grad_out, int N, int S, int M, int D, int Lq, int L, int P, float* grad_value, float* grad_loc,
+                                   float* grad_weight, hipStream_t s);

@@ -6,6 +6,7 @@ convention of the library (include/sola_hip.h).  No CPU path exists: CPU tensors
 from __future__ import annotations
 
 import math
+import warnings
 
 import torch
 
@@ -309,49 +310,117 @@ MSDA_MAX_LEVELS = 8            # SOLA_MSDA_MAX_LEVELS
 MSDA_MAX_POINTS = 8            # SOLA_MSDA_MAX_POINTS
 
 
-def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations, attention_weights):
-    """Multi-scale deformable attention, forward (sola_ms_deform_attn in the header has the contract): value [N,S,M,D],
-    spatial_shapes int64 [L,2] = (H_l, W_l), level_start_index int64 [L], sampling_locations [N,Lq,M,L,P,2] normalised (x, y),
-    attention_weights [N,Lq,M,L,P] -> [N,Lq,M*D].  float32 only; the level tables stay on the device (never copied to the
-    host, so S is not compared with them: a row outside value contributes nothing).  Inference only."""
-    v, loc, w, shp, lsi = value, sampling_locations, attention_weights, spatial_shapes, level_start_index
-    for name, t in (("value", v), ("sampling_locations", loc), ("attention_weights", w)):
+def _msda_checked(who, value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output=None):
+    """The argument checks ms_deform_attn and ms_deform_attn_backward share (``who`` names the caller in the texts): returns the
+    contiguous tensors (value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output) and
+    (N, S, M, D, Lq, L, P)."""
+    v, loc, w, shp, lsi, go = value, sampling_locations, attention_weights, spatial_shapes, level_start_index, grad_output
+    for name, t in (("value", v), ("sampling_locations", loc), ("attention_weights", w), ("grad_output", go)):
+        if t is None:
+            continue
         if t.dtype in (torch.float16, torch.bfloat16):
-            raise _lib.SolaError(f"ms_deform_attn: {name} is {t.dtype}; the operator is float32 only (GroundingDINO itself casts with "
+            raise _lib.SolaError(f"{who}: {name} is {t.dtype}; the operator is float32 only (GroundingDINO itself casts with "
                                  ".float() before the call)")
         if t.dtype != torch.float32:
-            raise _lib.SolaError(f"ms_deform_attn: {name} must be float32, got {t.dtype}")
+            raise _lib.SolaError(f"{who}: {name} must be float32, got {t.dtype}")
     if v.dim() != 4 or loc.dim() != 6 or w.dim() != 5 or loc.shape[-1] != 2:
-        raise _lib.SolaError(f"ms_deform_attn: expected value [N,S,M,D], sampling_locations [N,Lq,M,L,P,2], attention_weights "
+        raise _lib.SolaError(f"{who}: expected value [N,S,M,D], sampling_locations [N,Lq,M,L,P,2], attention_weights "
                              f"[N,Lq,M,L,P], got {tuple(v.shape)}, {tuple(loc.shape)}, {tuple(w.shape)}")
     N, S, M, D = v.shape
     Lq, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
     if tuple(loc.shape) != (N, Lq, M, L, P, 2) or tuple(w.shape) != (N, Lq, M, L, P):
-        raise _lib.SolaError(f"ms_deform_attn: shapes disagree: value {tuple(v.shape)} = [N,S,M,D], sampling_locations "
+        raise _lib.SolaError(f"{who}: shapes disagree: value {tuple(v.shape)} = [N,S,M,D], sampling_locations "
                              f"{tuple(loc.shape)} = [N,Lq,M,L,P,2], attention_weights {tuple(w.shape)} = [N,Lq,M,L,P]")
+    if go is not None and tuple(go.shape) != (N, Lq, M * D):
+        raise _lib.SolaError(f"{who}: grad_output must be [N,Lq,M*D] = {[N, Lq, M * D]}, got {list(go.shape)}")
     for name, t, shape in (("spatial_shapes", shp, (L, 2)), ("level_start_index", lsi, (L,))):
         if t.dtype != torch.int64 or tuple(t.shape) != shape:
-            raise _lib.SolaError(f"ms_deform_attn: {name} must be int64 {list(shape)} (L = {L} levels in sampling_locations), got "
+            raise _lib.SolaError(f"{who}: {name} must be int64 {list(shape)} (L = {L} levels in sampling_locations), got "
                                  f"{t.dtype} {list(t.shape)}")
     if D not in MSDA_HEAD_DIMS:
-        raise _lib.SolaError(f"ms_deform_attn: D = {D} channels per head, supported are {MSDA_HEAD_DIMS}")
+        raise _lib.SolaError(f"{who}: D = {D} channels per head, supported are {MSDA_HEAD_DIMS}")
     if not 1 <= L <= MSDA_MAX_LEVELS:
-        raise _lib.SolaError(f"ms_deform_attn: L = {L} levels, supported are 1 to {MSDA_MAX_LEVELS}")
+        raise _lib.SolaError(f"{who}: L = {L} levels, supported are 1 to {MSDA_MAX_LEVELS}")
     if not 1 <= P <= MSDA_MAX_POINTS:
-        raise _lib.SolaError(f"ms_deform_attn: P = {P} points, supported are 1 to {MSDA_MAX_POINTS}")
+        raise _lib.SolaError(f"{who}: P = {P} points, supported are 1 to {MSDA_MAX_POINTS}")
     if min(N, S, M, Lq) < 1:
-        raise _lib.SolaError(f"ms_deform_attn: N {N}, S {S}, M {M}, Lq {Lq} must all be >= 1")
-    require_cuda(v, shp, lsi, loc, w)
-    v, loc, w, shp, lsi = v.contiguous(), loc.contiguous(), w.contiguous(), shp.contiguous(), lsi.contiguous()
+        raise _lib.SolaError(f"{who}: N {N}, S {S}, M {M}, Lq {Lq} must all be >= 1")
+    require_cuda(v, shp, lsi, loc, w, go)
+    go = None if go is None else go.contiguous()
+    return (v.contiguous(), shp.contiguous(), lsi.contiguous(), loc.contiguous(), w.contiguous(), go), (N, S, M, D, Lq, L, P)
+
+
+def _msda_forward(v, shp, lsi, loc, w, dims):
+    N, S, M, D, Lq, L, P = dims
     out = torch.empty((N, Lq, M * D), device=v.device, dtype=torch.float32)
     check(lib().sola_ms_deform_attn(ptr(v), ptr(shp), ptr(lsi), ptr(loc), ptr(w), N, S, M, D, Lq, L, P, ptr(out),
                                     current_stream(v.device)), "sola_ms_deform_attn")
     return out
 
 
+def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations, attention_weights):
+    """Multi-scale deformable attention (sola_ms_deform_attn in the header has the contract): value [N,S,M,D],
+    spatial_shapes int64 [L,2] = (H_l, W_l), level_start_index int64 [L], sampling_locations [N,Lq,M,L,P,2] normalised (x, y),
+    attention_weights [N,Lq,M,L,P] -> [N,Lq,M*D].  float32 only; the level tables stay on the device (never copied to the
+    host, so S is not compared with them: a row outside value contributes nothing).
+    With grad mode on and value, sampling_locations or attention_weights requiring grad, the result carries a backward
+    (ms_deform_attn_backward below, once differentiable); otherwise nothing is recorded.  The forward's bits, and the gradients
+    of the locations and the weights, are the same on every run; the gradient of value is NOT (float atomic adds)."""
+    (v, shp, lsi, loc, w, _), dims = _msda_checked("ms_deform_attn", value, spatial_shapes, level_start_index, sampling_locations,
+                                                   attention_weights)
+    if torch.is_grad_enabled() and (value.requires_grad or sampling_locations.requires_grad or attention_weights.requires_grad):
+        return _MsdaFunction.apply(v, shp, lsi, loc, w)
+    return _msda_forward(v, shp, lsi, loc, w, dims)
+
+
+def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output,
+                            need=(True, True, True)):
+    """The gradients of ms_deform_attn for grad_output [N,Lq,M*D] (sola_ms_deform_attn_backward in the header has the contract):
+    (grad_value [N,S,M,D], grad_loc [N,Lq,M,L,P,2], grad_weight [N,Lq,M,L,P]); where ``need`` is false the gradient is not
+    computed and None stands in its place.  grad_loc and grad_weight have the same bits on every run and stream, with or without
+    the others.  grad_value is a scatter of float32 atomic adds: its last bits differ from run to run - the one result of this
+    library that is not bit-repeatable.  Under torch.use_deterministic_algorithms(True) a call that wants it raises (warns in
+    warn-only mode): no ordered variant exists."""
+    who = "ms_deform_attn_backward"
+    need = tuple(bool(x) for x in need)
+    if len(need) != 3 or not any(need):
+        raise _lib.SolaError(f"{who}: need = {need} must name (grad_value, grad_loc, grad_weight) and ask for at least one")
+    (v, shp, lsi, loc, w, go), (N, S, M, D, Lq, L, P) = _msda_checked(who, value, spatial_shapes, level_start_index, sampling_locations,
+                                                                       attention_weights, grad_output)
+    if need[0] and torch.are_deterministic_algorithms_enabled():
+        text = (f"{who}: grad_value is accumulated with float atomic adds and is not bit-repeatable; there is no deterministic "
+                "variant (torch.use_deterministic_algorithms is on)")
+        if not torch.is_deterministic_algorithms_warn_only_enabled():
+            raise _lib.SolaError(text)
+        warnings.warn(text)
+    grad_value = torch.empty_like(v) if need[0] else None  # zeroed by the entry point
+    grad_loc = torch.empty_like(loc) if need[1] else None
+    grad_weight = torch.empty_like(w) if need[2] else None
+    check(lib().sola_ms_deform_attn_backward(ptr(v), ptr(shp), ptr(lsi), ptr(loc), ptr(w), ptr(go), N, S, M, D, Lq, L, P, ptr(grad_value),
+                                             ptr(grad_loc), ptr(grad_weight), current_stream(v.device)), "sola_ms_deform_attn_backward")
+    return grad_value, grad_loc, grad_weight
+
+
+class _MsdaFunction(torch.autograd.Function):
+    """ms_deform_attn with a recorded backward; its arguments are already checked and contiguous."""
+
+    @staticmethod
+    def forward(ctx, v, shp, lsi, loc, w):
+        ctx.save_for_backward(v, shp, lsi, loc, w)
+        N, S, M, D = v.shape
+        return _msda_forward(v, shp, lsi, loc, w, (N, S, M, D, loc.shape[1], loc.shape[3], loc.shape[4]))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4])
+        grad_value, grad_loc, grad_weight = ms_deform_attn_backward(*ctx.saved_tensors, grad_output, need)
+        return grad_value, None, None, grad_loc, grad_weight
+
+
 class _GdinoExt:
     """Stand-in for GroundingDINO's CUDA extension module ``groundingdino._C`` (the two names ms_deform_attn.py calls;
-    INTEGRATION.md 2 shows where it is bound)."""
+    INTEGRATION.md 2 shows where it is bound).  Inference only: gdino_train_ext below is the one with a backward."""
 
     @staticmethod
     def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step):
@@ -360,8 +429,19 @@ class _GdinoExt:
 
     @staticmethod
     def ms_deform_attn_backward(*args, **kwargs):
-        raise _lib.SolaError("ms_deform_attn_backward: inference only (sola_ms_deform_attn has no backward; run the model under "
-                             "torch.no_grad())")
+        raise _lib.SolaError("ms_deform_attn_backward: inference only (ops.gdino_ext has no backward: run the model under "
+                             "torch.no_grad(), or bind ops.gdino_train_ext to train it)")
+
+
+class _GdinoTrainExt(_GdinoExt):
+    """``groundingdino._C`` for training: upstream's autograd Function calls ms_deform_attn_backward with the saved inputs and
+    the output's gradient and expects (grad_value, grad_sampling_loc, grad_attn_weight)."""
+
+    @staticmethod
+    def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output, im2col_step):
+        """``im2col_step`` is accepted and ignored, as in the forward."""
+        return ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output)
 
 
 gdino_ext = _GdinoExt()
+gdino_train_ext = _GdinoTrainExt()
