@@ -78,7 +78,7 @@ __device__ __forceinline__ void store_o(float* op, int g4, const f32x4 (&oacc)[N
         *reinterpret_cast<half4v*>(dst) = hi;
         *reinterpret_cast<half4v*>(dst + 16) = lo;
     }
-    attn_range_guard(guard, m);
+    f16_range_guard(guard, m);
 }
 
 // SPLIT shape of the shared mode (inference fast path): q, k, v arrive as split-f16 rows straight from the projection

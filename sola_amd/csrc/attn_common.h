@@ -1,5 +1,5 @@
 // What the attention kernels (attn.hip, attn_simple.hip, attn_reg.hip, attn_res.hip, attn_f16.hip, attn_bwd.hip, lab/attn_ring.hip) share,
-// stated once: where a (group) unit's rows are, how a 16-query output tile leaves a wave, the split-f16 / bf16 register helpers, and on the
+// stated once: where a (group) unit's rows are, how a 16-query output tile leaves a wave, the split-f16 register helpers, and on the
 // host the AttnDesc -> kernel-argument fill, the profiler scope, the grid check, the head-dim dispatch and the entry points the files call
 // across.  Every args struct keeps its own members and order (the kernarg layout is the kernel's); the templates below only rely on the
 // shared member NAMES.  profiles/attn_common_isa.txt: kernel by kernel, what the compiler makes of these helpers against the written-out forms.
@@ -9,8 +9,8 @@
 
 #include "kernels.h"
 
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
+typedef half4 half4v;  // common.h's 16-bit vectors under the names the attention files use
+typedef half8 half8v;
 
 // ---- device: where a unit's rows are ---------------------------------------------------------------------------------------
 // Group grp attends rows q0 + i * q_rs (i < Sq) over rows k0 + j * k_rs (j < Sk) of the one [B, N, T', D] token-major layout.
@@ -59,17 +59,7 @@ __device__ __forceinline__ float xor16_32_sum(float v) {
     return v + __shfl_xor(v, 32, 64);
 }
 
-// four bfloat16 values of one 8-byte load as floats (a bf16 is the upper half of an f32), and back (round to nearest even)
-__device__ __forceinline__ float4 bf16x4_to_f32(uint2 w) {
-    return make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                       __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
-}
-__device__ __forceinline__ uint2 f32x4_to_bf16(float x, float y, float z, float w) {
-    typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-    bf4 b;
-    b[0] = (__bf16)x; b[1] = (__bf16)y; b[2] = (__bf16)z; b[3] = (__bf16)w;
-    return __builtin_bit_cast(uint2, b);
-}
+// (the bf16 converters bf16x4_to_f32 / f32x4_to_bf16 and the f16 range guard f16_range_guard are common.h's: the GEMMs and the norms use them too)
 
 // Split-f16 operands: four consecutive values as (hi4, lo4) (cast.hip: every 8 values = 32 bytes [hi8 | lo8]); a product runs as
 // lo*hi + hi*lo + hi*hi on v_mfma_f32_16x16x16_f16 with f32 accumulation (~22-bit products, as in gemm_glds.hip).
@@ -95,13 +85,6 @@ __device__ __forceinline__ f32x4 mfma3(const HL4& a, const HL4& b, f32x4 c) {
     c = __builtin_amdgcn_mfma_f32_16x16x16f16(a.lo, b.hi, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x16f16(a.hi, b.lo, c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x16f16(a.hi, b.hi, c, 0, 0, 0);
-}
-
-// The range-guard rule of every 16-bit output (split-f16 pairs, plain f16 rows): m = the largest |value| a lane wrote (or, attn_res.hip's
-// split arithmetic, read); anything not below 65000 - the f16 range with margin; a NaN fails the comparison too - sets bit 0 of the
-// guard word (null = unchecked) and the caller repeats the forward in f32.
-__device__ __forceinline__ void attn_range_guard(int* guard, float m) {
-    if (guard && !(m < 65000.f)) atomicOr(guard, 1);
 }
 
 // ---- device: how an output tile leaves a wave ----------------------------------------------------------------------------------
@@ -135,7 +118,7 @@ __device__ __forceinline__ void attn_store_tile(float* op, int g4, const f32x4 (
         *reinterpret_cast<half4v*>(dst) = hi;
         *reinterpret_cast<half4v*>(dst + 16) = lo;
     }
-    attn_range_guard(guard, m);
+    f16_range_guard(guard, m);
 }
 
 // ---- host: AttnDesc / AttnBwdDesc -> kernel arguments ---------------------------------------------------------------------------

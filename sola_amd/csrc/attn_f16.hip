@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256, WPU ? 2 : 4) void attn_fwd_f16_kernel(const At
                     *reinterpret_cast<half4v*>(op + cp * 32 + 4) = half4v{o8[4], o8[5], o8[6], o8[7]};
                 }
             }
-            attn_range_guard(a.guard, m);
+            f16_range_guard(a.guard, m);
         }
     }
 }
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(256) void attn_fwd_small_f16_kernel(const AttnHArgs
         }
         *reinterpret_cast<half8v*>(a.o + (q0 + (long long)i * q_rs) * a.ldo + h * DH + 8 * c) = o8;
     }
-    attn_range_guard(a.guard, m);
+    f16_range_guard(a.guard, m);
 }
 
 // TRAIN: the training forward on bfloat16 q / k / v (head_dim 128 / 64; the BF + TR instantiations): one wave per unit for sequences

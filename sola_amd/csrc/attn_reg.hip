@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_f32_reg_kernel(const AttnR
             *reinterpret_cast<half4v*>(dst) = hi;
             *reinterpret_cast<half4v*>(dst + 16) = lo;
         }
-    attn_range_guard(a.guard, m);
+    f16_range_guard(a.guard, m);
 }
 
 }  // namespace

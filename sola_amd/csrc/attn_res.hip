@@ -229,7 +229,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_sm_res_kernel(const AttnQArgs
         else sm_tile<1>(a, Kh, Kl, Vh, Vl, qf, op, lsep, Sk, x, g4, q_ok, amax);
     }
     // anything that left the f16 range (q, k, v or the output pairs; NaN fails the comparison too): the forward repeats in f32
-    attn_range_guard(a.guard, amax);
+    f16_range_guard(a.guard, amax);
 }
 #endif
 

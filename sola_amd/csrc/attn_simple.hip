@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(const AttnSArgs a) 
             // even lane: [my hi4 | partner's hi4] at block + 0;  odd lane: [partner's lo4 | my lo4] at block + 16
             const int4 piece = odd ? make_int4(rx, ry, lw2.x, lw2.y) : make_int4(hw2.x, hw2.y, rx, ry);
             *reinterpret_cast<int4*>(reinterpret_cast<char*>(op + 8 * (c >> 1)) + (odd ? 16 : 0)) = piece;
-            attn_range_guard(a.guard, m);
+            f16_range_guard(a.guard, m);
         }
     }
 }

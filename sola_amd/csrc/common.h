@@ -56,6 +56,66 @@ __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
     lo = (_Float16)(x - (float)hi);
 }
 
+// ---- 16-bit values: vector types, the range guard, the f16 / bf16 converters ---------------------------------------------------
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+
+// The range-guard rule of every 16-bit output (split-f16 pairs, plain f16 rows), stated once: m = the largest |value| written (or, in
+// attn_res.hip's split arithmetic, read); anything not below 65000 - the f16 range with margin - sets bit 0 of the guard word (null =
+// unchecked) and the caller repeats the inference forward in exact f32.  The comparison is written so that a NaN fails it too.
+constexpr float F16_GUARD_LIMIT = 65000.f;
+// (each form spells the test out: routed through a bool helper, the compiler exchanged the sense of the guard-pointer test in the GEMM
+// epilogues and moved scalar spills in attn.hip's kernels - profiles/gemm_common_isa.txt)
+__device__ __forceinline__ void f16_range_guard(int* guard, float m) {
+    if (guard && !(m < F16_GUARD_LIMIT)) atomicOr(guard, 1);
+}
+// four values of one store: the maximum as a tree (fmaxf drops NaNs, so the ballot form tests for them separately)
+__device__ __forceinline__ void f16_range_guard4(int* guard, const float (&v)[4]) {
+    const float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    if (guard && !(m < F16_GUARD_LIMIT)) atomicOr(guard, 1);
+}
+// the lanes of the wave whose four values leave the range or hold a NaN, as a mask kept in scalar registers: the epilogues that must not
+// branch per store OR these together and test once per tile
+__device__ __forceinline__ unsigned long long f16_range_ballot4(const float (&v)[4]) {
+    const float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    return __builtin_amdgcn_ballot_w64(!(m < F16_GUARD_LIMIT) || __builtin_isunordered(v[0], v[1]) || __builtin_isunordered(v[2], v[3]));
+}
+
+// One 16-bit value in the bits of a _Float16: f16, or with bf the bfloat16 bit pattern (a bf16 is the upper half of an f32)
+__device__ __forceinline__ _Float16 cvt16(float v, int bf) {
+    if (bf) return __builtin_bit_cast(_Float16, (__bf16)v);
+    return (_Float16)v;
+}
+__device__ __forceinline__ float cvt16_in(_Float16 h, bool bf) {
+    if (bf) return __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, h) << 16);
+    return (float)h;
+}
+// four values as one 8-byte word (16-bit outputs / residuals: _Float16, or bfloat16 where the operands are)
+__device__ __forceinline__ half4 cvt16x4_out(const float (&v)[4], bool bf) {
+    if (bf) {
+        typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
+        bf4 b;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) b[e] = (__bf16)v[e];
+        return __builtin_bit_cast(half4, b);
+    }
+    half4 hh;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) hh[e] = (_Float16)v[e];
+    return hh;
+}
+// four bfloat16 values of one 8-byte load as floats, and back (round to nearest even)
+__device__ __forceinline__ float4 bf16x4_to_f32(uint2 w) {
+    return make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
+                       __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
+}
+__device__ __forceinline__ uint2 f32x4_to_bf16(float x, float y, float z, float w) {
+    typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
+    bf4 b;
+    b[0] = (__bf16)x; b[1] = (__bf16)y; b[2] = (__bf16)z; b[3] = (__bf16)w;
+    return __builtin_bit_cast(uint2, b);
+}
+
 // A 64-lane xor butterfly on the vector ALU.  __shfl_xor is a ds_bpermute round trip through the LDS crossbar (~100+ cycles of latency
 // each; six dependent ones per wave_sum).  Every step below exchanges with exactly lane ^ o, so a sum / max taken with them in the same
 // order (32, 16, 8, 4, 2, 1) has the bits of the __shfl_xor form (tools/micro/wave_reduce_check.hip compares every lane of every step):
@@ -201,3 +261,24 @@ static inline int sola_cu_count() {
             return SOLA_ERR_HIP;                                                                 \
         }                                                                                        \
     } while (0)
+
+// A launch whose dynamic LDS exceeds the default limit: the MaxDynamicSharedMemorySize attribute is set the first time each device
+// launches the kernel (`once` belongs to that kernel), then the launch and its check.  kargs = the addresses of the kernel's arguments.
+inline int launch_lds_fn(const void* fn, DeviceOnce& once, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, void** kargs) {
+    int dev;
+    if (once.needed(&dev)) {
+        SOLA_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        once.done(dev);
+    }
+    SOLA_HIP(hipLaunchKernel(fn, grid, block, kargs, lds_bytes, s));
+    SOLA_LAUNCH_CHECK();
+    return SOLA_OK;
+}
+// ... for a kernel named at compile time and taking one argument struct: launch_lds<kernel<...>>(grid, block, lds_bytes, stream, args)
+// keeps the DeviceOnce of that instantiation
+template <auto Kernel, class A>
+int launch_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const A& args) {
+    static DeviceOnce once;
+    void* kargs[] = {const_cast<A*>(&args)};
+    return launch_lds_fn(reinterpret_cast<const void*>(Kernel), once, grid, block, lds_bytes, s, kargs);
+}

@@ -14,7 +14,7 @@
 // Up to three problems that share all dimensions run in one launch (q/k/v projections) via blockIdx.z.
 #include <algorithm>
 
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace {
 
@@ -35,13 +35,6 @@ struct GemmArgs {
     const float* w_nn[3];  // few-row shape, NN form (GemmDesc::w_nn)
     int w_nn_rows;
 };
-
-// |v| must stay inside the f16 range to be written as a split-f16 pair; NaN fails the comparison too
-__device__ __forceinline__ void guard_sp16(int* guard, float m) {
-    if (guard && !(m < 65000.f)) atomicOr(guard, 1);
-}
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK = 32;
 constexpr int LDP = 36;  // LDS row pitch in floats (144 B: 16-byte aligned, conflict-free for b128 fragment reads)
@@ -75,17 +68,7 @@ void gemm_nt_f32_kernel(const GemmArgs a) {  // two blocks per CU (their LDS all
     // block -> tile.  With 8 XCDs (block b runs on XCD b % 8) keep all column tiles of one row panel on one XCD so
     // the A panel is fetched into a single L2.
     int rt, ct;
-    {
-        const int bid = blockIdx.x;
-        if (a.xcd_remap) {
-            const int x = bid & 7, j = bid >> 3;
-            rt = x + 8 * (j / a.tiles_n);
-            ct = j % a.tiles_n;
-        } else {
-            rt = bid / a.tiles_n;
-            ct = bid % a.tiles_n;
-        }
-    }
+    tile_decode(a, blockIdx.x, rt, ct);
     const int m0 = rt * BM, n0 = ct * BN;
 
     // ---- per-thread load coordinates: 8 lanes cover one 32-float (128 B) row segment
@@ -391,7 +374,7 @@ void gemm_nt_f32_kernel(const GemmArgs a) {  // two blocks per CU (their LDS all
                         split_f16(v, hi, lo);
                         cb[n & 7] = hi;
                         cb[8 + (n & 7)] = lo;
-                        guard_sp16(a.guard, fabsf(v));
+                        f16_range_guard(a.guard, fabsf(v));
                     } else {
                         pr.C[(long long)m * a.ldc + n] = v;
                     }
@@ -439,7 +422,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs a) {
             cb[e] = hi;
             cb[8 + e] = lo;
         }
-        guard_sp16(a.guard, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+        f16_range_guard4(a.guard, v);
     } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) pr.C[(long long)m * a.ldc + n + e] = v[e];
@@ -498,7 +481,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void gemm_nt_f32_small_ke
             } else {
                 const int r = m / a.T_out, to = m - r * a.T_out, t0 = to * a.stride - a.pad;
                 ap[i] = pr.A + ((long long)r * a.T_in + t0) * a.Cin + lk;
-                int bits = 0;
+                int bits = 0;  // (gemm_common.h's conv_window sets all 8 tap bits unrolled; this few-row kernel loops over the taps that exist)
                 for (int kk = 0; kk < a.K / a.Cin; ++kk) bits |= (t0 + kk >= 0 && t0 + kk < a.T_in) ? 1 << kk : 0;
                 amask[i] = bits;
             }
@@ -658,21 +641,13 @@ template <int NW, bool CONV, bool NN = false>
 static int launch_small_n(const GemmArgs& a, int nprob, hipStream_t s) {
     constexpr size_t lds = (size_t)NW * 2 * 2 * 32 * SM_LD * sizeof(float);  // NW waves x two stages (73.7 / 147.5 KB); the reduction reuses it
     static_assert(NW * 32 * 33 <= NW * 2 * 2 * 32 * SM_LD, "the reduction tile must fit in the stages");
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_small_kernel<NW, CONV, NN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
-    hipLaunchKernelGGL((gemm_nt_f32_small_kernel<NW, CONV, NN>), dim3(a.tiles_m * a.tiles_n, 1, nprob), dim3(64 * NW), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
+    return launch_lds<gemm_nt_f32_small_kernel<NW, CONV, NN>>(dim3(a.tiles_m * a.tiles_n, 1, nprob), dim3(64 * NW), lds, s, a);
 }
 static int launch_small(const GemmArgs& base, int nprob, hipStream_t s) {
     GemmArgs a = base;
     a.tiles_m = (a.M + 31) / 32;
     a.tiles_n = a.N / 32;
-    a.xcd_remap = ((a.tiles_m * a.tiles_n) % 8 == 0) ? 1 : 0;
+    a.xcd_remap = ((a.tiles_m * a.tiles_n) % 8 == 0) ? 1 : 0;  // (not xcd_remap_rows: this kernel's order is W-panel-major over ALL tiles, an eighth of them per XCD)
     const long long tiles = (long long)a.tiles_m * a.tiles_n * nprob;
     const bool nw8 = g_gemm_small_nw8 && a.K % 256 == 0 && tiles <= 2 * sola_cu_count();
     if (a.w_nn_rows) return nw8 ? launch_small_n<8, false, true>(a, nprob, s) : launch_small_n<4, false, true>(a, nprob, s);
@@ -680,29 +655,24 @@ static int launch_small(const GemmArgs& base, int nprob, hipStream_t s) {
     return nw8 ? launch_small_n<8, false>(a, nprob, s) : launch_small_n<4, false>(a, nprob, s);
 }
 
+// the ordered reduce of a split-K launch's partial sums (a.part, a.ksplit slabs per problem) into C, with the epilogue's scales
+int launch_reduce(const GemmArgs& a, int nprob, hipStream_t s) {
+    const long long quads = (long long)a.M * (a.N >> 2);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256), 1, nprob), dim3(256), 0, s, a);
+    SOLA_LAUNCH_CHECK();
+    return SOLA_OK;
+}
+
 template <int BM, int BN, int PIPE, int ARITH, int NW = 4>
 int launch_tile(const GemmArgs& base, int nprob, hipStream_t s) {
     GemmArgs a = base;
     a.tiles_m = (a.M + BM - 1) / BM;
     a.tiles_n = (a.N + BN - 1) / BN;
-    a.xcd_remap = (a.tiles_m % 8 == 0) ? 1 : 0;
+    a.xcd_remap = xcd_remap_rows(a.tiles_m);
     constexpr size_t lds = (size_t)(BM + BN) * 2 * LDP * sizeof(float);
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_kernel<BM, BN, PIPE, ARITH, NW>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
     dim3 grid(a.tiles_m * a.tiles_n, a.ksplit > 1 ? a.ksplit : 1, nprob);
-    hipLaunchKernelGGL((gemm_nt_f32_kernel<BM, BN, PIPE, ARITH, NW>), grid, dim3(64 * NW), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    if (a.ksplit > 1) {
-        const long long quads = (long long)a.M * (a.N >> 2);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256), 1, nprob), dim3(256), 0, s, a);
-        SOLA_LAUNCH_CHECK();
-    }
-    return SOLA_OK;
+    SOLA_TRY((launch_lds<gemm_nt_f32_kernel<BM, BN, PIPE, ARITH, NW>>(grid, dim3(64 * NW), lds, s, a)));
+    return a.ksplit > 1 ? launch_reduce(a, nprob, s) : SOLA_OK;
 }
 
 }  // namespace
@@ -732,16 +702,22 @@ int launch_splitk_reduce(const float* part, int ksplit, int nprob, float* const*
     a.M = M; a.N = N; a.ldc = ldc;
     a.out_scale = 1.f; a.out_scale_dev = out_scale_dev;
     a.ksplit = ksplit; a.part = const_cast<float*>(part);
-    const long long quads = (long long)M * (N >> 2);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256), 1, nprob), dim3(256), 0, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
+    return launch_reduce(a, nprob, s);
 }
 
 int launch_gemm_split_glds(const GemmDesc& d, hipStream_t s);
 int gemm_split_glds_shape(const GemmDesc& d);  // 4 = 256x256 blocks, 1 = 128x128
 bool gemm_f32_persist_applies(const GemmDesc& d);  // gemm_f32p.hip: exact f32, persistent direct-to-LDS form (bit-identical to the kernels here)
 int launch_gemm_f32_persist(const GemmDesc& d, hipStream_t s);
+
+// split-K through the direct-to-LDS persistent kernel (the K ranges are work items of their own and leave raw partial sums in the caller's
+// scratch), then the ordered reduce; `a` carries the epilogue's view of the launch (C, scales, output format)
+static int launch_split_glds_reduce(GemmArgs& a, const GemmDesc& d, hipStream_t s) {
+    a.ksplit = d.ksplit;
+    a.part = d.splitk_ws;
+    SOLA_TRY(launch_gemm_split_glds(d, s));
+    return launch_reduce(a, d.nprob, s);
+}
 
 int launch_gemm(const GemmDesc& d, hipStream_t s) {
     SOLA_ARG(d.nprob >= 1 && d.nprob <= 3, "gemm: nprob %d", d.nprob);
@@ -752,10 +728,7 @@ int launch_gemm(const GemmDesc& d, hipStream_t s) {
         SOLA_ARG(d.lda % 4 == 0, "gemm: lda %d must be a multiple of 4", d.lda);
     }
     GemmArgs a;
-    for (int i = 0; i < 3; ++i) a.p[i] = d.p[i < d.nprob ? i : 0];
-    a.M = d.M; a.N = d.N; a.K = d.K; a.lda = d.lda; a.ldr = d.ldr; a.ldc = d.ldc;
-    a.conv = d.conv; a.T_in = d.T_in; a.T_out = d.T_out; a.stride = d.stride; a.pad = d.pad; a.Cin = d.Cin;
-    a.rowmap = d.conv == 1 ? d.rowmap : nullptr;
+    gemm_fill_common(a, d);
     a.tiles_m = a.tiles_n = a.xcd_remap = 0;
     a.out_scale = d.arith >= 1 && d.out_scale != 0.f ? d.out_scale : 1.f;
     a.out_scale_dev = d.arith >= 1 ? d.out_scale_dev : nullptr;
@@ -779,13 +752,7 @@ int launch_gemm(const GemmDesc& d, hipStream_t s) {
             SOLA_ARG(d.splitk_ws && d.K % (64 * d.ksplit) == 0 && d.K / 64 / d.ksplit >= 2 && d.N % 4 == 0 && d.ldc % 4 == 0 && !d.c_f16 &&
                          d.splitk_bytes >= (size_t)d.nprob * d.ksplit * d.M * d.N * sizeof(float),
                      "f16 gemm: split-K over %d ranges needs K %% (64 * ksplit) == 0 (K=%d) and a scratch of nprob*ksplit*M*N floats", d.ksplit, d.K);
-            a.ksplit = d.ksplit;
-            a.part = d.splitk_ws;
-            SOLA_TRY(launch_gemm_split_glds(d, s));
-            const long long quads = (long long)a.M * (a.N >> 2);
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256), 1, d.nprob), dim3(256), 0, s, a);
-            SOLA_LAUNCH_CHECK();
-            return SOLA_OK;
+            return launch_split_glds_reduce(a, d, s);
         }
         return launch_gemm_split_glds(d, s);
     }
@@ -817,13 +784,7 @@ int launch_gemm(const GemmDesc& d, hipStream_t s) {
         SOLA_ARG(d.splitk_ws && d.K % (32 * d.ksplit) == 0 && d.K / 32 / d.ksplit >= 2 && d.N % 4 == 0 && d.ldc % 4 == 0 &&
                      d.splitk_bytes >= (size_t)d.nprob * d.ksplit * d.M * d.N * sizeof(float),
                  "gemm: split-K over %d ranges needs K %% (32 * ksplit) == 0 (K=%d) and a scratch of nprob*ksplit*M*N floats", d.ksplit, d.K);
-        a.ksplit = d.ksplit;
-        a.part = d.splitk_ws;
-        SOLA_TRY(launch_gemm_split_glds(d, s));
-        const long long quads = (long long)a.M * (a.N >> 2);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256), 1, d.nprob), dim3(256), 0, s, a);
-        SOLA_LAUNCH_CHECK();
-        return SOLA_OK;
+        return launch_split_glds_reduce(a, d, s);
     }
     if (glds) return launch_gemm_split_glds(d, s);
     SOLA_ARG(!d.gn_gamma, "gemm: the fused GroupNorm epilogue needs the persistent direct-to-LDS kernel (check gemm_gn_fusable)");

@@ -23,7 +23,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace {
 
@@ -36,23 +36,10 @@ struct F32pArgs {
     unsigned long long* trace;  // SOLA_EXPERIMENTS, ABL & 16: per (block, wave) cycle sums (k-loops, barrier waits, epilogues, tiles)
 };
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __attribute__((aligned(16))) float g_zero_page_f32p[4] = {0.f, 0.f, 0.f, 0.f};
-
 constexpr int PBK = 32;     // k values per k-tile
 constexpr int PROWB = 128;  // bytes per tile row
 
-__device__ __forceinline__ int tap_bits(int t0, int T_in) {
-    int bits = 0;
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) bits |= ((unsigned)(t0 + kk) < (unsigned)T_in) ? (1 << kk) : 0;
-    return bits;
-}
-
 struct FragF32 { f32x4 a[2], b[2]; };
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // RMODE: 0 = no residual, 1 = f32 residual [M][ldr]
 // ABL (measurement, SOLA_EXPERIMENTS builds only; results are garbage): 1 = no two-level fold, 2 = no DMA in the k-loop, 4 = no epilogue,
@@ -86,15 +73,8 @@ __global__ __launch_bounds__(512) void gemm_nt_f32_persist_kernel(const F32pArgs
     const int total = a.tiles_m * tiles_row;
     auto decode = [&](int tile, int& z, int& m0, int& n0) {
         int rt, c;
-        if (a.xcd_remap) {
-            const int x = tile & 7, j = tile >> 3;
-            rt = x + 8 * (j / tiles_row);
-            c = j % tiles_row;
-        } else {
-            rt = tile / tiles_row;
-            c = tile % tiles_row;
-        }
-        z = c / a.tiles_n;
+        tile_decode(TileGrid{tiles_row, a.xcd_remap}, tile, rt, c);
+        z = c / a.tiles_n;  // (gemm_common.h's composite-column rule, without k ranges)
         m0 = rt * GBM;
         n0 = (c - z * a.tiles_n) * GBN;
     };
@@ -112,7 +92,7 @@ __global__ __launch_bounds__(512) void gemm_nt_f32_persist_kernel(const F32pArgs
     }
     unsigned c_vo[APW], c_eff[APW];  // CONV: per-lane offset of the piece's window start; ... with taps outside the sequence sent out of range
     int a_t0[APW];                   // CONV: tap-validity bits of the piece's row
-    __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(g_zero_page_f32p, 0, 0, 0x00020000), rs_w = rs_a;
+    __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(g_zero_page, 0, 0, 0x00020000), rs_w = rs_a;
     int a_so = 0, w_so = 0;          // scalar offsets of this wave's first piece at the stream's k position
     const int a_pitch8 = CONV ? 0 : a.lda * 32, w_pitch8 = a.K * 32;  // bytes between pieces (8 rows)
     int conv_kk = 0, conv_c = 0;     // CONV: tap and channel of the next k-tile to issue
@@ -137,26 +117,20 @@ __global__ __launch_bounds__(512) void gemm_nt_f32_persist_kernel(const F32pArgs
         if constexpr (CONV) {
             // window start of output row m: source row of tap 0 (may lie outside its sequence: the tap bits say which taps exist).
             // Source rows ascend with m (sequences are concatenated in order), so offsets are taken from the tile's first row.
-            auto window = [&](int m, int& row0, int& bits) {
-                if (a.rowmap) {
-                    const int2 rm = a.rowmap[m];
-                    row0 = rm.x;
-                    bits = rm.y;
-                } else {
-                    const int rr = m / a.T_out, to = m - rr * a.T_out, t0 = to * a.stride - a.pad;
-                    row0 = rr * a.T_in + t0;
-                    bits = tap_bits(t0, a.T_in);
-                }
+            auto window = [&](int m, int& row0, int& bits) {  // (32-bit rows: a tile's offsets are taken from base_row)
+                long long r0;
+                conv_window(a, m, r0, bits);
+                row0 = (int)r0;
             };
             int base_row, base_bits;
-            window(min(m0, a.M - 1), base_row, base_bits);
+            window(dma_clamp_row(m0, a.M), base_row, base_bits);
             base_row = __builtin_amdgcn_readfirstlane(base_row);
             rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A + (long long)base_row * a.Cin), 0, 0x7fffff00, 0x00020000);
 #pragma unroll
             for (int q = 0; q < APW; ++q) {
                 const int r = (wave * APW + q) * 8 + lrow;
                 int row0, bits;
-                window(min(m0 + r, a.M - 1), row0, bits);  // rows past M: clamped (never stored)
+                window(dma_clamp_row(m0 + r, a.M), row0, bits);  // rows past M: clamped (never stored)
                 a_t0[q] = bits;
                 c_vo[q] = (unsigned)((row0 - base_row) * a.Cin * 4 + ((chunk ^ (lrow >> 1) ^ ((q & 1) << 2)) << 4));
             }
@@ -493,17 +467,9 @@ __global__ __launch_bounds__(512) void gemm_nt_f32_persist_kernel(const F32pArgs
 template <bool CONV, int RMODE, int ABL = 0>
 int launch_f32p_t(const F32pArgs& a, hipStream_t s) {
     constexpr size_t lds = 2 * (256 + 128) * PROWB + 8 * 16 * 64 * 4;  // two stages + the epilogue strips: 128 KiB
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_persist_kernel<CONV, RMODE, ABL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
     const int total = a.tiles_m * a.tiles_n * a.nprob;
     const int grid = std::min(total, sola_cu_count());
-    hipLaunchKernelGGL((gemm_nt_f32_persist_kernel<CONV, RMODE, ABL>), dim3(grid), dim3(512), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
+    return launch_lds<gemm_nt_f32_persist_kernel<CONV, RMODE, ABL>>(dim3(grid), dim3(512), lds, s, a);
 }
 
 }  // namespace
@@ -543,14 +509,12 @@ bool gemm_f32_persist_applies(const GemmDesc& d) {
 
 int launch_gemm_f32_persist(const GemmDesc& d, hipStream_t s) {
     F32pArgs a;
-    for (int i = 0; i < 3; ++i) a.p[i] = d.p[i < d.nprob ? i : 0];
-    a.M = d.M; a.N = d.N; a.K = d.K; a.lda = d.lda; a.ldr = d.ldr; a.ldc = d.ldc;
-    a.conv = d.conv; a.T_in = d.T_in; a.T_out = d.T_out; a.stride = d.stride; a.pad = d.pad; a.Cin = d.Cin;
-    a.rowmap = d.conv == 1 ? d.rowmap : nullptr;
+    gemm_fill_common(a, d);
     a.tiles_m = (d.M + 255) / 256;
     a.tiles_n = (d.N + 127) / 128;
     a.nprob = d.nprob;
-    a.xcd_remap = (a.tiles_m % 8 == 0 && sola_cu_count() % 8 == 0) ? 1 : 0;
+    // (a variant of xcd_remap_rows: a block keeps its tiles b, b + grid, ... on XCD b % 8 only if the grid - one block per CU - is a multiple of 8 too)
+    a.xcd_remap = (xcd_remap_rows(a.tiles_m) && sola_cu_count() % 8 == 0) ? 1 : 0;
     const bool res = d.p[0].R != nullptr;
     a.trace = nullptr;
 #ifdef SOLA_EXPERIMENTS

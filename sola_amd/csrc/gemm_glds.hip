@@ -28,188 +28,15 @@
 // overlap + ~28 us epilogue (HBM-bound: C once, residual once; with one round of blocks nothing overlaps it).  Also
 // tried and dropped: a 256x128 / 3-stage shape (DMA two tiles ahead: no faster, latency was not the bound) and
 // sched_group_barrier interleaving of fragment reads (+2-5 % on 64x64 wave tiles only, subsumed by this schedule).
-// Also in this file (round 3): gemm_nt_split_glds_k16_kernel - an experiment, 16-deep k-tiles and two four-wave blocks per CU (slower:
-// DESIGN.md Appendix A) - and gemm_tn_tr_kernel, the weight-gradient product on ROW-MAJOR 16-bit operands (transposing LDS reads
-// instead of transposed copies; the training modes' default dW route).
-#include "kernels.h"
+// This file: the one-tile-per-block kernel, the persistent kernel and the shape routing.  The kernel arguments and the one-tile epilogue
+// are in gemm_glds.h: gemm_tn_tr.hip (the weight-gradient product on row-major 16-bit operands) and the two closed experiments of this
+// family, lab/gemm_k16.hip and lab/gemm_pp.hip (EXPERIMENTS=1 builds), share them.
 #include <algorithm>
 #include <type_traits>
 
+#include "gemm_glds.h"
+
 namespace {
-
-struct GldsArgs {
-    GemmProblem p[3];
-    int M, N, K, lda, ldr, ldc;
-    int conv, T_in, T_out, stride, pad, Cin;
-    const int2* rowmap;  // conv, ragged batches: (source row of tap 0, tap-validity bits) per output row (GemmDesc::rowmap)
-    int tiles_m, tiles_n, xcd_remap, nprob;
-    int ksplit, kper;  // persistent kernel: > 1 = the reduction dim is cut into ksplit ranges of kper k-tiles, each an own work item
-    float* part;       // ... writing raw partial sums to part[(problem * ksplit + range)][M][N] (gemm.hip reduces them)
-    float out_scale;
-    const float* out_scale_dev;
-    int r_sp16, c_sp16;
-    int r_f16, c_f16;  // PURE kernels: residual / output stored as _Float16 (ldr / ldc in halfs)
-    int bf16;          // PURE kernels: the 16-bit operands are bfloat16 (launch-time selection of the PURE = 2 instantiations)
-    const float* bias_scale_dev;  // optional device multiplier of the bias (GemmDesc::bias_scale_dev)
-    int ablate;  // measurement only (sola_tune "gemm_ablate"): 4 = no epilogue
-    int* guard;  // c_sp16: range guard word (GemmDesc::guard), null = unchecked
-    // GNF instantiation of the persistent kernel: GroupNorm (64 channels per group = a wave's 64 output columns, instances of
-    // gn_tokens = 4 / 8 / 16 consecutive rows) + LeakyReLU applied to the tile in the epilogue (GemmDesc::gn_gamma)
-    const float *gn_gamma, *gn_beta;
-    int gn_tokens;
-    float gn_eps, gn_slope, gn_icnt;  // gn_icnt = 1 / (gn_tokens * 64)
-    // persistent kernel, measurement (sola_tune "gemm_stagger" / "gemm_order" / "gemm_trace"; all 0 in production)
-    int stagger;  // > 0: block b sleeps ((b >> 3) % 4) * stagger * 64 clocks before its first tile (de-synchronises the CUs' epilogues)
-    // round 6, 16-bit launches whose tiles are not whole rounds of the CUs: the blocks that get one tile FEWER than the others start late, at
-    // phases spread over most of a tile's time (slack * 64 clocks per k-tile at phase 1; 0 = off).  Their delay is free - they would idle at
-    // the end instead - and their epilogues (and k-loops) no longer coincide with those of the full-count blocks: the HBM bursts of the
-    // synchronised epilogues had every CU's matrix pipe waiting at once (sola_tune "gemm_slack_stagger"; profiles/r06_train_ragged_bf16.txt)
-    // (carried as a NEGATIVE `stagger`: one more kernel argument cost the f16 conv instantiation a spilled register)
-    int order;    // tile order variant (decode())
-    unsigned long long* trace;  // TRACE instantiation: per (block, wave) record, see gemm_trace_words
-};
-constexpr int gemm_trace_words = 8 + 2 * 64;  // 64-bit words per (block, wave): sums, then the tiles' stamps (lane t = tile t of the block)
-
-__device__ __forceinline__ void guard_sp16x4(int* guard, const float (&v)[4]) {
-    const float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-    if (guard && !(m < 65000.f)) atomicOr(guard, 1);  // NaN fails the comparison too
-}
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-// 16-bit outputs / residuals of the PURE kernels: _Float16, or bfloat16 when the operands are (GemmDesc::bf16 with c_f16 / r_f16: the bf16
-// STORAGE of the training step, round 6).  Four values as one 8-byte word.
-typedef __bf16 bf16x4g __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ half4 cvt16x4_out(const float (&v)[4], bool bf) {
-    if (bf) {
-        bf16x4g b;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) b[e] = (__bf16)v[e];
-        return __builtin_bit_cast(half4, b);
-    }
-    half4 hh;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) hh[e] = (_Float16)v[e];
-    return hh;
-}
-__device__ __forceinline__ float cvt16_in(_Float16 h, bool bf) {
-    if (bf) return __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, h) << 16);
-    return (float)h;
-}
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __attribute__((aligned(16))) float g_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
-
-constexpr int GBK = 32;
-constexpr int ROWB = 128;  // bytes per tile row (32 elements x 4 B)
-
-// bit kk set <=> 0 <= t0 + kk < T_in, for the (at most 8) taps of a conv window starting at time t0
-__device__ __forceinline__ int conv_tap_bits(int t0, int T_in) {
-    int bits = 0;
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) bits |= ((unsigned)(t0 + kk) < (unsigned)T_in) ? (1 << kk) : 0;
-    return bits;
-}
-
-// Epilogue of the one-tile-per-block kernels: shared by the 32-deep and the 16-deep (two blocks per CU) k-loops.
-template <int MI, int WAVES_N>
-__device__ __forceinline__ void glds_tile_epilogue(const GldsArgs& a, const GemmProblem& pr, f32x16 (&acc)[MI][2], char* lds, int wave, int lane,
-                                                   int wr, int wc, int m0, int n0) {
-    // ---- epilogue: the accumulators (one column per lane, 16 scattered rows) go through this wave's 16 KiB of the
-    //      now idle stage buffers, 64 rows at a time, and leave as whole 16-byte row pieces (16 lanes cover one 256-byte
-    //      row segment) instead of 64 strided dword stores per lane.  Bias, output scale and the residual are applied on
-    //      the way out.
-    if (a.ablate & 4) return;
-    const float osc = (a.out_scale_dev ? a.out_scale * *a.out_scale_dev : a.out_scale) * (pr.scale_dev ? *pr.scale_dev : 1.f);
-    float* tile = reinterpret_cast<float*>(lds) + wave * (64 * 64);  // [64 rows][64 cols] f32 (256-B rows: b32 writes and b128 reads are conflict-free)
-    const int col_l = lane & 31, row_l = (lane >> 5) << 2;
-    const int c4 = lane & 15;    // 16-byte column piece
-    const int rsub = lane >> 4;  // 4 rows per pass
-    const int n = n0 + wc * 64 + c4 * 4;
-    const bool vec_ok = (a.ldc & 3) == 0 && n + 3 < a.N && (!pr.R || a.r_sp16 || (a.ldr & 3) == 0);
-    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pr.bias) {
-        const float bsc = a.bias_scale_dev ? *a.bias_scale_dev : 1.f;
-        bv.x = n < a.N ? pr.bias[n] * bsc : 0.f;
-        bv.y = n + 1 < a.N ? pr.bias[n + 1] * bsc : 0.f;
-        bv.z = n + 2 < a.N ? pr.bias[n + 2] * bsc : 0.f;
-        bv.w = n + 3 < a.N ? pr.bias[n + 3] * bsc : 0.f;
-    }
-#pragma unroll
-    for (int h = 0; h < MI / 2; ++h) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = i * 32 + (r & 3) + 8 * (r >> 2) + row_l;
-                    const int col = j * 32 + col_l;
-                    tile[row * 64 + col] = acc[h * 2 + i][j][r];
-                }
-        __syncthreads();
-#pragma unroll 4
-        for (int pass = 0; pass < 16; ++pass) {
-            const int row = pass * 4 + rsub;
-            const int m = m0 + wr * MI * 32 + h * 64 + row;
-            const float4 t = *reinterpret_cast<const float4*>(&tile[row * 64 + c4 * 4]);
-            if (m >= a.M) continue;
-            float v[4] = {t.x * osc + bv.x, t.y * osc + bv.y, t.z * osc + bv.z, t.w * osc + bv.w};
-            if (pr.R) {
-                if (a.r_f16) {
-                    const _Float16* rb = reinterpret_cast<const _Float16*>(pr.R) + (long long)m * a.ldr + n;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (n + e < a.N) v[e] += cvt16_in(rb[e], a.bf16 != 0);
-                } else if (a.r_sp16) {
-                    // 4 consecutive columns sit in one 8-wide block: hi[4] and lo[4] are two aligned 8-byte loads
-                    const _Float16* rb = reinterpret_cast<const _Float16*>(pr.R + (long long)m * a.ldr + (n & ~7)) + (n & 4);
-                    if (n + 3 < a.N) {
-                        const half4 hh = *reinterpret_cast<const half4*>(rb), ll = *reinterpret_cast<const half4*>(rb + 8);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] += (float)hh[e] + (float)ll[e];
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (n + e < a.N) v[e] += (float)rb[e] + (float)rb[8 + e];
-                    }
-                } else if (vec_ok) {
-                    const float4 rv = *reinterpret_cast<const float4*>(pr.R + (long long)m * a.ldr + n);
-                    v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (n + e < a.N) v[e] += pr.R[(long long)m * a.ldr + n + e];
-                }
-            }
-            if (a.c_f16) {
-                if (n >= a.N) continue;  // N % 4 == 0: the four columns are in range together
-                *reinterpret_cast<half4*>(reinterpret_cast<_Float16*>(pr.C) + (long long)m * a.ldc + n) = cvt16x4_out(v, a.bf16 != 0);
-                if (!a.bf16) guard_sp16x4(a.guard, v);
-            } else if (a.c_sp16) {
-                if (n >= a.N) continue;  // N % 8 == 0 and n % 4 == 0: the four columns are in range together
-                // 4 consecutive columns of one 8-wide block: hi[4] and lo[4] leave as two aligned 8-byte stores
-                _Float16* cb = reinterpret_cast<_Float16*>(pr.C + (long long)m * a.ldc + (n & ~7)) + (n & 4);
-                half4 hh, ll;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { _Float16 h1, l1; split_f16(v[e], h1, l1); hh[e] = h1; ll[e] = l1; }
-                *reinterpret_cast<half4*>(cb) = hh;
-                *reinterpret_cast<half4*>(cb + 8) = ll;
-                guard_sp16x4(a.guard, v);
-            } else if (vec_ok) {
-                *reinterpret_cast<float4*>(pr.C + (long long)m * a.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (n + e < a.N) pr.C[(long long)m * a.ldc + n + e] = v[e];
-            }
-        }
-        if (h + 1 < MI / 2) __syncthreads();  // this wave's reads of the staging rows are done before they are rewritten
-    }
-}
 
 // PURE = plain f16 operands (GemmDesc::arith 2): the same 128-byte tile rows now hold 64 consecutive halfs instead of 32
 // (hi, lo) pairs, so nothing about the DMA, the swizzle or the fragment reads changes - a "hi" chunk is simply halfs
@@ -229,17 +56,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_split_glds_ker
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave / WAVES_N, wc = wave % WAVES_N;
     int rt, ct;
-    {
-        const int bid = blockIdx.x;
-        if (a.xcd_remap) {
-            const int x = bid & 7, j = bid >> 3;
-            rt = x + 8 * (j / a.tiles_n);
-            ct = j % a.tiles_n;
-        } else {
-            rt = bid / a.tiles_n;
-            ct = bid % a.tiles_n;
-        }
-    }
+    tile_decode(a, blockIdx.x, rt, ct);
     const int m0 = rt * GBM, n0 = ct * GBN;
 
     // ---- DMA coordinates: this wave owns row groups wave*APW + i (8 rows each) of the A tile and wave*WPW + i of the
@@ -247,27 +64,19 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_split_glds_ker
     //      pointer that advances 128 B per k-tile: also for the implicit-im2col conv, where the receptive field of an
     //      output row is (t0*Cin + k) contiguous floats of the channels-last input, so only the zero-padding test
     //      depends on k.
-    const int lrow = lane >> 3, chunk = lane & 7;
+    const int lrow = dma_lane_row(lane), chunk = dma_lane_chunk(lane);
     const char* a_ptr[APW];
     const char* w_ptr[WPW];
-    int a_t0[APW];
+    int a_t0[APW];  // CONV: validity bits of the window's taps
 #pragma unroll
     for (int i = 0; i < APW; ++i) {
         const int r = (wave * APW + i) * 8 + lrow;     // tile-local A row
-        const int col_bytes = (chunk ^ ((r >> 1) & 7)) * 16;  // logical 16-byte chunk that must land in this physical slot
-        const int m = min(m0 + r, a.M - 1);
+        const int col_bytes = dma_src_chunk_bytes(chunk, r);
+        const int m = dma_clamp_row(m0 + r, a.M);
         if (CONV) {
-            // a_t0 = validity bits of the window's taps (bit kk: tap kk lies inside the sequence)
-            if (a.rowmap) {
-                const int2 rm = a.rowmap[m];
-                a_t0[i] = rm.y;
-                a_ptr[i] = reinterpret_cast<const char*>(pr.A) + (long long)rm.x * a.Cin * 4 + col_bytes;
-            } else {
-                const int rr = m / a.T_out, to = m - rr * a.T_out;
-                const int t0 = to * a.stride - a.pad;
-                a_t0[i] = conv_tap_bits(t0, a.T_in);
-                a_ptr[i] = reinterpret_cast<const char*>(pr.A) + ((long long)rr * a.T_in + t0) * a.Cin * 4 + col_bytes;
-            }
+            long long row0;
+            conv_window(a, m, row0, a_t0[i]);
+            a_ptr[i] = reinterpret_cast<const char*>(pr.A) + row0 * a.Cin * 4 + col_bytes;
         } else {
             a_t0[i] = 0;
             a_ptr[i] = reinterpret_cast<const char*>(pr.A + (long long)m * a.lda) + col_bytes;
@@ -276,8 +85,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_split_glds_ker
 #pragma unroll
     for (int i = 0; i < WPW; ++i) {
         const int r = (wave * WPW + i) * 8 + lrow;  // tile-local W row
-        const int n = min(n0 + r, a.N - 1);
-        w_ptr[i] = reinterpret_cast<const char*>(pr.W + (long long)n * a.K) + (chunk ^ ((r >> 1) & 7)) * 16;
+        const int n = dma_clamp_row(n0 + r, a.N);
+        w_ptr[i] = reinterpret_cast<const char*>(pr.W + (long long)n * a.K) + dma_src_chunk_bytes(chunk, r);
     }
     const char* zero = reinterpret_cast<const char*>(g_zero_page);
     const int nk = a.K / GBK;
@@ -409,515 +218,6 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_nt_split_glds_ker
 }
 
 
-// ---- 16-deep k-tiles, two blocks per CU (experiment, sola_tune "gemm_k16") ------------------------------------------
-// What the persistent kernel cannot hide is its epilogue: one block owns the CU, so while its eight waves drain a tile the
-// matrix pipes idle.  Here a block is FOUR waves (one per SIMD) on a 256x128 tile with the same 128x64 wave tiles, and its
-// LDS is small enough for TWO blocks per CU (3 stages x 24 KiB): the second block's k-loop runs under the first one's
-// epilogue and prologue, and in the loop the two blocks give every SIMD its two waves back.  That needs k-tiles of 16:
-//   * tile rows are 64 bytes (4 chunks of 16 B: hi/lo of two 8-wide k-blocks), a 1-KiB DMA piece is 16 rows; the chunk
-//     swizzle key is (row >> 2) & 3 (16 consecutive rows x one logical chunk = 16 distinct slots of the 256-byte bank line);
-//   * one k-tile is ONE MFMA batch (24 MFMAs, 16 with plain 16-bit operands); the next tile's 12 fragment reads go behind
-//     its first MFMA and the 6 DMA pieces of the tile three ahead are spread over the rest;
-//   * three stages: tile kt+1 is read, kt+2 is landing, kt+3 is issued into the stage tile kt's fragments came from (every
-//     wave has them in registers behind the barrier).  One barrier per k-tile; the DMA has two batches to land.
-template <bool CONV, int PURE = 0>
-__global__ __launch_bounds__(256, 2) void gemm_nt_split_glds_k16_kernel(const GldsArgs a) {
-    constexpr int MI = 4, WAVES_N = 2, NWAVE = 4;
-    constexpr int GBM = 256, GBN = 128, KB = 16, RB = 64;
-    constexpr int STAGES = 3, STAGE_BYTES = (GBM + GBN) * RB;
-    constexpr int APW = GBM / 16 / NWAVE, WPW = GBN / 16 / NWAVE;  // 16-row DMA pieces per wave per k-tile
-    static_assert(NWAVE * 64 * 64 * 4 <= STAGES * STAGE_BYTES, "epilogue staging must fit in the stage buffers");
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const GemmProblem pr = a.p[blockIdx.z];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave / WAVES_N, wc = wave % WAVES_N;
-    int rt, ct;
-    {
-        const int bid = blockIdx.x;
-        if (a.xcd_remap) {
-            const int x = bid & 7, j = bid >> 3;
-            rt = x + 8 * (j / a.tiles_n);
-            ct = j % a.tiles_n;
-        } else {
-            rt = bid / a.tiles_n;
-            ct = bid % a.tiles_n;
-        }
-    }
-    const int m0 = rt * GBM, n0 = ct * GBN;
-
-    // DMA coordinates: lane -> (row = piece * 16 + lane / 4, physical chunk = lane % 4)
-    const int lrow = lane >> 2, chunk = lane & 3;
-    const char* a_ptr[APW];
-    const char* w_ptr[WPW];
-    int a_t0[APW];
-#pragma unroll
-    for (int i = 0; i < APW; ++i) {
-        const int r = (wave * APW + i) * 16 + lrow;
-        const int col_bytes = (chunk ^ ((r >> 2) & 3)) * 16;
-        const int m = min(m0 + r, a.M - 1);
-        if (CONV) {
-            if (a.rowmap) {
-                const int2 rm = a.rowmap[m];
-                a_t0[i] = rm.y;
-                a_ptr[i] = reinterpret_cast<const char*>(pr.A) + (long long)rm.x * a.Cin * 4 + col_bytes;
-            } else {
-                const int rr = m / a.T_out, to = m - rr * a.T_out;
-                const int t0 = to * a.stride - a.pad;
-                a_t0[i] = conv_tap_bits(t0, a.T_in);
-                a_ptr[i] = reinterpret_cast<const char*>(pr.A) + ((long long)rr * a.T_in + t0) * a.Cin * 4 + col_bytes;
-            }
-        } else {
-            a_t0[i] = 0;
-            a_ptr[i] = reinterpret_cast<const char*>(pr.A + (long long)m * a.lda) + col_bytes;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < WPW; ++i) {
-        const int r = (wave * WPW + i) * 16 + lrow;
-        const int n = min(n0 + r, a.N - 1);
-        w_ptr[i] = reinterpret_cast<const char*>(pr.W + (long long)n * a.K) + (chunk ^ ((r >> 2) & 3)) * 16;
-    }
-    const char* zero = reinterpret_cast<const char*>(g_zero_page);
-    const int nk = a.K / KB;
-    int conv_kk = 0, conv_c = 0;
-    int dma_kt = 0;
-
-    auto issue = [&](int stage) {  // k-tiles in increasing order, one per call; past the last one the pointers stop (see the kernel above)
-        char* sbase = lds + stage * STAGE_BYTES;
-#pragma unroll
-        for (int i = 0; i < APW; ++i) {
-            const char* src = a_ptr[i];
-            if (CONV) src = ((a_t0[i] >> conv_kk) & 1) ? src : zero;
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sbase + (wave * APW + i) * 1024), 16, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < WPW; ++i) {
-            __builtin_amdgcn_global_load_lds((gptr_t)w_ptr[i], (lptr_t)(sbase + GBM * RB + (wave * WPW + i) * 1024), 16, 0, 0);
-        }
-        const bool more = dma_kt + 1 < nk;
-        const int adv = more ? KB * 4 : 0;
-#pragma unroll
-        for (int i = 0; i < APW; ++i) a_ptr[i] += adv;
-#pragma unroll
-        for (int i = 0; i < WPW; ++i) w_ptr[i] += adv;
-        if (CONV) {
-            conv_c += more ? KB : 0;
-            const bool wrap = conv_c == a.Cin;
-            conv_c = wrap ? 0 : conv_c;
-            conv_kk += wrap ? 1 : 0;
-        }
-        ++dma_kt;
-    };
-
-    f32x16 acc[MI][2];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int fr = lane & 31, fh = lane >> 5, key = (lane >> 2) & 3;  // the key is the same for all of a lane's rows (they differ by multiples of 32)
-    const int a_frag = (wr * MI * 32 + fr) * RB, w_frag = GBM * RB + (wc * 64 + fr) * RB;
-    const int hi_off = ((fh * 2) ^ key) << 4, lo_off = hi_off ^ 16;
-
-    // The fragment reads are inline asm: in front of a compiler-visible LDS read the waitcnt pass puts vmcnt(0) (LDS-DMA pieces are in
-    // flight, and it cannot tell the stages apart), which would cut the DMA's two batches of cover to none.  land() is their wait: it
-    // names the fragments as in/out operands, so every use of them is ordered behind it.
-    struct Frags { half8 ah[MI], al[MI], bh[2], bl[2]; };
-    const unsigned a_hi = (unsigned)(a_frag + hi_off), a_lo = (unsigned)(a_frag + lo_off);
-    const unsigned w_hi = (unsigned)(w_frag + hi_off), w_lo = (unsigned)(w_frag + lo_off);
-#define K16_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr) : "memory")
-    auto load_frags = [&](int stage, Frags& f) {
-        const unsigned sb = (unsigned)(uintptr_t)(lptr_t)lds + (unsigned)(stage * STAGE_BYTES);
-        const unsigned wh = sb + w_hi, wl = sb + w_lo, ah = sb + a_hi, al = sb + a_lo;
-        K16_RD(f.bh[0], wh, 0);
-        K16_RD(f.bl[0], wl, 0);
-        K16_RD(f.bh[1], wh, 2048);
-        K16_RD(f.bl[1], wl, 2048);
-        K16_RD(f.ah[0], ah, 0);
-        K16_RD(f.al[0], al, 0);
-        K16_RD(f.ah[1], ah, 2048);
-        K16_RD(f.al[1], al, 2048);
-        K16_RD(f.ah[2], ah, 4096);
-        K16_RD(f.al[2], al, 4096);
-        K16_RD(f.ah[3], ah, 6144);
-        K16_RD(f.al[3], al, 6144);
-    };
-#undef K16_RD
-    static_assert(MI == 4 && 32 * RB == 2048, "the offsets above");
-    auto land = [&](Frags& f, auto vm) {  // the DMA of the next k-tile and this wave's fragment reads are complete
-        asm volatile("s_waitcnt vmcnt(%12) lgkmcnt(0)"
-                     : "+v"(f.ah[0]), "+v"(f.ah[1]), "+v"(f.ah[2]), "+v"(f.ah[3]), "+v"(f.al[0]), "+v"(f.al[1]), "+v"(f.al[2]), "+v"(f.al[3]),
-                       "+v"(f.bh[0]), "+v"(f.bh[1]), "+v"(f.bl[0]), "+v"(f.bl[1])
-                     : "n"(decltype(vm)::value)
-                     : "memory");
-    };
-    auto mfma1 = [&](const Frags& f, int i, int j, int which) {
-        if constexpr (PURE == 2) {
-            if (which == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.al[i]), __builtin_bit_cast(bf16x8, f.bl[j]), acc[i][j], 0, 0, 0);
-            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.ah[i]), __builtin_bit_cast(bf16x8, f.bh[j]), acc[i][j], 0, 0, 0);
-        } else if constexpr (PURE == 1) {
-            if (which == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[i], f.bl[j], acc[i][j], 0, 0, 0);
-            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[i], f.bh[j], acc[i][j], 0, 0, 0);
-        } else {
-            if (which == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[i], f.bh[j], acc[i][j], 0, 0, 0);
-            else if (which == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[i], f.bl[j], acc[i][j], 0, 0, 0);
-            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[i], f.bh[j], acc[i][j], 0, 0, 0);
-        }
-    };
-    constexpr int PER = PURE ? 2 : 3;  // MFMAs per accumulator and k-tile, in the order lo terms first (as in the kernels above)
-    auto mfmas_rest = [&](const Frags& f) {  // everything but (0, 0, term 0), which the step issues in front of the fragment reads
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int w = 0; w < PER; ++w)
-                    if (i || j || w) mfma1(f, i, j, w);
-    };
-
-    constexpr int NMF = PER * 2 * MI;
-    constexpr int NDMA = APW + WPW, DMA_GAP = (NMF - 1) / NDMA;
-    issue(0);
-    issue(1);
-    issue(2);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NDMA) : "memory");  // k-tile 0 is the oldest third of what is in flight
-    __builtin_amdgcn_s_barrier();
-    Frags f0, f1;
-    load_frags(0, f0);
-    int s0 = 0;  // stage of k-tile kt (whose fragments are in registers): it takes the DMA of k-tile kt + 3
-    auto step = [&](Frags& cur, Frags& nx) {
-        land(cur, std::integral_constant<int, NDMA>());  // k-tile kt+1 has landed (kt+2 may still be in flight); cur is in registers
-        __builtin_amdgcn_s_barrier();                    // ... for every wave, and nobody reads stage s0 any more
-        __builtin_amdgcn_sched_barrier(0);
-        const int s1 = s0 == 2 ? 0 : s0 + 1;
-        mfma1(cur, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        load_frags(s1, nx);  // behind the first MFMA: a batch to land
-        __builtin_amdgcn_sched_barrier(0);
-        issue(s0);
-        mfmas_rest(cur);
-#pragma unroll
-        for (int g = 0; g < NDMA; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, DMA_GAP, 0);
-            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - 1 - NDMA * DMA_GAP, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        s0 = s1;
-    };
-    for (int kt = 0; kt < nk; kt += 2) {  // K is a multiple of 32: an even number of 16-deep k-tiles
-        step(f0, f1);
-        step(f1, f0);
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the surplus DMA and fragment reads of the last iteration must not reach the epilogue's staging
-    __syncthreads();
-
-    glds_tile_epilogue<MI, WAVES_N>(a, pr, acc, lds, wave, lane, wr, wc, m0, n0);
-}
-
-
-// ---- weight gradients without transposed copies: dW[n][k] = sum_m dY[m][n] X[m][k] on ROW-MAJOR 16-bit operands -------------------
-// The reduction runs over the rows of both operands.  gemm_tn_split.hip's first route writes both matrices transposed (a streaming
-// pass of its own per operand, 12 % of a ragged training step) and runs the NT kernel above; this kernel reads the row-major 16-bit
-// casts the step has anyway (dY's is the dX GEMM's operand, X's the forward GEMM's) and transposes on the way from LDS to the
-// matrix pipe with gfx950's ds_read_b64_tr_b16: a k-tile is 64 rows x 256 columns of each operand (512-byte rows, two rows per 1-KiB
-// DMA piece), and a 4 (rows) x 16 (columns) block read by sixteen lanes - each supplying the address of one 8-byte piece - comes
-// back with lane j holding column j's four row values, i.e. half of a 32x32x16 MFMA operand.  The 16-byte chunks of a row are
-// XOR-swizzled by 4 * (row & 3): the eight rows one instruction touches (r..r+3 and r+8..r+11, 64 bytes each) then spread over all
-// sixteen 16-byte slots of the 256-byte bank line, two each - the minimum for a 512-byte read.
-// Same block shape, stages, halves and accumulator layout as the 256x256 NT kernel; split over the reduction like its ksplit mode:
-// work item = (tile, row range), partial sums to `part` for gemm.hip's ordered reduce.  Rows beyond M read the zero page.
-struct TnTrArgs {
-    GldsArgs e;  // the epilogue's view: M x N = the dW tile grid (N_out x K_out), ldc, part, ksplit, tiles_m / tiles_n
-    const char* A[3];      // dY as 16-bit rows [Mred][lda]
-    const char* B[3];      // X as 16-bit rows [Mred][ldb]
-    long long lda, ldb;    // row pitch in BYTES
-    int a_sp, b_sp;        // 1: the operand is a SPLIT-f16 row-major matrix (8-value blocks [hi8 | lo8], 4 bytes per value) and the
-                           // kernel takes its hi halves - exactly the plain f16 cast of the same values - by fetching every other
-                           // 16-byte chunk (the split-f16 step's dX operand doubles as the dW operand: no second cast of dY)
-    int Mred, kper, nkt;   // rows of the reduction; 64-row k-tiles per range / in total
-    // CONV kernels: B is the channels-last conv input [rows_in][Cin] and the product's column k = tap * Cin + ci (implicit im2col; a
-    // 256-column tile lies inside one tap: Cin % 256 == 0).  Reduction row m = (sequence r, output step to) reads source row
-    // r * T_in + to * stride + tap - pad, zeros outside [0, T_in); or, with rowmap (ragged batches), row rowmap[m].x + tap where bit
-    // `tap` of rowmap[m].y is set (GemmDesc::rowmap).
-    int Cin, T_in, T_out, stride, pad;
-    const int2* rowmap;
-};
-
-typedef short short4v __attribute__((__vector_size__(4 * sizeof(short))));
-
-template <int BF, int CONV = 0>  // CONV: 0 = plain rows, 1 = conv taps by geometry, 2 = conv taps by rowmap
-__global__ __launch_bounds__(512) void gemm_tn_tr_kernel(const TnTrArgs t) {
-    constexpr int MI = 4, WAVES_N = 4, NWAVE = 8, KT = 64;
-    constexpr int OPB = KT * 512, STAGE_BYTES = 2 * OPB;  // one operand's k-tile, one stage (A then B)
-    constexpr int PPW = KT / 2 / NWAVE;                   // two-row DMA pieces per wave, operand and k-tile
-    static_assert(NWAVE * 64 * 64 * 4 <= 2 * STAGE_BYTES, "epilogue staging must fit in the stage buffers");
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const GldsArgs& a = t.e;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave / WAVES_N, wc = wave % WAVES_N;
-    const int tiles = a.tiles_m * a.tiles_n;
-    int range, tile;
-    {   // consecutive block ids go to different XCDs: the tiles of one row range (they share its rows) stay on one XCD's L2
-        const int bid = blockIdx.x;
-        if ((a.ksplit & 7) == 0) {
-            const int x = bid & 7, q = bid >> 3;
-            range = x + 8 * (q / tiles);
-            tile = q % tiles;
-        } else {
-            range = bid / tiles;
-            tile = bid % tiles;
-        }
-    }
-    const int m0 = (tile / a.tiles_n) * 256, n0 = (tile % a.tiles_n) * 256;  // origin of the dW tile: row (dY column), column (X column)
-    const int kt0 = range * t.kper;
-    const int nk = min(t.nkt, kt0 + t.kper) - kt0;
-    const long long mstart = (long long)kt0 * KT;
-
-    // DMA coordinates: piece P = wave * PPW + i holds rows 2P, 2P+1 (lane / 32) of the k-tile; row & 3 = 2 * (i & 1) + lane / 32, so the
-    // swizzled source column is the same for pieces i and i + 2 (four rows apart): one pointer per parity and operand
-    const int prow = lane >> 5, pch = lane & 31;
-    const char* Ab = t.A[blockIdx.z];
-    const char* Bb = t.B[blockIdx.z];
-    const int row0 = wave * PPW * 2 + prow;
-    const char* a_ptr[2];
-    const char* b_ptr[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const int row = row0 + 2 * e;
-        const int logical = pch ^ (4 * (row & 3));
-        a_ptr[e] = Ab + (mstart + row) * t.lda + ((long long)(m0 * 2 + logical * 16) << t.a_sp);
-        b_ptr[e] = Bb + (mstart + row) * t.ldb + ((long long)(n0 * 2 + logical * 16) << t.b_sp);
-    }
-    const char* zero = reinterpret_cast<const char*>(g_zero_page);
-    const int rem0 = (int)min((long long)t.Mred - mstart, 1LL << 30);
-    int rem_a = rem0, rem_b = rem0;  // rows left from the start of the next k-tile to issue, per operand
-    const long long a_adv = (long long)KT * t.lda, b_adv = (long long)KT * t.ldb;
-    const long long a_r4 = 4 * t.lda, b_r4 = 4 * t.ldb;  // four rows further
-    // one operand's k-tile per call, in order; surplus calls behind the range fill a stage nobody reads; rows beyond M read zeros
-    auto issue_a = [&](int stage) {
-        char* sbase = lds + stage * STAGE_BYTES + wave * PPW * 1024;
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            const char* src = a_ptr[i & 1] + (i >> 1) * a_r4;
-            __builtin_amdgcn_global_load_lds((gptr_t)(row0 + 2 * i < rem_a ? src : zero), (lptr_t)(sbase + i * 1024), 16, 0, 0);
-        }
-        a_ptr[0] += a_adv;
-        a_ptr[1] += a_adv;
-        rem_a -= KT;
-    };
-    // CONV: the tile's tap and first channel; per piece the (sequence, step) of its row (geometry) or the prefetched rowmap entry
-    const int tap = CONV ? n0 / t.Cin : 0;
-    const int bcol = CONV ? ((n0 - tap * t.Cin) * 2 + (pch ^ (4 * (row0 & 3))) * 16) << t.b_sp : 0;  // even pieces; odd ones flip chunk bit 3
-    const int bcol_odd = CONV ? ((n0 - tap * t.Cin) * 2 + (pch ^ (4 * ((row0 + 2) & 3))) * 16) << t.b_sp : 0;
-    int c_rr[PPW], c_to[PPW];
-    int2 c_rm[PPW];
-    const int q64 = CONV == 1 ? KT / t.T_out : 0, r64 = CONV == 1 ? KT % t.T_out : 0;
-    long long m_b = mstart;  // first row of the next B k-tile to issue
-    if constexpr (CONV == 1) {
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            const long long m = mstart + row0 + 2 * i;
-            c_rr[i] = (int)(m / t.T_out);
-            c_to[i] = (int)(m - (long long)c_rr[i] * t.T_out);
-        }
-    }
-    if constexpr (CONV == 2) {
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) c_rm[i] = t.rowmap[min(mstart + row0 + 2 * i, (long long)t.Mred - 1)];
-    }
-    auto issue_b = [&](int stage) {
-        char* sbase = lds + stage * STAGE_BYTES + OPB + wave * PPW * 1024;
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            const char* src;
-            bool ok = row0 + 2 * i < rem_b;
-            if constexpr (CONV == 0) {
-                src = b_ptr[i & 1] + (i >> 1) * b_r4;
-            } else {
-                long long srow;
-                if constexpr (CONV == 1) {
-                    const int ti = c_to[i] * t.stride + tap - t.pad;
-                    ok = ok && (unsigned)ti < (unsigned)t.T_in;
-                    srow = (long long)c_rr[i] * t.T_in + ti;
-                    c_rr[i] += q64;
-                    c_to[i] += r64;
-                    const bool wrap = c_to[i] >= t.T_out;
-                    c_to[i] -= wrap ? t.T_out : 0;
-                    c_rr[i] += wrap ? 1 : 0;
-                } else {
-                    ok = ok && ((c_rm[i].y >> tap) & 1);
-                    srow = (long long)c_rm[i].x + tap;
-                }
-                src = Bb + srow * t.ldb + ((i & 1) ? bcol_odd : bcol);
-            }
-            __builtin_amdgcn_global_load_lds((gptr_t)(ok ? src : zero), (lptr_t)(sbase + i * 1024), 16, 0, 0);
-        }
-        if constexpr (CONV == 0) {
-            b_ptr[0] += b_adv;
-            b_ptr[1] += b_adv;
-        }
-        rem_b -= KT;
-        if constexpr (CONV == 2) {  // the next k-tile's entries: a k-tile (and its barrier's vmcnt(0)) ahead of their use
-            m_b += KT;
-#pragma unroll
-            for (int i = 0; i < PPW; ++i) c_rm[i] = t.rowmap[min(m_b + row0 + 2 * i, (long long)t.Mred - 1)];
-        }
-    };
-
-    f32x16 acc[MI][2];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // transposing fragment reads: sixteen-lane group (g2, g1) = (k half of the operand, 16-column half of the 32-wide fragment);
-    // lane j of the group addresses row j >> 2 of the group's four rows, 8-byte piece j & 3 of its 16 columns
-    const int j16 = lane & 15, g1 = (lane >> 4) & 1, g2 = lane >> 5;
-    const int q = j16 >> 2;  // = row & 3 of every row this lane addresses: the swizzle key
-    const int lane_off = (8 * g2 + q) * 512 + (2 * g1 + ((j16 & 3) >> 1)) * 16 + 8 * (j16 & 1);
-    int a_off[MI], b_off[2];
-#pragma unroll
-    for (int i = 0; i < MI; ++i) a_off[i] = lane_off + ((wr * 4 + (i ^ q)) << 6);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) b_off[j] = OPB + lane_off + (((wc * 2 + j) ^ q) << 6);
-
-    // The fragment reads are inline asm (as in the k16 kernel above): in front of a compiler-visible LDS read the waitcnt pass puts
-    // vmcnt(0) while LDS-DMA pieces are in flight, which would expose the whole DMA latency once per k-tile.  land() is their wait.
-    struct Frags { half8 a[MI], b[2]; };  // one 16-row step
-    const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)lds;
-#define TR_RD(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #off : "=v"(dst) : "v"(addr) : "memory")
-#define TR_STEP(f, base, OFF)                                                                                                        \
-    {                                                                                                                                \
-        short4v l_, h_;                                                                                                              \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                                              \
-            TR_RD(l_, base + b_off[j], OFF); TR_RD(h_, base + b_off[j], OFF + 2048);                                                 \
-            f.b[j] = __builtin_bit_cast(half8, __builtin_shufflevector(l_, h_, 0, 1, 2, 3, 4, 5, 6, 7));                             \
-        }                                                                                                                            \
-        _Pragma("unroll") for (int i = 0; i < MI; ++i) {                                                                             \
-            TR_RD(l_, base + a_off[i], OFF); TR_RD(h_, base + a_off[i], OFF + 2048);                                                 \
-            f.a[i] = __builtin_bit_cast(half8, __builtin_shufflevector(l_, h_, 0, 1, 2, 3, 4, 5, 6, 7));                             \
-        }                                                                                                                            \
-    }
-    auto land = [&](Frags& f) {  // this wave's fragment reads are complete; every use of f is ordered behind this
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.b[0]), "+v"(f.b[1])::"memory");
-    };
-    auto mfma1 = [&](const Frags& f, int i, int j) {
-        if constexpr (BF) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.a[i]), __builtin_bit_cast(bf16x8, f.b[j]), acc[i][j], 0, 0, 0);
-        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[i], f.b[j], acc[i][j], 0, 0, 0);
-    };
-    auto mfmas_rest = [&](const Frags& f) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                if (i || j) mfma1(f, i, j);
-    };
-    constexpr int NMF = 2 * MI;  // MFMAs of one 16-row step
-    auto spread_dma = [&]() {    // the PPW DMA pieces of one operand, one behind each of the step's following MFMAs
-#pragma unroll
-        for (int g = 0; g < PPW; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - 1 - PPW, 0);
-    };
-
-    // A k-tile is four 16-row steps on two alternating fragment sets; the next step's reads go right behind a step's first MFMA.
-    // ONE barrier per k-tile, in front of its last step: by then every wave has its last fragments of the stage in registers (so the
-    // stage can take the DMA of k-tile kt+2: A during that last step, B during the next k-tile's first) and k-tile kt+1 has had three
-    // steps to land, so its first fragments are fetched under the last step's MFMAs.
-    issue_a(0);
-    issue_b(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    int stage = 0;
-    Frags f0, f1;
-    TR_STEP(f0, lds0, 0);
-    issue_a(1);
-    for (int kt = 0; kt < nk; ++kt) {
-        const unsigned cur = lds0 + (unsigned)(stage * STAGE_BYTES), nxt = lds0 + (unsigned)((stage ^ 1) * STAGE_BYTES);
-        // step 0
-        land(f0);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma1(f0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        TR_STEP(f1, cur, 8192);
-        __builtin_amdgcn_sched_barrier(0);
-        issue_b(stage ^ 1);
-        mfmas_rest(f0);
-        spread_dma();
-        __builtin_amdgcn_sched_barrier(0);
-        // step 1
-        land(f1);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma1(f1, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        TR_STEP(f0, cur, 16384);
-        __builtin_amdgcn_sched_barrier(0);
-        mfmas_rest(f1);
-        __builtin_amdgcn_sched_barrier(0);
-        // step 2
-        land(f0);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma1(f0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        TR_STEP(f1, cur, 24576);
-        __builtin_amdgcn_sched_barrier(0);
-        mfmas_rest(f0);
-        __builtin_amdgcn_sched_barrier(0);
-        // step 3, behind the barrier
-        land(f1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // k-tile kt+1 has landed
-        __builtin_amdgcn_s_barrier();                      // ... for every wave, and nobody reads this stage any more
-        __builtin_amdgcn_sched_barrier(0);
-        mfma1(f1, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        TR_STEP(f0, nxt, 0);  // past the last k-tile this reads stale LDS and is never used
-        __builtin_amdgcn_sched_barrier(0);
-        issue_a(stage);
-        mfmas_rest(f1);
-        spread_dma();
-        __builtin_amdgcn_sched_barrier(0);
-        stage ^= 1;
-    }
-#undef TR_STEP
-#undef TR_RD
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the surplus DMA and reads must not reach the epilogue's staging
-    __syncthreads();
-
-    GemmProblem pr{};
-    const long long slab = ((long long)blockIdx.z * a.ksplit + range) * a.M * a.N;
-    // (c_f16: the partial sums leave as 16-bit rows - bfloat16 in the bf16 step: GemmTnTrDesc::part_bf16)
-    pr.C = a.c_f16 ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(a.part) + slab) : a.part + slab;
-    glds_tile_epilogue<MI, WAVES_N>(a, pr, acc, lds, wave, lane, wr, wc, m0, n0);
-}
-
-// the ordered reduce of bfloat16 partial sums: C = scales * (sum over the slabs, in index order), four columns per thread
-__global__ __launch_bounds__(256) void splitk_reduce_bf16_kernel(const unsigned short* __restrict__ part, int ksplit, long long mn, int N, int ldc,
-                                                                 float* c0, float* c1, float* c2, const float* __restrict__ s0,
-                                                                 const float* __restrict__ s1) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;  // quad index within one problem
-    if (i * 4 >= mn) return;
-    const int z = blockIdx.z;
-    const unsigned short* p = part + (long long)z * ksplit * mn + i * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = 0; k < ksplit; ++k) {
-        const uint2 w = *reinterpret_cast<const uint2*>(p + (long long)k * mn);
-        acc.x += __builtin_bit_cast(float, w.x << 16); acc.y += __builtin_bit_cast(float, w.x & 0xffff0000u);
-        acc.z += __builtin_bit_cast(float, w.y << 16); acc.w += __builtin_bit_cast(float, w.y & 0xffff0000u);
-    }
-    const float osc = (s0 ? *s0 : 1.f) * (s1 ? *s1 : 1.f);
-    float* c = z == 0 ? c0 : (z == 1 ? c1 : c2);
-    const long long e = i * 4, m = e / N, n = e - m * N;
-    *reinterpret_cast<float4*>(c + m * ldc + n) = make_float4(acc.x * osc, acc.y * osc, acc.z * osc, acc.w * osc);
-}
-
-
 // ---- persistent 256x256 variant ----------------------------------------------------------------------------------
 // One block per CU walks tiles blockIdx.x, +gridDim.x, ...  What the one-tile-per-block kernel above loses between
 // tiles (measured, M=65536 N=K=1024: loop 70 us per tile, + ~12 us of DMA start-up and block turnover, + 20 us
@@ -976,6 +276,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_split_glds_persist_kernel(con
     // Tile order: the problems of a launch (q/k/v projections of the same rows) are the innermost index next to the column
     // tile, so the nprob * tiles_n tiles that read one 256-row block of A run back to back on one XCD and A comes from HBM once.
     // The k ranges of a split-K launch are further "problems" in that order.
+    // LOCAL FORMS: this kernel sits at a spill boundary.  Its decode and the row / window / swizzle arithmetic of setup_dma are
+    // gemm_common.h's tile_decode and composite-column rule, conv_window and dma_* helpers written out: taken through the helpers, every
+    // instantiation's register row moves and the conv ones spill vector registers (profiles/gemm_common_isa.txt).  a.order == 1 is
+    // a measurement order of this kernel alone.
     const int tiles_row = a.tiles_n * a.nprob * ks_n;
     const int total = a.tiles_m * tiles_row;
     auto decode = [&](int tile, int& z, int& ks, int& m0, int& n0) {
@@ -988,7 +292,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_split_glds_persist_kernel(con
             const int rg = g / cg;                         // row-panel group (8 panels) of this XCD
             c = (g - rg * cg) * 4 + (l & 3);
             rt = x + 8 * (rg * 8 + (l >> 2));
-        } else if (a.xcd_remap) {
+        } else if (a.xcd_remap) {  // gemm_common.h's tile_decode and composite-column rule, written out (below)
             const int x = tile & 7, j = tile >> 3;
             rt = x + 8 * (j / tiles_row);
             c = j % tiles_row;
@@ -1411,10 +715,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_split_glds_persist_kernel(con
             // subtract that followed the exec restore lost its low half in lanes 48..63 about five times per 65536 strips
             // (measured on the fused-norm epilogue: the element left the epilogue uncentred).
             unsigned long long out_of_range = 0;  // lane mask, kept in scalar registers
-            auto note_range = [&](const float (&v)[4]) {
-                const float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));  // drops NaNs
-                out_of_range |= __builtin_amdgcn_ballot_w64(!(m < 65000.f) || __builtin_isunordered(v[0], v[1]) || __builtin_isunordered(v[2], v[3]));
-            };
+            auto note_range = [&](const float (&v)[4]) { out_of_range |= f16_range_ballot4(v); };
 #pragma unroll
             for (int b = 0; b < 8 / RB; ++b) {
                 f32x4 rbuf[RB * 4];
@@ -1600,7 +901,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_split_glds_persist_kernel(con
                     if (CSP == 2) {
                         if (n >= a.N) continue;  // N % 4 == 0: the four columns are in range together
                         *reinterpret_cast<half4*>(reinterpret_cast<_Float16*>(pr.C) + (long long)m * ldc + n) = cvt16x4_out(v, PURE == 2);
-                        if (PURE != 2) guard_sp16x4(a.guard, v);
+                        if (PURE != 2) f16_range_guard4(a.guard, v);
                     } else if (CSP == 1) {
                         if (n >= a.N) continue;  // N % 8 == 0 and n % 4 == 0: the four columns are in range together
                         _Float16* cb = reinterpret_cast<_Float16*>(pr.C + (long long)m * ldc + (n & ~7)) + (n & 4);
@@ -1609,7 +910,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_split_glds_persist_kernel(con
                         for (int e = 0; e < 4; ++e) { _Float16 h1, l1; split_f16(v[e], h1, l1); hh[e] = h1; ll[e] = l1; }
                         *reinterpret_cast<half4*>(cb) = hh;
                         *reinterpret_cast<half4*>(cb + 8) = ll;
-                        guard_sp16x4(a.guard, v);
+                        f16_range_guard4(a.guard, v);
                     } else if (vec_ok) {
                         *reinterpret_cast<float4*>(pr.C + (long long)m * ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
                     } else {
@@ -1649,400 +950,14 @@ bool gemm_split_glds_supported(const GemmDesc& d) {
     return d.lda % 8 == 0;
 }
 
-// Ping-pong variant (sola_tune "gemm_pp"; plain launches without residual whose tiles are all interior and K >= 352): 256x128
-// tiles, four waves = ONE per SIMD with up to 512 registers, TWO accumulator sets.  The epilogue of a tile does not run behind
-// its k-loop: its eight strips are drained one per k-tile under the first eight k-tiles of the block's NEXT tile (LDS transpose
-// and conversion between that k-tile's MFMAs, the strip's stores behind the k-tile's last DMA piece, so the next k-tile's wait
-// names them - vmcnt(stores per strip) - instead of waiting for their acknowledgement).  Same fragments, same accumulation
-// order and the same epilogue arithmetic as the kernel above: results are bit-identical.
-template <bool CONV, int CSP>
-__global__ __launch_bounds__(256) void gemm_nt_split_glds_pp_kernel(const GldsArgs a) {
-    constexpr int NW = 4;
-    constexpr bool PURE = false;
-    constexpr int MI = 4, WAVES_N = NW / 2, GBM = 256, GBN = WAVES_N * 64, NWAVE = NW;
-    constexpr int STAGE_BYTES = (GBM + GBN) * ROWB;
-    constexpr int APW = GBM / 8 / NWAVE, WPW = GBN / 8 / NWAVE;
-    constexpr int STRIP_ROWS = 16;
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave / WAVES_N, wc = wave % WAVES_N;
-    const int ks_n = a.ksplit > 1 ? a.ksplit : 1;
-    const int nk = a.ksplit > 1 ? a.kper : a.K / GBK;
-
-    // Tile order: the problems of a launch (q/k/v projections of the same rows) are the innermost index next to the column
-    // tile, so the nprob * tiles_n tiles that read one 256-row block of A run back to back on one XCD and A comes from HBM once.
-    // The k ranges of a split-K launch are further "problems" in that order.
-    const int tiles_row = a.tiles_n * a.nprob * ks_n;
-    const int total = a.tiles_m * tiles_row;
-    auto decode = [&](int tile, int& z, int& ks, int& m0, int& n0) {
-        int rt, c;
-        if (a.xcd_remap) {
-            const int x = tile & 7, j = tile >> 3;
-            rt = x + 8 * (j / tiles_row);
-            c = j % tiles_row;
-        } else {
-            rt = tile / tiles_row;
-            c = tile % tiles_row;
-        }
-        const int zz = c / a.tiles_n;
-        z = zz / ks_n;
-        ks = zz - z * ks_n;
-        m0 = rt * GBM;
-        n0 = (c - zz * a.tiles_n) * GBN;
-    };
-
-    // ---- DMA stream state (same piece layout as the kernel above)
-    const int lrow = lane >> 3, chunk = lane & 7;
-    const char* a_ptr0;  // piece 0's running source pointer; pieces 1.. are a_ptr0 + a_d[i] (rows of a tile ascend in memory)
-    const char* w_ptr0;
-    int a_d[APW], w_d[WPW];
-    int a_t0[APW];
-    int conv_kk = 0, conv_c = 0;
-    int dma_kt = 0;  // next k-tile of the DMA stream within its tile
-    const char* zero = reinterpret_cast<const char*>(g_zero_page);
-    auto setup_dma = [&](int tile) {
-        int z, ks, m0, n0;
-        decode(tile, z, ks, m0, n0);
-        const int k0 = ks * nk * GBK;  // first reduction index of this work item
-        const float* A = a.p[z].A + k0;
-        const float* Wt = a.p[z].W + k0;
-#pragma unroll
-        for (int i = 0; i < APW; ++i) {
-            const int r = (wave * APW + i) * 8 + lrow;
-            const int col_bytes = (chunk ^ ((r >> 1) & 7)) * 16;
-            const int m = min(m0 + r, a.M - 1);
-            const char* p;
-            if (CONV) {
-                if (a.rowmap) {
-                    const int2 rm = a.rowmap[m];
-                    a_t0[i] = rm.y;
-                    p = reinterpret_cast<const char*>(A) + (long long)rm.x * a.Cin * 4 + col_bytes;
-                } else {
-                    const int rr = m / a.T_out, to = m - rr * a.T_out;
-                    const int t0 = to * a.stride - a.pad;
-                    a_t0[i] = conv_tap_bits(t0, a.T_in);
-                    p = reinterpret_cast<const char*>(A) + ((long long)rr * a.T_in + t0) * a.Cin * 4 + col_bytes;
-                }
-            } else {
-                a_t0[i] = 0;
-                p = reinterpret_cast<const char*>(A + (long long)m * a.lda) + col_bytes;
-            }
-            if (i == 0) a_ptr0 = p;
-            a_d[i] = (int)(p - a_ptr0);
-        }
-#pragma unroll
-        for (int i = 0; i < WPW; ++i) {
-            const int r = (wave * WPW + i) * 8 + lrow;
-            const int n = min(n0 + r, a.N - 1);
-            const char* p = reinterpret_cast<const char*>(Wt + (long long)n * a.K) + (chunk ^ ((r >> 1) & 7)) * 16;
-            if (i == 0) w_ptr0 = p;
-            w_d[i] = (int)(p - w_ptr0);
-        }
-        conv_kk = CONV ? k0 / a.Cin : 0;
-        conv_c = CONV ? k0 - conv_kk * a.Cin : 0;
-        dma_kt = 0;
-    };
-    auto issue = [&](int stage) {
-        char* sbase = lds + stage * STAGE_BYTES;
-#pragma unroll
-        for (int i = 0; i < APW; ++i) {
-            const char* src = a_ptr0 + a_d[i];
-            if (CONV) src = ((a_t0[i] >> conv_kk) & 1) ? src : zero;
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sbase + (wave * APW + i) * 1024), 16, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < WPW; ++i) {
-            __builtin_amdgcn_global_load_lds((gptr_t)(w_ptr0 + w_d[i]), (lptr_t)(sbase + GBM * ROWB + (wave * WPW + i) * 1024), 16, 0, 0);
-        }
-        // past the last k-tile of the last tile the stream re-reads that k-tile (see the one-tile kernel)
-        const bool more = dma_kt + 1 < nk;
-        const int adv = more ? GBK * 4 : 0;
-        a_ptr0 += adv;
-        w_ptr0 += adv;
-        if (CONV) {  // branch-free: a branch here would split the basic block the DMA is interleaved in
-            conv_c += more ? GBK : 0;
-            const bool wrap = conv_c == a.Cin;
-            conv_c = wrap ? 0 : conv_c;
-            conv_kk += wrap ? 1 : 0;
-        }
-        ++dma_kt;
-    };
-
-    const int fr = lane & 31, fh = lane >> 5, key = (lane >> 1) & 7;
-    const int a_frag = (wr * MI * 32 + fr) * ROWB, w_frag = GBM * ROWB + (wc * 64 + fr) * ROWB;
-    struct Frags { half8 ah[MI], al[MI], bh[2], bl[2]; };
-    auto load_frags = [&](const char* sbase, int s16, Frags& f) {
-        const int hi_off = (((s16 * 2 + fh) * 2) ^ key) << 4;
-        const int lo_off = hi_off ^ 16;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const char* q = sbase + w_frag + j * 32 * ROWB;
-            f.bh[j] = *reinterpret_cast<const half8*>(q + hi_off);
-            f.bl[j] = *reinterpret_cast<const half8*>(q + lo_off);
-        }
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-            const char* p = sbase + a_frag + i * 32 * ROWB;
-            f.ah[i] = *reinterpret_cast<const half8*>(p + hi_off);
-            f.al[i] = *reinterpret_cast<const half8*>(p + lo_off);
-        }
-    };
-    f32x16 acc[2][MI][2];  // accumulator sets of the tile in flight and of the tile being drained
-    auto mfmas = [&](auto pc, const Frags& f) {
-        constexpr int P = decltype(pc)::value;
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                if constexpr (PURE) {
-                    acc[P][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[i], f.bl[j], acc[P][i][j], 0, 0, 0);
-                    acc[P][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[i], f.bh[j], acc[P][i][j], 0, 0, 0);
-                } else {
-                    acc[P][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[i], f.bh[j], acc[P][i][j], 0, 0, 0);
-                    acc[P][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[i], f.bl[j], acc[P][i][j], 0, 0, 0);
-                    acc[P][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[i], f.bh[j], acc[P][i][j], 0, 0, 0);
-                }
-            }
-    };
-
-
-    int tile = blockIdx.x;
-    if (tile >= total) return;
-    setup_dma(tile);
-    issue(0);
-    issue(1);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(APW + WPW) : "memory");
-    __syncthreads();
-    int stage = 0;
-    constexpr int NRD = 2 * MI + 4, NMF = 6 * MI;
-    constexpr int NDMA = APW + WPW, DMA_GAP = (NMF - 1) / NDMA;
-    constexpr int NST = CSP == 1 ? 8 : 4;  // global stores per strip and wave
-
-    // Lane coordinates of the epilogue are re-derived from an opaque copy of the thread id inside every strip: derived once, the
-    // compiler hoists the addresses of all eight strips out of the tile loop and keeps them - spilled - across the k-loops.
-    const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: costs no vector register across the k-loops
-#define PP_LANE_COORDS                                                                                   \
-    int le = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));                    \
-    asm volatile("" : "+v"(le));                                                                         \
-    const int lane_e = le, wave_e = wave_s;                                                              \
-    const int fh_e = lane_e >> 5;                                                                        \
-    float* strip = reinterpret_cast<float*>(lds + 2 * STAGE_BYTES) + wave_e * (STRIP_ROWS * 64);         \
-    const int col_l = lane_e & 31;                                                                       \
-    const int c4 = lane_e & 15, rsub = lane_e >> 4;                                                      \
-    const int wr_e = wave_e / WAVES_N, wc_e = wave_e % WAVES_N;                                          \
-    (void)fh_e; (void)strip; (void)col_l; (void)c4; (void)rsub; (void)wr_e; (void)wc_e;
-
-    // the tile whose accumulators wait to be drained
-    float* pend_C = nullptr;
-    float pend_osc = 1.f;
-    float4 pend_bv = make_float4(0.f, 0.f, 0.f, 0.f);
-    int pend_m0 = 0, pend_n = 0;
-    unsigned long long out_of_range = 0;
-
-    // one strip (16 rows x this wave's 64 columns) of accumulator set Q: LDS transpose + conversion (part 1), stores (part 2)
-    f32x4 sv[4];
-    auto strip_compute = [&](auto qc, auto stc) {
-        constexpr int Q = decltype(qc)::value, st = decltype(stc)::value, i = st >> 1, hf = st & 1;
-        PP_LANE_COORDS
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int row = (q & 3) + 8 * (q >> 2) + 4 * fh_e;
-                const int col = (j * 32 + col_l) ^ (fh_e << 5);
-                strip[row * 64 + col] = acc[Q][i][j][hf * 8 + q];
-            }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the strip is written (in-order LDS queue; wave-private region)
-        __builtin_amdgcn_wave_barrier();
-        // The four reads go through inline asm with their own lgkmcnt wait: in front of a compiler-visible LDS read the waitcnt pass
-        // puts vmcnt(0) here (LDS-DMA pieces and the previous strip's stores are in flight) - exactly the wait this kernel avoids.
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-            const int row = pass * 4 + rsub;
-            const unsigned addr = (unsigned)(uintptr_t)(lptr_t)&strip[row * 64 + ((c4 ^ ((pass & 1) << 3)) << 2)];
-            asm volatile("ds_read_b128 %0, %1" : "=v"(sv[pass]) : "v"(addr) : "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sv[0]), "+v"(sv[1]), "+v"(sv[2]), "+v"(sv[3])::"memory");
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-            sv[pass][0] = sv[pass][0] * pend_osc + pend_bv.x; sv[pass][1] = sv[pass][1] * pend_osc + pend_bv.y;
-            sv[pass][2] = sv[pass][2] * pend_osc + pend_bv.z; sv[pass][3] = sv[pass][3] * pend_osc + pend_bv.w;
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto strip_store = [&](auto stc) {
-        constexpr int st = decltype(stc)::value, i = st >> 1, hf = st & 1;
-        PP_LANE_COORDS
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-            const int m = pend_m0 + wr_e * 128 + i * 32 + hf * 16 + pass * 4 + rsub;
-            if (CSP == 1) {
-                _Float16* cb = reinterpret_cast<_Float16*>(pend_C + (long long)m * a.ldc + (pend_n & ~7)) + (pend_n & 4);
-                half4 hh, ll;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { _Float16 h1, l1; split_f16(sv[pass][e], h1, l1); hh[e] = h1; ll[e] = l1; }
-                *reinterpret_cast<half4*>(cb) = hh;
-                *reinterpret_cast<half4*>(cb + 8) = ll;
-                const float mx = fmaxf(fmaxf(fabsf(sv[pass][0]), fabsf(sv[pass][1])), fmaxf(fabsf(sv[pass][2]), fabsf(sv[pass][3])));
-                out_of_range |= __builtin_amdgcn_ballot_w64(!(mx < 65000.f) || __builtin_isunordered(sv[pass][0], sv[pass][1]) || __builtin_isunordered(sv[pass][2], sv[pass][3]));
-            } else {
-                *reinterpret_cast<float4*>(pend_C + (long long)m * a.ldc + pend_n) = make_float4(sv[pass][0], sv[pass][1], sv[pass][2], sv[pass][3]);
-            }
-        }
-    };
-    auto flush_guard = [&]() {
-        if (CSP == 1 && a.guard && out_of_range != 0 && (tid & 63) == 0) atomicOr(a.guard, 1);
-        out_of_range = 0;
-    };
-
-    Frags f0, f1;
-    // one k-tile of the tile accumulating into set P; ST >= 0: strip ST of set P ^ 1 is drained under it; RELAX: the previous
-    // k-tile ended with NST stores, which the wait for this k-tile's DMA may leave in flight
-    auto ktile = [&](auto pc, auto stc, auto relaxc) {
-        constexpr int P = decltype(pc)::value, ST = decltype(stc)::value;  // ST = 0..8: stores of strip ST - 1, transpose of strip ST
-        constexpr bool STORES = ST >= 1 && ST <= 8, COMPUTE = ST >= 0 && ST <= 7;
-        load_frags(lds + stage * STAGE_BYTES, 1, f1);
-        mfmas(pc, f0);
-        if constexpr (STORES) strip_store(std::integral_constant<int, STORES ? ST - 1 : 0>{});
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);
-        if constexpr (STORES) {  // the previous strip's stores, one per two MFMAs (a wave stuck at a full memory queue issues no MFMAs)
-#pragma unroll
-            for (int g = 0; g < NST; ++g) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, NMF - 1 - 2 * NST, 0);
-        } else {
-            __builtin_amdgcn_sched_group_barrier(0x008, NMF - 1, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // this strip's transpose through LDS behind the half's last MFMA issue (it runs under that MFMA and the barrier wait)
-        if constexpr (COMPUTE) strip_compute(std::integral_constant<int, P ^ 1>{}, std::integral_constant<int, COMPUTE ? ST : 0>{});
-        if constexpr (decltype(relaxc)::value) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);
-        load_frags(lds + (stage ^ 1) * STAGE_BYTES, 0, f0);
-        issue(stage);
-        mfmas(pc, f1);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);
-#pragma unroll
-        for (int g = 0; g < NDMA; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, DMA_GAP, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - 1 - NDMA * DMA_GAP, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        stage ^= 1;
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using NoStrip = std::integral_constant<int, -1>;
-    // one tile into accumulator set P; DRAIN: the other set holds the previous tile (strips under k-tiles 0..7)
-    auto run_tile = [&](auto pc, auto drainc) {
-        constexpr int P = decltype(pc)::value;
-        constexpr bool DRAIN = decltype(drainc)::value;
-        int z, ks, m0, n0;
-        decode(tile, z, ks, m0, n0);
-        const int next = tile + gridDim.x;
-        const bool has_next = next < total;
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[P][i][j][r] = 0.f;
-        load_frags(lds + stage * STAGE_BYTES, 0, f0);
-        if constexpr (DRAIN) {
-            ktile(pc, std::integral_constant<int, 0>{}, std::false_type{});
-            ktile(pc, std::integral_constant<int, 1>{}, std::true_type{});
-            ktile(pc, std::integral_constant<int, 2>{}, std::true_type{});
-            ktile(pc, std::integral_constant<int, 3>{}, std::true_type{});
-            ktile(pc, std::integral_constant<int, 4>{}, std::true_type{});
-            ktile(pc, std::integral_constant<int, 5>{}, std::true_type{});
-            ktile(pc, std::integral_constant<int, 6>{}, std::true_type{});
-            ktile(pc, std::integral_constant<int, 7>{}, std::true_type{});
-            ktile(pc, std::integral_constant<int, 8>{}, std::true_type{});
-            flush_guard();
-        } else {
-            for (int q = 0; q < 9; ++q) ktile(pc, NoStrip{}, std::false_type{});
-        }
-        int kt = 9;  // nk >= 11 (checked by the launcher)
-        for (; kt < nk - 2; ++kt) ktile(pc, NoStrip{}, std::false_type{});
-        if (has_next) setup_dma(next);
-        for (; kt < nk; ++kt) ktile(pc, NoStrip{}, std::false_type{});
-        // this tile's accumulators now wait for the next tile's k-loop (or the drain below)
-        const GemmProblem pr = a.p[z];
-        pend_C = pr.C;
-        pend_osc = (a.out_scale_dev ? a.out_scale * *a.out_scale_dev : a.out_scale) * (pr.scale_dev ? *pr.scale_dev : 1.f);
-        pend_m0 = m0;
-        {
-            PP_LANE_COORDS
-            pend_n = n0 + wc_e * 64 + c4 * 4;
-        }
-        pend_bv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (pr.bias) {
-            const float bsc = a.bias_scale_dev ? *a.bias_scale_dev : 1.f;
-            const float4 b4 = *reinterpret_cast<const float4*>(pr.bias + pend_n);
-            pend_bv = make_float4(b4.x * bsc, b4.y * bsc, b4.z * bsc, b4.w * bsc);
-        }
-    };
-    auto drain = [&](auto qc) {  // behind the block's last tile
-        strip_compute(qc, std::integral_constant<int, 0>{}); strip_store(std::integral_constant<int, 0>{});
-        strip_compute(qc, std::integral_constant<int, 1>{}); strip_store(std::integral_constant<int, 1>{});
-        strip_compute(qc, std::integral_constant<int, 2>{}); strip_store(std::integral_constant<int, 2>{});
-        strip_compute(qc, std::integral_constant<int, 3>{}); strip_store(std::integral_constant<int, 3>{});
-        strip_compute(qc, std::integral_constant<int, 4>{}); strip_store(std::integral_constant<int, 4>{});
-        strip_compute(qc, std::integral_constant<int, 5>{}); strip_store(std::integral_constant<int, 5>{});
-        strip_compute(qc, std::integral_constant<int, 6>{}); strip_store(std::integral_constant<int, 6>{});
-        strip_compute(qc, std::integral_constant<int, 7>{}); strip_store(std::integral_constant<int, 7>{});
-        flush_guard();
-    };
-    if (a.ablate & 4) {  // measurement: k-loops only, nothing is drained or stored
-        for (; tile < total; tile += gridDim.x) run_tile(I0{}, std::false_type{});
-        float keep = 0.f;
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) keep += acc[0][i][j][r];
-        if (keep == 12345.678f) a.p[0].C[tid] = keep;  // keeps the MFMAs alive
-        return;
-    }
-#undef PP_LANE_COORDS_UNUSED
-    run_tile(I0{}, std::false_type{});
-    tile += gridDim.x;
-    for (;;) {
-        if (tile >= total) { drain(I0{}); return; }
-        run_tile(I1{}, std::true_type{});
-        tile += gridDim.x;
-        if (tile >= total) { drain(I1{}); return; }
-        run_tile(I0{}, std::true_type{});
-        tile += gridDim.x;
-    }
-}
-
 template <int MI, int WAVES_M, int WAVES_N, bool CONV, int PURE = 0>
 static int launch_glds(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
     constexpr int GBM = MI * 32 * WAVES_M, GBN = 64 * WAVES_N;
     a.tiles_m = (M + GBM - 1) / GBM;
     a.tiles_n = (N + GBN - 1) / GBN;
-    a.xcd_remap = (a.tiles_m % 8 == 0) ? 1 : 0;
+    a.xcd_remap = xcd_remap_rows(a.tiles_m);
     constexpr size_t lds = (size_t)2 * (GBM + GBN) * ROWB;
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_split_glds_kernel<MI, WAVES_M, WAVES_N, CONV, PURE>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
-    hipLaunchKernelGGL((gemm_nt_split_glds_kernel<MI, WAVES_M, WAVES_N, CONV, PURE>), dim3(a.tiles_m * a.tiles_n, 1, nprob),
-                       dim3(WAVES_M * WAVES_N * 64), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
+    return launch_lds<gemm_nt_split_glds_kernel<MI, WAVES_M, WAVES_N, CONV, PURE>>(dim3(a.tiles_m * a.tiles_n, 1, nprob), dim3(WAVES_M * WAVES_N * 64), lds, s, a);
 }
 
 // sola_tune "gemm_gn_fuse" (EXPERIMENTS builds): 1 = encoder conv0-2 apply their GroupNorm + LeakyReLU in the GEMM epilogue.  Round 5 decision: CLOSED.
@@ -2053,9 +968,7 @@ static int launch_glds(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
 // change in the interior epilogue; the repeatability stress in the GPU suite), but a ~2 % step-time gain does not justify shipping an
 // unexplained fault's containment as the default.
 int g_gemm_gn_fuse = 0;
-int g_gemm_pp = 0;  // experiment (sola_tune "gemm_pp"): 1 = ping-pong kernel where it applies
 int g_gemm_nw4 = 0;  // experiment (sola_tune "gemm_nw4"): plain f32-output launches on 256x128 tiles with four waves, one per SIMD
-int g_gemm_k16 = 0;  // experiment (sola_tune "gemm_k16"): 256x128 tiles, 16-deep k-tiles, two four-wave blocks per CU
 int g_gemm_persist = 1;  // 256x256 shape: 1 = persistent kernel (one block per CU walks the tiles), 0 = one tile per block
 // measurement switches of the persistent kernel (sola_tune "gemm_stagger" / "gemm_order" / "gemm_trace"), all off in production
 int g_gemm_stagger = 0, g_gemm_order = 0, g_gemm_trace = 0, g_gemm_ld = 0;
@@ -2071,82 +984,24 @@ extern "C" long long sola_gemm_trace_read(void* host, long long bytes) {
     return (long long)n;
 }
 
-#ifdef SOLA_EXPERIMENTS
-template <bool CONV, int PURE>
-static int launch_k16(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
-    a.tiles_m = (M + 255) / 256;
-    a.tiles_n = (N + 127) / 128;
-    a.xcd_remap = (a.tiles_m % 8 == 0) ? 1 : 0;
-    constexpr size_t lds = (size_t)3 * (256 + 128) * 64;
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_split_glds_k16_kernel<CONV, PURE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
-    hipLaunchKernelGGL((gemm_nt_split_glds_k16_kernel<CONV, PURE>), dim3(a.tiles_m * a.tiles_n, 1, nprob), dim3(256), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-#endif
-
 template <bool CONV, int RMODE, int CSP, int PURE = 0, int GNT = 0, int NW = 8, int TRACE = 0, int LD = 0>
 static int launch_persist_t(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
     constexpr int GBN = NW / 2 * 64;
     a.tiles_m = (M + 255) / 256;
     a.tiles_n = (N + GBN - 1) / GBN;
-    a.xcd_remap = (a.tiles_m % 8 == 0) ? 1 : 0;
+    a.xcd_remap = xcd_remap_rows(a.tiles_m);
     a.nprob = nprob;
     constexpr size_t lds = (size_t)2 * (256 + GBN) * ROWB + NW * 16 * 64 * 4;  // two stages + one epilogue strip per wave (160 KiB at NW = 8)
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_split_glds_persist_kernel<CONV, RMODE, CSP, PURE, GNT, NW, TRACE, LD>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
-    const int n_cu = sola_cu_count();
     const int total = a.tiles_m * a.tiles_n * nprob * (a.ksplit > 1 ? a.ksplit : 1);
-    const int grid = total < n_cu ? total : n_cu;
-    hipLaunchKernelGGL((gemm_nt_split_glds_persist_kernel<CONV, RMODE, CSP, PURE, GNT, NW, TRACE, LD>), dim3(grid), dim3(NW * 64), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
+    const int grid = std::min(total, sola_cu_count());  // one block per CU walks the tiles
+    return launch_lds<gemm_nt_split_glds_persist_kernel<CONV, RMODE, CSP, PURE, GNT, NW, TRACE, LD>>(dim3(grid), dim3(NW * 64), lds, s, a);
 }
 
-
-#ifdef SOLA_EXPERIMENTS
-template <bool CONV, int CSP>
-static int launch_pp_t(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
-    a.tiles_m = M / 256;
-    a.tiles_n = N / 128;
-    a.xcd_remap = (a.tiles_m % 8 == 0) ? 1 : 0;
-    a.nprob = nprob;
-    constexpr size_t lds = (size_t)2 * (256 + 128) * ROWB + 4 * 16 * 64 * 4;
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_split_glds_pp_kernel<CONV, CSP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
-    const int n_cu = sola_cu_count();
-    const int total = a.tiles_m * a.tiles_n * nprob;
-    const int grid = total < n_cu ? total : n_cu;
-    hipLaunchKernelGGL((gemm_nt_split_glds_pp_kernel<CONV, CSP>), dim3(grid), dim3(256), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-// the ping-pong kernel takes launches without residual / norm / split-K whose tiles are all interior and whose k-loop is long
-// enough to drain eight strips under it
-static bool pp_applies(const GldsArgs& a, int M, int N) {
-    return g_gemm_pp && !a.p[0].R && !a.gn_gamma && a.ksplit <= 1 && M % 256 == 0 && N % 128 == 0 && (a.ldc & 3) == 0 && a.K / GBK >= 11 &&
-           (!a.p[0].bias || (reinterpret_cast<uintptr_t>(a.p[0].bias) & 15) == 0);
-}
-#endif
 
 template <bool CONV>
 static int launch_persist(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
 #ifdef SOLA_EXPERIMENTS
-    if (pp_applies(a, M, N)) return a.c_sp16 ? launch_pp_t<CONV, 1>(a, M, N, nprob, s) : launch_pp_t<CONV, 0>(a, M, N, nprob, s);
+    if (gemm_pp_applies(a, M, N)) return launch_gemm_pp(a, CONV, M, N, nprob, s);
 #endif
     if (a.ksplit > 1) return launch_persist_t<CONV, 0, 0>(a, M, N, nprob, s);  // partial sums: f32, no residual
 #ifdef SOLA_EXPERIMENTS
@@ -2188,26 +1043,22 @@ static int launch_persist(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
 }
 // plain f16 operands: C and the residual f16 (16-bit storage mode, inference) or both f32 (f16-operand training: the
 // activations stay f32, only the GEMM inputs are cast); split-K partial sums are always f32 without residual
+template <bool CONV, int PURE>
+static int launch_persist_pure_t(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
+    const bool has_r = a.p[0].R != nullptr;
+    if (a.ksplit > 1) return launch_persist_t<CONV, 0, 0, PURE>(a, M, N, nprob, s);
+    if (a.c_f16) {  // 16-bit outputs (with a 16-bit residual)
+        if (CONV || !has_r) return launch_persist_t<CONV, 0, 2, PURE>(a, M, N, nprob, s);
+        return launch_persist_t<false, 3, 2, PURE>(a, M, N, nprob, s);
+    }
+    if (has_r && !CONV) return launch_persist_t<false, 1, 0, PURE>(a, M, N, nprob, s);
+    return launch_persist_t<CONV, 0, 0, PURE>(a, M, N, nprob, s);
+}
+// PURE = 2: bf16 operands (training with bf16 GEMM operands, BASELINE config C2): f32 outputs / residuals, or - round 6, the step's 16-bit
+// storage - bf16 outputs; PURE = 1: f16
 template <bool CONV>
 static int launch_persist_pure(GldsArgs& a, int M, int N, int nprob, hipStream_t s) {
-    const bool has_r = a.p[0].R != nullptr;
-    if (a.bf16) {  // bf16 operands (training with bf16 GEMM operands, BASELINE config C2): f32 outputs / residuals, or - round 6, the
-        // step's 16-bit storage - bf16 outputs (with a bf16 residual)
-        if (a.ksplit > 1) return launch_persist_t<CONV, 0, 0, 2>(a, M, N, nprob, s);
-        if (a.c_f16) {
-            if (CONV || !has_r) return launch_persist_t<CONV, 0, 2, 2>(a, M, N, nprob, s);
-            return launch_persist_t<false, 3, 2, 2>(a, M, N, nprob, s);
-        }
-        if (has_r && !CONV) return launch_persist_t<false, 1, 0, 2>(a, M, N, nprob, s);
-        return launch_persist_t<CONV, 0, 0, 2>(a, M, N, nprob, s);
-    }
-    if (a.ksplit > 1) return launch_persist_t<CONV, 0, 0, true>(a, M, N, nprob, s);
-    if (a.c_f16) {
-        if (CONV || !has_r) return launch_persist_t<CONV, 0, 2, true>(a, M, N, nprob, s);
-        return launch_persist_t<false, 3, 2, true>(a, M, N, nprob, s);
-    }
-    if (has_r && !CONV) return launch_persist_t<false, 1, 0, true>(a, M, N, nprob, s);
-    return launch_persist_t<CONV, 0, 0, true>(a, M, N, nprob, s);
+    return a.bf16 ? launch_persist_pure_t<CONV, 2>(a, M, N, nprob, s) : launch_persist_pure_t<CONV, 1>(a, M, N, nprob, s);
 }
 
 // the persistent kernel takes residual / no residual from the launch, so every problem of the launch must agree
@@ -2232,7 +1083,7 @@ template <bool CONV>
 static int launch_shape(GldsArgs& a, int shape, int M, int N, int nprob, hipStream_t s) {
     if (a.ksplit > 1) return launch_persist<CONV>(a, M, N, nprob, s);
 #ifdef SOLA_EXPERIMENTS
-    if (shape == 4 && g_gemm_k16 && !a.gn_gamma) return launch_k16<CONV, 0>(a, M, N, nprob, s);
+    if (shape == 4 && g_gemm_k16 && !a.gn_gamma) return launch_gemm_k16(a, CONV, M, N, nprob, s);
 #endif
     if (shape == 4 && g_gemm_persist && a.K / GBK >= 2 && persist_uniform(a, CONV)) return launch_persist<CONV>(a, M, N, nprob, s);
     if (shape == 4) return launch_glds<4, 2, 4, CONV>(a, M, N, nprob, s);
@@ -2256,9 +1107,7 @@ bool gemm_gn_fusable(const GemmDesc& d, int channels_per_group, int tokens) {
 
 int launch_gemm_split_glds(const GemmDesc& d, hipStream_t s) {
     GldsArgs a;
-    for (int i = 0; i < 3; ++i) a.p[i] = d.p[i < d.nprob ? i : 0];
-    a.M = d.M; a.N = d.N; a.K = d.K; a.lda = d.lda; a.ldr = d.ldr; a.ldc = d.ldc;
-    a.conv = d.conv; a.T_in = d.T_in; a.T_out = d.T_out; a.stride = d.stride; a.pad = d.pad; a.Cin = d.Cin;
+    gemm_fill_common(a, d);
     a.r_f16 = a.c_f16 = 0;
     a.bf16 = 0;
     a.bias_scale_dev = d.bias_scale_dev;
@@ -2268,7 +1117,6 @@ int launch_gemm_split_glds(const GemmDesc& d, hipStream_t s) {
         a.bf16 = d.bf16 ? 1 : 0;
         SOLA_ARG(!(a.bf16 && a.r_f16 && !a.c_f16), "gemm: a bf16 residual goes with a bf16 output");
     }
-    a.rowmap = d.conv == 1 ? d.rowmap : nullptr;
     a.out_scale = d.out_scale != 0.f ? d.out_scale : 1.f;
     a.out_scale_dev = d.out_scale_dev;
     a.r_sp16 = d.r_sp16;
@@ -2298,73 +1146,3 @@ int gemm_split_glds_shape(const GemmDesc& d) {
     return (t >= 256 && 4 * t >= 3 * rounds * 256) ? 4 : 1;
 }
 
-// ---- weight gradients on row-major 16-bit operands (gemm_tn_tr_kernel) -------------------------------------------------------------
-int g_train_tn_tr = 1;  // sola_tune "train_tn_tr": 0 = always the transposed-copy route of gemm_tn_split.hip
-bool gemm_tn_tr_supported(int M, int N, int K, long long lda, long long ldb) {
-    return g_train_tn_tr && N % 256 == 0 && K % 256 == 0 && lda % 8 == 0 && ldb % 8 == 0 && M >= 128;
-}
-// the number of row ranges: about one work item per CU, every range at least two 64-row k-tiles, at most max_ranges (the scratch)
-void gemm_tn_tr_geometry(int M, int N, int K, int nprob, int max_ranges, int& ksplit, int& kper) {
-    const int nkt = (M + 63) / 64;
-    const int tiles = (N / 256) * (K / 256) * nprob;
-    int ks = std::max(1, sola_cu_count() / std::max(1, tiles));
-    ks = std::min(ks, std::min(max_ranges, std::max(1, nkt / 2)));
-    if (ks >= 8) ks &= ~7;  // whole XCD groups (the kernel's work-item order)
-    kper = (nkt + ks - 1) / ks;
-    ksplit = (nkt + kper - 1) / kper;  // no empty range
-}
-int launch_splitk_reduce_bf16(const void* part, int ksplit, int nprob, float* const* C, int M, int N, int ldc, const float* out_scale_dev,
-                              const float* scale_dev, hipStream_t s) {
-    SOLA_ARG(part && ksplit >= 1 && nprob >= 1 && nprob <= 3 && N % 4 == 0 && ldc % 4 == 0, "splitk_reduce_bf16: ksplit %d nprob %d N %d", ksplit, nprob, N);
-    const long long mn = (long long)M * N;
-    hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3((unsigned)((mn / 4 + 255) / 256), 1, nprob), dim3(256), 0, s, static_cast<const unsigned short*>(part),
-                       ksplit, mn, N, ldc, C[0], C[nprob > 1 ? 1 : 0], C[nprob > 2 ? 2 : 0], out_scale_dev, scale_dev);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-
-int launch_gemm_tn_tr(const GemmTnTrDesc& d, hipStream_t s) {
-    SOLA_ARG(d.nprob >= 1 && d.nprob <= 3 && d.part && d.ksplit >= 1 && d.kper >= 1, "gemm_tn_tr: nprob %d ksplit %d", d.nprob, d.ksplit);
-    SOLA_ARG(gemm_tn_tr_supported(d.M, d.N, d.K, d.lda, d.ldb), "gemm_tn_tr: M=%d N=%d K=%d", d.M, d.N, d.K);
-    SolaProfScope prof(SOLA_PROF_GEMM_SPLIT256, s, 2.0 * d.M * d.N * (double)d.K * d.nprob,
-                       2.0 * d.nprob * ((double)d.M * d.N + (double)d.M * d.K) + 4.0 * d.nprob * d.ksplit * (double)d.N * d.K);
-    TnTrArgs t{};
-    GldsArgs& a = t.e;
-    a.M = d.N; a.N = d.K; a.ldc = d.K; a.K = 0;
-    a.tiles_m = d.N / 256; a.tiles_n = d.K / 256;
-    a.out_scale = 1.f;
-    a.ksplit = d.ksplit; a.part = d.part; a.nprob = d.nprob;
-    a.ablate = g_gemm_ablate;
-    if (d.part_bf16) { SOLA_ARG(d.bf16 && d.K % 4 == 0, "gemm_tn_tr: bfloat16 partial sums go with bfloat16 operands"); a.c_f16 = 1; a.bf16 = 1; }
-    for (int j = 0; j < 3; ++j) {
-        t.A[j] = static_cast<const char*>(d.A[j < d.nprob ? j : 0]);
-        t.B[j] = static_cast<const char*>(d.B[j < d.nprob ? j : 0]);
-        SOLA_ARG((reinterpret_cast<uintptr_t>(t.A[j]) & 15) == 0 && (reinterpret_cast<uintptr_t>(t.B[j]) & 15) == 0, "gemm_tn_tr: operands must be 16-byte aligned");
-    }
-    t.a_sp = d.a_split ? 1 : 0; t.b_sp = d.b_split ? 1 : 0;
-    t.lda = d.lda * (d.a_split ? 4 : 2); t.ldb = d.ldb * (d.b_split ? 4 : 2); t.Mred = d.M; t.kper = d.kper; t.nkt = (d.M + 63) / 64;
-    SOLA_ARG((long long)d.ksplit * d.kper >= t.nkt && (long long)(d.ksplit - 1) * d.kper < t.nkt, "gemm_tn_tr: ranges %d x %d k-tiles do not cover %d", d.ksplit, d.kper, t.nkt);
-    constexpr size_t lds = 2 * 2 * 64 * 512;
-    t.Cin = d.Cin; t.T_in = d.T_in; t.T_out = d.T_out; t.stride = d.stride; t.pad = d.pad; t.rowmap = d.rowmap;
-    const int conv = !d.conv ? 0 : (d.rowmap ? 2 : 1);
-    SOLA_ARG(!conv || (d.Cin % 256 == 0 && d.K % d.Cin == 0 && d.K / d.Cin <= 8 && (d.rowmap || (d.T_out > 0 && d.T_in > 0 && d.stride >= 1))),
-             "gemm_tn_tr: conv geometry Cin=%d K=%d", d.Cin, d.K);
-    SOLA_ARG(!(d.bf16 && (d.a_split || d.b_split)), "gemm_tn_tr: split-f16 operands are f16");
-    if (conv) t.ldb = (long long)d.Cin * (d.b_split ? 4 : 2);
-    static DeviceOnce once[2][3];
-    int dev;
-    const dim3 grid(a.tiles_m * a.tiles_n * d.ksplit, 1, d.nprob);
-    const void* fn = nullptr;
-#define TN_TR_PICK(BFV, CV) if ((d.bf16 ? 1 : 0) == BFV && conv == CV) fn = reinterpret_cast<const void*>(&gemm_tn_tr_kernel<BFV, CV>);
-    TN_TR_PICK(0, 0) TN_TR_PICK(0, 1) TN_TR_PICK(0, 2) TN_TR_PICK(1, 0) TN_TR_PICK(1, 1) TN_TR_PICK(1, 2)
-#undef TN_TR_PICK
-    DeviceOnce& o = once[d.bf16 ? 1 : 0][conv];
-    if (o.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        o.done(dev);
-    }
-    void* kargs[] = {&t};
-    SOLA_HIP(hipLaunchKernel(fn, grid, dim3(512), kargs, lds, s));
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}

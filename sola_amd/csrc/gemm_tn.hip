@@ -10,7 +10,7 @@
 #include <algorithm>
 #include <utility>
 
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace {
 
@@ -461,8 +461,7 @@ int launch_gemm_tn(const GemmTnDesc& d, hipStream_t s) {
     if (d.conv) SOLA_ARG(d.Cin % 4 == 0 && d.K % d.Cin == 0, "gemm_tn conv: Cin=%d K=%d", d.Cin, d.K);
     TnArgs a;
     a.A = d.A; a.B = d.B; a.P = d.scratch; a.Pb = nullptr; a.M = d.M; a.N = d.N; a.K = d.K; a.lda = d.lda; a.ldb = d.ldb;
-    a.conv = d.conv; a.T_in = d.T_in; a.T_out = d.T_out; a.stride = d.stride; a.pad = d.pad; a.Cin = d.Cin;
-    a.rowmap = d.conv ? d.rowmap : nullptr;
+    gemm_fill_conv(a, d);
     a.tiles_n = (d.N + TB - 1) / TB;
     a.tiles_k = (d.K + TB - 1) / TB;
     const size_t need = gemm_tn_scratch_bytes(d.M, d.N, d.K);
@@ -502,18 +501,10 @@ int launch_gemm_tn(const GemmTnDesc& d, hipStream_t s) {
     mps = (mps + TM - 1) / TM * TM;
     a.m_per_split = mps;
     constexpr size_t lds = (size_t)4 * TM * TP * sizeof(float);
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_f32_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_f32_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
     {
         SolaProfScope prof(SOLA_PROF_GEMM_TN, s, 2.0 * d.M * d.N * (double)d.K, 4.0 * ((double)d.M * (d.N + d.K) + (double)splits * d.N * d.K));
-        if (g_gemm_tn_nw8) hipLaunchKernelGGL(gemm_tn_f32_kernel<8>, dim3(a.tiles_n * a.tiles_k, splits), dim3(512), lds, s, a);
-        else hipLaunchKernelGGL(gemm_tn_f32_kernel<4>, dim3(a.tiles_n * a.tiles_k, splits), dim3(256), lds, s, a);
-        SOLA_LAUNCH_CHECK();
+        const dim3 grid(a.tiles_n * a.tiles_k, splits);
+        SOLA_TRY(g_gemm_tn_nw8 ? launch_lds<gemm_tn_f32_kernel<8>>(grid, dim3(512), lds, s, a) : launch_lds<gemm_tn_f32_kernel<4>>(grid, dim3(256), lds, s, a));
     }
     {
         const long long n4 = (long long)d.N * d.K / 4;
@@ -551,18 +542,9 @@ int launch_gemm_tn_group(const GemmTnGroupDesc& d, hipStream_t s) {
         bytes += 4.0 * ((double)q.M * (q.N + q.K) + (double)q.N * q.K);
     }
     constexpr size_t lds = (size_t)4 * TM * TP * sizeof(float);
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_f32_group_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_f32_group_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
     SolaProfScope prof(SOLA_PROF_GEMM_TN, s, flops, bytes);
-    if (g_gemm_tn_nw8) hipLaunchKernelGGL(gemm_tn_f32_group_kernel<8>, dim3((unsigned)tiles), dim3(512), lds, s, g);
-    else hipLaunchKernelGGL(gemm_tn_f32_group_kernel<4>, dim3((unsigned)tiles), dim3(256), lds, s, g);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
+    if (g_gemm_tn_nw8) return launch_lds<gemm_tn_f32_group_kernel<8>>(dim3((unsigned)tiles), dim3(512), lds, s, g);
+    return launch_lds<gemm_tn_f32_group_kernel<4>>(dim3((unsigned)tiles), dim3(256), lds, s, g);
 }
 
 int launch_transpose(const float* in, float* out, int rows, int cols, int ldi, int ldo, int col_off, hipStream_t s) {

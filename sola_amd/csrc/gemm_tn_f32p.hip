@@ -18,7 +18,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace {
 
@@ -32,11 +32,7 @@ struct TnpArgs {
     int tiles_n, tiles_k, splits, m_per_split, xcd_order;
 };
 
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __attribute__((aligned(16))) float g_zero_page_tnp[4] = {0.f, 0.f, 0.f, 0.f};
 
 struct FragTn { f32x2 a[2][2], b[2][2]; };  // [row-pair pair][32-column block]: .x = row pair t, .y = row pair t + 1
 
@@ -55,14 +51,8 @@ __global__ __launch_bounds__(512) void gemm_tn_f32_persist_kernel(const TnpArgs 
     const int total = tiles * a.splits;
     auto decode = [&](int item, int& split, int& n0, int& k0) {
         int tile;
-        if (a.xcd_order) {  // splits % 8 == 0: XCD x (blocks x, x + 8, ...) takes the splits = x mod 8 - all tiles of a split share its rows in one L2
-            const int x = item & 7, j = item >> 3;
-            split = x + 8 * (j / tiles);
-            tile = j % tiles;
-        } else {
-            split = item / tiles;
-            tile = item % tiles;
-        }
+        // xcd_order (splits % 8 == 0): XCD x (blocks x, x + 8, ...) takes the splits = x mod 8 - all tiles of a split share its rows in one L2
+        tile_decode(TileGrid{tiles, a.xcd_order}, item, split, tile);
         const int tn = tile / a.tiles_k;
         n0 = tn * GBN;
         k0 = (tile - tn * a.tiles_k) * GBK;
@@ -71,7 +61,7 @@ __global__ __launch_bounds__(512) void gemm_tn_f32_persist_kernel(const TnpArgs 
     // ---- DMA stream state
     const unsigned a_vo = (unsigned)(lane * 16);                                  // A piece = one row's 1-KiB window
     const unsigned b_vo = (unsigned)((lane >> 5) * a.ldb * 4 + (lane & 31) * 16);  // B piece = two rows' 512-byte windows (plain rows)
-    __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(g_zero_page_tnp, 0, 0, 0x00020000), rs_b = rs_a;
+    __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(g_zero_page, 0, 0, 0x00020000), rs_b = rs_a;
     int a_so = 0, b_so = 0;  // scalar offsets of this wave's first piece at the stream's stage
     const int a_pitch = a.lda * 4, b_pitch2 = a.ldb * 8;
     int dma_st = 0, dma_nst = 0;  // next stage of the stream within its work item, and that item's stage count (even)
@@ -79,18 +69,10 @@ __global__ __launch_bounds__(512) void gemm_tn_f32_persist_kernel(const TnpArgs 
     int cv_mbeg = 0, cv_mend = 0, cv_tap = 0, cv_base_row = 0, cv_col = 0;
     unsigned c_eff[WPW];
     auto window_row = [&](int m, int& row0, int& bits) {  // source row of tap 0 of output row m, and which taps lie inside the sequence
-        if constexpr (CONV == 2) {
-            const int2 rm = a.rowmap[m];
-            row0 = rm.x;
-            bits = rm.y;
-        } else {
-            const int rr = m / a.T_out, to = m - rr * a.T_out, t0 = to * a.stride - a.pad;
-            row0 = rr * a.T_in + t0;
-            int b = 0;
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) b |= ((unsigned)(t0 + kk) < (unsigned)a.T_in) ? (1 << kk) : 0;
-            bits = b;
-        }
+        long long r0;  // (32-bit rows: a split's offsets are taken from cv_base_row)
+        if constexpr (CONV == 2) conv_window_map(a.rowmap, m, r0, bits);
+        else conv_window_geom(a, m, r0, bits);
+        row0 = (int)r0;
     };
     // CONV == 1: the (sequence, output step) of each piece's row, advanced by 32 rows per stage without a division
     int g_rr[WPW], g_to[WPW];
@@ -317,16 +299,8 @@ __global__ __launch_bounds__(512) void gemm_tn_f32_persist_kernel(const TnpArgs 
 template <int CONV>
 int launch_tnp_t(const TnpArgs& a, hipStream_t s) {
     constexpr size_t lds = 2 * (32 * 256 * 4 + 32 * 128 * 4);  // two stages: 96 KiB
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_f32_persist_kernel<CONV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
     const int total = a.tiles_n * a.tiles_k * a.splits;
-    hipLaunchKernelGGL((gemm_tn_f32_persist_kernel<CONV>), dim3(std::min(total, sola_cu_count())), dim3(512), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
+    return launch_lds<gemm_tn_f32_persist_kernel<CONV>>(dim3(std::min(total, sola_cu_count())), dim3(512), lds, s, a);
 }
 
 }  // namespace
@@ -373,8 +347,7 @@ int gemm_tn_persist_splits(const GemmTnDesc& d, int max_splits) {
 int launch_gemm_tn_f32_persist(const GemmTnDesc& d, int splits, float* P, int* splits_out, hipStream_t s) {
     TnpArgs a;
     a.A = d.A; a.B = d.B; a.P = P; a.M = d.M; a.N = d.N; a.K = d.K; a.lda = d.lda; a.ldb = d.ldb;
-    a.conv = d.conv; a.T_in = d.T_in; a.T_out = d.T_out; a.stride = d.stride; a.pad = d.pad; a.Cin = d.Cin;
-    a.rowmap = d.conv ? d.rowmap : nullptr;
+    gemm_fill_conv(a, d);
     a.tiles_n = d.N / 256;
     a.tiles_k = d.K / 128;
     a.splits = splits;

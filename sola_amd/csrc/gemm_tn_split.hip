@@ -8,14 +8,12 @@
 // (cast.hip's amax pass; all problems of a launch share the scale), undone by the GEMM's out_scale_dev.
 // Second route (round 3, the default for 16-bit operands - GemmTnSplitDesc::pure - when N and K are multiples of 256): NO transposed
 // copies.  The operands are cast ROW-MAJOR (dY's cast is the dX GEMM's operand anyway, X's comes from the training forward's kept
-// casts or one plain cast; convs: one cast of the conv input) and gemm_glds.hip's gemm_tn_tr_kernel transposes them in its LDS reads.
+// casts or one plain cast; convs: one cast of the conv input) and gemm_tn_tr.hip's gemm_tn_tr_kernel transposes them in its LDS reads.
 #include <algorithm>
 
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float auto_scale_t(unsigned amax_bits) {  // as cast.hip: max|x| -> [2^13, 2^14)
     if (amax_bits == 0u) return 1.f;
@@ -31,10 +29,6 @@ __device__ __forceinline__ float auto_scale_t(unsigned amax_bits) {  // as cast.
 // r * conv_T_in + to * conv_stride + conv_toff (tap - pad), zeros outside [0, conv_T_in).
 // PURE: the output is plain _Float16 ([cols][ld_out halfs]) for the one-MFMA-per-product GEMM (GemmDesc::arith 2); bf != 0: the
 // 16-bit values are bfloat16 bit patterns instead.
-__device__ __forceinline__ _Float16 cvt16(float v, int bf) {
-    if (bf) return __builtin_bit_cast(_Float16, (__bf16)v);
-    return (_Float16)v;
-}
 // RMP: the format of the optional row-major copy (PURE = as the transposed output; false with PURE = true: the weight-gradient
 // product takes plain f16 operands while the dX GEMM of the same gradient matrix keeps split-f16 ones - sola_tune "train_dw_f16")
 template <bool PURE, bool RMP = PURE>
@@ -280,7 +274,7 @@ int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s) {
     const bool rm = gemm_tn_split_writes_rm(d);
     const long long conv_rows_in = !d.conv ? 0 : (d.rowmap ? d.B_rows : (long long)d.M / d.T_out * d.T_in);
     if (pure && d.ldb % 4 == 0 && gemm_tn_tr_supported(d.M, d.N, d.K, 8, 8) && (!d.conv || (d.Cin % 256 == 0 && d.ldb == d.Cin && conv_rows_in > 0))) {
-        // 16-bit operands, linear layers: NO transposed copies.  gemm_glds.hip's gemm_tn_tr_kernel takes the ROW-MAJOR casts - dY's is the
+        // 16-bit operands, linear layers: NO transposed copies.  gemm_tn_tr.hip's gemm_tn_tr_kernel takes the ROW-MAJOR casts - dY's is the
         // dX GEMM's operand anyway - and transposes between LDS and the matrix pipe (ds_read_b64_tr_b16).
         const int bf = pure_fmt == 2 ? 1 : 0;
         GemmTnTrDesc t{};

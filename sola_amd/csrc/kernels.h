@@ -131,7 +131,7 @@ size_t gemm_tn_split_scratch_bytes(int M, int N, int K, int nprob);
 int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s);
 size_t gemm_tn_scratch_bytes(int M, int N, int K);
 int launch_gemm_tn(const GemmTnDesc& d, hipStream_t s);
-// dW_j[n][k] = sum_m A_j[m][n] B_j[m][k] on ROW-MAJOR 16-bit operands (gemm_glds.hip's gemm_tn_tr_kernel: transposing LDS reads,
+// dW_j[n][k] = sum_m A_j[m][n] B_j[m][k] on ROW-MAJOR 16-bit operands (gemm_tn_tr.hip's gemm_tn_tr_kernel: transposing LDS reads,
 // no transposed copies): raw partial sums of `ksplit` row ranges of `kper` 64-row k-tiles into part[(j * ksplit + range)][N][K]
 struct GemmTnTrDesc {
     const void* A[3];  // 16-bit rows [M][lda], 16-byte aligned

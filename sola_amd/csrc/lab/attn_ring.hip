@@ -334,7 +334,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_ring_kernel(const AttnRAr
                         *reinterpret_cast<half4v*>(dst) = h4;
                         *reinterpret_cast<half4v*>(dst + 16) = l4;
                     }
-                    attn_range_guard(a.guard, m);
+                    f16_range_guard(a.guard, m);
                 }
             }
             issued += a.o_sp16 ? 16 : 8;

@@ -172,8 +172,6 @@ __device__ __forceinline__ GnUnit gn_unit(const GnArgs& a, int inst) {
     return u;
 }
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 // normalise + affine (+ LeakyReLU, dropout, the y + pe side output, split-f16 emission) of one float4 and its store
 __device__ __forceinline__ void gn_apply_store(const GnArgs& a, long long off, const float4 v, float mean, float rstd, const float4 ga,
                                                const float4 be, const float4 pe, int c4) {
@@ -203,7 +201,8 @@ __device__ __forceinline__ void gn_apply_store(const GnArgs& a, long long off, c
             h[0] = (_Float16)(o.x + pe.x); h[1] = (_Float16)(o.y + pe.y); h[2] = (_Float16)(o.z + pe.z); h[3] = (_Float16)(o.w + pe.w);
             *reinterpret_cast<half4n*>(reinterpret_cast<_Float16*>(a.y2) + off) = h;
         }
-        if (a.guard && !(fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))) < 65000.f)) atomicOr(a.guard, 1);
+        // (common.h's f16_range_guard written out, here and twice below: through the helper the norm kernels' scalar register rows move - profiles/gemm_common_isa.txt)
+        if (a.guard && !(fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))) < F16_GUARD_LIMIT)) atomicOr(a.guard, 1);
         return;
     }
     if (a.out_sp16) {
@@ -223,7 +222,7 @@ __device__ __forceinline__ void gn_apply_store(const GnArgs& a, long long off, c
                 float m = 0.f;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v8[j]));
-                if (!(m < 65000.f)) atomicOr(a.guard, 1);
+                if (!(m < F16_GUARD_LIMIT)) atomicOr(a.guard, 1);
             }
             if (a.y2) {
                 const float w8[8] = {o2.x, o2.y, o2.z, o2.w, n2.x, n2.y, n2.z, n2.w};
@@ -448,7 +447,7 @@ __global__ __launch_bounds__(NTHR) void group_norm_reg_h8_kernel(const GnArgs a,
             if (a.y2) *reinterpret_cast<half8*>(y216 + off) = h2;
         }
     }
-    if (a.guard && !(m < 65000.f)) atomicOr(a.guard, 1);
+    if (a.guard && !(m < F16_GUARD_LIMIT)) atomicOr(a.guard, 1);
 }
 
 // Large units (the object->language norm of a long video: N*T' = 2048 tokens x 128 channels = 1 MiB per unit; ragged batches

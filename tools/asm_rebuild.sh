@@ -1,5 +1,7 @@
 #!/bin/bash
 # Rebuild libsola with gemm_glds.hip's DEVICE code taken from an (edited) assembly file - the ISA bisection of the fused GroupNorm epilogue's fault.
+# (gemm_glds.o holds the one-tile and the persistent NT kernels, the fused epilogue among them; gemm_tn_tr_kernel is in gemm_tn_tr.o, the k16 and
+# ping-pong experiments in build/obj_exp/lab_gemm_*.o)
 #   tools/asm_rebuild.sh <device.s> <host object with the same kernels> <out.so>
 set -e
 L=/opt/rocm/lib/llvm/bin

@@ -1,4 +1,4 @@
-"""Disassembly of one kernel of a built object: python tools/co_dis.py gemm_glds.o '<demangled substring>' [out.s]; prints a summary of
+"""Disassembly of one kernel of a built object: python tools/co_dis.py gemm_glds.o '<demangled substring>' [out.s] (or gemm_tn_tr.o, build/obj_exp/lab_gemm_k16.o, ...); prints a summary of
 scratch / barrier / waitcnt / branch lines and MFMA positions (line numbers within the kernel body)."""
 import os, re, subprocess, sys, shutil
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))

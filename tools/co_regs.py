@@ -1,5 +1,5 @@
 """Register / spill / scratch metadata of every kernel in a built object file (build/obj/<name>.o), from the gfx950 code object's ELF notes.
-usage: python tools/co_regs.py gemm_glds.o [substring]"""
+usage: python tools/co_regs.py gemm_glds.o [substring]   (any object of build/obj or build/obj_exp: gemm_tn_tr.o, lab_gemm_pp.o, ...)"""
 import os, re, subprocess, sys, tempfile, shutil
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"

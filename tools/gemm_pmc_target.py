@@ -1,5 +1,5 @@
 """One split-f16 GEMM shape, one kernel variant, a few launches: the target of rocprofv3 --pmc passes.
-usage: gemm_pmc_target.py <variant 0|1|2> [M N K]"""
+usage: gemm_pmc_target.py <variant 0|1|2> [M N K]   (SOLA_K16=1: the lab/gemm_k16.hip experiment, EXPERIMENTS=1 builds)"""
 import sys, torch
 sys.path.insert(0, "/root/repo")
 from sola_amd import ops, _lib

@@ -1,4 +1,4 @@
-"""Where does the fused conv + GroupNorm epilogue go wrong in a build that fails (e.g. gemm_glds.hip compiled WITH the SLP vectoriser:
+"""Where does the fused conv + GroupNorm epilogue go wrong in a build that fails (e.g. gemm_glds.hip - the persistent kernel's file - compiled WITH the SLP vectoriser:
 SOLA_HIP_LIB=build/libsola_slp.so)?  One fused forward against the unfused launches; the wrong elements of the three taps by row within the
 16-row strip, strip index within the wave tile, wave row / column, column within the wave's 64, and GroupNorm instance."""
 import sys, collections
