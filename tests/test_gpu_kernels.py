@@ -298,7 +298,8 @@ def test_attention_three_layouts(B, N, Tp, D, attn_reg_mode):
 def test_attention_cross_shapes(G, Sq, Sk, attn_reg_mode):
     """Queries and keys of different counts from different matrices (the object->language pattern) at head_dim 128, through
     whatever shape the routing / the forced register-only mode picks: ragged tails of the 16-row tiles, one key, 64 keys
-    exactly (four key tiles of the resident shape), more keys than it takes."""
+    exactly (four key tiles of the resident shape), more keys than it takes.  Which kernel each shape takes, and a case for
+    every kernel, pitch and switch setting: test_gpu_attn_fwd.py."""
     H, D = 8, 1024
     rng = np.random.default_rng(Sq * 131 + Sk)
     q, k, v = rnd(rng, G, Sq, D), rnd(rng, G, Sk, D), rnd(rng, G, Sk, D)
