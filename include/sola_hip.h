@@ -686,6 +686,39 @@ int sola_index_hist(const uint8_t* dev_idx, int T, int h, int w, int64_t* dev_co
 int sola_index_pack(const uint8_t* dev_idx, int T, int h, int w, const int32_t* dev_ids, int K, const int32_t* dev_first_plane,
                     int layout, int64_t words_stride, uint32_t* dev_bits, int64_t* dev_area, void* stream);
 
+/* ---- frame preprocessing: Pillow's 8-bit resize and the normalisation behind it (SAM2's init_state does
+ * `Image.open(p).convert("RGB").resize((1024, 1024))`, `/ 255.0`, `-= mean`, `/= std` per frame on the host; GroundingDINO's
+ * transform is a PIL bilinear resize, ToTensor, Normalize).  Upstream details are from the public sources. -------------------
+ * filter: SOLA_RESAMPLE_BILINEAR (triangle, support 1) or SOLA_RESAMPLE_BICUBIC (a = -0.5, support 2): PIL's own numbers.
+ * sola_resample_taps: the taps of one axis, ceil(support * max(in/out, 1)) * 2 + 1; -1 for a filter or a size it refuses.
+ * sola_resample_coeffs (host only, double arithmetic, Pillow's precompute_coeffs + normalize_coeffs_8bpc): for every output index
+ *   bounds [out,2] = (first source index, taps used) and coeffs [out,taps] = the weights times 2^22 rounded half away from zero,
+ *   zero past the taps used.  Both host arrays.
+ * An axis TABLE of sola_resample_u8 is int32 [out][2 + taps] ON THE DEVICE: row o = (bounds[o][0], bounds[o][1], coeffs[o][:]).
+ * sola_resample_u8: dev_src uint8 [T,H,W,C], interleaved, C 1 or 3, any byte alignment.  A null table (with taps 0) means that
+ *   axis keeps its size and its pass is skipped, as Pillow does.  dev_lut null: dev_out uint8 [T,h,w,C].  dev_lut float32
+ *   [C,256]: dev_out float32 planar [T,C,h,w] = lut[c][byte] (4-byte aligned; 16-byte aligned with w % 4 == 0 gets 16-byte
+ *   stores).  Per pass a 32-bit accumulator starts at 1 << 21, adds pixel * k, is shifted right by 22 and clamped to 0..255;
+ *   the horizontal result is a byte before the vertical pass reads it: the bytes of PIL.Image.resize.  One launch per batch
+ *   (tiles of SOLA_RESAMPLE_TILE_W x SOLA_RESAMPLE_TILE_H output pixels staged in LDS); reductions whose staging does not fit
+ *   take two launches through a byte intermediate in dev_scratch, >= sola_resample_u8_scratch_bytes(...) (host only; 0 for the
+ *   one-launch geometries, where dev_scratch may be null).  No atomics, no allocation, asynchronous; the same bits on every run
+ *   and stream.  Bounds read from a table are clamped to the source: a table that sola_resample_coeffs did not write gives
+ *   wrong pixels, no access outside the buffers.  Refused before any launch: null src / out, C other than 1 / 3, an axis of 0
+ *   or beyond SOLA_RESAMPLE_MAX_SIZE, a table without taps or taps without a table, a null table on an axis whose size
+ *   changes, a short scratch.  T == 0 is a successful no-op. */
+#define SOLA_RESAMPLE_BILINEAR 2
+#define SOLA_RESAMPLE_BICUBIC 3
+#define SOLA_RESAMPLE_MAX_SIZE 16384
+#define SOLA_RESAMPLE_TILE_W 64
+#define SOLA_RESAMPLE_TILE_H 64
+int sola_resample_taps(int in_size, int out_size, int filter);
+int sola_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* coeffs);
+size_t sola_resample_u8_scratch_bytes(int T, int H, int W, int C, int h, int w, int taps_x, int taps_y);
+int sola_resample_u8(const uint8_t* dev_src, int T, int H, int W, int C, int h, int w, const int32_t* dev_table_x, int taps_x,
+                     const int32_t* dev_table_y, int taps_y, const float* dev_lut, void* dev_out, void* dev_scratch,
+                     size_t scratch_bytes, void* stream);
+
 /* ---- multi-scale deformable attention, forward (Deformable-DETR; GroundingDINO's one custom operator,
  * groundingdino._C.ms_deform_attn_forward; Mask2Former's pixel decoder).  Upstream details are from its public source. -------
  * All float32, contiguous:

@@ -152,6 +152,10 @@ SIGNATURES = {
     "sola_box_nms_profile": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp, C.POINTER(_f)]),
     "sola_index_hist": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "sola_index_pack": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp]),
+    "sola_resample_taps": (_i, [_i, _i, _i]),
+    "sola_resample_coeffs": (_i, [_i, _i, _i, _vp, _vp]),
+    "sola_resample_u8_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "sola_resample_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "sola_ms_deform_attn": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sola_ms_deform_attn_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sola_mask_iou_scratch_bytes": (_sz, [_i, _i, _i, _i]),
