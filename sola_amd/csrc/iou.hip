@@ -454,11 +454,16 @@ __global__ __launch_bounds__(256) void mask_iou_onepass_kernel(const OnepassArgs
     // ---- the group's last block folds.  No agent-scope FENCE: on gfx950 a __threadfence() is an L2 write-back + invalidate, and one per
     //      block (512-2048 of them) serialised per XCD made this kernel 3-8x slower than its predecessor (51 / 120 / 285 us at R = 16 / 64 /
     //      256, profiles/r06_iou.txt).  The row is written with agent-scope ATOMIC stores (performed at the level all XCDs share), the
-    //      storing lanes wait for their completion (workgroup-scope release = s_waitcnt), then the ticket; the folding block reads the
-    //      rows with agent-scope atomic loads behind the ticket it took.
-    if ((int)threadIdx.x < NV)
+    //      storing lanes WAIT for their completion - an explicit s_waitcnt vmcnt(0): the workgroup-scope release below compiles to no
+    //      wait on the vector-memory counter (that scope orders the accesses for the block's own waves only), so without it the ticket, an
+    //      atomic on another address, could reach L2 before a row and the folding block would add what the scratch held before
+    //      (tests/test_iou_cpu.py checks the built code object; profiles/iou_ticket_wait.txt has its price) - then the barrier, then the
+    //      ticket; the folding block reads the rows with agent-scope atomic loads behind the ticket it took.
+    if ((int)threadIdx.x < NV) {
         __hip_atomic_store(&rows[(long long)chunk * NV + threadIdx.x], (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     const unsigned slot = ((a.ticket_base + (unsigned)grp) & (OP_TICKETS - 1)) * OP_TICKET_PITCH;

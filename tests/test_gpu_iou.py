@@ -111,12 +111,13 @@ def test_full_size_properties():
 
 
 @pytest.mark.parametrize("P,R,H,W", [(4, 16, 540, 960), (1, 1, 540, 960), (3, 64, 540, 960), (4, 7, 64, 96), (2, 5, 960, 540), (4, 300, 128, 256),
-                                     (4, 33, 1080, 1920), (2, 3, 8, 4), (4, 129, 36, 100)])
+                                     (4, 33, 1080, 1920), (2, 3, 8, 4), (4, 129, 36, 100), (4, 129, 36, 96)])
 def test_fused_one_launch_path_equals_pack_and_pair(P, R, H, W):
     """uint8 masks at the comparison resolution with P <= 4 (the de-dup loop's calls) take the one-launch kernel (round 6: no memset,
     per-block count rows + a ticket per prompt group, iou.hip); its counts are the oracle's and the three-kernel path's, including
     empty masks, a mask equal to its partner, a last chunk that is mostly out of range (1080 x 1920: 127 chunks; 8 x 4: one word)
-    and prompt counts that leave the last group ragged."""
+    and prompt counts that leave the last group ragged.  36 x 100 is no whole number of 32-pixel words: both of its calls are pack +
+    pair (the generic pack kernel); 36 x 96 next to it does take the one-launch kernel (tests/iou_cases.py restates the routing)."""
     rng = np.random.default_rng(P * 1000 + R)
     A = (rng.uniform(size=(P, H, W)) < 0.3).astype(np.uint8)
     B = (rng.uniform(size=(R, H, W)) < 0.5).astype(np.uint8) * rng.integers(1, 255, size=(R, H, W)).astype(np.uint8)  # any non-zero byte counts
@@ -126,7 +127,7 @@ def test_fused_one_launch_path_equals_pack_and_pair(P, R, H, W):
     A[P - 1, : H // 2] = 0
     ri, ru = iou_oracle.iou_matrix(A, (B != 0).astype(np.uint8))
     outs = []
-    for fused in (2, 0):  # 2 = the fused kernel for any R (by default it serves calls with up to 32 prompts)
+    for fused in (2, 0):  # 1 (default) / 2 = the one-launch kernel wherever it can run, 0 = always pack + pair
         with tuned(iou_fused=fused):
             inter, union = seg_utils.mask_iou_matrix(cuda(A), cuda(B))
             outs.append((inter.cpu().numpy(), union.cpu().numpy()))

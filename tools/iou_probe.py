@@ -1,7 +1,10 @@
 """Mask IoU at the de-dup loop's call sizes (P = 4 tracks x R prompts, 540x960 uint8 resident in HBM): the one-launch kernel
 (sola_tune iou_fused 1, default) against pack + pair (iou_fused 0): wall per call, in-library kernel time, fraction of the HBM peak.
 
-    python tools/iou_probe.py [reps = 200]        (rocprofv3 --kernel-trace --stats -- python3 tools/iou_probe.py 50 for per-kernel times)
+    python tools/iou_probe.py [reps = 200 [H W = 540 960]]   (rocprofv3 --kernel-trace --stats -- python3 tools/iou_probe.py 50 for per-kernel times)
+
+Masks of 2^19 pixels or more (1080 1920) take the one-launch kernel's ticket form; SOLA_TUNE=iou_packed=0 gives it to the smaller ones too
+(profiles/iou_ticket_wait.txt).
 """
 import json
 import os
@@ -16,7 +19,8 @@ from oracle import iou_oracle  # noqa: E402  (checker only)
 from sola_amd import _lib, seg_utils  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-H, W, P = 540, 960, 4
+H, W = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (540, 960)
+P = 4
 rng = np.random.default_rng(0)
 
 
