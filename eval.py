@@ -55,7 +55,7 @@ import numpy as np
 import torch
 
 from sola_amd import dist as sdist
-from sola_amd.config import load_configs
+from sola_amd.config import load_configs, parse_sweep_thresholds
 from sola_amd.data import make_ragged_batches
 from sola_amd.module import LanguageAlignedTrackSelectionModule
 from sola_amd.text import TextEncoder
@@ -71,26 +71,6 @@ def jf_skip_reason(cfg, ds):
     if not getattr(ds, "has_mask_gt", False):
         return f"no mask ground truth (mask_dict.json / Annotations) for {getattr(ds, 'data_type', 'this split')}"
     return None
-
-
-def parse_sweep_thresholds(value):
-    """``--sweep_thresholds`` as load_configs hands it over (a comma list as a string, or one value already coerced to a
-    number) -> list of floats in the caller's order, or None when the flag is absent.  Anything else is a ValueError."""
-    if value is None:
-        return None
-    if isinstance(value, bool):
-        raise ValueError("--sweep_thresholds needs a value: a comma list of thresholds in [0, 1], such as 0.1,0.3,0.5")
-    parts = [value] if isinstance(value, (int, float)) else [p.strip() for p in str(value).split(",")]
-    out = []
-    for p in parts:
-        try:
-            t = float(p)
-        except (TypeError, ValueError):
-            raise ValueError(f"--sweep_thresholds: {p!r} in {value!r} is not a number (expected a comma list such as 0.1,0.3,0.5)")
-        if not 0.0 <= t <= 1.0:  # (also refuses nan)
-            raise ValueError(f"--sweep_thresholds: {p} is outside [0, 1]")
-        out.append(t)
-    return out
 
 
 class SelectionCollector:

@@ -590,6 +590,32 @@ int sola_png_deflate_sizes(const void* dev_masks, int elem_type, int n, int h, i
 int sola_png_deflate_write(const void* dev_masks, int elem_type, int n, int h, int w, const int64_t* dev_byte_off,
                            const uint32_t* dev_adler, uint8_t* dev_bytes, void* dev_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- PNG streams of selections of bit planes: every threshold's files of a video from one decode -------------------------
+ * sola_planes_cm_to_rm: the column-major planes of sola_rle_pack_cm / sola_index_pack (bit x*h + y, stride >=
+ *   sola_jf_plane_words(h, w)) -> the flat row-major layout of sola_mask_pack (bit j of word i is pixel 32*i + j at position
+ *   y*w + x), plane p at dev_bits_rm + p * words_stride_rm.  Both strides are multiples of 4 and words_stride_rm >=
+ *   sola_mask_words(h, w); both buffers 16-byte aligned; h*w < 2^31; any n_planes >= 1.  EVERY word of every output plane is
+ *   written by exactly one thread (no atomics, no memset), tail and pad bits zero.  A bit-matrix transpose through ballots and
+ *   LDS: up to 64 image rows per workgroup, fewer when 64 rows of w bits exceed 48 KiB (w > 393 152 is refused).
+ * sola_png_deflate_sizes_select: sola_png_deflate_sizes for n = E*K*T streams that are never materialised as masks.  Stream
+ *   (e*K + k)*T + t is the PNG zlib stream (format above) of the OR of the row-major planes m*T + t over m in
+ *   dev_sel_idx[dev_sel_off[e] .. dev_sel_off[e] + end(e, k)), with the CSR list and level rules of sola_mask_nested_counts:
+ *   end(e, k) = min(max(dev_level_end[e*K + k], end(e, k-1)), len_e), a null dev_level_end (K == 1 only) = the whole list, ids
+ *   outside [0, n_masks) are ignored, ids may repeat, an empty list is an all-zero frame.  1 <= K <= SOLA_NESTED_MAX_LEVELS
+ *   (more levels: several calls; a later call's first level is the whole prefix up to it).  One thread per 64-bit word of a
+ *   raw stream carries the OR over the levels in one register and stores each level's bitmap word, so every plane of the
+ *   largest selection is read once per (e, t).  dev_byte_off [n+1], dev_adler [n] and dev_scratch (>=
+ *   sola_png_deflate_scratch_bytes(n, h, w), 8-byte aligned) are those of sola_png_deflate_sizes, and
+ *   sola_png_deflate_write(dev_bits_rm, 0, n, h, w, ...) completes the streams (it reads the scratch, not the planes).
+ *   E*K*T < 2^31, h*(w+1) < 2^31, words_stride a multiple of 4 and >= sola_mask_words(h, w), planes 16-byte aligned.
+ * Both are asynchronous on the stream and refuse bad arguments before any launch. */
+int sola_planes_cm_to_rm(const uint32_t* dev_bits_cm, int64_t words_stride_cm, int64_t n_planes, int h, int w,
+                         uint32_t* dev_bits_rm, int64_t words_stride_rm, void* stream);
+int sola_png_deflate_sizes_select(const uint32_t* dev_bits_rm, int64_t words_stride, int n_masks, int T, int h, int w,
+                                  const int32_t* dev_sel_off, const int32_t* dev_sel_idx, const int32_t* dev_level_end,
+                                  int K, int E, int64_t* dev_byte_off, uint32_t* dev_adler,
+                                  void* dev_scratch, size_t scratch_bytes, void* stream);
+
 /* Connected components of the set pixels of n independent frames [n,h,w] (row-major), and the fused rewrite of the small
  * ones: what SAM2's fill_holes_in_mask_scores needs in front of the `> 0` threshold.  connectivity 8 or 4; n*h*w < 2^31
  * and at most 2^24 - 1 tiles of SOLA_CC_TILE_W x SOLA_CC_TILE_H in one call.  elem_type: 0 = uint8 != 0, 1 = float32 != 0,

@@ -142,6 +142,8 @@ SIGNATURES = {
     "sola_png_deflate_scratch_bytes": (_sz, [_i, _i, _i]),
     "sola_png_deflate_sizes": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sola_png_deflate_write": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sola_png_deflate_sizes_select": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "sola_planes_cm_to_rm": (_i, [_vp, _i64, _i64, _i, _i, _vp, _i64, _vp]),
     "sola_mask_components_scratch_bytes": (_sz, [_i, _i, _i]),
     "sola_mask_components": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sola_mask_fill_small": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _f, _vp, _vp, _sz, _vp]),

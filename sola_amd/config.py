@@ -6,7 +6,9 @@ coerced, bare flags -> True).  Output directories follow the reference layout (S
     train      results.output_dir/<exp_name>/<train.data_name>/epoch_K.pth
     eval       results.eval_output_dir/<exp_name>/<valid.data_name>/pred_threshold_<t>/epoch_K/
     inference  results.test_output_dir/<exp_name>/<test.data_name>/pred_threshold_<t>/epoch_K/<video>/<exp>/<frame>.png
-               (``--gpu_png true`` -> ``configs["gpu_png"]``: the same files written from the GPU deflate, inference.py)
+               (``--gpu_png true`` -> ``configs["gpu_png"]``: the same files written from the GPU deflate, inference.py;
+               ``--sweep_thresholds 0.3,0.5`` -> ``configs["sweep_thresholds"]``: inference.py also writes a sibling
+               ``pred_threshold_<t>`` directory per listed threshold, eval.py the J&F curve; parse_sweep_thresholds reads it)
 """
 from __future__ import annotations
 
@@ -38,6 +40,31 @@ def parse_overrides(unknown):
         else:
             i += 1
     return out
+
+
+def parse_sweep_thresholds(value):
+    """``--sweep_thresholds`` as load_configs hands it over (a comma list as a string, or one value already coerced to a
+    number) -> list of floats in the caller's order, or None when the flag is absent.  Anything else is a ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, bool):
+        raise ValueError("--sweep_thresholds needs a value: a comma list of thresholds in [0, 1], such as 0.1,0.3,0.5")
+    parts = [value] if isinstance(value, (int, float)) else [p.strip() for p in str(value).split(",")]
+    out = []
+    for p in parts:
+        try:
+            t = float(p)
+        except (TypeError, ValueError):
+            raise ValueError(f"--sweep_thresholds: {p!r} in {value!r} is not a number (expected a comma list such as 0.1,0.3,0.5)")
+        if not 0.0 <= t <= 1.0:  # (also refuses nan)
+            raise ValueError(f"--sweep_thresholds: {p} is outside [0, 1]")
+        out.append(t)
+    return out
+
+
+def sweep_dir_name(t):
+    """A threshold's directory name part, the rule of load_configs below: 0.5 -> "05", 0.25 -> "025", 1.0 -> "10"."""
+    return str(t).replace(".", "")
 
 
 def load_configs(mode: str, argv=None, config_root="configs"):

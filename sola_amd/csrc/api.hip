@@ -1170,6 +1170,15 @@ extern "C" int sola_png_deflate_write(const void* masks, int elem_type, int n, i
                                     scratch_bytes, as_stream(stream_));
 }
 
+extern "C" int sola_png_deflate_sizes_select(const uint32_t* bits, int64_t words_stride, int n_masks, int T, int h, int w,
+                                             const int32_t* sel_off, const int32_t* sel_idx, const int32_t* level_end, int K, int E,
+                                             int64_t* byte_off, uint32_t* adler, void* scratch, size_t scratch_bytes, void* stream_) {
+    SOLA_ARG(bits && sel_off && sel_idx && byte_off && adler && scratch, "png_deflate_sizes_select: null argument");
+    SOLA_ARG((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "png_deflate_sizes_select: scratch must be 8-byte aligned");
+    return launch_png_deflate_sizes_select(bits, (long long)words_stride, n_masks, T, h, w, sel_off, sel_idx, level_end, K, E,
+                                           reinterpret_cast<long long*>(byte_off), adler, scratch, scratch_bytes, as_stream(stream_));
+}
+
 // connected components / small-component rewrite (components.hip)
 extern "C" size_t sola_mask_components_scratch_bytes(int n, int h, int w) { return components_scratch_bytes(n, h, w); }
 

@@ -494,6 +494,11 @@ int launch_png_deflate_sizes(const void* masks, int elem_type, int n, int h, int
                              void* scratch, size_t scratch_bytes, hipStream_t s);
 int launch_png_deflate_write(const void* masks, int elem_type, int n, int h, int w, const long long* byte_off,
                              const uint32_t* adler, uint8_t* bytes, void* scratch, size_t scratch_bytes, hipStream_t s);
+// ... the sizes call over the OR of selected row-major bit planes at nested prefixes (every argument check but null / alignment of
+// the scratch is in the launcher); launch_png_deflate_write completes its streams
+int launch_png_deflate_sizes_select(const uint32_t* bits, long long words_stride, int n_masks, int T, int h, int w, const int* sel_off,
+                                    const int* sel_idx, const int* level_end, int K, int E, long long* byte_off, uint32_t* adler,
+                                    void* scratch, size_t scratch_bytes, hipStream_t s);
 
 // ---- connected components of masks, small-component rewrite (components.hip) --------------------------------------
 size_t components_scratch_bytes(int n, int h, int w);

@@ -13,6 +13,8 @@
 //   sizes (launch_png_deflate_sizes)
 //     1. png_bitmap_kernel   reads the masks ONCE (16-byte loads, shifted to the segment) and writes the raw bitmap to the
 //        scratch; per workgroup the last run start and the two Adler-32 partial sums (sum of bytes, position-weighted sum).
+//        (launch_png_deflate_sizes_select: png_bitmap_select_kernel instead - the bitmap of the OR of selected row-major bit
+//        planes at nested prefixes, one stream per (expression, level, frame); everything after it is the same code.)
 //     2. png_count_kernel    bitmap -> bits of each segment's tokens, summed per workgroup, and the workgroup's first 7 bits.
 //        The start of the run that enters a segment is a max-scan of run starts: inside the workgroup by shuffles, across
 //        workgroups by reading back through kernel 1's per-workgroup values (almost always one step).
@@ -28,6 +30,7 @@
 
 #include "kernels.h"
 #include "mask_elems.h"
+#include "png_select.h"
 
 namespace {
 
@@ -130,6 +133,31 @@ __device__ __forceinline__ uint32_t last_start(u64 B, uint32_t prevbit, uint32_t
     return T ? p0 + (63u - (uint32_t)__clzll((long long)T)) + 1u : 0u;
 }
 
+// The workgroup's records of frame f after its bitmap words: the last run start and the two Adler-32 partial sums.  `prevbit` is
+// the raw bit in front of the thread's word (0 in front of the frame's first).  Ends on a barrier.
+__device__ __forceinline__ void group_records(const PngArgs a, int f, uint32_t blk, uint32_t k, uint32_t p0, uint32_t nv, u64 B,
+                                              uint32_t prevbit, uint32_t* r32, u64* r64) {
+    u64 tr;
+    const uint32_t lt = last_start(B, prevbit, k, p0, nv, tr);
+    // Adler-32 partial sums in units of 255: set bytes, and the sum of (R - p) over them
+    const uint32_t cnt = (uint32_t)__popcll(B);
+    const uint32_t widx = (uint32_t)__popcll(B & 0xaaaaaaaaaaaaaaaaull) + ((uint32_t)__popcll(B & 0xccccccccccccccccull) << 1) +
+                          ((uint32_t)__popcll(B & 0xf0f0f0f0f0f0f0f0ull) << 2) + ((uint32_t)__popcll(B & 0xff00ff00ff00ff00ull) << 3) +
+                          ((uint32_t)__popcll(B & 0xffff0000ffff0000ull) << 4) + ((uint32_t)__popcll(B & 0xffffffff00000000ull) << 5);
+    const u64 w2 = cnt ? (u64)cnt * (u64)(a.R - p0) - widx : 0ull;
+    uint32_t e32, tmax, tcnt;
+    u64 e64, tw2;
+    block_scan<uint32_t>(lt, 0u, OpMax(), r32, e32, tmax);
+    block_scan<uint32_t>(cnt, 0u, OpAdd(), r32, e32, tcnt);
+    block_scan<u64>(w2, 0ull, OpAdd(), r64, e64, tw2);
+    if (threadIdx.x == 0) {
+        const size_t i = (size_t)f * a.NB + blk;
+        a.lasttr[i] = tmax;
+        a.s1[i] = tcnt;
+        a.s2[i] = tw2;
+    }
+}
+
 // ---- phase 1 ------------------------------------------------------------------------------------------------------------
 template <int KIND>
 __global__ __launch_bounds__(256) void png_bitmap_kernel(const PngArgs a) {
@@ -172,24 +200,53 @@ __global__ __launch_bounds__(256) void png_bitmap_kernel(const PngArgs a) {
         const uint32_t p = p0 - 1u, y = p / row, c = p - y * row;
         if (c) prevbit = mask_is_set<KIND>(base[fpix + (long long)y * a.w + (c - 1)]);
     }
-    u64 tr;
-    const uint32_t lt = last_start(B, prevbit, k, p0, nv, tr);
-    // Adler-32 partial sums in units of 255: set bytes, and the sum of (R - p) over them
-    const uint32_t cnt = (uint32_t)__popcll(B);
-    const uint32_t widx = (uint32_t)__popcll(B & 0xaaaaaaaaaaaaaaaaull) + ((uint32_t)__popcll(B & 0xccccccccccccccccull) << 1) +
-                          ((uint32_t)__popcll(B & 0xf0f0f0f0f0f0f0f0ull) << 2) + ((uint32_t)__popcll(B & 0xff00ff00ff00ff00ull) << 3) +
-                          ((uint32_t)__popcll(B & 0xffff0000ffff0000ull) << 4) + ((uint32_t)__popcll(B & 0xffffffff00000000ull) << 5);
-    const u64 w2 = cnt ? (u64)cnt * (u64)(a.R - p0) - widx : 0ull;
-    uint32_t e32, tmax, tcnt;
-    u64 e64, tw2;
-    block_scan<uint32_t>(lt, 0u, OpMax(), r32, e32, tmax);
-    block_scan<uint32_t>(cnt, 0u, OpAdd(), r32, e32, tcnt);
-    block_scan<u64>(w2, 0ull, OpAdd(), r64, e64, tw2);
-    if (threadIdx.x == 0) {
-        const size_t i = (size_t)f * a.NB + blk;
-        a.lasttr[i] = tmax;
-        a.s1[i] = tcnt;
-        a.s2[i] = tw2;
+    group_records(a, f, blk, k, p0, nv, B, prevbit, r32, r64);
+}
+
+// ---- phase 1 from bit planes: the OR of a selection of row-major planes, at up to SOLA_NESTED_MAX_LEVELS nested prefixes ----------
+// One thread per 64-bit raw word of one (expression e, frame t); the grid is (workgroup of 256 words, t, e).  e's list is ordered so
+// that the selection of level l is its prefix of end(e, l) entries (the rules of mask_nested_counts_kernel, jf.hip: ends clamped
+// here to non-decreasing values within the list, a null level_end = the whole list, ids outside [0, n_masks) skipped).  The thread
+// gathers its 64 raw bits from every plane that ENTERS at a level (png_select.h) and carries the OR over the levels in one
+// register; at the end of each level it stores the word into stream (e*K + l)*T + t's bitmap and the workgroup leaves that stream's
+// records.  Every plane of the largest selection is read once per (e, t); list and level reads are block-uniform.
+struct PngSelArgs {
+    const ps_u64* planes;  // [n_masks * T][nq]
+    long long nq;          // 64-bit words of a plane
+    int n_masks, T, K, e0, t0;
+    const int *sel_off, *sel_idx, *level_end;
+};
+
+__global__ __launch_bounds__(256) void png_bitmap_select_kernel(const PngArgs a, const PngSelArgs s) {
+    __shared__ uint32_t top[256];
+    __shared__ uint32_t r32[4];
+    __shared__ u64 r64[4];
+    const int e = s.e0 + blockIdx.z, t = s.t0 + blockIdx.y;
+    const uint32_t blk = blockIdx.x, k = blk * 256u + threadIdx.x, p0 = k * PNG_SEG;
+    const PsWord wd = ps_word(k, a.W, a.R, (uint32_t)a.w + 1u);
+    // the raw byte before this workgroup's first: its flat position, -1 = a filter byte or not this thread's to fetch
+    const long long before = (threadIdx.x == 0 && k > 0 && k < a.W) ? ps_raw_to_flat(p0 - 1u, (uint32_t)a.w) : -1ll;
+    const int l0 = s.sel_off[e], len = max(s.sel_off[e + 1] - l0, 0);
+    const int* le = s.level_end ? s.level_end + (long long)e * s.K : nullptr;
+    u64 B = 0;
+    uint32_t pb = 0;
+    int j = 0, prev = 0;
+    for (int l = 0; l < s.K; ++l) {
+        const int end = le ? min(max(le[l], prev), len) : len;
+        for (; j < end; ++j) {
+            const int m = s.sel_idx[l0 + j];
+            if ((unsigned)m >= (unsigned)s.n_masks) continue;
+            const ps_u64* plane = s.planes + ((long long)m * s.T + t) * s.nq;
+            if (wd.nv) B |= ps_gather(plane, s.nq, wd, (uint32_t)a.w);
+            if (before >= 0) pb |= (uint32_t)ps_fetch(plane, s.nq, before, 1);
+        }
+        prev = end;
+        const int f = (e * s.K + l) * s.T + t;
+        if (wd.nv) a.bitmap[(size_t)f * a.W + k] = B;
+        top[threadIdx.x] = (uint32_t)(B >> 63);
+        __syncthreads();
+        const uint32_t prevbit = threadIdx.x ? top[threadIdx.x - 1] : pb;
+        group_records(a, f, blk, k, p0, wd.nv, B, prevbit, r32, r64);  // (ends on a barrier: top is free again)
     }
 }
 
@@ -533,6 +590,48 @@ int launch_png_deflate_sizes(const void* masks, int elem_type, int n, int h, int
         hipLaunchKernelGGL(png_count_kernel, grid, block, 0, s, a);
         SOLA_LAUNCH_CHECK();
         hipLaunchKernelGGL(png_frame_kernel, dim3(nf), block, 0, s, a);
+        SOLA_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(png_offsets_kernel, dim3(1), dim3(256), 0, s, byte_off, n);
+    SOLA_LAUNCH_CHECK();
+    return SOLA_OK;
+}
+
+int launch_png_deflate_sizes_select(const uint32_t* bits, long long words_stride, int n_masks, int T, int h, int w, const int* sel_off,
+                                    const int* sel_idx, const int* level_end, int K, int E, long long* byte_off, uint32_t* adler,
+                                    void* scratch, size_t scratch_bytes, hipStream_t s) {
+    const char* what = "png_deflate_sizes_select";
+    SOLA_ARG(K >= 1 && E >= 1 && T >= 1 && h >= 1 && w >= 1 && n_masks >= 0 && K <= SOLA_NESTED_MAX_LEVELS,
+             "%s: bad sizes K=%d (1..%d) E=%d T=%d n_masks=%d h=%d w=%d", what, K, SOLA_NESTED_MAX_LEVELS, E, T, n_masks, h, w);
+    SOLA_ARG(level_end || K == 1, "%s: null level_end needs K == 1", what);
+    SOLA_ARG((long long)E * K * T < (1ll << 31), "%s: E*K*T too large (must be < 2^31)", what);
+    const int n = E * K * T;
+    SOLA_ARG((long long)h * ((long long)w + 1) < (1ll << 31), "%s: image too large (h*(w+1) must be < 2^31)", what);
+    SOLA_ARG(words_stride % 4 == 0 && words_stride >= sola_mask_words(h, w), "%s: words_stride %lld must be a multiple of 4 and >= %lld", what,
+             words_stride, (long long)sola_mask_words(h, w));
+    SOLA_ARG((reinterpret_cast<uintptr_t>(bits) & 15) == 0, "%s: planes must be 16-byte aligned", what);
+    SOLA_TRY(check_sizes(what, 0, n, h, w, scratch_bytes));
+    PngArgs a = make_args(bits, n, h, w, scratch);
+    a.byte_off = byte_off;
+    a.adler = adler;
+    PngSelArgs sel{};
+    sel.planes = reinterpret_cast<const ps_u64*>(bits);
+    sel.nq = words_stride / 2;
+    sel.n_masks = n_masks; sel.T = T; sel.K = K;
+    sel.sel_off = sel_off; sel.sel_idx = sel_idx; sel.level_end = level_end;
+    for (int e0 = 0; e0 < E; e0 += PNG_FRAMES)  // gridDim.y, gridDim.z <= 65535
+        for (int t0 = 0; t0 < T; t0 += PNG_FRAMES) {
+            sel.e0 = e0; sel.t0 = t0;
+            const dim3 grid(a.NB, (unsigned)std::min(PNG_FRAMES, T - t0), (unsigned)std::min(PNG_FRAMES, E - e0));
+            hipLaunchKernelGGL(png_bitmap_select_kernel, grid, dim3(256), 0, s, a, sel);
+            SOLA_LAUNCH_CHECK();
+        }
+    for (int f0 = 0; f0 < n; f0 += PNG_FRAMES) {
+        a.frame0 = f0;
+        const unsigned nf = (unsigned)std::min(PNG_FRAMES, n - f0);
+        hipLaunchKernelGGL(png_count_kernel, dim3(a.NB, nf), dim3(256), 0, s, a);
+        SOLA_LAUNCH_CHECK();
+        hipLaunchKernelGGL(png_frame_kernel, dim3(nf), dim3(256), 0, s, a);
         SOLA_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(png_offsets_kernel, dim3(1), dim3(256), 0, s, byte_off, n);

@@ -868,6 +868,147 @@ def encode_png_masklets(masklets, logits=False):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# PNG files of selections of a video's masklets, at one or many thresholds, from one decode per video (inference.py)
+# ----------------------------------------------------------------------------------------------------------------
+def rm_plane_words(h, w):
+    """Stride (uint32 words) of a row-major plane that planes_cm_to_rm writes: sola_mask_words rounded up to a multiple of 4."""
+    return (lib().sola_mask_words(h, w) + 3) // 4 * 4
+
+
+@torch.no_grad()
+def planes_cm_to_rm(bits_cm, h, w, out=None):
+    """Column-major bit planes ``[n, sola_jf_plane_words(h, w)]`` int32 (sola_rle_pack_cm / pack_index_masklets ``layout="cm"``)
+    -> row-major planes ``[n, rm_plane_words(h, w)]`` int32 in the layout of pack_masks (bit y*w + x; tail and pad bits zero),
+    which pair_counts and the PNG selection front-end read: RLE masklets reach them without a uint8 stage.  One launch
+    (sola_planes_cm_to_rm); every word of ``out`` is written whatever it held."""
+    require_cuda(bits_cm)
+    if bits_cm.dim() != 2 or bits_cm.dtype != torch.int32 or not bits_cm.is_contiguous():
+        raise SolaError(f"planes_cm_to_rm: planes must be a contiguous int32 [n, words] tensor, got {bits_cm.dtype} {tuple(bits_cm.shape)}")
+    n, stride = bits_cm.shape
+    words = rm_plane_words(h, w)
+    if out is None:
+        out = torch.empty((n, words), device=bits_cm.device, dtype=torch.int32)
+    elif not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == n and
+              out.shape[1] >= words):
+        raise SolaError(f"planes_cm_to_rm: out must be a contiguous int32 device tensor [{n}, >= {words}]")
+    if n:
+        check(lib().sola_planes_cm_to_rm(ptr(bits_cm), stride, n, h, w, ptr(out), out.shape[1], current_stream(bits_cm.device)),
+              "sola_planes_cm_to_rm")
+    return out
+
+
+def _png_levels(who, masklets, lists, ends, K, device, max_plane_bytes, max_scratch_bytes):
+    """The PNG path under encode_png_selections and encode_png_sweep: ``out[e][k][t]`` = the complete PNG file (bytes) of frame
+    t of the OR over ``lists[e][:ends[e][k]]``; ``ends[e]`` holds K non-decreasing prefix lengths.  Per group of _plane_groups
+    (every referenced track parsed and decoded once): one sola_planes_cm_to_rm, then for blocks of (expressions, at most
+    SOLA_NESTED_MAX_LEVELS levels) whose scratch stays under ``max_scratch_bytes`` (a single expression's block runs alone
+    whatever it needs) one int32 upload of the lists, sola_png_deflate_sizes_select, one host read of the offsets,
+    sola_png_deflate_write and one copy of the streams.  A later block of levels starts from the whole prefix of its first."""
+    E, M = len(lists), len(masklets)
+    if M == 0:
+        raise SolaError(f"{who}: no masklets")
+    for s in lists:
+        for i in s:
+            if not 0 <= int(i) < M:
+                raise SolaError(f"{who}: index {i} outside the {M} masklets")
+    T, size = _masklet_geometry(masklets)
+    if size is None:
+        raise SolaError(f"{who}: every frame of every masklet is missing: there is no size to write a PNG at")
+    if E == 0 or T == 0:
+        return [[[] for _ in range(K)] for _ in range(E)]
+    h, w = size
+    L = lib()
+    dev = torch.device(device)
+    stream = current_stream(dev)
+    stride_cm, stride_rm = L.sola_jf_plane_words(h, w), rm_plane_words(h, w)
+    head = b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0))
+    tail = _png_chunk(b"IEND", b"")
+    preds = [[int(i) for i in lists[e][:ends[e][-1]]] for e in range(E)]  # what the largest level selects
+    NL = 16  # SOLA_NESTED_MAX_LEVELS
+    out = [[None] * K for _ in range(E)]
+    for grp, local, bits_cm, n_ids in _plane_groups(masklets, preds, T, h, w, stride_cm, dev, max_plane_bytes):
+        if n_ids:
+            bits = planes_cm_to_rm(bits_cm, h, w)
+        else:  # no expression of the group selects a track: no plane is read
+            bits = torch.zeros((1, stride_rm), device=dev, dtype=torch.int32)
+        del bits_cm
+        for k0 in range(0, K, NL):
+            kc = min(NL, K - k0)
+            fit = 1
+            while fit < len(grp) and L.sola_png_deflate_scratch_bytes((fit + 1) * kc * T, h, w) <= max_scratch_bytes:
+                fit += 1
+            for b0 in range(0, len(grp), fit):
+                blk = grp[b0:b0 + fit]
+                off, idx, lend = [0], [], []
+                for e in blk:
+                    idx += [local[i] for i in preds[e][:ends[e][k0 + kc - 1]]]
+                    off.append(len(idx))
+                    lend += ends[e][k0:k0 + kc]
+                parts = [lend, off, idx + [0]]  # (the pad entry keeps the pointer of an empty list non-null)
+                ints = torch.tensor([x for part in parts for x in part], dtype=torch.int32).to(dev)  # one copy for every list
+                d, o = [], 0
+                for part in parts:
+                    d.append(ptr(ints[o:o + len(part)]))
+                    o += len(part)
+                n = len(blk) * kc * T
+                nb = L.sola_png_deflate_scratch_bytes(n, h, w)
+                scratch = _stream_scratch("png_select", dev, max(nb, 8), torch.int64)
+                byte_off = torch.empty((n + 1,), device=dev, dtype=torch.int64)
+                adler = torch.empty((n,), device=dev, dtype=torch.int32)
+                check(L.sola_png_deflate_sizes_select(ptr(bits), stride_rm, n_ids, T, h, w, d[1], d[2], d[0], kc, len(blk), ptr(byte_off),
+                                                      ptr(adler), ptr(scratch), nb, stream), "sola_png_deflate_sizes_select")
+                offs = byte_off.cpu().tolist()  # the host read: every stream's first byte, offs[n] = the size of the buffer
+                data = torch.empty((offs[n],), device=dev, dtype=torch.uint8)
+                check(L.sola_png_deflate_write(ptr(bits), 0, n, h, w, ptr(byte_off), ptr(adler), ptr(data), ptr(scratch), nb, stream),
+                      "sola_png_deflate_write")
+                data = data.cpu().numpy().tobytes()
+                for j, e in enumerate(blk):
+                    for k in range(kc):
+                        s0 = (j * kc + k) * T
+                        out[e][k0 + k] = [head + _png_chunk(b"IDAT", data[offs[s0 + t]:offs[s0 + t + 1]]) + tail for t in range(T)]
+    return out
+
+
+@torch.no_grad()
+def encode_png_selections(masklets, pred_sets, device, max_plane_bytes=2 << 30, max_scratch_bytes=1 << 30):
+    """``out[e][t]``: the PNG file (bytes) of frame t of the OR of ``masklets[i]`` for i in ``pred_sets[e]`` - byte for byte the
+    files of ``encode_png_masklet(rle_merge_or([masklets[i] for i in pred_sets[e]], device))``, for every expression of a video
+    from ONE parse and ONE decode of the tracks some expression selects (``masklets`` as masklet_select_counts takes them).  No
+    ``[T,h,w]`` masklet is materialised: the decoded bit planes are transposed to row-major once (planes_cm_to_rm) and the PNG
+    encoder's bitmap front-end ORs a selection's planes while it reads them (sola_png_deflate_sizes_select).  An empty
+    selection gives all-zero frames; masklets without any sized frame raise SolaError (there is nothing to size a PNG by).
+    This is encode_png_sweep's path with one level that ends at the list's end."""
+    lists = [list(s) for s in pred_sets]
+    return [ek[0] for ek in _png_levels("encode_png_selections", masklets, lists, [[len(s)] for s in lists], 1, device, max_plane_bytes,
+                                        max_scratch_bytes)]
+
+
+@torch.no_grad()
+def encode_png_sweep(masklets, cand_sets, probs, thresholds, device, max_plane_bytes=2 << 30, max_scratch_bytes=1 << 30):
+    """encode_png_selections at every threshold of a sweep from one decode: ``out[e][j][t]`` is the PNG file (bytes) of frame t
+    of the OR of {``masklets[cand_sets[e][i]]`` : ``probs[e][i]`` > ``thresholds[j]``} (float32, strict: the rule of sweep_levels
+    and of ops.select), thresholds in the caller's order.  The selections at descending thresholds are nested, so each track of
+    the largest one is decoded once per group of expressions and read once per (expression, frame) and 16 levels: the encoder's
+    front-end carries the OR from level to level and emits every level's raw bitmap."""
+    import numpy as np
+    E, K = len(cand_sets), len(thresholds)
+    if K == 0:
+        raise SolaError("encode_png_sweep: no thresholds")
+    if len(probs) != E:
+        raise SolaError(f"encode_png_sweep: {E} candidate sets but {len(probs)} score vectors")
+    ordered, ends, perm = [], [], np.arange(K)
+    for e in range(E):
+        if len(probs[e]) != len(cand_sets[e]):
+            raise SolaError(f"encode_png_sweep: expression {e} has {len(cand_sets[e])} tracks but {len(probs[e])} scores")
+        order, level_end, perm = sweep_levels(probs[e], thresholds)
+        rest = np.setdiff1d(np.arange(len(probs[e])), order)  # never selected: range-checked with the others, never read
+        ordered.append([cand_sets[e][i] for i in order] + [cand_sets[e][i] for i in rest])
+        ends.append(level_end.tolist())
+    levels = _png_levels("encode_png_sweep", masklets, ordered, ends, K, device, max_plane_bytes, max_scratch_bytes)
+    return [[le[int(perm[j])] for j in range(K)] for le in levels]
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # connected components, SAM2's fill_holes_in_mask_scores, small-region removal (components.hip)
 # ----------------------------------------------------------------------------------------------------------------
 CC_TILE = (16, 64)  # (rows, columns) of the labelling kernel's tile: include/sola_hip.h SOLA_CC_TILE_H / _W
