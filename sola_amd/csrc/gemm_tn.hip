@@ -31,7 +31,8 @@ constexpr int TP = TB + 4;    // LDS pitch (floats), 16-byte aligned rows
 
 // one (tile, row split) work item: tile = tn * tiles_k + tk
 // NW = 4: 2 x 2 waves of 64 x 64; NW = 8 (round 4): 4 x 2 waves of 32 x 64 - the CU's two blocks (LDS) put four waves on every SIMD instead of
-// two, as in the NT kernel (gemm.hip); the same reduction order per output element: bit-identical.
+// two, as in the NT kernel (gemm.hip); the same reduction order per output element: bit-identical.  (The bias gradient Pb is not: a
+// thread sums rows 16 apart there and 8 apart at NW = 4, another fixed order - tests/test_gpu_gemm_tn.py holds it to float64 under both.)
 template <int NW>
 __device__ __forceinline__ void tn_tile(const TnArgs& a, int tile, int split, float* smem) {
     constexpr int TMW = NW == 8 ? 1 : 2;     // 32-row MFMA tiles per wave along n
