@@ -138,6 +138,7 @@ extern "C" int sola_ctx_create(const SolaConfig* cfg, int device, SolaCtx** out)
     SolaCtx* c = new SolaCtx();
     c->cfg = *cfg;
     c->device = device;
+    c->reset_sites();
     const int d = cfg->object_token_dim, h = 2 * d, D = cfg->lang_token_dim;
     const ConvGeom geo[6] = {{d, h, 3, 2, 1}, {h, h, 3, 2, 1}, {h, h, 3, 2, 1}, {h, D, 3, 1, 1}, {D, D, 3, 1, 1}, {D, D, 1, 1, 0}};
     // state_dict order of the reference: own buffer, encoder, layers, embedding

@@ -75,16 +75,26 @@ struct SolaCtx {
     const float* last_obj = nullptr;  // input of the last training forward (conv0's weight gradient reads it)
     RagTables last_rag;               // last.rag: the unit tables that forward left in its workspace
     const void* last_ws = nullptr;    // workspace of the last forward (sola_backward_ragged checks it gets the same one)
-    // round 6, bf16 training step: attention site (layer * 3 + which) of the last training forward keeps its q / k / v as BFLOAT16 rows
-    // (written by the projection GEMM's epilogue, read by the attention forward and backward; the backward then writes dq / dk / dv as
-    // bfloat16 too - the dW / dX GEMMs' operand, no f32 copy, no cast pass).  Decided per site by the shapes the kernels take.
-    std::vector<char> qkv16;
-    // ... and sub-block (layer * 3 + which) keeps its PRE-NORM rows (out-projection + residual, the GroupNorm's input) as bfloat16: the
-    // out-projection GEMM reads the residual from the sub-block input's bf16 operand copy and writes bf16, the GroupNorm forward and
-    // backward read bf16 (sola_tune "train_bf16_store" 2)
-    std::vector<char> res16;
-    std::vector<char> attn_o16;   // per (layer, site): the last training forward wrote that attention's output as bfloat16 rows ONLY (arena slot keyed by the f32 buffer)
+    // What the last training forward kept per attention site (layer, which) - its contract with the backward.  Sized at sola_ctx_create,
+    // reset by every training forward (reset_sites), read through site(l, a).
+    struct SiteKeep {
+        // bf16 steps (round 6): the site keeps its q / k / v as BFLOAT16 rows (written by the projection GEMM's epilogue, read by the attention
+        // forward and backward; the backward then writes dq / dk / dv as bfloat16 too - the dW / dX GEMMs' operand, no f32 copy, no cast
+        // pass).  Decided per site by the shapes the kernels take.
+        bool qkv16 = false;
+        // ... the sub-block keeps its PRE-NORM rows (out-projection + residual, the GroupNorm's input) as bfloat16: the out-projection GEMM
+        // reads the residual from the sub-block input's bf16 operand copy and writes bf16, the GroupNorm forward and backward read bf16
+        // (sola_tune "train_bf16_store" 2)
+        bool res16 = false;
+        bool o16 = false;  // ... the attention's output exists as bfloat16 rows ONLY (arena slot keyed by the f32 buffer)
+    };
+    std::vector<SiteKeep> sites;  // [3 * n_layers]
     std::vector<char> gn2_stats;  // per layer: the last training forward left the object->language norm's (mean, rstd) in "l<l>_gn2st" (forward.hip)
+    SiteKeep& site(int layer, int a) { return sites[(size_t)layer * 3 + a]; }
+    void reset_sites() {
+        sites.assign((size_t)cfg.n_layers * 3, SiteKeep{});
+        gn2_stats.assign((size_t)cfg.n_layers, 0);
+    }
     // inference precision: 0 = exact f32 MFMA; 1 = split-f16 operands, 3 x f16 MFMA with f32 accumulation (cast.hip).
     // ctx-owned split-f16 copies of the weights: standardised conv weights (same offsets as ws_buf) and the
     // 12 * n_layers linear weights pre-scaled by 64 (index (layer * 3 + attn) * 4 + proj, D*D floats each).
@@ -189,6 +199,16 @@ inline std::string abuf(bool train, int layer, const char* attn, const char* wha
     if (!train) return what;
     return "l" + std::to_string(layer) + "_" + attn + "_" + what;
 }
+
+// sola_tune keys that the training forward (forward.hip) and the backward (backward.hip) read of each other
+extern int g_train_split_min_rows, g_train_bf16_store, g_train_dw_f16;
+
+// Geometry of attention site `a` (0 inter-object, 1 motion, 2 object -> language) in the backward of plan `p` (rt != null: a ragged batch):
+// group count, Sq, Sk, inner, the strides, the pitches (q / k / v / o: D; dq: 3D; dk / dv: 3D, or 2D for the text side of site 2), the
+// unit tables, the softmax scale and, for site 2, the extents of the chunked launch's `part` scratch (the pointer is the caller's).
+// backward.hip launches with this record and the training forward asks attention_bwd_bf16_supported with it: one statement, so the
+// forward keeps bf16 rows exactly where the backward can read them.
+AttnBwdDesc attn_bwd_site_desc(const SolaCtx* c, const Plan& p, const RagTables* rt, int a, float* part);
 
 struct RagShape;
 Plan make_plan(const SolaCtx* c, int B, int N, int T, int L, bool train);

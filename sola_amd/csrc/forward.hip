@@ -10,7 +10,6 @@
 #include "ragged.h"
 
 int g_train_gn_cast = 1;  // sola_tune "train_gn_cast": 1 = a GroupNorm of the training forward also writes the operand cast of the GEMM behind it
-extern int g_train_dw_f16;
 int g_train_attn_cast = 1;  // sola_tune "train_attn_cast": 1 = f16 / bf16 operand steps: the training forward's attention kernels also write the out-projection's operand cast; 2 = the split-f16 step too
 int g_train_bf16_store = 3;  // sola_tune "train_bf16_store" (round 6): 1 = bf16 steps keep q / k / v and the backward's gradient operands as bfloat16 rows where the kernels take
                              // them; 2 = also the pre-norm rows of the layers (out-projection + residual -> GroupNorm); 3 (default) = also the conv input gradients' per-tap
@@ -321,8 +320,9 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     };
     // bf16 steps: does attention site `ad` keep q / k / v (forward) and dq / dk / dv (backward) as bfloat16 rows?  Both kernels must take
     // the shape (attn_simple.hip's training instantiation; attn_bwd.hip's one-pass kernel)
-    c->qkv16.assign((size_t)c->cfg.n_layers * 3, 0);
-    auto site16 = [&](const AttnDesc& ad, bool o2l) -> bool {
+    c->reset_sites();
+    auto site16 = [&](const AttnDesc& ad, int a) -> bool {
+        const bool o2l = a == 2;
         if (!(split && pure && bf && g_train_bf16_store)) return false;
         // the backward's dW products of these gradients must take the row-major 16-bit kernel (no f32 copy exists to transpose)
         if (!gemm_tn_tr_supported(M, D, D, D, D) || (o2l && !gemm_tn_tr_supported((int)text_rows, D, D, D, D))) return false;
@@ -330,18 +330,8 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
         f.in_bf16 = 1;
         f.o_cast = reinterpret_cast<void*>(1); f.o_cast_fmt = 3;  // (what attention() below hands the launch)
         if (!attention_in_bf16_supported(f) && !attention_bf16_mfma_supported(f)) return false;
-        AttnBwdDesc b{};
-        b.ldq = b.ldk = b.ldv = b.ldo = D;
-        b.ld_dq = 3 * D; b.ld_dk = b.ld_dv = o2l ? 2 * D : 3 * D;
-        b.G = ad.G; b.H = ad.H; b.DH = ad.DH; b.Sq = ad.Sq; b.Sk = ad.Sk; b.inner = ad.inner;
-        b.q_outer = ad.q_outer; b.q_inner = ad.q_inner; b.q_rs = ad.q_rs; b.k_outer = ad.k_outer; b.k_inner = ad.k_inner; b.k_rs = ad.k_rs;
-        b.q_units = ad.q_units; b.k_units = ad.k_units;
-        if (o2l) {  // what backward.hip hands the chunked launch
-            b.part = reinterpret_cast<float*>(1);
-            b.part_floats = attention_bwd_part_floats((long long)M, B, H, 64);
-            b.part_rows = (long long)M;
-        }
-        return attention_bwd_bf16_supported(b);
+        // the backward's own record of the site (the chunked launch of site 2 gets its scratch there)
+        return attention_bwd_bf16_supported(attn_bwd_site_desc(c, p, rs ? &rt : nullptr, a, reinterpret_cast<float*>(1)));
     };
     // The attention output's operand cast for the out-projection is written by the attention kernel itself where its shape can
     // (AttnDesc::o_cast, round 4; sola_tune "train_attn_cast" 0 = always the separate cast launch)
@@ -349,8 +339,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     float* ac_dst = nullptr;
     void* ac_side = nullptr;
     bool ac_done = false;
-    int o16_site = -1;  // set by the layer loop in front of a site's attention() call: index l * 3 + a of c->attn_o16
-    c->attn_o16.assign((size_t)c->cfg.n_layers * 3, 0);
+    SolaCtx::SiteKeep* o16_site = nullptr;  // set by the layer loop in front of a site's attention() call: the site's record
     auto attention = [&](AttnDesc& ad) -> int {
         ac_src = nullptr; ac_done = false;
         // measured on the 64-sample ragged mix (same box): f16 operands 22.67 -> 22.55 ms per step (attention +0.10 ms, cast launches -0.26 ms);
@@ -364,13 +353,13 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
             // bf16 steps (train_bf16_store 3): where the bf16-MFMA kernel writes the out-projection's operand rows itself and they have an arena
             // slot of their own, the f32 rows are not written at all - the out-projection, its weight gradient and the attention backward
             // (D = dO . O) read the bfloat16 rows (4 of the launch's 12 bytes per element)
-            if (o16_site >= 0 && ad.in_bf16 && g_train_bf16_store >= 3 && ac_dst != sp_a && ac_dst != sp_b && ad.o_cast_fmt == 3 &&
+            if (o16_site && ad.in_bf16 && g_train_bf16_store >= 3 && ac_dst != sp_a && ac_dst != sp_b && ad.o_cast_fmt == 3 &&
                 attention_bf16_mfma_supported(ad) && attention_bwd_dout_bf16_enabled()) {
                 ad.o = nullptr;
-                c->attn_o16[(size_t)o16_site] = 1;
+                o16_site->o16 = true;
             }
         }
-        o16_site = -1;
+        o16_site = nullptr;
         return launch_attention(ad, s);
     };
     // r16 != null (bf16 steps, sola_tune "train_bf16_store" 2): the residual is read from the sub-block input's bfloat16 operand copy and
@@ -416,7 +405,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
             }
             nd.cast_fmt = gn_fmt;
         }
-            nd.slice_ws = buf("gn_slots"); nd.slice_ws_bytes = (size_t)p.bufs.at("gn_slots").rows * p.bufs.at("gn_slots").cols * sizeof(float);
+        nd.slice_ws = buf("gn_slots"); nd.slice_ws_bytes = (size_t)p.bufs.at("gn_slots").rows * p.bufs.at("gn_slots").cols * sizeof(float);
         nd.x = res; nd.y = y; nd.y2 = y2; nd.pe = y2 ? buf("pe") : nullptr;
         nd.gamma = W(lp + "norm." + std::to_string(idx) + ".weight");
         nd.beta = W(lp + "norm." + std::to_string(idx) + ".bias");
@@ -430,13 +419,11 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
             nd.stats_out = buf("l" + std::to_string(l) + "_gn2st");
             nd.stats_written = &wrote;
             SOLA_TRY(launch_group_norm(nd, s));
-            if ((size_t)l < c->gn2_stats.size()) c->gn2_stats[l] = (char)wrote;
+            c->gn2_stats[l] = (char)wrote;
             return SOLA_OK;
         }
         return launch_group_norm(nd, s);
     };
-    c->gn2_stats.assign((size_t)c->cfg.n_layers, 0);
-    c->res16.assign((size_t)c->cfg.n_layers * 3, 0);
     // the bf16 operand copy of a sub-block's input, if it sits in the kept-operand arena (a shared cast buffer is overwritten before the
     // out-projection runs) - then the sub-block's pre-norm rows are bfloat16 (out_proj / gn above)
     auto resid16 = [&](const float* resid) -> const void* {
@@ -459,15 +446,15 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
                         (long long)N * Tp, 1, Tp, (long long)N * Tp, 1, Tp, scale, ab(0, "lse")};
             if (rs) { ad.G = rt.sumTpS; ad.inner = 1; ad.q_units = rt.u_st; }
             ad.drop = c->attn_drop(l, 0);
-            const bool s16 = site16(ad, false);
+            const bool s16 = site16(ad, 0);
             SOLA_TRY(linear3(xin, xin, xin, lp + "obj_attn", 3, M, ab(0, "q"), ab(0, "k"), ab(0, "v"), 0, nullptr, s16));
             ad.in_bf16 = s16 ? 1 : 0;
-            c->qkv16[(size_t)l * 3 + 0] = s16;
-            o16_site = l * 3 + 0;
+            c->site(l, 0).qkv16 = s16;
+            o16_site = &c->site(l, 0);
             SOLA_TRY(attention(ad));
         }
         const void* r16_0 = resid16(xin);
-        c->res16[(size_t)l * 3 + 0] = r16_0 != nullptr;
+        c->site(l, 0).res16 = r16_0 != nullptr;
         SOLA_TRY(out_proj(lp + "obj_attn", ab(0, "attn"), xin, ab(0, "res"), r16_0));
         if (rs) SOLA_TRY(gn(lp, 0, ab(0, "res"), x_obj, x_pe, rt.sumTpS, 1, 0, 0, 1, N, rt.u_st, x_pe, x_obj, r16_0 != nullptr));
         else SOLA_TRY(gn(lp, 0, ab(0, "res"), x_obj, x_pe, B * Tp, Tp, (long long)N * Tp, 1, Tp, N, nullptr, x_pe, x_obj, r16_0 != nullptr));
@@ -477,15 +464,15 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
                         (long long)Tp, 0, 1, (long long)Tp, 0, 1, scale, ab(1, "lse")};
             if (rs) { ad.G = rt.sumNS; ad.q_units = rt.u_strk; }
             ad.drop = c->attn_drop(l, 1);
-            const bool s16 = site16(ad, false);
+            const bool s16 = site16(ad, 1);
             SOLA_TRY(linear3(x_pe, x_pe, x_obj, lp + "motion_attn", 3, M, ab(1, "q"), ab(1, "k"), ab(1, "v"), 0, nullptr, s16));
             ad.in_bf16 = s16 ? 1 : 0;
-            c->qkv16[(size_t)l * 3 + 1] = s16;
-            o16_site = l * 3 + 1;
+            c->site(l, 1).qkv16 = s16;
+            o16_site = &c->site(l, 1);
             SOLA_TRY(attention(ad));
         }
         const void* r16_1 = resid16(x_obj);
-        c->res16[(size_t)l * 3 + 1] = r16_1 != nullptr;
+        c->site(l, 1).res16 = r16_1 != nullptr;
         SOLA_TRY(out_proj(lp + "motion_attn", ab(1, "attn"), x_obj, ab(1, "res"), r16_1));
         if (rs) SOLA_TRY(gn(lp, 1, ab(1, "res"), x_mot, nullptr, rt.sumNS, 1, 0, 0, 1, Tp, rt.u_strk, x_mot, nullptr, r16_1 != nullptr));
         else SOLA_TRY(gn(lp, 1, ab(1, "res"), x_mot, nullptr, B * N, 1, Tp, 0, 1, Tp, nullptr, x_mot, nullptr, r16_1 != nullptr));
@@ -495,17 +482,17 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
                         (long long)N * Tp, 0, 1, (long long)Wn, 0, 1, scale, ab(2, "lse")};
             if (rs) { ad.Sq = rt.maxRowsSample; ad.q_units = rt.u_smp; ad.k_units = rt.u_langk; }
             ad.drop = c->attn_drop(l, 2);
-            const bool s16 = site16(ad, true);
+            const bool s16 = site16(ad, 2);
             SOLA_TRY(linear3(x_mot, nullptr, nullptr, lp + "object2lang_attn", 1, M, ab(2, "q"), nullptr, nullptr, 0, nullptr, s16));
             SOLA_TRY(linear3(buf("lang"), buf("lang"), nullptr, lp + "object2lang_attn", 2, (int)text_rows, ab(2, "lk"), ab(2, "lv"), nullptr, 1,
                              split ? c->scal_pair(1) : nullptr, s16));
             ad.in_bf16 = s16 ? 1 : 0;
-            c->qkv16[(size_t)l * 3 + 2] = s16;
-            o16_site = l * 3 + 2;
+            c->site(l, 2).qkv16 = s16;
+            o16_site = &c->site(l, 2);
             SOLA_TRY(attention(ad));
         }
         const void* r16_2 = resid16(x_mot);
-        c->res16[(size_t)l * 3 + 2] = r16_2 != nullptr;
+        c->site(l, 2).res16 = r16_2 != nullptr;
         SOLA_TRY(out_proj(lp + "object2lang_attn", ab(2, "attn"), x_mot, ab(2, "res"), r16_2));
         // the next layer's q / k / v projections read x_o2l: its norm writes their operand (nothing reads it behind the last layer)
         const float* nxt_in = l + 1 < c->cfg.n_layers ? x_o2l : nullptr;

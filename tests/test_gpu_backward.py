@@ -520,21 +520,25 @@ def test_bf16_statistics_pass_that_is_the_cast_gives_the_same_gradients_bit_for_
     default 1).  The two-pass path scales by a power of two before rounding and undoes it behind the f32 accumulation: the same
     products, so every gradient must keep its bits with the switch off.  (Round 6: with the step's bf16 STORAGE on, the producers write the
     bfloat16 rows themselves and the bias sums are taken from those rounded rows - as autocast's grad_output.sum(0) is - so this A/B of
-    the pass runs with sola_tune "train_bf16_store" 0.)"""
+    the pass runs with sola_tune "train_bf16_store" 0.)
+    The third setting, sola_tune "bwd_dual_cast" 0, is the same step once more without any row-major cast left behind for the dX GEMMs
+    (neither by the statistics pass nor by the weight gradients' transposing cast): they cast the gradient matrix themselves, with the
+    same scale - the same 16-bit values, so the same bits again."""
     m, _ = full_model
     cfg = synth.DEFAULT_MODEL_CFG
     got = {}
     try:
         m.precision = "bf16"
-        for fused in (1, 0):
-            with tuned(train_bf16_store=0, bwd_fused_bf16_cast=fused):
+        for fused, dual in ((1, 1), (0, 1), (1, 0)):
+            with tuned(train_bf16_store=0, bwd_fused_bf16_cast=fused, bwd_dual_cast=dual):
                 _, l3, g = train_step_grads(m, cfg, 8, 40, 32, 10, 77)
-            got[fused] = ({k: v.clone() for k, v in g.items()}, l3.detach().clone())
+            got[fused, dual] = ({k: v.clone() for k, v in g.items()}, l3.detach().clone())
     finally:
         m.precision = "f32"
-    assert torch.equal(got[1][1], got[0][1])
-    bad = [k for k in got[1][0] if not torch.equal(got[1][0][k], got[0][0][k])]
-    assert not bad, bad
+    for other in ((0, 1), (1, 0)):
+        assert torch.equal(got[1, 1][1], got[other][1]), other
+        bad = [k for k in got[1, 1][0] if not torch.equal(got[1, 1][0][k], got[other][0][k])]
+        assert not bad, (other, bad)
 
 
 @pytest.mark.parametrize("fused", [True, False])
