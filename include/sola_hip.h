@@ -140,6 +140,17 @@ int sola_gemm_nt_split(const float* dev_a_sp, int lda, const float* dev_w_sp, co
 int sola_gemm_nt_split_scaled(const float* dev_a_sp, int lda, const float* dev_w_sp, const float* dev_bias, const float* dev_r,
                               int ldr, int r_is_split, float* dev_c, int ldc, int c_is_split, int M, int N, int K,
                               float out_scale, const float* dev_out_scale, void* stream);
+/* Channels-last 1-d conv on split-f16 operands, exposed for the parity tests: x_sp [R * T_in][cin], w_sp [cout][k * cin] (both
+ * from sola_cast_sp16, cin % 32 == 0), f32 y [R * T_out][cout] = conv + bias.  mode 0: one implicit-im2col GEMM (the taps in the
+ * zero padding are multiplied); mode 1: one plain GEMM per output frame on the taps inside the sequence (at most five output
+ * frames; an error where the conv has no such form); mode -1: what the split-f16 forward would take for this shape.  Both forms
+ * give the same bits for finite weights.  The call synchronises the stream in modes 1 / -1. */
+int sola_conv1d_cl_split(const float* dev_x_sp, const float* dev_w_sp, const float* dev_bias, float* dev_y, int64_t R, int T_in, int cin,
+                         int cout, int k, int stride, int pad, int mode, void* stream);
+/* The split-f16 standardised conv weights the context holds after a split-f16 forward, for the tests: encoder conv `layer` (0..5),
+ * its whole [cout][k * cin] matrix (range -1) or the packed copy of tap range `range` (0 .. *n_ranges - 1: taps *lo .. *hi, a
+ * [cout][(*hi - *lo + 1) * cin] matrix), copied to dev_out (NULL = only the numbers). */
+int sola_conv_weights_split(const SolaCtx* ctx, int layer, int range, float* dev_out, int* lo, int* hi, int* n_ranges, void* stream);
 
 /* Building blocks of precision 2 (16-bit activation storage), exposed for the parity tests: f32 rows -> _Float16 rows (fixed
  * power-of-two scale, or data-dependent with dev_scal as for sola_cast_sp16_auto); C = out_scale * (A W^T) + bias (+ R) on

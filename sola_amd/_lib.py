@@ -66,6 +66,8 @@ SIGNATURES = {
     "sola_gemm_nt_split": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "sola_cast_sp16_auto": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp, _vp]),
     "sola_gemm_nt_split_scaled": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "sola_conv1d_cl_split": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sola_conv_weights_split": (_i, [_vp, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp]),
     "sola_cast_f16": (_i, [_vp, _i, _vp, _i, _i64, _i, _f, _vp, _vp]),
     "sola_gemm_nt_f16": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "sola_gemm_nn": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),

@@ -185,6 +185,7 @@ extern "C" int sola_ctx_destroy(SolaCtx* c) {
     if (!c) return SOLA_OK;
     if (c->ws_buf) (void)hipFree(c->ws_buf);
     if (c->ws16_buf) (void)hipFree(c->ws16_buf);
+    if (c->ws16_taps_buf) (void)hipFree(c->ws16_taps_buf);
     if (c->lin16_buf) (void)hipFree(c->lin16_buf);
     if (c->scal_buf) (void)hipFree(c->scal_buf);
     if (c->guard_host) (void)hipHostFree(c->guard_host);
@@ -414,6 +415,20 @@ extern "C" int sola_set_precision(SolaCtx* c, int precision) {
         for (int i = 0; i < 6; ++i) ws_total += (size_t)c->conv[i].cout * c->conv[i].cin * c->conv[i].k;
         SOLA_HIP(hipSetDevice(c->device));
         SOLA_HIP(hipMalloc(&c->ws16_buf, ws_total * sizeof(float)));
+        // the edge frames' column ranges of the stride-1 padded convs (ctx.h: ws_taps), packed; split-f16 pairs need cin % 8 == 0
+        size_t taps_total = 0;
+        for (int i = 0; i < 6; ++i) {
+            const ConvGeom& g = c->conv[i];
+            c->ws_ntaps[i] = 0;
+            if (g.stride != 1 || g.pad < 1 || g.pad >= g.k || g.cin % 8 != 0) continue;
+            const int range[2][2] = {{g.pad, g.k - 1}, {0, g.k - 1 - g.pad}};
+            for (int j = 0; j < 2; ++j) {
+                c->ws_taps[i][j] = SolaCtx::TapRange{range[j][0], range[j][1], taps_total};
+                taps_total += (size_t)g.cout * g.cin * (range[j][1] - range[j][0] + 1);
+            }
+            c->ws_ntaps[i] = 2;
+        }
+        if (taps_total) SOLA_HIP(hipMalloc(&c->ws16_taps_buf, taps_total * sizeof(float)));
         SOLA_HIP(hipMalloc(&c->lin16_buf, (size_t)c->cfg.n_layers * 12 * D * D * sizeof(float)));
         const size_t n_pairs = 2 + (size_t)c->cfg.n_layers * 12;
         SOLA_HIP(hipMalloc(&c->scal_buf, (2 * n_pairs + 2 + 4) * sizeof(float)));
@@ -442,6 +457,70 @@ extern "C" int sola_gemm_nt_split(const float* a_sp, int lda, const float* w_sp,
     gd.M = M; gd.N = N; gd.K = K; gd.lda = lda; gd.ldr = ldr; gd.ldc = ldc;
     gd.arith = 1; gd.out_scale = out_scale; gd.r_sp16 = r_sp16; gd.c_sp16 = c_sp16;
     return launch_gemm(gd, as_stream(stream_));
+}
+
+// channels-last conv on split-f16 operands (tests): x_sp [R * T_in][cin], w_sp [cout][k * cin], f32 y [R * T_out][cout].
+// mode 0: the implicit-im2col launch; 1: the per-frame plain GEMMs wherever the conv has that form (an error where not);
+// -1: the split-f16 forward's own rule.  Same planner and launcher as the forward (conv_frames.hip); the packed column ranges
+// the forward keeps in its context are cut out of w_sp here, into a buffer that lives for the call (the call synchronises).
+extern "C" int sola_conv1d_cl_split(const float* x_sp, const float* w_sp, const float* bias, float* y, int64_t R, int T_in, int cin, int cout,
+                                    int k, int stride, int pad, int mode, void* stream_) {
+    SOLA_ARG(x_sp && w_sp && y, "conv1d_cl_split: null argument");
+    SOLA_ARG(R > 0 && T_in > 0 && cin > 0 && cout > 0 && k >= 1 && k <= 8 && stride >= 1 && pad >= 0 && mode >= -1 && mode <= 1,
+             "conv1d_cl_split: R=%lld T_in=%d cin=%d cout=%d k=%d stride=%d pad=%d mode=%d", (long long)R, T_in, cin, cout, k, stride, pad, mode);
+    const int T_out = (T_in + 2 * pad - k) / stride + 1;
+    SOLA_ARG(T_in + 2 * pad >= k && R * T_out < (1LL << 31), "conv1d_cl_split: no output frame, or more than 2^31 output rows");
+    hipStream_t s = as_stream(stream_);
+    GemmDesc gd{};
+    gd.nprob = 1;
+    gd.p[0] = GemmProblem{x_sp, w_sp, bias, nullptr, y};
+    gd.M = (int)(R * T_out); gd.N = cout; gd.K = k * cin; gd.lda = cin; gd.ldc = cout;
+    gd.arith = 1; gd.out_scale = 1.f;
+    gd.conv = 1; gd.T_in = T_in; gd.T_out = T_out; gd.stride = stride; gd.pad = pad; gd.Cin = cin;
+    ConvFramePlan fp;
+    const bool has = conv_frames_plan(gd, fp);
+    SOLA_ARG(mode != 1 || has, "conv1d_cl_split: this conv has no per-frame form");
+    if (mode == 0 || !has || (mode == -1 && !conv_frames_pays(gd, fp))) return launch_gemm(gd, s);
+    // at most one partial range per output frame; each gets room for a whole matrix
+    float* packed = nullptr;
+    SOLA_HIP(hipMalloc(&packed, (size_t)5 * cout * k * cin * sizeof(float)));
+    ConvTapWeights tw;
+    int rc = SOLA_OK;
+    for (int i = 0; i < fp.n && rc == SOLA_OK; ++i)
+        for (int j = 0; j < fp.l[i].nprob && fp.l[i].taps < k && rc == SOLA_OK; ++j) {
+            const int lo = fp.l[i].lo[j], hi = lo + fp.l[i].taps - 1;
+            if (tw.find(lo, hi)) continue;
+            float* dst = packed + (size_t)tw.n * cout * k * cin;
+            const size_t width = (size_t)fp.l[i].taps * cin * sizeof(float);
+            if (hipMemcpy2DAsync(dst, width, w_sp + (size_t)lo * cin, (size_t)k * cin * sizeof(float), width, cout, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+                sola_set_error("conv1d_cl_split: packing taps %d..%d failed", lo, hi);
+                rc = SOLA_ERR_HIP;
+            }
+            tw.e[tw.n].lo = lo; tw.e[tw.n].hi = hi;
+            tw.e[tw.n++].w = dst;
+        }
+    if (rc == SOLA_OK) rc = launch_conv_frames(gd, fp, tw, s);
+    if (packed) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(packed);
+    }
+    return rc;
+}
+
+// the split-f16 conv weights the context holds after a split-f16 forward (tests): layer's whole [cout][k * cin] matrix (range -1) or
+// its packed tap range `range` (0 .. *n_ranges - 1; taps *lo .. *hi), copied to dev_out (null = sizes only)
+extern "C" int sola_conv_weights_split(const SolaCtx* c, int layer, int range, float* dev_out, int* lo, int* hi, int* n_ranges, void* stream_) {
+    SOLA_ARG(c && layer >= 0 && layer < 6 && range >= -1 && range < c->ws_ntaps[layer], "conv_weights_split: layer %d range %d", layer, range);
+    SOLA_ARG(c->ws16_buf && c->ws16_fmt == 1, "conv_weights_split: run a split-f16 forward first");
+    const ConvGeom& g = c->conv[layer];
+    const int l = range < 0 ? 0 : c->ws_taps[layer][range].lo, h = range < 0 ? g.k - 1 : c->ws_taps[layer][range].hi;
+    if (lo) *lo = l;
+    if (hi) *hi = h;
+    if (n_ranges) *n_ranges = c->ws_ntaps[layer];
+    if (!dev_out) return SOLA_OK;
+    const float* src = range < 0 ? c->ws16_buf + c->ws_off[layer] : c->ws16_taps_buf + c->ws_taps[layer][range].off;
+    SOLA_HIP(hipMemcpyAsync(dev_out, src, (size_t)g.cout * (h - l + 1) * g.cin * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream_)));
+    return SOLA_OK;
 }
 
 // ---- 16-bit storage mode building blocks (tests) ----------------------------------------------------------------

@@ -221,6 +221,34 @@ __global__ __launch_bounds__(256) void cast_sp16_auto_multi_kernel(const MultiAr
     }
 }
 
+// ---- cast_sp16_kernel for a set of matrices of DIFFERENT shapes and pitches under one fixed scale (the conv weights): blockIdx.y
+//      picks the job, its blocks stride over the job's 8-value groups (a small job's surplus blocks leave at once)
+struct CastJobs {
+    CastJob j[CAST_JOBS_MAX];
+};
+__global__ __launch_bounds__(256) void cast_sp16_multi_kernel(const CastJobs a, float scale) {
+    const CastJob jb = a.j[blockIdx.y];
+    const int blocks_per_row = jb.K / 8;
+    const long long n = (long long)jb.rows * blocks_per_row;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long r = i / blocks_per_row;
+        const int b = (int)(i - r * blocks_per_row);
+        const float4 v0 = *reinterpret_cast<const float4*>(jb.in + r * jb.ld_in + b * 8);
+        const float4 v1 = *reinterpret_cast<const float4*>(jb.in + r * jb.ld_in + b * 8 + 4);
+        const float v[8] = {v0.x * scale, v0.y * scale, v0.z * scale, v0.w * scale, v1.x * scale, v1.y * scale, v1.z * scale, v1.w * scale};
+        half8 hi, lo;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            _Float16 h1, l1;
+            split_f16(v[j], h1, l1);
+            hi[j] = h1; lo[j] = l1;
+        }
+        half8* o = reinterpret_cast<half8*>(jb.out + r * jb.ld_out + b * 8);
+        o[0] = hi;
+        o[1] = lo;
+    }
+}
+
 // ---- f32 -> plain f16 rows (the 16-bit storage mode): 8 values per thread, 16-byte stores --------------------------------
 // SCALED: the power-of-two scale comes from the amax slot (cast_sp16_auto_kernel's rule), else from the argument
 // eight scaled f32 values -> eight 16-bit values: f16, or (bf) bfloat16 - both round to nearest even; the bits travel as a half8
@@ -447,6 +475,27 @@ int launch_cast_sp16_auto(const float* in, int ld_in, float* out, int ld_out, lo
     SOLA_LAUNCH_CHECK();
     const long long n = rows * (K / 8);
     hipLaunchKernelGGL(cast_sp16_auto_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, rows, K / 8, ld_in, ld_out, scal);
+    SOLA_LAUNCH_CHECK();
+    return SOLA_OK;
+}
+
+int launch_cast_sp16_multi(const CastJob* jobs, int n, float scale, hipStream_t s) {
+    SOLA_ARG(jobs && n > 0 && n <= CAST_JOBS_MAX, "cast_sp16_multi: %d jobs (at most %d)", n, CAST_JOBS_MAX);
+    CastJobs a;
+    long long most = 0;
+    double bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const CastJob& j = jobs[i];
+        SOLA_ARG(j.in && j.out && j.rows > 0 && j.K > 0 && j.K % 8 == 0 && j.ld_in % 4 == 0 && j.ld_out % 8 == 0,
+                 "cast_sp16_multi: job %d K=%d ld_in=%d ld_out=%d", i, j.K, j.ld_in, j.ld_out);
+        a.j[i] = j;
+        most = std::max(most, (long long)j.rows * (j.K / 8));
+        bytes += 8.0 * j.rows * j.K;
+    }
+    for (int i = n; i < CAST_JOBS_MAX; ++i) a.j[i] = CastJob{nullptr, nullptr, 0, 8, 0, 0};
+    SolaProfScope prof(SOLA_PROF_MISC, s, 0, bytes);
+    const unsigned blocks = (unsigned)std::min<long long>(2048, (most + 255) / 256);
+    hipLaunchKernelGGL(cast_sp16_multi_kernel, dim3(blocks, (unsigned)n), dim3(256), 0, s, a, scale);
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
 }

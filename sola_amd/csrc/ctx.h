@@ -102,6 +102,13 @@ struct SolaCtx {
     bool lin16_dirty = true;  // split copies of the projection weights are stale
     float* ws16_buf = nullptr;
     float* lin16_buf = nullptr;
+    // split-f16 mode, the stride-1 convs with padding (conv3, conv4): packed split-f16 copies of the two column ranges of their
+    // standardised matrix that an edge frame of the per-frame form multiplies - taps pad..k-1 (first frame) and 0..k-1-pad (last
+    // frame) - each the column slice of the layer's ws16_buf matrix, bit for bit (kernels.h: ConvTapWeights).  Written with ws16_buf.
+    struct TapRange { int lo, hi; size_t off; };
+    TapRange ws_taps[6][2];
+    int ws_ntaps[6] = {0, 0, 0, 0, 0, 0};
+    float* ws16_taps_buf = nullptr;
     // 16-bit operand modes, training: the row-major casts of the forward's GEMM inputs are KEPT (one arena slot each instead of two
     // shared buffers) and listed by their f32 source, so that the backward's weight-gradient products take them as their X operand
     // instead of casting the same activations again (sola_tune "train_x16_keep").  The arena grows between steps to the last need.

@@ -93,12 +93,31 @@ int sola_refresh_conv_weights(SolaCtx* c, int fmt, bool force, hipStream_t s) {
     }
     SOLA_TRY(launch_ws_standardize(layers, 6, s));
     c->ws16_fmt = 0;  // ws_buf is new: ws16_buf is current once the casts below have rewritten it
-    for (int i = 0; i < 6 && fmt != 0; ++i) {
+    if (fmt == 1) {
+        // one launch for the six matrices and the packed tap ranges of the per-frame convs (ctx.h: ws_taps): the reference's policy
+        // repeats this on every forward, at the head of the step where the queue is empty and each launch is paid in full.  A range
+        // starts at a multiple of cin (a multiple of 8), so it is a whole number of 8-value pair groups: the packed copy is the
+        // column slice of the full cast, bit for bit.
+        std::vector<CastJob> jobs;
+        for (int i = 0; i < 6; ++i) {
+            const ConvGeom& g = c->conv[i];
+            const int kc = g.k * g.cin;
+            const float* w = c->ws_buf + c->ws_off[i];
+            jobs.push_back(CastJob{w, c->ws16_buf + c->ws_off[i], g.cout, kc, kc, kc});
+            for (int j = 0; j < c->ws_ntaps[i]; ++j) {
+                const SolaCtx::TapRange& r = c->ws_taps[i][j];
+                const int kr = (r.hi - r.lo + 1) * g.cin;
+                jobs.push_back(CastJob{w + r.lo * g.cin, c->ws16_taps_buf + r.off, g.cout, kr, kc, kr});
+            }
+        }
+        for (size_t i0 = 0; i0 < jobs.size(); i0 += CAST_JOBS_MAX)  // (ten jobs with the default geometry)
+            SOLA_TRY(launch_cast_sp16_multi(jobs.data() + i0, (int)std::min<size_t>(CAST_JOBS_MAX, jobs.size() - i0), 1.f, s));
+    }
+    for (int i = 0; i < 6 && fmt >= 2; ++i) {
         const int kc = c->conv[i].k * c->conv[i].cin;
         const float* w = c->ws_buf + c->ws_off[i];
-        if (fmt == 1) SOLA_TRY(launch_cast_sp16(w, kc, c->ws16_buf + c->ws_off[i], kc, c->conv[i].cout, kc, 1.f, s));
-        else SOLA_TRY(launch_cast_f16(w, kc, reinterpret_cast<_Float16*>(c->ws16_buf) + c->ws_off[i], kc, c->conv[i].cout, kc, 1.f, nullptr, s, 13,
-                                      nullptr, fmt == 3 ? 1 : 0));
+        SOLA_TRY(launch_cast_f16(w, kc, reinterpret_cast<_Float16*>(c->ws16_buf) + c->ws_off[i], kc, c->conv[i].cout, kc, 1.f, nullptr, s, 13,
+                                 nullptr, fmt == 3 ? 1 : 0));
     }
     c->ws_dirty = false;
     c->ws16_fmt = fmt;
@@ -252,6 +271,24 @@ struct InferBuilder {
         }
         return gd;
     }
+    // Launches encoder conv i of a UNIFORM batch (gd.T_in / gd.T_out set).  Split-f16 mode: where the conv has a per-frame form whose
+    // launches all fill the persistent 256x256 kernel and save at least a sixteenth of the conv launch's rounds x K (conv3 and conv4
+    // over T' = 4 frames from 128 samples of 64 tracks on: their two padding taps of twelve are not multiplied), it runs as plain
+    // GEMMs per frame - same bits (conv_frames.hip).  conv0-2 (one padding tap, its launch would fill half a round), T' = 16 and
+    // small batches keep the implicit-im2col launch by that rule.  So do, by construction, the exact-f32 and 16-bit storage modes,
+    // the ragged forward (row maps, T varying by sequence) and the training forward: they do not come through here.
+    int launch_conv(int i, const GemmDesc& gd) const {
+        ConvFramePlan fp;
+        if (sp && conv_frames_plan(gd, fp) && conv_frames_pays(gd, fp)) {
+            ConvTapWeights tw;
+            for (int j = 0; j < c->ws_ntaps[i]; ++j) {
+                tw.e[tw.n].lo = c->ws_taps[i][j].lo; tw.e[tw.n].hi = c->ws_taps[i][j].hi;
+                tw.e[tw.n++].w = c->ws16_taps_buf + c->ws_taps[i][j].off;
+            }
+            if (conv_frames_has_weights(gd, fp, tw)) return launch_conv_frames(gd, fp, tw, s);
+        }
+        return launch_gemm(gd, s);
+    }
     // nprob projections first_proj.. of one attention in one launch.  out_sp16: split-f16 q/k/v for the split attention kernel
     // (the 16-bit storage mode writes f16 always, f32 ignores it)
     int linear3(const float* a0, const float* a1, const float* a2, int layer, int attn_i, int nprob, long long rows, float* o0, float* o1,
@@ -377,7 +414,7 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
                 fused_norm = true;
             }
         }
-        SOLA_TRY(launch_gemm(gd, s));
+        SOLA_TRY(b.launch_conv(i, gd));
         if (i < 5 && !fused_norm) {
             GroupNormDesc nd = b.encoder_norm(i, buf("conv" + is), buf("act" + is));
             nd.n_inst = R; nd.inner = 1; nd.outer_stride = p.Tl[i]; nd.inner_stride = 0; nd.tok_stride = 1; nd.ntok = p.Tl[i];

@@ -62,6 +62,39 @@ bool gemm_nn_supported(const GemmDesc& d);  // the launch takes the w_nn form (e
 int launch_gemm(const GemmDesc& d, hipStream_t s);
 bool gemm_gn_fusable(const GemmDesc& d, int channels_per_group, int tokens);
 
+// ---- a uniform conv as one plain GEMM per output frame (conv_frames.hip) -----------------------------------------------------------
+// Frame t of a channels-last conv (GemmDesc::conv == 1, no row map) reads, for every track, ONE contiguous window of the input - the
+// taps lo..hi that lie inside the sequence - so it is a plain GEMM with M = tracks, lda = T_in * Cin, K = (hi - lo + 1) * Cin on the
+// columns [lo * Cin, (hi + 1) * Cin) of the layer's [N][k * Cin] matrix, writing C + t * ldc with pitch T_out * ldc.  The taps in the
+// zero padding are not multiplied at all.  Frames with the same number of taps share K and go into one launch of up to three problems.
+struct ConvFrameLaunch {
+    int nprob, taps;       // problems of the launch; taps inside the sequence, the same for all of them (K = taps * Cin)
+    int frame[3], lo[3];   // output frame and first inside tap of each problem
+};
+struct ConvFramePlan {
+    int n = 0;             // launches; 0 = the conv has no per-frame form
+    ConvFrameLaunch l[5];  // at most five output frames
+};
+// GemmDesc::ldw == K in every kernel, so a frame that drops taps needs ITS column range as a matrix of its own: the packed copies
+// the caller holds, by tap range (the full range is the layer's own matrix, GemmDesc::p[0].W of the conv)
+struct ConvTapWeights {
+    int n = 0;
+    struct { int lo, hi; const float* w; } e[5];
+    const float* find(int lo, int hi) const {
+        for (int i = 0; i < n; ++i)
+            if (e[i].lo == lo && e[i].hi == hi) return e[i].w;
+        return nullptr;
+    }
+};
+// the frame classes of the conv launch `conv` and their launches; false (plan.n == 0) where the form does not exist: more than five
+// output frames, a frame with no tap inside, a row map, a residual, split K, Cin no multiple of the 32-wide k-tile, other arithmetic
+bool conv_frames_plan(const GemmDesc& conv, ConvFramePlan& plan);
+// the forward's rule: every launch of the plan is routed to the persistent 256x256 direct-to-LDS kernel, and together they take at
+// most 15/16 of the conv launch's rounds x K
+bool conv_frames_pays(const GemmDesc& conv, const ConvFramePlan& plan);
+bool conv_frames_has_weights(const GemmDesc& conv, const ConvFramePlan& plan, const ConvTapWeights& w);  // a packed copy for every partial range
+int launch_conv_frames(const GemmDesc& conv, const ConvFramePlan& plan, const ConvTapWeights& w, hipStream_t s);
+
 // ---- weight-gradient GEMM + helpers (gemm_tn.hip) ----------------------------------------------------------------
 struct GemmTnDesc {
     const float* A;   // dY [M, N]
@@ -407,6 +440,15 @@ int launch_cast_sp16_auto(const float* in, int ld_in, float* out, int ld_out, lo
 // The same for up to 64 equally shaped matrices in three launches (the projection weights): in[i] [rows][K] -> out[i], scale pair
 // of matrix i at scal + 2 * i
 int launch_cast_sp16_auto_multi(const float* const* in, float* const* out, int n, int rows, int K, float* scal, hipStream_t s);
+// launch_cast_sp16 for up to 16 matrices of any shapes in ONE launch, one fixed scale for all (the standardised conv weights and
+// their packed column ranges: unit-variance rows, no amax pass).  Each job's output has launch_cast_sp16's bits.
+struct CastJob {
+    const float* in;
+    float* out;
+    int rows, K, ld_in, ld_out;
+};
+constexpr int CAST_JOBS_MAX = 16;
+int launch_cast_sp16_multi(const CastJob* jobs, int n, float scale, hipStream_t s);
 // f32 rows -> plain _Float16 rows (16-bit storage mode).  scal != null: data-dependent power-of-two scale as above (scal[1]
 // receives its inverse), else the fixed `scale`.  ld_out counts halfs.
 // target_exp: the largest magnitude lands in [2^target_exp, 2^(target_exp+1)); scale_out (optional, device): receives the scale itself

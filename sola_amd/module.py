@@ -791,6 +791,19 @@ class LanguageAlignedTrackSelectionModule(nn.Module):
         flat = self._workspace[off.value: off.value + 4 * n].view(torch.float32)
         return flat.reshape(rows.value, cols.value).clone()
 
+    def conv_weights_split(self, layer, tap_range=-1):
+        """The split-f16 standardised weights of encoder conv ``layer`` (0..5) as the last split-f16 forward left them in the
+        context (see sola_conv_weights_split): ``(matrix, lo, hi, n_ranges)`` with the whole [cout, k*cin] matrix for
+        ``tap_range`` -1, else the packed copy of taps lo..hi the per-frame convs read; for parity tests."""
+        convs = [m for m in self.short_motion_encoder if isinstance(m, nn.Conv1d)]
+        cout, cin = convs[layer].out_channels, convs[layer].in_channels
+        lo, hi, n = C.c_int(), C.c_int(), C.c_int()
+        args = (self._ctx, int(layer), int(tap_range))
+        check(lib().sola_conv_weights_split(*args, None, C.byref(lo), C.byref(hi), C.byref(n), None), "sola_conv_weights_split")
+        out = torch.empty((cout, (hi.value - lo.value + 1) * cin), device=self._workspace.device, dtype=torch.float32)
+        check(lib().sola_conv_weights_split(*args, ptr(out), None, None, None, current_stream(out.device)), "sola_conv_weights_split")
+        return out, lo.value, hi.value, n.value
+
     # ------------------------------------------------------------------------------------------ a7
     def _grad_groups(self):
         groups = self.__dict__.get("_group_cache")

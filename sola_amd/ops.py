@@ -107,6 +107,23 @@ def conv1d_cl(x, w_std, bias, k, stride, pad):
     return y
 
 
+def conv1d_cl_split(x_sp, w_sp, bias, k, stride, pad, mode=-1, out=None):
+    """Channels-last conv along T on split-f16 operands: x_sp [R,T,cin] and w_sp [cout,k*cin] from ``cast_sp16`` -> f32 [R,T_out,cout].
+    ``mode`` 0: one implicit-im2col GEMM; 1: one plain GEMM per output frame on the taps inside the sequence; -1: the split-f16
+    forward's own choice.  ``out``: a contiguous [R,T_out,cout] tensor to write into."""
+    require_cuda(x_sp, w_sp, bias, out)
+    x_sp, w_sp = _f32c(x_sp), _f32c(w_sp)
+    R, T, cin = x_sp.shape
+    cout = w_sp.shape[0]
+    t_out = (T + 2 * pad - k) // stride + 1
+    y = torch.empty((R, t_out, cout), device=x_sp.device, dtype=torch.float32) if out is None else out
+    if y.shape != (R, t_out, cout) or not y.is_contiguous() or y.dtype != torch.float32:
+        raise _lib.SolaError("conv1d_cl_split: out must be a contiguous float32 [R, T_out, cout] tensor")
+    check(lib().sola_conv1d_cl_split(ptr(x_sp), ptr(w_sp), ptr(None if bias is None else _f32c(bias)), ptr(y), R, T, cin, cout,
+                                     k, stride, pad, int(mode), current_stream(x_sp.device)), "sola_conv1d_cl_split")
+    return y
+
+
 def group_norm(x, gamma, beta, groups, n_inst, inner, outer_stride, inner_stride, tok_stride, ntok, eps=1e-5,
                leaky_slope=None, pe=None):
     """nn.GroupNorm over token sets of an [rows, C] matrix (see sola_group_norm in the header).
