@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ragged.h"
+#include "sites.h"
 
 int g_bwd_dual_cast = 1;  // sola_tune "bwd_dual_cast": the transposing cast of a gradient matrix also writes its row-major cast (A/B)
 int g_bwd_fused_bf16_cast = 1;  // sola_tune "bwd_fused_bf16_cast": bf16 storage - the gradient statistics pass is the cast as well (A/B)
@@ -199,26 +200,15 @@ extern "C" size_t sola_backward_ragged_workspace_bytes(const SolaCtx* c, const S
 }
 
 AttnBwdDesc attn_bwd_site_desc(const SolaCtx* c, const Plan& p, const RagTables* rt, int a, float* part) {
-    const int D = c->cfg.lang_token_dim, H = c->cfg.num_heads, N = p.N, Tp = p.Tp;
+    const int D = c->cfg.lang_token_dim, H = c->cfg.num_heads;
     AttnBwdDesc d{};
     d.ldq = d.ldk = d.ldv = d.ldo = D;
     d.ld_dq = 3 * D;
     d.ld_dk = d.ld_dv = a == 2 ? 2 * D : 3 * D;
-    d.H = H; d.DH = D / H; d.inner = 1;
+    d.H = H; d.DH = D / H;
     d.scale = 1.0f / sqrtf((float)d.DH);
-    if (a == 0) {  // inter-object: the N tracks of each (sample, t')
-        d.G = rt ? rt->sumTpS : p.B * Tp; d.Sq = d.Sk = N; d.inner = rt ? 1 : Tp;
-        d.q_outer = d.k_outer = (long long)N * Tp; d.q_inner = d.k_inner = 1; d.q_rs = d.k_rs = Tp;
-        if (rt) d.q_units = rt->u_st;
-    } else if (a == 1) {  // motion: the T' steps of each track
-        d.G = rt ? rt->NT : p.B * N; d.Sq = d.Sk = Tp;
-        d.q_outer = d.k_outer = Tp; d.q_rs = d.k_rs = 1;
-        if (rt) d.q_units = rt->u_strk;
-    } else {  // object -> language: a sample's N * T' query rows against its text ++ negative rows
-        d.G = p.B; d.Sq = rt ? rt->maxRowsSample : N * Tp; d.Sk = p.W;
-        d.q_outer = (long long)N * Tp; d.k_outer = p.W; d.q_rs = d.k_rs = 1;
-        if (rt) { d.q_units = rt->u_smp; d.k_units = rt->u_langk; }
-        // a sample's query rows are consecutive and the samples follow each other: the chunked one-pass launch applies
+    site_fill_attn(d, site_geom(rt ? site_shape_samples(*rt) : site_shape_uniform(p.B, p.N, p.Tp, p.W), a));
+    if (a == 2) {  // a sample's query rows are consecutive and the samples follow each other: the chunked one-pass launch applies
         d.part = part;
         d.part_floats = attention_bwd_part_floats((long long)p.M, p.B, H, 64);
         d.part_rows = (long long)p.M;
@@ -242,8 +232,7 @@ struct BwdRun {
     const int B = p.B, N = p.N, Tp = p.Tp, M = p.M, Wn = p.W, L = p.L, D = c->cfg.lang_token_dim, H = c->cfg.num_heads;
     const int R = rt ? rt->NT : B * N;                    // tracks
     const int BW = rt ? (int)rt->LW : B * Wn;             // text ++ negative rows
-    const int n_bt = rt ? rt->sumTpS : B * Tp;            // inter-object units (one per sample and encoded step)
-    const int max_rows_smp = rt ? rt->maxRowsSample : N * Tp;
+    const SiteShape shape = rt ? site_shape_samples(*rt) : site_shape_uniform(B, N, Tp, Wn);  // the layers' units (sites.h)
     // ---- modes
     // split: every GEMM of the backward on f16 MFMAs - (hi, lo) operand pairs, three products (precision 1), or plain f16
     // operands, one product (precision 2: "pure"; mixed precision - activations, gradients and accumulation stay f32)
@@ -598,8 +587,9 @@ struct BwdRun {
 
     int score_head(const float* d_score_map, const float* d_score_tokens) {
         HeadBwdDesc d{fb("l" + std::to_string(c->cfg.n_layers - 1) + "_o2l"), fb("lbar"), d_score_map, d_score_tokens, gbuf[cur],
-                      ar.get(S_DLBAR_PART), B, N, Tp, D};
-        if (rt) { d.B = 1; d.N = R; d.units = rt->u_strk; }
+                      ar.get(S_DLBAR_PART)};
+        d.D = D;
+        site_fill_head(d, shape);
         SOLA_TRY(launch_score_head_bwd(d, s));
         if (rt) return launch_segsum_rows(ar.get(S_DLBAR_PART), ar.get(S_DLBAR), rt->trk_off, B, D, s);
         return launch_colsum(ar.get(S_DLBAR_PART), ar.get(S_DLBAR), B, N, D, D, 1.f, 0, nullptr, 0, s);
@@ -611,19 +601,10 @@ struct BwdRun {
     int site_gn_bwd(int l, int a) {
         GroupNormBwdDesc d{};
         d.x = ab(l, a, "res"); d.dy = gbuf[cur]; d.dx = dres;
-        d.C = D; d.groups = c->cfg.n_groups_module; d.inner = 1; d.tok_stride = 1;
-        if (a == 2) {  // one unit per sample
-            d.n_inst = B; d.outer_stride = (long long)N * Tp; d.ntok = max_rows_smp;
-            if (rt) d.units = rt->u_smp;
-            if (c->gn2_stats[l]) d.stats_in = fb("l" + std::to_string(l) + "_gn2st");
-        } else if (a == 1) {  // per track
-            d.n_inst = R; d.outer_stride = Tp; d.ntok = Tp;
-            if (rt) d.units = rt->u_strk;
-        } else {  // per (sample, t'): the N tracks, T' rows apart
-            d.n_inst = n_bt; d.inner = rt ? 1 : Tp; d.outer_stride = (long long)N * Tp; d.inner_stride = 1; d.tok_stride = Tp; d.ntok = N;
-            if (rt) d.units = rt->u_st;
-            d.dy2 = egrad; d.dy2_bf16 = egrad_bf16 ? 1 : 0;
-        }
+        d.C = D; d.groups = c->cfg.n_groups_module;
+        site_fill_norm(d, shape.fam[a]);
+        if (a == 2 && c->gn2_stats[l]) d.stats_in = fb("l" + std::to_string(l) + "_gn2st");
+        if (a == 0) { d.dy2 = egrad; d.dy2_bf16 = egrad_bf16 ? 1 : 0; }
         // dx16 (round 6, bf16 steps): the norm's input gradient once more as bfloat16 rows - the consumer GEMMs' operand, written here instead of
         // by a statistics-and-cast pass that read the f32 matrix back (launch_cast_bf16_colsum); the f32 rows stay (residual stream)
         if (gn16) d.dx16 = dy16;
@@ -917,9 +898,9 @@ struct BwdRun {
                    tns_fits((int)e.rows_in, g.cin, c->conv[i - 1].k * c->conv[i - 1].cin, 1);
         GroupNormBwdDesc d{};
         d.x = fb("conv" + std::to_string(i - 1)); d.dy = dact; d.dx = enc[1];
-        d.n_inst = R; d.inner = 1; d.outer_stride = t_in; d.tok_stride = 1; d.ntok = t_in; d.C = g.cin; d.groups = c->cfg.n_groups; d.leaky = 1;
+        site_fill_norm(d, rt ? site_tracks(*rt, i) : site_tracks(R, t_in));
+        d.C = g.cin; d.groups = c->cfg.n_groups; d.leaky = 1;
         d.drop = c->enc_drop(i - 1);
-        if (rt) d.units = rt->u_lvl[i];
         if (enc_dy16) d.dx16 = dy16;
         SOLA_TRY(gn_bwd(d, "short_motion_encoder." + std::to_string(kNormIdx[i - 1])));
         dy = enc[1];  // dact (enc[0]) is consumed; the next stage's dX may overwrite it, its GN backward overwrites enc[1]

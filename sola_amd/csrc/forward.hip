@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "ragged.h"
+#include "sites.h"
 
 int g_train_gn_cast = 1;  // sola_tune "train_gn_cast": 1 = a GroupNorm of the training forward also writes the operand cast of the GEMM behind it
 int g_train_attn_cast = 1;  // sola_tune "train_attn_cast": 1 = f16 / bf16 operand steps: the training forward's attention kernels also write the out-projection's operand cast; 2 = the split-f16 step too
@@ -252,9 +253,8 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
             nd.slice_ws = buf("gn_slots"); nd.slice_ws_bytes = (size_t)p.bufs.at("gn_slots").rows * p.bufs.at("gn_slots").cols * sizeof(float);
             nd.x = buf("conv" + std::to_string(i)); nd.y = buf("act" + std::to_string(i)); nd.y2 = nullptr; nd.pe = nullptr;
             nd.gamma = W(np + ".weight"); nd.beta = W(np + ".bias");
-            nd.n_inst = R; nd.inner = 1; nd.outer_stride = p.Tl[i]; nd.inner_stride = 0; nd.tok_stride = 1;
-            nd.ntok = p.Tl[i]; nd.C = g.cout; nd.groups = c->cfg.n_groups; nd.eps = 1e-5f; nd.slope = 0.01f; nd.leaky = 1;
-            if (rs) nd.units = rt.u_lvl[i + 1];
+            site_fill_norm(nd, rs ? site_tracks(rt, i + 1) : site_tracks(R, p.Tl[i]));
+            nd.C = g.cout; nd.groups = c->cfg.n_groups; nd.eps = 1e-5f; nd.slope = 0.01f; nd.leaky = 1;
             nd.drop = c->enc_drop(i);
             if (gn_fmt && c->conv[i + 1].cin % 64 == 0) {  // conv i+1 takes the cast from here
                 float* dst = slot16(0, nd.y, level_rows(i + 1), g.cout);
@@ -389,10 +389,8 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     };
     // next_src0 / next_src1: the FIRST / SECOND distinct input of the projection launch that follows (linear3 casts them into sp_a / sp_b in
     // that order): when one of them is this norm's y or y2, the norm writes the cast itself
-    int gn_layer = 0;  // the layer whose norms the loop below is launching
-    auto gn = [&](const std::string& lp, int idx, const float* res, float* y, float* y2, int n_inst, int inner,
-                  long long outer, long long inner_stride, long long tok_stride, int ntok, const int4* units = nullptr,
-                  const float* next_src0 = nullptr, const float* next_src1 = nullptr, bool res_bf16 = false) -> int {
+    auto gn = [&](const std::string& lp, int l, int idx, const float* res, float* y, float* y2, const RowFamily& units, const float* next_src0,
+                  const float* next_src1, bool res_bf16) -> int {
         GroupNormDesc nd{};
         nd.in_f16 = res_bf16 ? 2 : 0;
         if (gn_fmt) {
@@ -409,12 +407,10 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
         nd.x = res; nd.y = y; nd.y2 = y2; nd.pe = y2 ? buf("pe") : nullptr;
         nd.gamma = W(lp + "norm." + std::to_string(idx) + ".weight");
         nd.beta = W(lp + "norm." + std::to_string(idx) + ".bias");
-        nd.n_inst = n_inst; nd.inner = inner; nd.outer_stride = outer; nd.inner_stride = inner_stride;
-        nd.tok_stride = tok_stride; nd.ntok = ntok; nd.C = D; nd.groups = c->cfg.n_groups_module;
+        site_fill_norm(nd, units);
+        nd.C = D; nd.groups = c->cfg.n_groups_module;
         nd.eps = 1e-5f; nd.slope = 0.f; nd.leaky = 0;
-        nd.units = units;
         if (idx == 2 && g_train_gn_stats) {
-            const int l = gn_layer;
             int wrote = 0;
             nd.stats_out = buf("l" + std::to_string(l) + "_gn2st");
             nd.stats_written = &wrote;
@@ -430,80 +426,58 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
         if (!(split && pure && bf && g_train_bf16_store >= 2 && keep16 && D % 8 == 0)) return nullptr;
         return c->x16_find(resid, D, 1 + bf);
     };
+    const SiteShape shape = rs ? site_shape_samples(rt) : site_shape_uniform(B, N, Tp, Wn);
     const float* xin = buf("conv5");
     for (int l = 0; l < c->cfg.n_layers; ++l) {
         const std::string lp = "object_lang_align_layers." + std::to_string(l) + ".";
-        gn_layer = l;
         const std::string ls = "l" + std::to_string(l);
         auto ab = [&](int a, const char* what) { return buf(abuf(true, l, kAttnShort[a], what)); };
         float* x_obj = buf(ls + "_obj");
         float* x_pe = buf(ls + "_xpe");
         float* x_mot = buf(ls + "_motion");
         float* x_o2l = buf(ls + "_o2l");
-        // (i) inter-object attention over the N tracks of each (b, t'): module.py:31-35
-        {
-            AttnDesc ad{ab(0, "q"), ab(0, "k"), ab(0, "v"), ab(0, "attn"), D, D, D, D, B * Tp, H, DH, N, N, Tp,
-                        (long long)N * Tp, 1, Tp, (long long)N * Tp, 1, Tp, scale, ab(0, "lse")};
-            if (rs) { ad.G = rt.sumTpS; ad.inner = 1; ad.q_units = rt.u_st; }
-            ad.drop = c->attn_drop(l, 0);
-            const bool s16 = site16(ad, 0);
-            SOLA_TRY(linear3(xin, xin, xin, lp + "obj_attn", 3, M, ab(0, "q"), ab(0, "k"), ab(0, "v"), 0, nullptr, s16));
-            ad.in_bf16 = s16 ? 1 : 0;
-            c->site(l, 0).qkv16 = s16;
-            o16_site = &c->site(l, 0);
-            SOLA_TRY(attention(ad));
-        }
-        const void* r16_0 = resid16(xin);
-        c->site(l, 0).res16 = r16_0 != nullptr;
-        SOLA_TRY(out_proj(lp + "obj_attn", ab(0, "attn"), xin, ab(0, "res"), r16_0));
-        if (rs) SOLA_TRY(gn(lp, 0, ab(0, "res"), x_obj, x_pe, rt.sumTpS, 1, 0, 0, 1, N, rt.u_st, x_pe, x_obj, r16_0 != nullptr));
-        else SOLA_TRY(gn(lp, 0, ab(0, "res"), x_obj, x_pe, B * Tp, Tp, (long long)N * Tp, 1, Tp, N, nullptr, x_pe, x_obj, r16_0 != nullptr));
-        // (ii) motion attention over T' per track, PE on q and k only: module.py:38-43
-        {
-            AttnDesc ad{ab(1, "q"), ab(1, "k"), ab(1, "v"), ab(1, "attn"), D, D, D, D, B * N, H, DH, Tp, Tp, 1,
-                        (long long)Tp, 0, 1, (long long)Tp, 0, 1, scale, ab(1, "lse")};
-            if (rs) { ad.G = rt.sumNS; ad.q_units = rt.u_strk; }
-            ad.drop = c->attn_drop(l, 1);
-            const bool s16 = site16(ad, 1);
-            SOLA_TRY(linear3(x_pe, x_pe, x_obj, lp + "motion_attn", 3, M, ab(1, "q"), ab(1, "k"), ab(1, "v"), 0, nullptr, s16));
-            ad.in_bf16 = s16 ? 1 : 0;
-            c->site(l, 1).qkv16 = s16;
-            o16_site = &c->site(l, 1);
-            SOLA_TRY(attention(ad));
-        }
-        const void* r16_1 = resid16(x_obj);
-        c->site(l, 1).res16 = r16_1 != nullptr;
-        SOLA_TRY(out_proj(lp + "motion_attn", ab(1, "attn"), x_obj, ab(1, "res"), r16_1));
-        if (rs) SOLA_TRY(gn(lp, 1, ab(1, "res"), x_mot, nullptr, rt.sumNS, 1, 0, 0, 1, Tp, rt.u_strk, x_mot, nullptr, r16_1 != nullptr));
-        else SOLA_TRY(gn(lp, 1, ab(1, "res"), x_mot, nullptr, B * N, 1, Tp, 0, 1, Tp, nullptr, x_mot, nullptr, r16_1 != nullptr));
-        // (iii) object -> language cross attention: module.py:46-50
-        {
-            AttnDesc ad{ab(2, "q"), ab(2, "lk"), ab(2, "lv"), ab(2, "attn"), D, D, D, D, B, H, DH, N * Tp, Wn, 1,
-                        (long long)N * Tp, 0, 1, (long long)Wn, 0, 1, scale, ab(2, "lse")};
-            if (rs) { ad.Sq = rt.maxRowsSample; ad.q_units = rt.u_smp; ad.k_units = rt.u_langk; }
-            ad.drop = c->attn_drop(l, 2);
-            const bool s16 = site16(ad, 2);
-            SOLA_TRY(linear3(x_mot, nullptr, nullptr, lp + "object2lang_attn", 1, M, ab(2, "q"), nullptr, nullptr, 0, nullptr, s16));
-            SOLA_TRY(linear3(buf("lang"), buf("lang"), nullptr, lp + "object2lang_attn", 2, (int)text_rows, ab(2, "lk"), ab(2, "lv"), nullptr, 1,
-                             split ? c->scal_pair(1) : nullptr, s16));
-            ad.in_bf16 = s16 ? 1 : 0;
-            c->site(l, 2).qkv16 = s16;
-            o16_site = &c->site(l, 2);
-            SOLA_TRY(attention(ad));
-        }
-        const void* r16_2 = resid16(x_mot);
-        c->site(l, 2).res16 = r16_2 != nullptr;
-        SOLA_TRY(out_proj(lp + "object2lang_attn", ab(2, "attn"), x_mot, ab(2, "res"), r16_2));
-        // the next layer's q / k / v projections read x_o2l: its norm writes their operand (nothing reads it behind the last layer)
+        // What differs per site - the projections' inputs, the residual, the norm's outputs y / y2 = y + PE and the inputs of the NEXT
+        // projection launch whose operand cast the norm may write (gn above): (i) inter-object attention over the N tracks of each (b, t'),
+        // module.py:31-35; (ii) motion attention over T' per track, PE on q and k only, :38-43; (iii) object -> language cross attention,
+        // :46-50 - the next layer's q / k / v projections read x_o2l (nothing reads its cast behind the last layer)
         const float* nxt_in = l + 1 < c->cfg.n_layers ? x_o2l : nullptr;
-        if (rs) SOLA_TRY(gn(lp, 2, ab(2, "res"), x_o2l, nullptr, B, 1, 0, 0, 1, rt.maxRowsSample, rt.u_smp, nxt_in, nullptr, r16_2 != nullptr));
-        else SOLA_TRY(gn(lp, 2, ab(2, "res"), x_o2l, nullptr, B, 1, (long long)N * Tp, 0, 1, N * Tp, nullptr, nxt_in, nullptr, r16_2 != nullptr));
+        const struct { const float *xq, *xk, *xv, *resid; float *y, *y2; const float *next_src0, *next_src1; } io[3] = {
+            {xin, xin, xin, xin, x_obj, x_pe, x_pe, x_obj},
+            {x_pe, x_pe, x_obj, x_obj, x_mot, nullptr, x_mot, nullptr},
+            {x_mot, nullptr, nullptr, x_mot, x_o2l, nullptr, nxt_in, nullptr}};
+        for (int a = 0; a < 3; ++a) {
+            const SiteGeom g = site_geom(shape, a);
+            const std::string an = lp + kAttnLong[a];
+            float *const k = ab(a, a == 2 ? "lk" : "k"), *const v = ab(a, a == 2 ? "lv" : "v");
+            AttnDesc ad{};
+            ad.q = ab(a, "q"); ad.k = k; ad.v = v; ad.o = ab(a, "attn");
+            ad.ldq = ad.ldk = ad.ldv = ad.ldo = D;
+            ad.H = H; ad.DH = DH; ad.scale = scale; ad.lse = ab(a, "lse");
+            site_fill_attn(ad, g);
+            ad.drop = c->attn_drop(l, a);
+            const bool s16 = site16(ad, a);
+            if (a < 2) {
+                SOLA_TRY(linear3(io[a].xq, io[a].xk, io[a].xv, an, 3, M, ab(a, "q"), k, v, 0, nullptr, s16));
+            } else {  // q over the layer rows, k / v over the text rows (their data-dependent scale: scal_pair(1))
+                SOLA_TRY(linear3(io[a].xq, nullptr, nullptr, an, 1, M, ab(a, "q"), nullptr, nullptr, 0, nullptr, s16));
+                SOLA_TRY(linear3(buf("lang"), buf("lang"), nullptr, an, 2, (int)text_rows, k, v, nullptr, 1, split ? c->scal_pair(1) : nullptr, s16));
+            }
+            ad.in_bf16 = s16 ? 1 : 0;
+            c->site(l, a).qkv16 = s16;
+            o16_site = &c->site(l, a);
+            SOLA_TRY(attention(ad));
+            const void* r16 = resid16(io[a].resid);
+            c->site(l, a).res16 = r16 != nullptr;
+            SOLA_TRY(out_proj(an, ab(a, "attn"), io[a].resid, ab(a, "res"), r16));
+            SOLA_TRY(gn(lp, l, a, ab(a, "res"), io[a].y, io[a].y2, g.q, io[a].next_src0, io[a].next_src1, r16 != nullptr));
+        }
         xin = x_o2l;
     }
 
     // a6: score head (module/module.py:152-160)
-    HeadDesc hd{xin, buf("lbar"), score_map, score_tokens, B, N, Tp, D};
-    if (rs) { hd.B = 1; hd.N = rt.sumNS; hd.units = rt.u_strk; }
+    HeadDesc hd{xin, buf("lbar"), score_map, score_tokens};
+    hd.D = D;
+    site_fill_head(hd, shape);
     SOLA_TRY(launch_score_head(hd, s));
     c->last = p;
     c->last_rag = rt;

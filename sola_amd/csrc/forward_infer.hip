@@ -2,7 +2,7 @@
 // precisions (sola_set_precision(ctx, 0 / 1 / 2)).  Same network, same kernels and the same single [B,N,T',D] layout as the
 // training forward (forward.hip) without what only its backward reads; the modes differ in the arithmetic of the dense
 // contractions (98 % of the FLOPs) and in the storage.  Both sequences are written on ONE set of layer builders (InferBuilder
-// below), which holds everything that depends on the mode; a sequence adds the geometry: strides or the unit tables of ragged.hip.
+// below), which holds everything that depends on the mode; a sequence says which units a sub-block runs over (sites.h).
 //
 // Precision 0: exact f32 MFMA on f32 activations.
 //
@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "ragged.h"
+#include "sites.h"
 
 // Split-f16 copies of the 12 * n_layers projection weights, each with its own power-of-two scale (max|w| -> [2^13, 2^14),
 // found on the device: a trained matrix may be far from the U(-1/32, 1/32) of the default init, and a few outliers must not
@@ -155,8 +156,8 @@ namespace {
 const char* const kProj[4] = {"q_proj", "k_proj", "v_proj", "out_proj"};
 
 // What the two inference sequences below (uniform batch, ragged batch) have in common: the ctx's precision mode, written ONCE
-// into every descriptor.  The methods fill everything but the geometry - strides or unit tables, instance counts, sequence
-// lengths - which the sequence adds before the launch.
+// into every descriptor.  The geometry - strides or unit tables, instance counts, sequence lengths - comes from sites.h: the encoder
+// norms' from the sequence, a layer sub-block's through sub_block().
 struct InferBuilder {
     SolaCtx* c;
     hipStream_t s;
@@ -170,7 +171,10 @@ struct InferBuilder {
     void* gn_slots = nullptr;
     size_t gn_slots_bytes = 0;
     const float* pe = nullptr;
-    float *attn = nullptr, *res = nullptr;  // attention output / pre-norm rows of the current sub-block
+    float *q = nullptr, *k = nullptr, *v = nullptr, *attn = nullptr, *res = nullptr;  // projections / attention output / pre-norm rows of the current sub-block
+    const float* text = nullptr;     // text ++ negative rows in the mode's operand format, and their key / value projections (use_text)
+    long long text_rows = 0;
+    float *lk = nullptr, *lv = nullptr;
 
     InferBuilder(SolaCtx* ctx, hipStream_t stream)
         : c(ctx), s(stream), sp(ctx->precision == 1), h16(ctx->precision == 2), op16(sp || h16), guard(op16 ? ctx->guard : nullptr),
@@ -188,11 +192,14 @@ struct InferBuilder {
                      "16-bit storage mode needs object_token_dim and lang_token_dim to be multiples of 64");
         return SOLA_OK;
     }
-    void use_workspace(float* splitk, size_t splitk_b, void* slots, size_t slots_b, const float* pe_, float* attn_, float* res_) {
+    template <class Buf>  // buf(name): the sequence's workspace buffers
+    void use_workspace(float* splitk, size_t splitk_b, void* slots, size_t slots_b, Buf&& buf) {
         splitk_ws = h16 ? nullptr : splitk;  // the 16-bit GEMMs never split K
         splitk_bytes = splitk_ws ? splitk_b : 0;
-        gn_slots = slots; gn_slots_bytes = slots_b; pe = pe_; attn = attn_; res = res_;
+        gn_slots = slots; gn_slots_bytes = slots_b; pe = buf("pe");
+        q = buf("q"); k = buf("k"); v = buf("v"); attn = buf("attn"); res = buf("res"); lk = buf("lk"); lv = buf("lv");
     }
+    void use_text(const float* rows_in, long long rows) { text = rows_in; text_rows = rows; }
     // The projection weights are used as they are by the reference (no per-forward transform), so their 16-bit copies are
     // refreshed only when a weight pointer or value changed (sola_set_weight / sola_weights_changed).
     int prepare_weights() const {
@@ -352,6 +359,29 @@ struct InferBuilder {
         return ad;
     }
     int launch(const AttnDesc& ad) const { return h16 ? launch_attention_f16(ad, s) : launch_attention(ad, s); }
+
+    // ---- one sub-block: site a of `layer` over `rows` token rows whose units are g.  Projections (sites 0 and 1: q / k / v of xq / xk /
+    // xv in one launch; site 2: q of xq, k / v of the text rows in a second) -> attention -> out-projection + resid -> norm into y (y2: y + PE).
+    // Split-f16: q/k/v leave the projection GEMM already split when the attention that reads them runs the split-f16 MFMA shape.  Measured
+    // (tools/attn_probe.py): with <= 64 keys per unit the exact-f32 MFMA kernel is as fast or faster (bound by latency and LDS traffic, not
+    // by the matrix pipe); with 65..128 keys the split shape wins by 14 %.  Never the packed short-sequence shape (uniform: > 16 keys).
+    int sub_block(int layer, int a, const SiteGeom& g, long long rows, const float* xq, const float* xk, const float* xv, const float* resid,
+                  float* y, float* y2, int out16) const {
+        const int in_sp = (sp && g.k.len > g_attn_split_min_keys && (a == 2 || g.q.units || g.k.len > 16) && DH % 16 == 0) ? 1 : 0;
+        if (a < 2) {
+            SOLA_TRY(linear3(xq, xk, xv, layer, a, 3, rows, q, k, v, 0, in_sp));
+        } else {
+            SOLA_TRY(linear3(xq, nullptr, nullptr, layer, a, 1, rows, q, nullptr, nullptr, 0, in_sp));
+            SOLA_TRY(linear3(text, text, nullptr, layer, a, 2, text_rows, lk, lv, nullptr, 1, in_sp, lang_inv_scale()));
+        }
+        AttnDesc ad = attention(q, a < 2 ? k : lk, a < 2 ? v : lv, in_sp);
+        site_fill_attn(ad, g);
+        SOLA_TRY(launch(ad));
+        SOLA_TRY(out_proj(layer, a, rows, resid));
+        GroupNormDesc nd = layer_norm(layer, a, y, y2, out16);
+        site_fill_norm(nd, g.q);
+        return launch_group_norm(nd, s);
+    }
 };
 
 }  // namespace
@@ -373,8 +403,7 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
     auto buf = [&](const std::string& name) { return reinterpret_cast<float*>(base + p.bufs.at(name).off); };
     auto bytes = [&](const char* name) { return (size_t)p.bufs.at(name).rows * p.bufs.at(name).cols * sizeof(float); };
     const bool has_splitk = p.bufs.count("splitk") != 0;
-    b.use_workspace(has_splitk ? buf("splitk") : nullptr, has_splitk ? bytes("splitk") : 0, buf("gn_slots"), bytes("gn_slots"), buf("pe"),
-                    buf("attn"), buf("res"));
+    b.use_workspace(has_splitk ? buf("splitk") : nullptr, has_splitk ? bytes("splitk") : 0, buf("gn_slots"), bytes("gn_slots"), buf);
     const int D = b.D, H = b.H, DH = b.DH;
     const int Tp = p.Tp, M = p.M, Wn = p.W;
     const int R = B * N;
@@ -417,7 +446,7 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
         SOLA_TRY(b.launch_conv(i, gd));
         if (i < 5 && !fused_norm) {
             GroupNormDesc nd = b.encoder_norm(i, buf("conv" + is), buf("act" + is));
-            nd.n_inst = R; nd.inner = 1; nd.outer_stride = p.Tl[i]; nd.inner_stride = 0; nd.tok_stride = 1; nd.ntok = p.Tl[i];
+            site_fill_norm(nd, site_tracks(R, p.Tl[i]));
             SOLA_TRY(launch_group_norm(nd, s));
         }
         if (i < 5) x = buf("act" + is);
@@ -446,31 +475,10 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
         lang_in = buf("lang_sp");
     }
 
+    b.use_text(lang_in, lang_rows);
     // ---- alignment layers (module/module.py:22-52)
-    auto attention = [&](const float* q, const float* k, const float* v, int G, int Sq, int Sk, int inner, long long qo, long long qi,
-                         long long qr, long long ko, long long ki, long long kr, int in_sp16, int k_private = 0,
-                         long long k_shared_row = 0) -> int {
-        AttnDesc ad = b.attention(q, k, v, in_sp16);
-        ad.G = G; ad.Sq = Sq; ad.Sk = Sk; ad.inner = inner;
-        ad.q_outer = qo; ad.q_inner = qi; ad.q_rs = qr; ad.k_outer = ko; ad.k_inner = ki; ad.k_rs = kr;
-        ad.k_private = k_private; ad.k_shared_row = k_shared_row;
-        return b.launch(ad);
-    };
-    auto gn = [&](int layer, int idx, float* y, float* y2, int out16, int n_inst, int inner, long long outer, long long inner_stride,
-                  long long tok_stride, int ntok) -> int {
-        GroupNormDesc nd = b.layer_norm(layer, idx, y, y2, out16);
-        nd.n_inst = n_inst; nd.inner = inner; nd.outer_stride = outer; nd.inner_stride = inner_stride; nd.tok_stride = tok_stride; nd.ntok = ntok;
-        return launch_group_norm(nd, s);
-    };
-    // split-f16: q/k/v leave the projection GEMM already split when the attention that reads them runs the split-f16 MFMA shape.
-    // Measured (tools/attn_probe.py): with <= 64 keys per unit the exact-f32 MFMA kernel is as fast or faster (the kernel is then
-    // bound by latency and LDS traffic, not by the matrix pipe); with 65..128 keys the split shape wins by 14 %.
-    const int obj_sp = (sp && N > g_attn_split_min_keys && N > 16 && DH % 16 == 0) ? 1 : 0;
-    const int mot_sp = (sp && Tp > g_attn_split_min_keys && Tp > 16 && DH % 16 == 0) ? 1 : 0;
-    const int o2l_sp = (sp && Wn > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;
-
+    const SiteShape shape = site_shape_uniform(B, N, Tp, Wn, shared_neg ? L : 0);
     const float* xin = b.op16 ? buf("conv5_sp") : buf("conv5");  // A operand of the layer and residual of its first sub-block
-    float *q = buf("q"), *k = buf("k"), *v = buf("v");
     for (int l = 0; l < c->cfg.n_layers; ++l) {
         const std::string ls = "l" + std::to_string(l);
         const bool last = l + 1 == c->cfg.n_layers;
@@ -479,27 +487,18 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
         float* x_mot = buf(ls + "_motion");
         float* x_o2l = buf(ls + "_o2l");
         // (i) inter-object attention over the N tracks of each (b, t'): module.py:31-35
-        SOLA_TRY(b.linear3(xin, xin, xin, l, 0, 3, M, q, k, v, 0, obj_sp));
-        SOLA_TRY(attention(q, k, v, B * Tp, N, N, Tp, (long long)N * Tp, 1, Tp, (long long)N * Tp, 1, Tp, obj_sp));
-        SOLA_TRY(b.out_proj(l, 0, M, xin));
-        SOLA_TRY(gn(l, 0, x_obj, x_pe, 1, B * Tp, Tp, (long long)N * Tp, 1, Tp, N));
+        SOLA_TRY(b.sub_block(l, 0, site_geom(shape, 0), M, xin, xin, xin, xin, x_obj, x_pe, 1));
         // (ii) motion attention over T' per track, PE on q and k only: module.py:38-43
-        SOLA_TRY(b.linear3(x_pe, x_pe, x_obj, l, 1, 3, M, q, k, v, 0, mot_sp));
-        SOLA_TRY(attention(q, k, v, B * N, Tp, Tp, 1, (long long)Tp, 0, 1, (long long)Tp, 0, 1, mot_sp));
-        SOLA_TRY(b.out_proj(l, 1, M, x_obj));
-        SOLA_TRY(gn(l, 1, x_mot, nullptr, 1, B * N, 1, Tp, 0, 1, Tp));
-        // (iii) object -> language cross attention: module.py:46-50
-        SOLA_TRY(b.linear3(x_mot, nullptr, nullptr, l, 2, 1, M, q, nullptr, nullptr, 0, o2l_sp));
-        SOLA_TRY(b.linear3(lang_in, lang_in, nullptr, l, 2, 2, lang_rows, buf("lk"), buf("lv"), nullptr, 1, o2l_sp, b.lang_inv_scale()));
-        if (shared_neg) SOLA_TRY(attention(q, buf("lk"), buf("lv"), B, N * Tp, Wn, 1, (long long)N * Tp, 0, 1, (long long)L, 0, 1, o2l_sp, L, (long long)B * L));
-        else SOLA_TRY(attention(q, buf("lk"), buf("lv"), B, N * Tp, Wn, 1, (long long)N * Tp, 0, 1, (long long)Wn, 0, 1, o2l_sp));
-        SOLA_TRY(b.out_proj(l, 2, M, x_mot));
-        SOLA_TRY(gn(l, 2, x_o2l, nullptr, last ? 0 : 1, B, 1, (long long)N * Tp, 0, 1, N * Tp));  // the score head reads f32
+        SOLA_TRY(b.sub_block(l, 1, site_geom(shape, 1), M, x_pe, x_pe, x_obj, x_obj, x_mot, nullptr, 1));
+        // (iii) object -> language cross attention: module.py:46-50 (the score head reads f32)
+        SOLA_TRY(b.sub_block(l, 2, site_geom(shape, 2), M, x_mot, nullptr, nullptr, x_mot, x_o2l, nullptr, last ? 0 : 1));
         xin = x_o2l;
     }
 
     // ---- score head (module/module.py:152-160)
-    HeadDesc hd{xin, buf("lbar"), score_map, score_tokens, B, N, Tp, D};
+    HeadDesc hd{xin, buf("lbar"), score_map, score_tokens};
+    hd.D = D;
+    site_fill_head(hd, shape);
     SOLA_TRY(launch_score_head(hd, s));
     c->last = p;
     c->last_obj = nullptr;
@@ -586,7 +585,6 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
     SOLA_ARG(c && obj && lang && batch && score_map && score_tokens && workspace, "forward_ragged: null argument");
     InferBuilder b(c, s);
     SOLA_TRY(b.check_mode());
-    const bool sp = b.sp;
     RagShape r;
     SOLA_TRY(rag_shape(c, batch, r));
     const RagPlan p = rag_plan(c, r, c->precision);
@@ -594,9 +592,8 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
     char* base = static_cast<char*>(workspace);
     auto raw = [&](const std::string& name) { return base + p.off.at(name); };
     auto buf = [&](const std::string& name) { return reinterpret_cast<float*>(raw(name)); };
-    b.use_workspace(p.off.count("splitk") ? buf("splitk") : nullptr, kRagSplitkBytes, raw("gn_slots"), rag_gn_slots_bytes(r), buf("pe"), buf("attn"),
-                    buf("res"));
-    const int D = b.D, DH = b.DH, S = r.S;
+    b.use_workspace(p.off.count("splitk") ? buf("splitk") : nullptr, kRagSplitkBytes, raw("gn_slots"), rag_gn_slots_bytes(r), buf);
+    const int D = b.D, S = r.S;
 
     // ---- descriptors -> device, unit tables
     RagTables rt;
@@ -619,7 +616,7 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
         SOLA_TRY(launch_gemm(gd, s));
         if (i < 5) {
             GroupNormDesc nd = b.encoder_norm(i, buf("conv" + is), buf("act" + is));
-            nd.n_inst = r.NT; nd.inner = 1; nd.tok_stride = 1; nd.units = rt.u_lvl[i + 1]; nd.ntok = r.maxT[i + 1];
+            site_fill_norm(nd, site_tracks(rt, i + 1));
             SOLA_TRY(launch_group_norm(nd, s));
             x = buf("act" + is);
         }
@@ -633,38 +630,13 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
         lang_in = buf("lang_sp");
     }
 
-    auto attention = [&](const float* q, const float* k, const float* v, int G, const int4* qu, const int4* ku, int maxSq, int maxSk,
-                         int in_sp16) -> int {
-        AttnDesc ad = b.attention(q, k, v, in_sp16);
-        ad.G = G; ad.Sq = maxSq; ad.Sk = maxSk; ad.inner = 1; ad.q_rs = 1; ad.k_rs = 1;
-        ad.q_units = qu; ad.k_units = ku;
-        return b.launch(ad);
-    };
-    auto gn = [&](int layer, int idx, float* y, float* y2, int out16, const int4* units, int n_inst, int max_tok) -> int {
-        GroupNormDesc nd = b.layer_norm(layer, idx, y, y2, out16);
-        nd.n_inst = n_inst; nd.inner = 1; nd.tok_stride = 1; nd.units = units; nd.ntok = max_tok;
-        return launch_group_norm(nd, s);
-    };
-    // q/k/v leave the projection already split where the attention runs the split-f16 MFMA shape (units of more than
-    // g_attn_split_min_keys keys; never the packed short-sequence shape)
-    const int obj_in_sp = (sp && r.maxN > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;
-    const int mot_in_sp = (sp && maxTp > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;
-    const int o2l_in_sp = (sp && r.maxW > g_attn_split_min_keys && DH % 16 == 0) ? 1 : 0;
-    float *q = buf("q"), *k = buf("k"), *v = buf("v");
+    b.use_text(lang_in, r.LW);
+    const SiteShape videos = site_shape_videos(rt), samples = site_shape_samples(rt);
 
     // ---- layer 0, text-independent half, once per VIDEO (module/module.py:31-43)
-    {
-        const float* xin = buf("conv5");
-        const long long M = r.Mv;
-        SOLA_TRY(b.linear3(xin, xin, xin, 0, 0, 3, M, q, k, v, 0, obj_in_sp));
-        SOLA_TRY(attention(q, k, v, r.sumTpV, rt.u_vt, nullptr, r.maxN, r.maxN, obj_in_sp));
-        SOLA_TRY(b.out_proj(0, 0, M, xin));
-        SOLA_TRY(gn(0, 0, buf("v_obj"), buf("v_xpe"), 1, rt.u_vt, r.sumTpV, r.maxN));
-        SOLA_TRY(b.linear3(buf("v_xpe"), buf("v_xpe"), buf("v_obj"), 0, 1, 3, M, q, k, v, 0, mot_in_sp));
-        SOLA_TRY(attention(q, k, v, r.NT, rt.u_lvl[6], nullptr, maxTp, maxTp, mot_in_sp));
-        SOLA_TRY(b.out_proj(0, 1, M, buf("v_obj")));
-        SOLA_TRY(gn(0, 1, buf("v_motion"), nullptr, 1, rt.u_lvl[6], r.NT, maxTp));
-    }
+    const float* xin = buf("conv5");
+    SOLA_TRY(b.sub_block(0, 0, site_geom(videos, 0), r.Mv, xin, xin, xin, xin, buf("v_obj"), buf("v_xpe"), 1));
+    SOLA_TRY(b.sub_block(0, 1, site_geom(videos, 1), r.Mv, buf("v_xpe"), buf("v_xpe"), buf("v_obj"), buf("v_obj"), buf("v_motion"), nullptr, 1));
     // ---- from here on rows are per SAMPLE: repeat the video's activations for each of its expressions
     const float* x_mot = buf("v_motion");
     if (!r.identity) {
@@ -672,34 +644,24 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
         x_mot = buf("s_motion0");
     }
     const long long M = r.Ms;
-    const float* xin = nullptr;
     for (int l = 0; l < c->cfg.n_layers; ++l) {
         const std::string ls = "s" + std::to_string(l);
         const bool last = l + 1 == c->cfg.n_layers;
         if (l > 0) {
             float* x_obj = buf(ls + "_obj");
             float* x_pe = buf(ls + "_xpe");
-            SOLA_TRY(b.linear3(xin, xin, xin, l, 0, 3, M, q, k, v, 0, obj_in_sp));
-            SOLA_TRY(attention(q, k, v, r.sumTpS, rt.u_st, nullptr, r.maxN, r.maxN, obj_in_sp));
-            SOLA_TRY(b.out_proj(l, 0, M, xin));
-            SOLA_TRY(gn(l, 0, x_obj, x_pe, 1, rt.u_st, r.sumTpS, r.maxN));
-            SOLA_TRY(b.linear3(x_pe, x_pe, x_obj, l, 1, 3, M, q, k, v, 0, mot_in_sp));
-            SOLA_TRY(attention(q, k, v, r.sumNS, rt.u_strk, nullptr, maxTp, maxTp, mot_in_sp));
-            SOLA_TRY(b.out_proj(l, 1, M, x_obj));
-            SOLA_TRY(gn(l, 1, buf(ls + "_motion"), nullptr, 1, rt.u_strk, r.sumNS, maxTp));
+            SOLA_TRY(b.sub_block(l, 0, site_geom(samples, 0), M, xin, xin, xin, xin, x_obj, x_pe, 1));
+            SOLA_TRY(b.sub_block(l, 1, site_geom(samples, 1), M, x_pe, x_pe, x_obj, x_obj, buf(ls + "_motion"), nullptr, 1));
             x_mot = buf(ls + "_motion");
         }
-        // object -> language attention (module/module.py:46-50)
+        // object -> language attention (module/module.py:46-50; the score head reads f32)
         float* x_o2l = buf(ls + "_o2l");
-        SOLA_TRY(b.linear3(x_mot, nullptr, nullptr, l, 2, 1, M, q, nullptr, nullptr, 0, o2l_in_sp));
-        SOLA_TRY(b.linear3(lang_in, lang_in, nullptr, l, 2, 2, r.LW, buf("lk"), buf("lv"), nullptr, 1, o2l_in_sp, b.lang_inv_scale()));
-        SOLA_TRY(attention(q, buf("lk"), buf("lv"), S, rt.u_smp, rt.u_langk, r.maxRowsSample, r.maxW, o2l_in_sp));
-        SOLA_TRY(b.out_proj(l, 2, M, x_mot));
-        SOLA_TRY(gn(l, 2, x_o2l, nullptr, last ? 0 : 1, rt.u_smp, S, r.maxRowsSample));  // the score head reads f32
+        SOLA_TRY(b.sub_block(l, 2, site_geom(samples, 2), M, x_mot, nullptr, nullptr, x_mot, x_o2l, nullptr, last ? 0 : 1));
         xin = x_o2l;
     }
-    HeadDesc hd{xin, buf("lbar"), score_map, score_tokens, 1, r.sumNS, maxTp, D};
-    hd.units = rt.u_strk;
+    HeadDesc hd{xin, buf("lbar"), score_map, score_tokens};
+    hd.D = D;
+    site_fill_head(hd, samples);
     SOLA_TRY(launch_score_head(hd, s));
     return SOLA_OK;
 }
