@@ -124,6 +124,11 @@ int sola_set_split_guard(SolaCtx* ctx, int enable);
  * (sola_amd/module.py keeps a torch tensor 1/8 above the largest need seen).  Round 4; before, the ctx allocated this arena itself. */
 int sola_set_x16_arena(SolaCtx* ctx, void* dev_ptr, size_t bytes);
 int sola_x16_arena_info(const SolaCtx* ctx, size_t* need_bytes, size_t* capacity_bytes, size_t* used_bytes);
+/* What the LAST training forward of the context decided for attention site `site` (0 inter-object, 1 motion, 2 object -> language) of
+ * alignment layer `layer` - read-only, changes nothing: *qkv16 = q / k / v (and, in the backward, dq / dk / dv) are bfloat16 rows only,
+ * *o16 = the attention output exists as bfloat16 rows only, *prenorm16 = the sub-block's pre-norm rows are bfloat16 (sola_tune
+ * "train_bf16_store" 1 / 3 / 2).  Any pointer may be null.  All zero before the first training forward and outside the bf16 step. */
+int sola_train_site_flags(const SolaCtx* ctx, int layer, int site, int* qkv16, int* o16, int* prenorm16);
 int sola_split_fallback_count(const SolaCtx* ctx, int64_t* count, int32_t* last_guard);
 /* f32 rows -> split-f16 rows (same bytes per element; K % 8 == 0); scale must be a power of two */
 int sola_cast_sp16(const float* dev_in, int ld_in, float* dev_out, int ld_out, int64_t rows, int K, float scale, void* stream);

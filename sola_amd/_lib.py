@@ -169,6 +169,7 @@ SIGNATURES = {
     "sola_grad_clip": (_i, [_vp, _vp, _i, _vp, _f, _vp]),
     "sola_set_x16_arena": (_i, [_vp, _vp, _sz]),
     "sola_x16_arena_info": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "sola_train_site_flags": (_i, [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "sola_tune": (_i, [C.c_char_p, _i]),
     "sola_tune_query": (_i, [C.c_char_p, C.POINTER(_i), C.POINTER(_i)]),
     "sola_tune_key": (C.c_char_p, [_i]),
@@ -237,6 +238,14 @@ def tune_query(key):
 
 def tune_default(key):
     return tune_query(key)[1]
+
+
+def train_site_flags(ctx, layer, site):
+    """(qkv16, o16, prenorm16) of attention site `site` (0 inter-object, 1 motion, 2 object -> language) of alignment layer `layer`, as the
+    context's last training forward decided them (sola_train_site_flags: read-only)."""
+    q, o, r = _i(), _i(), _i()
+    check(lib().sola_train_site_flags(ctx, layer, site, C.byref(q), C.byref(o), C.byref(r)), "sola_train_site_flags")
+    return bool(q.value), bool(o.value), bool(r.value)
 
 
 @contextlib.contextmanager

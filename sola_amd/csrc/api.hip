@@ -753,6 +753,17 @@ extern "C" int sola_x16_arena_info(const SolaCtx* c, size_t* need_bytes, size_t*
     return SOLA_OK;
 }
 
+extern "C" int sola_train_site_flags(const SolaCtx* c, int layer, int site, int* qkv16, int* o16, int* prenorm16) {
+    SOLA_ARG(c, "train_site_flags: null ctx");
+    SOLA_ARG(layer >= 0 && layer < c->cfg.n_layers && site >= 0 && site < 3, "train_site_flags: layer %d, site %d", layer, site);
+    const size_t i = (size_t)layer * 3 + site;
+    const SolaCtx::SiteKeep k = i < c->sites.size() ? c->sites[i] : SolaCtx::SiteKeep{};
+    if (qkv16) *qkv16 = k.qkv16 ? 1 : 0;
+    if (o16) *o16 = k.o16 ? 1 : 0;
+    if (prenorm16) *prenorm16 = k.res16 ? 1 : 0;
+    return SOLA_OK;
+}
+
 extern "C" int sola_split_fallback_count(const SolaCtx* c, int64_t* count, int32_t* last_guard) {
     SOLA_ARG(c && count, "split_fallback_count: null argument");
     *count = c->split_fallbacks;

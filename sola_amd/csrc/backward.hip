@@ -302,6 +302,11 @@ struct BwdRun {
     const float* nn_w[3] = {nullptr, nullptr, nullptr};
     int nn_rows = 0;
     bool side_pending[4] = {false, false, false, false};
+    // bf16 steps: operands of the current site's products that exist as bfloat16 rows ONLY - the forward's contract (SiteKeep), decided under
+    // the switches of the forward.  dy16_only: dq / dk / dv of a qkv16 site (set by site_attention_bwd, cleared by the next site_head);
+    // x16_only: the attention output of an o16 site (out_proj_bwd, around its weight gradient).  A product that would read their f32 rows
+    // fails (need16) instead of reading a buffer nothing wrote.
+    bool dy16_only = false, x16_only = false;
 
     BwdRun(SolaCtx* c_, const RagTables* rt_, const Arena& ar_, const void* fwd_workspace, hipStream_t s_)
         : c(c_), rt(rt_), ar(ar_), fbase(static_cast<const char*>(fwd_workspace)), s(s_) {}
@@ -328,6 +333,11 @@ struct BwdRun {
     bool tns_fits(int rows, int n_out, int k_in, int nprob) const {
         return split && ar.present(S_TNS) && gemm_tn_split_supported(rows, n_out, k_in) &&
                ar.bytes_from(S_TNS) >= gemm_tn_split_scratch_bytes(rows, n_out, k_in, nprob);
+    }
+
+    int need16(bool ok, const char* what) const {
+        SOLA_ARG(ok, "backward: %s exist as bf16 rows only, but this backward reads their f32 rows (a switch changed between the forward and the backward)", what);
+        return SOLA_OK;
     }
 
     // ---- side lane.  dw_begin(): the side stream waits for everything the main stream has enqueued (the dY it reads); dw_end(slot): marks
@@ -438,6 +448,8 @@ struct BwdRun {
     int grad_w_many(const WG* g, int n, int ldy, int ldx, int rows, int n_out, int k_in, float* sc = nullptr, bool db_done = false,
                     bool* dy_rm_done = nullptr) {
         if (dy_rm_done) *dy_rm_done = false;
+        if (dy16_only || x16_only)  // neither the grouped nor the exact-f32 launch below reads bf16 rows
+            SOLA_TRY(need16(!group && tns_fits(rows, n_out, k_in, n), "operands of a weight gradient"));
         if (group && n_out == D && k_in == D) {  // deferred: one grouped launch behind the layers (the dY buffers are private: keep())
             for (int j = 0; j < n; ++j) {
                 GemmTnGroupDesc::Prob* q;
@@ -471,6 +483,10 @@ struct BwdRun {
             if ((pure || dw16) && ldx == k_in) d.B16[j] = c->x16_find(g[j].X, k_in, pure ? 1 + bf : 1);
         }
         d.scratch = ar.get(S_TNS); d.scratch_bytes = ar.bytes_from(S_TNS);
+        // ... and of launch_gemm_tn_split's two routes only the row-major 16-bit kernel does
+        if (dy16_only || x16_only) SOLA_TRY(need16(gemm_tn_split_takes_tr(d), "operands of a weight gradient"));
+        if (dy16_only) SOLA_TRY(need16(d.a_rm_ready && gemm_tn_split_writes_rm(d), "the gradient rows of a weight gradient"));
+        for (int j = 0; j < n && x16_only; ++j) SOLA_TRY(need16(d.B16[j] != nullptr, "the activation rows of a weight gradient"));
         if (dy_rm_done) *dy_rm_done = gemm_tn_split_writes_rm(d);
         SOLA_TRY(launch_gemm_tn_split(d, s));
         for (int j = 0; j < n && !db_done; ++j)
@@ -511,6 +527,7 @@ struct BwdRun {
                 d.p[0].A = pure ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(dy_sp) + col_off) : dy_sp + col_off;
                 d.lda = ldy;
             } else {
+                SOLA_TRY(need16(!dy16_only, "the gradient rows of an input gradient"));
                 cast.src = nullptr;  // "dy_sp" is rewritten
                 if (sc) SOLA_TRY(cast_scaled(dY, ldy, dy_sp, rows, n_cat, sl));
                 else SOLA_TRY(cast_auto(dY, ldy, dy_sp, rows, n_cat, sl));
@@ -523,6 +540,7 @@ struct BwdRun {
             d.arith = lowp_arith; d.bf16 = bf; d.out_scale = 1.f / kLinScale; d.out_scale_dev = sl + 1;
             if (c16) d.c_f16 = 1;
         } else {
+            SOLA_TRY(need16(!dy16_only, "the gradient rows of an input gradient"));
             SOLA_ARG(!c16, "backward: a bf16 input gradient needs the 16-bit GEMM");
         }
         return launch_gemm(d, s);
@@ -625,7 +643,9 @@ struct BwdRun {
         float* sc;
         bool rm;
         SOLA_TRY(dw_begin());
+        x16_only = c->site(l, a).o16;  // the weight gradient's X: the kept bf16 rows (grad_w_many: x16_find)
         SOLA_TRY(stats_dw(wo, 1, D, M, gn16 ? dy16 : nullptr, true, &sc, &rm));  // gn16: the norm's backward in front of this wrote the bf16 rows
+        x16_only = false;
         SOLA_TRY(dw_end(0));
         SOLA_TRY(transpose_into(W(an + ".out_proj.weight"), D, D, D, 0));
         return grad_x(dres, D, M, D, D, nullptr, dattn, sc, rm, 0, g16);
@@ -646,6 +666,8 @@ struct BwdRun {
             else { ad.dk16 = dy16 + D; ad.dv16 = dy16 + 2 * D; }
             cast.src = nullptr;
             ad.dout_bf16 = g16 ? 1 : 0;
+            // the forward asked this of the same record (site16); "attn_bwd_fused" / "attn_bwd_small" may have changed since
+            SOLA_TRY(need16(attention_bwd_bf16_supported(ad), "q / k / v of an attention site (the attention backward now takes another kernel)"));
             if (g16 && c->site(l, a).o16) {
                 ad.o = static_cast<const float*>(c->x16_find(ab(l, a, "attn"), D, 2));
                 ad.o_bf16 = 1;
@@ -653,6 +675,7 @@ struct BwdRun {
             }
         }
         SOLA_TRY(wait_side(1));  // dqkv / dlkv: the previous sub-block's weight gradients have read them
+        dy16_only = s16;
         return launch_attention_bwd(ad, s);
     }
 
@@ -670,6 +693,7 @@ struct BwdRun {
         if (group) { dres = keep((size_t)M * D); dqkv = keep((size_t)M * 3 * D); }
         if (group && a == 2) dlkv = keep((size_t)BW * 2 * D);
         bool g16;
+        dy16_only = false;
         SOLA_TRY(site_gn_bwd(l, a));
         SOLA_TRY(out_proj_bwd(l, a, &g16));
         return site_attention_bwd(l, a, g16, s16);
@@ -745,6 +769,7 @@ struct BwdRun {
         SOLA_TRY(site_o2l(l));
         SOLA_TRY(site_motion(l));
         SOLA_TRY(site_obj(l));
+        dy16_only = false;
         if (l > 0) {
             SOLA_TRY(join_side());
             SOLA_TRY(flush_bias());  // the layer's deferred bias sums

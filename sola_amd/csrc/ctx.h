@@ -208,7 +208,7 @@ inline std::string abuf(bool train, int layer, const char* attn, const char* wha
 }
 
 // sola_tune keys that the training forward (forward.hip) and the backward (backward.hip) read of each other
-extern int g_train_split_min_rows, g_train_bf16_store, g_train_dw_f16;
+extern int g_train_split_min_rows, g_train_bf16_store, g_train_dw_f16, g_bwd_dual_cast;
 
 // Geometry of attention site `a` (0 inter-object, 1 motion, 2 object -> language) in the backward of plan `p` (rt != null: a ragged batch):
 // group count, Sq, Sk, inner, the strides, the pitches (q / k / v / o: D; dq: 3D; dk / dv: 3D, or 2D for the text side of site 2), the

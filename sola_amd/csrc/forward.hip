@@ -326,6 +326,10 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
         if (!(split && pure && bf && g_train_bf16_store)) return false;
         // the backward's dW products of these gradients must take the row-major 16-bit kernel (no f32 copy exists to transpose)
         if (!gemm_tn_tr_supported(M, D, D, D, D) || (o2l && !gemm_tn_tr_supported((int)text_rows, D, D, D, D))) return false;
+        // ... and hand its row-major operand to the dX GEMMs: with sola_tune "bwd_dual_cast" 0 grad_w_many / grad_x cast the f32 matrix
+        // themselves.  (The rows are the attention backward's own, not the statistics pass's: "bwd_fused_bf16_cast" is not on this route.)
+        // The backward checks again (BwdRun::need16): a switch may change behind this forward
+        if (!g_bwd_dual_cast) return false;
         AttnDesc f = ad;
         f.in_bf16 = 1;
         f.o_cast = reinterpret_cast<void*>(1); f.o_cast_fmt = 3;  // (what attention() below hands the launch)

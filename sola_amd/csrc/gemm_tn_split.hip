@@ -245,6 +245,13 @@ bool gemm_tn_split_writes_rm(const GemmTnSplitDesc& d) {
     return true;
 }
 
+static long long conv_input_rows(const GemmTnSplitDesc& d) { return !d.conv ? 0 : (d.rowmap ? d.B_rows : (long long)d.M / d.T_out * d.T_in); }
+
+bool gemm_tn_split_takes_tr(const GemmTnSplitDesc& d) {
+    return d.pure != 0 && d.ldb % 4 == 0 && gemm_tn_tr_supported(d.M, d.N, d.K, 8, 8) &&
+           (!d.conv || (d.Cin % 256 == 0 && d.ldb == d.Cin && conv_input_rows(d) > 0));
+}
+
 size_t gemm_tn_split_scratch_bytes(int M, int N, int K, int nprob) {
     int ks; long long Mp;
     geometry(M, ks, Mp, true);  // the f16-operand layout pads the rows further; sized for either
@@ -272,8 +279,8 @@ int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s) {
         for (int j = 0; j < d.nprob; ++j) SOLA_TRY(launch_amax_accumulate(d.A[j], d.lda, d.M, d.N, scal, s));
     }
     const bool rm = gemm_tn_split_writes_rm(d);
-    const long long conv_rows_in = !d.conv ? 0 : (d.rowmap ? d.B_rows : (long long)d.M / d.T_out * d.T_in);
-    if (pure && d.ldb % 4 == 0 && gemm_tn_tr_supported(d.M, d.N, d.K, 8, 8) && (!d.conv || (d.Cin % 256 == 0 && d.ldb == d.Cin && conv_rows_in > 0))) {
+    const long long conv_rows_in = conv_input_rows(d);
+    if (gemm_tn_split_takes_tr(d)) {
         // 16-bit operands, linear layers: NO transposed copies.  gemm_tn_tr.hip's gemm_tn_tr_kernel takes the ROW-MAJOR casts - dY's is the
         // dX GEMM's operand anyway - and transposes between LDS and the matrix pipe (ds_read_b64_tr_b16).
         const int bf = pure_fmt == 2 ? 1 : 0;

@@ -160,6 +160,8 @@ int launch_col2im(const float* z, float* dx, long long R, int T_in, int T_out, i
 int launch_col2im_ragged(const float* z, float* dx, long long rows_in, const int4* imap, int cin, int k, int stride, int pad, hipStream_t s, int z_bf16 = 0);
 bool gemm_tn_split_supported(int M, int N, int K);
 bool gemm_tn_split_writes_rm(const GemmTnSplitDesc& d);
+// the launch takes gemm_tn_tr.hip's kernel on ROW-MAJOR 16-bit operands (no transposed copies; the only route that reads a_rm_ready / B16 rows)
+bool gemm_tn_split_takes_tr(const GemmTnSplitDesc& d);
 size_t gemm_tn_split_scratch_bytes(int M, int N, int K, int nprob);
 int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s);
 size_t gemm_tn_scratch_bytes(int M, int N, int K);
