@@ -761,6 +761,88 @@ int sola_resample_u8(const uint8_t* dev_src, int T, int H, int W, int C, int h, 
                      const int32_t* dev_table_y, int taps_y, const float* dev_lut, void* dev_out, void* dev_scratch,
                      size_t scratch_bytes, void* stream);
 
+/* ---- baseline JPEG decode: the bytes of PIL's `Image.open(f).convert("RGB")` (libjpeg's integer arithmetic) from the file's
+ * bytes, entropy decode included, on the device. ------------------------------------------------------------------------------
+ * Supported files: baseline sequential DCT (SOF0), 8-bit samples, Huffman coding (default or optimised tables), 8-bit
+ *   quantisation tables, ONE interleaved scan; one component (grey: three equal channels) or three read as YCbCr with luma
+ *   sampling 1x1, 2x1 or 2x2 and chroma 1x1; restart intervals (DRI / RSTn); any number of APPn / COM segments (skipped; EXIF
+ *   orientation is ignored, as PIL ignores it).
+ * sola_jpeg_parse REFUSES, with sola_last_error() naming which: progressive, extended, lossless, hierarchical or arithmetic
+ *   SOFs; 12-bit samples; 16-bit quantisation tables; four (or two) components; an Adobe segment with a transform other than 1
+ *   on three components, or components named R, G, B without a JFIF / Adobe segment (libjpeg reads those as RGB); other
+ *   sampling factors (4:4:0, 4:1:1, subsampled luma, chroma that is not 1x1); more than one scan (a non-interleaved scan, or a
+ *   DHT / DQT / DRI / SOS behind the first); a DNL marker; an 0xFF fill byte or any marker other than RSTn / EOI inside the
+ *   scan; RSTn out of order, without a DRI, or more of them than the frame has intervals; a missing table; a DHT that is no
+ *   prefix code or holds a DC category above 15; width or height of 0 or above SOLA_JPEG_MAX_SIZE; a scan of 2^28 bytes or
+ *   more; any length field that points outside the buffer.  A file cut short inside its scan (no EOI) is ACCEPTED: the scan
+ *   ends with the buffer.
+ * sola_jpeg_parse (host only, touches no device, reads data[0 .. len) and nothing else): fills *plan - geometry and sampling,
+ *   the quantisation tables of the components in natural (row-major) order, the Huffman tables of the components in the
+ *   lookup form below, the scan's byte range [scan_begin, scan_end) in the file, the restart interval (MCUs, 0 = none) and
+ *   n_segments - and writes the first seg_cap restart segments' byte ranges to host_segs, int32 [seg_cap][2] = [begin, end)
+ *   counted from scan_begin (a file without DRI is one segment; host_segs may be null with seg_cap 0: a caller that finds
+ *   n_segments > seg_cap calls again).  scan_offset and seg_offset are left 0: the caller of sola_jpeg_decode sets them.
+ * SolaJpegHuff: look[next 8 bits] = (length << 8) | symbol of the codes of <= 8 bits, else 0; a longer code has the smallest
+ *   length l (9 .. 16) with (next 16 bits) < limit[l], and is vals[((next 16 bits) >> (16 - l)) + valoff[l]].
+ * sola_jpeg_decode: T frames that share width, height, components and sampling (tables, restart intervals and scan lengths
+ *   are per frame).  dev_scan holds their raw scan bytes, byte stuffing and restart markers in place: frame t's bytes
+ *   [scan_begin, scan_end) of its file at dev_scan + plans[t].scan_offset.  dev_segs: the frames' segment ranges, int32
+ *   [n_segs][2], frame t's at row plans[t].seg_offset.  plans (host) and dev_plans (the same T structs in device memory).
+ *   dev_out uint8 [T,H,W,3].  Synchronous: the call returns when the pixels are written (it reads a device flag between the
+ *   rounds of the decoder's synchronisation).  host_err int32 [T] receives each frame's error word (0: every restart segment
+ *   decoded to its last block and no further; else bits 1 = a bit pattern without a code, 2 = a run past coefficient 63, 4 =
+ *   entropy data behind the last block, 8 = a segment that ends early); host_rounds (optional) the number of launches of the
+ *   synchronisation kernel.  The call succeeds whatever the error words say.
+ *   Arithmetic: DC predicted per component, reset at each restart; coefficients times their quantiser as int16; the 8x8
+ *   "islow" integer IDCT (13-bit constants, column pass descaled by 11, row pass by 18, + 128, clamped); each component plane
+ *   cropped to ceil(W*h_i/h_max) x ceil(H*v_i/v_max) before upsampling; "fancy" (triangle) chroma upsampling 2x1 and 2x2
+ *   with libjpeg's rounding (plain replication where the cropped chroma plane is 1 or 2 samples wide, as libjpeg does);
+ *   YCbCr -> RGB in 16-bit fixed point.  Equal to Pillow in every byte for files an encoder produced.
+ *   Entropy decode: each restart segment is cut into subsequences of subseq_bytes (0 = SOLA_JPEG_SUBSEQ_DEFAULT; a power of two
+ *   SOLA_JPEG_SUBSEQ_MIN .. SOLA_JPEG_SUBSEQ_MAX), one thread each; a thread's start state (bit position, block in the MCU,
+ *   zigzag index) is known at a segment start and guessed elsewhere, and is replaced by its predecessor's end state until
+ *   nothing changes: behind barriers inside a workgroup, by another launch across workgroups (the self-synchronising decode
+ *   of Weissenberger and Schmidt).  After round r the first r subsequences are final: at most as many launches as
+ *   a frame has workgroups, enforced by the host loop; no kernel waits for another workgroup.  Integer arithmetic and two
+ *   integer atomic ORs (error word, change flag): the same bits on every run and stream.
+ *   Nothing read from the device is trusted: every read of the scan is checked against the frame's range and its segment, every
+ *   coefficient write against the segment's block range, every table index is masked.  A damaged file, plan or segment table
+ *   gives wrong pixels or an error word, never an access outside dev_scan, dev_scratch or dev_out.
+ *   Refused before any launch: T < 1, null pointers, frames that differ in geometry, a plan whose numbers do not fit together,
+ *   ranges outside scan_bytes / n_segs, subseq_bytes not as above, a scratch below sola_jpeg_scratch_bytes(plans, T,
+ *   subseq_bytes) (host only; 0 for arguments it refuses) or not 16-byte aligned. */
+#define SOLA_JPEG_MAX_SIZE 16384
+#define SOLA_JPEG_SUBSEQ_MIN 16
+#define SOLA_JPEG_SUBSEQ_MAX 4096
+#define SOLA_JPEG_SUBSEQ_DEFAULT 128
+typedef struct SolaJpegHuff {
+    uint16_t look[256];
+    uint32_t limit[18];  /* [1 .. 16] used; 18 entries keep the struct a multiple of 16 bytes */
+    int32_t valoff[18];
+    uint8_t vals[256];
+} SolaJpegHuff;
+typedef struct SolaJpegPlan {
+    int32_t width, height, ncomp;
+    int32_t hs, vs;                  /* luma sampling factors (chroma is 1x1); 1, 1 for one component */
+    int32_t mcus_x, mcus_y, blocks_per_mcu, n_blocks;
+    int32_t restart_interval, n_segments, reserved;
+    int64_t scan_begin, scan_end;    /* the entropy-coded bytes of the file */
+    int64_t scan_offset, seg_offset; /* set by the caller of sola_jpeg_decode: where this frame's scan and segments lie */
+    uint16_t quant[3][64];           /* by component, natural order */
+    SolaJpegHuff huff[6];            /* component * 2 + (0 DC, 1 AC) */
+} SolaJpegPlan;
+int sola_jpeg_parse(const uint8_t* data, int64_t len, SolaJpegPlan* plan, int32_t* host_segs, int64_t seg_cap);
+size_t sola_jpeg_scratch_bytes(const SolaJpegPlan* plans, int T, int subseq_bytes);
+int sola_jpeg_decode(const uint8_t* dev_scan, int64_t scan_bytes, const int32_t* dev_segs, int64_t n_segs, const SolaJpegPlan* plans,
+                     const SolaJpegPlan* dev_plans, int T, int subseq_bytes, uint8_t* dev_out, void* dev_scratch, size_t scratch_bytes,
+                     int32_t* host_err, int32_t* host_rounds, void* stream);
+/* test / measurement hooks of the same call: sola_jpeg_coefficients copies frame t's coefficient buffer (int16 [n_blocks][64],
+ * natural order, times the quantiser, DC as values) of the LAST sola_jpeg_decode on that scratch to the host;
+ * sola_jpeg_profile: the HIP-event time in ms of each stage of the next calls is added to host_ms[6] (layout, synchronisation,
+ * block indices + coefficient write, DC scan, IDCT, upsample + colour) - null switches it off.  Not for concurrent use. */
+int sola_jpeg_coefficients(const SolaJpegPlan* plans, int T, int subseq_bytes, const void* dev_scratch, int t, int16_t* host_coef, void* stream);
+int sola_jpeg_profile(float* host_ms);
+
 /* ---- multi-scale deformable attention, forward (Deformable-DETR; GroundingDINO's one custom operator,
  * groundingdino._C.ms_deform_attn_forward; Mask2Former's pixel decoder).  Upstream details are from its public source. -------
  * All float32, contiguous:

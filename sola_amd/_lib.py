@@ -160,6 +160,11 @@ SIGNATURES = {
     "sola_resample_coeffs": (_i, [_i, _i, _i, _vp, _vp]),
     "sola_resample_u8_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "sola_resample_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "sola_jpeg_parse": (_i, [_vp, _i64, _vp, _vp, _i64]),
+    "sola_jpeg_scratch_bytes": (_sz, [_vp, _i, _i]),
+    "sola_jpeg_decode": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "sola_jpeg_coefficients": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "sola_jpeg_profile": (_i, [_vp]),
     "sola_ms_deform_attn": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sola_ms_deform_attn_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sola_mask_iou_scratch_bytes": (_sz, [_i, _i, _i, _i]),
