@@ -447,16 +447,24 @@ extern "C" int sola_cast_sp16(const float* in, int ld_in, float* out, int ld_out
     return launch_cast_sp16(in, ld_in, out, ld_out, rows, K, scale, as_stream(stream_));
 }
 
-// split-f16 GEMM entry point (tests): a_sp [M,K] and w_sp [N,K] in the split format, f32 result
-extern "C" int sola_gemm_nt_split(const float* a_sp, int lda, const float* w_sp, const float* bias, const float* r, int ldr,
-                                  int r_sp16, float* cmat, int ldc, int c_sp16, int M, int N, int K, float out_scale, void* stream_) {
-    SOLA_ARG(a_sp && w_sp && cmat, "gemm_nt_split: null argument");
+// The single-problem GEMM entry points (tests): C = A W^T + bias (+ R) on operands of format `ab`, R in format `r`, C in format `c`
+static int gemm_nt_one(const char* who, const void* a, int lda, const void* w, const float* bias, const void* r_mat, int ldr, void* cmat, int ldc,
+                       int M, int N, int K, Elem ab, Elem r, Elem c, float out_scale, const float* out_scale_dev, void* stream_) {
+    SOLA_ARG(a && w && cmat, "%s: null argument", who);
     GemmDesc gd{};
     gd.nprob = 1;
-    gd.p[0] = GemmProblem{a_sp, w_sp, bias, r, cmat};
+    gd.p[0] = GemmProblem{static_cast<const float*>(a), static_cast<const float*>(w), bias, static_cast<const float*>(r_mat), static_cast<float*>(cmat)};
     gd.M = M; gd.N = N; gd.K = K; gd.lda = lda; gd.ldr = ldr; gd.ldc = ldc;
-    gd.arith = 1; gd.out_scale = out_scale; gd.r_sp16 = r_sp16; gd.c_sp16 = c_sp16;
+    gd.ab = ab; gd.r = r; gd.c = c;
+    gd.out_scale = out_scale; gd.out_scale_dev = out_scale_dev;
     return launch_gemm(gd, as_stream(stream_));
+}
+
+// split-f16 GEMM entry point (tests): a_sp [M,K] and w_sp [N,K] in the split format, f32 result
+extern "C" int sola_gemm_nt_split(const float* a_sp, int lda, const float* w_sp, const float* bias, const float* r, int ldr,
+                                  int r_is_split, float* cmat, int ldc, int c_is_split, int M, int N, int K, float out_scale, void* stream_) {
+    return gemm_nt_one("gemm_nt_split", a_sp, lda, w_sp, bias, r, ldr, cmat, ldc, M, N, K, Elem::SP16, r_is_split ? Elem::SP16 : Elem::F32,
+                       c_is_split ? Elem::SP16 : Elem::F32, out_scale, nullptr, stream_);
 }
 
 // channels-last conv on split-f16 operands (tests): x_sp [R * T_in][cin], w_sp [cout][k * cin], f32 y [R * T_out][cout].
@@ -475,7 +483,7 @@ extern "C" int sola_conv1d_cl_split(const float* x_sp, const float* w_sp, const 
     gd.nprob = 1;
     gd.p[0] = GemmProblem{x_sp, w_sp, bias, nullptr, y};
     gd.M = (int)(R * T_out); gd.N = cout; gd.K = k * cin; gd.lda = cin; gd.ldc = cout;
-    gd.arith = 1; gd.out_scale = 1.f;
+    gd.ab = Elem::SP16; gd.out_scale = 1.f;
     gd.conv = 1; gd.T_in = T_in; gd.T_out = T_out; gd.stride = stride; gd.pad = pad; gd.Cin = cin;
     ConvFramePlan fp;
     const bool has = conv_frames_plan(gd, fp);
@@ -511,7 +519,7 @@ extern "C" int sola_conv1d_cl_split(const float* x_sp, const float* w_sp, const 
 // its packed tap range `range` (0 .. *n_ranges - 1; taps *lo .. *hi), copied to dev_out (null = sizes only)
 extern "C" int sola_conv_weights_split(const SolaCtx* c, int layer, int range, float* dev_out, int* lo, int* hi, int* n_ranges, void* stream_) {
     SOLA_ARG(c && layer >= 0 && layer < 6 && range >= -1 && range < c->ws_ntaps[layer], "conv_weights_split: layer %d range %d", layer, range);
-    SOLA_ARG(c->ws16_buf && c->ws16_fmt == 1, "conv_weights_split: run a split-f16 forward first");
+    SOLA_ARG(c->ws16_buf && c->ws16_fmt == Elem::SP16, "conv_weights_split: run a split-f16 forward first");
     const ConvGeom& g = c->conv[layer];
     const int l = range < 0 ? 0 : c->ws_taps[layer][range].lo, h = range < 0 ? g.k - 1 : c->ws_taps[layer][range].hi;
     if (lo) *lo = l;
@@ -525,17 +533,12 @@ extern "C" int sola_conv_weights_split(const SolaCtx* c, int layer, int range, f
 
 // ---- 16-bit storage mode building blocks (tests) ----------------------------------------------------------------
 extern "C" int sola_cast_f16(const float* in, int ld_in, void* out, int ld_out, int64_t rows, int K, float scale, float* dev_scal, void* stream_) {
-    return launch_cast_f16(in, ld_in, out, ld_out, rows, K, scale, dev_scal, as_stream(stream_));
+    return launch_cast_f16(in, ld_in, out, ld_out, rows, K, scale, dev_scal, Elem::F16, as_stream(stream_));
 }
 extern "C" int sola_gemm_nt_f16(const void* a_h, int lda, const void* w_h, const float* bias, const void* r_h, int ldr, void* cmat, int ldc,
                                 int c_is_f16, int M, int N, int K, float out_scale, void* stream_) {
-    SOLA_ARG(a_h && w_h && cmat, "gemm_nt_f16: null argument");
-    GemmDesc gd{};
-    gd.nprob = 1;
-    gd.p[0] = GemmProblem{static_cast<const float*>(a_h), static_cast<const float*>(w_h), bias, static_cast<const float*>(r_h), static_cast<float*>(cmat)};
-    gd.M = M; gd.N = N; gd.K = K; gd.lda = lda; gd.ldr = ldr; gd.ldc = ldc;
-    gd.arith = 2; gd.out_scale = out_scale; gd.r_f16 = r_h ? 1 : 0; gd.c_f16 = c_is_f16;
-    return launch_gemm(gd, as_stream(stream_));
+    return gemm_nt_one("gemm_nt_f16", a_h, lda, w_h, bias, r_h, ldr, cmat, ldc, M, N, K, Elem::F16, r_h ? Elem::F16 : Elem::F32,
+                       c_is_f16 ? Elem::F16 : Elem::F32, out_scale, nullptr, stream_);
 }
 extern "C" int sola_attention_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int G, int H,
                                   int head_dim, int Sq, int Sk, int inner, int64_t q_outer, int64_t q_inner, int64_t q_rs,
@@ -543,35 +546,31 @@ extern "C" int sola_attention_f16(const void* q, int ldq, const void* k, int ldk
     SOLA_ARG(q && k && v && o, "attention_f16: null argument");
     AttnDesc d{static_cast<const float*>(q), static_cast<const float*>(k), static_cast<const float*>(v), static_cast<float*>(o), ldq, ldk, ldv, ldo,
                G, H, head_dim, Sq, Sk, inner, q_outer, q_inner, q_rs, k_outer, k_inner, k_rs, scale, nullptr};
+    d.in = d.out = Elem::F16;
     return launch_attention_f16(d, as_stream(stream_));
 }
 
 // ---- building blocks of the bf16 training step's 16-bit storage (round 6), exposed for the parity tests --------------------------------
 extern "C" int sola_gemm_nt_bf16(const void* a_b, int lda, const void* w_b, const float* bias, const void* r, int ldr, int r_is_bf16, void* cmat, int ldc,
                                  int c_is_bf16, int M, int N, int K, void* stream_) {
-    SOLA_ARG(a_b && w_b && cmat, "gemm_nt_bf16: null argument");
-    GemmDesc gd{};
-    gd.nprob = 1;
-    gd.p[0] = GemmProblem{static_cast<const float*>(a_b), static_cast<const float*>(w_b), bias, static_cast<const float*>(r), static_cast<float*>(cmat)};
-    gd.M = M; gd.N = N; gd.K = K; gd.lda = lda; gd.ldr = ldr; gd.ldc = ldc;
-    gd.arith = 2; gd.bf16 = 1; gd.out_scale = 1.f; gd.r_f16 = (r && r_is_bf16) ? 1 : 0; gd.c_f16 = c_is_bf16;
-    return launch_gemm(gd, as_stream(stream_));
+    return gemm_nt_one("gemm_nt_bf16", a_b, lda, w_b, bias, r, ldr, cmat, ldc, M, N, K, Elem::BF16, (r && r_is_bf16) ? Elem::BF16 : Elem::F32,
+                       c_is_bf16 ? Elem::BF16 : Elem::F32, 1.f, nullptr, stream_);
 }
-extern "C" int sola_attention_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, float* o, void* o_bf16, int ldo, int G, int H,
+extern "C" int sola_attention_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, float* o, void* o16, int ldo, int G, int H,
                                    int head_dim, int Sq, int Sk, int inner, int64_t q_outer, int64_t q_inner, int64_t q_rs,
                                    int64_t k_outer, int64_t k_inner, int64_t k_rs, float scale, float* lse, void* stream_) {
-    SOLA_ARG(q && k && v && (o || o_bf16), "attention_bf16: null argument");
+    SOLA_ARG(q && k && v && (o || o16), "attention_bf16: null argument");
     AttnDesc d{static_cast<const float*>(q), static_cast<const float*>(k), static_cast<const float*>(v), o, ldq, ldk, ldv, ldo,
                G, H, head_dim, Sq, Sk, inner, q_outer, q_inner, q_rs, k_outer, k_inner, k_rs, scale, lse};
     d.drop = g_stage_drop;
-    d.in_bf16 = 1;
+    d.in = Elem::BF16;
     bool done = false;
-    if (o_bf16) { d.o_cast = o_bf16; d.o_cast_fmt = 3; d.o_cast_done = &done; }
+    if (o16) { d.o_cast = o16; d.cast = Elem::BF16; d.o_cast_done = &done; }
     SOLA_TRY(launch_attention(d, as_stream(stream_)));
-    SOLA_ARG(!o_bf16 || done, "attention_bf16: this shape does not write the bf16 output");
+    SOLA_ARG(!o16 || done, "attention_bf16: this shape does not write the bf16 output");
     return SOLA_OK;
 }
-extern "C" int sola_attention_backward_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int o_bf16, const void* dout, int dout_bf16, int ldo,
+extern "C" int sola_attention_backward_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int o_is_bf16, const void* dout, int dout_is_bf16, int ldo,
                                             const float* lse, void* dq16, void* dk16, void* dv16, int ld_dq, int ld_dk, int ld_dv, float* dq_scratch,
                                             float* dvec, int G, int H, int head_dim, int Sq, int Sk, int inner, int64_t q_outer, int64_t q_inner,
                                             int64_t q_rs, int64_t k_outer, int64_t k_inner, int64_t k_rs, float scale, int64_t q_rows, float* scratch,
@@ -581,9 +580,9 @@ extern "C" int sola_attention_backward_bf16(const void* q, int ldq, const void* 
                   ldq, ldk, ldv, ldo, ld_dq, ld_dk, ld_dv, G, H, head_dim, Sq, Sk, inner, q_outer, q_inner, q_rs, k_outer, k_inner, k_rs, scale};
     d.drop = g_stage_drop;
     d.part = scratch; d.part_floats = scratch_floats; d.part_rows = q_rows;
-    d.io_bf16 = 1; d.dq16 = dq16; d.dk16 = dk16; d.dv16 = dv16;
-    d.dout_bf16 = dout_bf16 ? 1 : 0;
-    d.o_bf16 = o_bf16 ? 1 : 0;
+    d.io_fmt = Elem::BF16; d.dq16 = dq16; d.dk16 = dk16; d.dv16 = dv16;
+    d.dout_fmt = dout_is_bf16 ? Elem::BF16 : Elem::F32;
+    d.o_fmt = o_is_bf16 ? Elem::BF16 : Elem::F32;
     return launch_attention_bwd(d, as_stream(stream_));
 }
 
@@ -592,15 +591,10 @@ extern "C" int sola_cast_sp16_auto(const float* in, int ld_in, float* out, int l
 }
 
 extern "C" int sola_gemm_nt_split_scaled(const float* a_sp, int lda, const float* w_sp, const float* bias, const float* r, int ldr,
-                                         int r_sp16, float* cmat, int ldc, int c_sp16, int M, int N, int K, float out_scale,
+                                         int r_is_split, float* cmat, int ldc, int c_is_split, int M, int N, int K, float out_scale,
                                          const float* out_scale_dev, void* stream_) {
-    SOLA_ARG(a_sp && w_sp && cmat, "gemm_nt_split_scaled: null argument");
-    GemmDesc gd{};
-    gd.nprob = 1;
-    gd.p[0] = GemmProblem{a_sp, w_sp, bias, r, cmat};
-    gd.M = M; gd.N = N; gd.K = K; gd.lda = lda; gd.ldr = ldr; gd.ldc = ldc;
-    gd.arith = 1; gd.out_scale = out_scale; gd.out_scale_dev = out_scale_dev; gd.r_sp16 = r_sp16; gd.c_sp16 = c_sp16;
-    return launch_gemm(gd, as_stream(stream_));
+    return gemm_nt_one("gemm_nt_split_scaled", a_sp, lda, w_sp, bias, r, ldr, cmat, ldc, M, N, K, Elem::SP16, r_is_split ? Elem::SP16 : Elem::F32,
+                       c_is_split ? Elem::SP16 : Elem::F32, out_scale, out_scale_dev, stream_);
 }
 
 // Reads the guard words the split-f16 forward left (ctx.h) and reports whether the call must be repeated in exact f32.
@@ -925,12 +919,7 @@ extern "C" int sola_ws_backward(const float* w, const float* dwstd, int cout, in
 
 extern "C" int sola_gemm_nt(const float* a, int lda, const float* w, const float* bias, const float* r, int ldr,
                             float* cmat, int ldc, int M, int N, int K, void* stream_) {
-    SOLA_ARG(a && w && cmat, "gemm_nt: null argument");
-    GemmDesc gd{};
-    gd.nprob = 1;
-    gd.p[0] = GemmProblem{a, w, bias, r, cmat};
-    gd.M = M; gd.N = N; gd.K = K; gd.lda = lda; gd.ldr = ldr; gd.ldc = ldc;
-    return launch_gemm(gd, as_stream(stream_));
+    return gemm_nt_one("gemm_nt", a, lda, w, bias, r, ldr, cmat, ldc, M, N, K, Elem::F32, Elem::F32, Elem::F32, 0.f, nullptr, stream_);
 }
 
 extern "C" int sola_gemm_nn(const float* a, int lda, const float* w0, const float* w1, const float* w2, int w_rows, const float* r, int ldr,
@@ -944,11 +933,14 @@ extern "C" int sola_gemm_nn(const float* a, int lda, const float* w0, const floa
     return launch_gemm(gd, as_stream(stream_));
 }
 
+// the `fmt` argument of the 16-bit weight-gradient entry points (sola_hip.h): 1 = f16, 2 = bf16 (the callers have checked the range)
+static Elem fmt16_arg(int fmt) { return fmt == 2 ? Elem::BF16 : Elem::F16; }
 extern "C" int sola_gemm_tn_f16(const float* a, int lda, const float* b, int ldb, float* cmat, int M, int N, int K, int fmt, void* scratch,
                                 size_t scratch_bytes, void* stream_) {
     SOLA_ARG(a && b && cmat && scratch && (fmt == 1 || fmt == 2), "gemm_tn_f16: null argument or fmt %d", fmt);
     GemmTnSplitDesc d{};
-    d.A[0] = a; d.B[0] = b; d.C[0] = cmat; d.nprob = 1; d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldb = ldb; d.pure = fmt;
+    d.A[0] = a; d.B[0] = b; d.C[0] = cmat; d.nprob = 1; d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldb = ldb;
+    d.ab = d.rm_fmt = d.b16_fmt = fmt16_arg(fmt);
     d.scratch = static_cast<float*>(scratch); d.scratch_bytes = scratch_bytes;
     return launch_gemm_tn_split(d, as_stream(stream_));
 }
@@ -958,7 +950,8 @@ extern "C" int sola_conv1d_cl_wgrad_f16(const float* x, const float* dy, float* 
     const int T_out = (T_in + 2 * pad - k) / stride + 1;
     SOLA_ARG(T_out > 0 && gemm_tn_split_supported(R * T_out, cout, k * cin), "conv1d_cl_wgrad_f16: R*T_out=%d cout=%d k*cin=%d", R * T_out, cout, k * cin);
     GemmTnSplitDesc d{};
-    d.nprob = 1; d.A[0] = dy; d.B[0] = x; d.C[0] = dwstd; d.M = R * T_out; d.N = cout; d.K = k * cin; d.lda = cout; d.ldb = cin; d.pure = fmt;
+    d.nprob = 1; d.A[0] = dy; d.B[0] = x; d.C[0] = dwstd; d.M = R * T_out; d.N = cout; d.K = k * cin; d.lda = cout; d.ldb = cin;
+    d.ab = d.rm_fmt = d.b16_fmt = fmt16_arg(fmt);
     d.conv = (k > 1 || stride > 1 || pad > 0) ? 1 : 0; d.T_in = T_in; d.T_out = T_out; d.stride = stride; d.pad = pad; d.Cin = cin;
     d.scratch = static_cast<float*>(scratch); d.scratch_bytes = scratch_bytes;
     return launch_gemm_tn_split(d, as_stream(stream_));
@@ -970,6 +963,7 @@ extern "C" int sola_gemm_tn_split(const float* a, int lda, const float* b, int l
     SOLA_ARG(a && b && cmat && scratch, "gemm_tn_split: null argument");
     GemmTnSplitDesc d{};
     d.A[0] = a; d.B[0] = b; d.C[0] = cmat; d.nprob = 1; d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldb = ldb;
+    d.ab = d.rm_fmt = d.b16_fmt = Elem::SP16;
     d.scratch = static_cast<float*>(scratch); d.scratch_bytes = scratch_bytes;
     return launch_gemm_tn_split(d, as_stream(stream_));
 }
@@ -1066,6 +1060,7 @@ extern "C" int sola_conv1d_cl_backward_split(const float* x, const float* wstd, 
     hipStream_t s = as_stream(stream_);
     GemmTnSplitDesc d{};
     d.nprob = 1; d.A[0] = dy; d.B[0] = x; d.C[0] = dwstd; d.M = M; d.N = cout; d.K = k * cin; d.lda = cout; d.ldb = cin;
+    d.ab = d.rm_fmt = d.b16_fmt = Elem::SP16;
     d.conv = (k > 1 || stride > 1 || pad > 0) ? 1 : 0; d.T_in = T_in; d.T_out = T_out; d.stride = stride; d.pad = pad; d.Cin = cin;
     d.scratch = reinterpret_cast<float*>(base + off[0]); d.scratch_bytes = off[1] - off[0];
     SOLA_TRY(launch_gemm_tn_split(d, s));
@@ -1082,9 +1077,9 @@ extern "C" int sola_conv1d_cl_backward_split(const float* x, const float* wstd, 
     const bool gather = d.conv != 0;
     gd.p[0] = GemmProblem{dy_sp, wt_sp, nullptr, nullptr, gather ? z : dx};
     gd.M = M; gd.N = k * cin; gd.K = cout; gd.lda = cout; gd.ldc = k * cin;
-    gd.arith = 1; gd.out_scale = 1.f; gd.out_scale_dev = scal + 1;
+    gd.ab = Elem::SP16; gd.out_scale = 1.f; gd.out_scale_dev = scal + 1;
     SOLA_TRY(launch_gemm(gd, s));
-    if (gather) SOLA_TRY(launch_col2im(z, dx, R, T_in, T_out, cin, k, stride, pad, s));
+    if (gather) SOLA_TRY(launch_col2im(z, dx, R, T_in, T_out, cin, k, stride, pad, Elem::F32, s));
     return SOLA_OK;
 }
 
@@ -1139,8 +1134,8 @@ extern "C" int sola_attention_split(const float* q_sp, int ldq, const float* k_s
     SOLA_ARG(q_sp && k_sp && v_sp && o, "attention_split: null argument");
     AttnDesc d{q_sp, k_sp, v_sp, o, ldq, ldk, ldv, ldo, G, H, head_dim, Sq, Sk, inner, q_outer, q_inner, q_rs, k_outer, k_inner, k_rs, scale, lse};
     d.drop = g_stage_drop;
-    d.o_sp16 = o_is_split;
-    d.in_sp16 = 1;
+    d.out = o_is_split ? Elem::SP16 : Elem::F32;
+    d.in = Elem::SP16;
     return launch_attention(d, as_stream(stream_));
 }
 

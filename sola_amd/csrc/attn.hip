@@ -555,7 +555,8 @@ int g_attn_splitm = 0;  // sola_tune "attn_splitm": 1 = f16-MFMA triples on f32 
 int launch_attention(const AttnDesc& d, hipStream_t s) {
     SOLA_ARG(d.G > 0 && d.H > 0 && d.Sq > 0 && d.Sk > 0 && d.inner > 0, "attention: bad sizes");
     SOLA_ARG(d.ldq % 4 == 0 && d.ldk % 4 == 0 && d.ldv % 4 == 0 && d.ldo % 4 == 0, "attention: strides must be multiples of 4");
-    if (d.in_bf16) {  // bf16 q / k / v (training step's 16-bit storage)
+    SOLA_ARG(d.in != Elem::F16 && attn_formats_ok(d.in, d.out, d.cast), "attention: no kernel for %s q / k / v with a %s output", elem_name(d.in), elem_name(d.out));
+    if (d.in == Elem::BF16) {  // bf16 q / k / v (training step's 16-bit storage)
         if (attention_bf16_mfma_supported(d)) return launch_attention_bf16_train(d, s);  // bf16 MFMA products, half the bytes per load (attn_f16.hip)
         return launch_attention_simple(d, s);                                            // f32 MFMA on the widened values (attn_simple.hip; it checks)
     }
@@ -595,7 +596,7 @@ int launch_attention(const AttnDesc& d, hipStream_t s) {
     attn_fill_common(a, d);
     a.lse = d.lse;
     a.drop = d.drop;
-    a.in_sp16 = d.in_sp16;
+    a.in_sp16 = d.in == Elem::SP16;
     a.nqb = 1; a.kv_rows = 64; a.qsplit = 1; a.sp_log2 = 4; a.tile_rows = 64;
     const SolaProfScope prof = attn_prof_scope(d, s);
     return attn_dispatch_dh(d.DH, "attention: head_dim %d unsupported (16/32/64/128)", [&](auto dh) { return launch_dh<decltype(dh)::value>(a, s); });

@@ -1388,7 +1388,7 @@ size_t attention_bwd_part_floats(long long q_rows, int G, int H, int Sk) {
 
 bool attention_bwd_dout_bf16_enabled() { return g_attn_bwd_bf16_mfma != 0; }
 
-// bf16 q / k / v in and bf16 dQ / dK / dV out (AttnBwdDesc::io_bf16): the one-pass kernel's shapes, 8-value-aligned rows
+// bf16 q / k / v in and bf16 dQ / dK / dV out (AttnBwdDesc::io_fmt BF16): the one-pass kernel's shapes, 8-value-aligned rows
 bool attention_bwd_bf16_supported(const AttnBwdDesc& d) {
     if (d.DH != 128 || d.ldq % 8 || d.ldk % 8 || d.ldv % 8 || d.ld_dq % 4 || d.ld_dk % 4 || d.ld_dv % 4) return false;
     if (g_attn_bwd_small && d.Sq <= 4 && d.Sk <= 4) return true;  // the register kernel of sequences of <= 4 steps
@@ -1406,14 +1406,16 @@ int launch_attention_bwd(const AttnBwdDesc& d, hipStream_t s) {
     a.ld_dq = d.ld_dq; a.ld_dk = d.ld_dk; a.ld_dv = d.ld_dv;
     a.ntile = 1;
     a.drop = d.drop;
-    a.io16 = d.io_bf16 ? 1 : 0;
-    a.g16 = d.dout_bf16 ? 1 : 0;
-    a.o16 = d.o_bf16 ? 1 : 0;
-    SOLA_ARG(!d.o_bf16 || d.dout_bf16, "attention backward: a bf16 O goes with a bf16 dO");
-    SOLA_ARG(!d.dout_bf16 || (d.io_bf16 && g_attn_bwd_bf16_mfma && d.ldo % 8 == 0), "attention backward: a bf16 dO goes with bf16 q / k / v and the bf16 products");
+    SOLA_ARG(attn_bwd_formats_ok(d.io_fmt, d.dout_fmt, d.o_fmt), "attention backward: a bf16 O goes with a bf16 dO, a bf16 dO with bf16 q / k / v (%s, %s, %s)",
+             elem_name(d.o_fmt), elem_name(d.dout_fmt), elem_name(d.io_fmt));
+    const bool io16 = d.io_fmt == Elem::BF16;
+    a.io16 = io16;
+    a.g16 = d.dout_fmt == Elem::BF16;
+    a.o16 = d.o_fmt == Elem::BF16;
+    SOLA_ARG(!a.g16 || (g_attn_bwd_bf16_mfma && d.ldo % 8 == 0), "attention backward: a bf16 dO goes with the bf16 products (ldo %% 8 == 0)");
     a.dq16 = static_cast<unsigned short*>(d.dq16);
-    if (d.io_bf16) { a.dk = static_cast<float*>(d.dk16); a.dv = static_cast<float*>(d.dv16); }
-    if (d.io_bf16) SOLA_ARG(attention_bwd_bf16_supported(d) && d.dq16 && d.dk16 && d.dv16 && d.dq, "attention backward: bf16 q / k / v and gradients need the one-pass kernel's shapes");
+    if (io16) { a.dk = static_cast<float*>(d.dk16); a.dv = static_cast<float*>(d.dv16); }
+    if (io16) SOLA_ARG(attention_bwd_bf16_supported(d) && d.dq16 && d.dk16 && d.dv16 && d.dq, "attention backward: bf16 q / k / v and gradients need the one-pass kernel's shapes");
     const double elems = (double)d.G * d.H * d.DH;
     SolaProfScope prof(SOLA_PROF_ATTN_BWD, s, 14.0 * elems * d.Sq * d.Sk, 4.0 * elems * (5.0 * d.Sq + 4.0 * d.Sk));
     if (g_attn_bwd_small && d.DH == 128 && d.Sq <= 4 && d.Sk <= 4) return launch_bwd_small(a, s);

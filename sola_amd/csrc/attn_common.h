@@ -137,7 +137,7 @@ void attn_fill_common(A& a, const D& d) {
     a.scale = d.scale;
     a.q_units = d.q_units; a.k_units = d.q_units ? (d.k_units ? d.k_units : d.q_units) : nullptr;
     if constexpr (attn_has_o_sp16<A>::value) {
-        a.o_sp16 = d.o_sp16; a.guard = d.o_sp16 ? d.guard : nullptr;
+        a.o_sp16 = d.out == Elem::SP16; a.guard = d.out == Elem::SP16 ? d.guard : nullptr;
     }
 }
 

@@ -32,7 +32,7 @@ struct AttnHArgs {
     int* guard;
     const int4 *q_units, *k_units;
     int qpb;  // consecutive 64-query blocks of a unit per thread block (> 1 only where the unit's keys fit one tile: K / V staged once)
-    // TR instantiation (round 6: the bf16 training forward on bfloat16 q / k / v, AttnDesc::in_bf16): f32 output rows (optional), the
+    // TR instantiation (round 6: the bf16 training forward on bfloat16 q / k / v, AttnDesc::in BF16): f32 output rows (optional), the
     // bfloat16 copy the out-projection takes as its operand (optional), the log-sum-exp of the scaled scores, dropout on the probabilities
     float* o32;
     float* lse;
@@ -427,10 +427,10 @@ int launch_h(const AttnHArgs& a0, hipStream_t s) {
 }  // namespace
 
 int g_attn_bf16_mfma = 1;  // sola_tune "attn_bf16_mfma": 1 = bf16 training forward on the bf16 MFMA (this file); 0 = the f32-MFMA kernel on widened values (attn_simple.hip)
-// AttnDesc::in_bf16 launches this kernel takes: head_dim 128 / 64, 16-byte aligned rows, no shared keys, f32 and / or bf16 (o_cast_fmt 3) output
+// the bfloat16 q / k / v launches this kernel takes: head_dim 128 / 64, 16-byte aligned rows, no shared keys, f32 and / or bf16 (o_cast) output
 bool attention_bf16_mfma_supported(const AttnDesc& d) {
-    return g_attn_bf16_mfma && d.in_bf16 && !d.o_sp16 && !d.in_sp16 && !d.k_private && (d.DH == 128 || d.DH == 64) && d.ldq % 8 == 0 && d.ldk % 8 == 0 &&
-           d.ldv % 8 == 0 && d.ldo % 8 == 0 && (!d.o_cast || d.o_cast_fmt == 3) && (d.o || d.o_cast);
+    return g_attn_bf16_mfma && d.in == Elem::BF16 && d.out != Elem::SP16 && !d.k_private && (d.DH == 128 || d.DH == 64) && d.ldq % 8 == 0 && d.ldk % 8 == 0 &&
+           d.ldv % 8 == 0 && d.ldo % 8 == 0 && (!d.o_cast || d.cast == Elem::BF16) && (d.o || d.o_cast);
 }
 int launch_attention_bf16_train(const AttnDesc& d, hipStream_t s) {
     SOLA_ARG(d.G > 0 && d.H > 0 && d.Sq > 0 && d.Sk > 0 && d.inner > 0 && attention_bf16_mfma_supported(d), "attention (bf16): unsupported launch");
@@ -450,6 +450,7 @@ void sola_attn_set_f16_qpb(int v) { g_attn_f16_qpb = v == 0 ? 1 : v; }
 
 // AttnDesc with q / k / v / o pointing at _Float16 matrices and ld* counting halfs
 int launch_attention_f16(const AttnDesc& d, hipStream_t s) {
+    SOLA_ARG(d.in == Elem::F16 && attn_formats_ok(d.in, d.out, d.cast), "attention (f16): q / k / v / o are f16 rows (%s in, %s out)", elem_name(d.in), elem_name(d.out));
     SOLA_ARG(d.G > 0 && d.H > 0 && d.Sq > 0 && d.Sk > 0 && d.inner > 0, "attention (f16): bad sizes");
     SOLA_ARG(d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 4 == 0, "attention (f16): row pitches must be multiples of 8 halfs");
     SOLA_ARG(!d.lse && !d.drop.enabled, "attention (f16): inference only (no log-sum-exp output, no dropout)");

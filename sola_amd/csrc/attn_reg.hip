@@ -234,7 +234,7 @@ int g_attn_reg_minw = 2;  // waves per SIMD the kernel is compiled for: 2 = 256 
 // Where it loses: 64 tracks 311 vs 279, 128 tracks 488 vs 414, object -> language (256 x 48) 250 vs 212 - every 16-query tile
 // re-reads the unit's K and V from L2 with one tile of prefetch, which two waves per SIMD do not cover.
 bool attention_reg_supported(const AttnDesc& d) {
-    if (!g_attn_reg || d.drop.enabled || d.in_sp16 || d.DH != 128 || (d.Sq <= 4 && d.Sk <= 4)) return false;
+    if (!g_attn_reg || d.drop.enabled || d.in == Elem::SP16 || d.DH != 128 || (d.Sq <= 4 && d.Sk <= 4)) return false;
     // the kernel addresses a unit's key rows with 32-bit byte offsets from the unit's first row
     const long long ld = d.ldk > d.ldv ? d.ldk : d.ldv;
     if (!d.q_units && (long long)d.Sk * d.k_rs * ld * 4 >= (1ll << 32)) return false;

@@ -325,7 +325,7 @@ void sola_attn_set_res_tiles(int v) { g_attn_res_tiles = v < 0 ? 0 : v; }
 // f32 q / k / v at head_dim 128, no dropout, at most 64 keys and enough queries per unit to pay for staging K/V
 bool attention_res_supported(const AttnDesc& d) {
     if (d.q_units && g_attn_res != 2) return false;  // ragged batches: see attention_reg_supported
-    return g_attn_res && !d.drop.enabled && !d.in_sp16 && d.DH == 128 && d.Sk <= 64 && d.Sq >= 128;
+    return g_attn_res && !d.drop.enabled && d.in != Elem::SP16 && d.DH == 128 && d.Sk <= 64 && d.Sq >= 128;
 }
 
 bool attention_shared_keys_supported(const AttnDesc& d) { return attention_res_supported(d) && !d.q_units && d.k_private > 0 && d.k_private <= d.Sk; }

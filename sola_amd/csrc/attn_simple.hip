@@ -26,10 +26,10 @@ struct AttnSArgs {
     int xcd_remap;
     float* lse;       // TR instantiation: optional [q rows][H] log-sum-exp of the scaled scores (saved for the backward)
     DropoutCfg drop;  // TR instantiation: dropout on the probabilities (tools/attention.py:71), same counter-based mask as attn.hip
-    void* o_cast;     // TR instantiation: AttnDesc::o_cast / o_side / o_cast_fmt
+    void* o_cast;     // TR instantiation: AttnDesc::o_cast / o_side / cast
     void* o_side;
     int o_cast_fmt;
-    int o_skip_f32;   // TR + IN16: the f32 output is not written (the bf16 o_cast is the only copy: AttnDesc::in_bf16 with o == nullptr)
+    int o_skip_f32;   // TR + IN16: the f32 output is not written (the bf16 o_cast is the only copy: AttnDesc::in BF16 with o == nullptr)
 };
 
 // DB: two LDS stages of TK keys; the next tile's K/V rows travel in registers while the current tile is multiplied and there
@@ -497,7 +497,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs
     attn_store_tile<NC>(a.o + (q0 + (long long)qi * q_rs) * a.ldo + h * DH, g4, oacc, inv, a.o_sp16, a.guard);
 }
 
-// ---- split-f16 q / k / v (written as split pairs by the projection GEMMs, GemmDesc::c_sp16), high-occupancy shape (round 3) -----
+// ---- split-f16 q / k / v (written as split pairs by the projection GEMMs, GemmDesc::c SP16), high-occupancy shape (round 3) -----
 // From ~48 keys per unit on, the exact-f32 products above take as long at the matrix pipe's peak as the traffic takes at the HBM
 // peak (object -> language at the headline shape: 82 us against 115 us; inter-object attention over 128 tracks: 219 against 134),
 // and the two do not overlap at four waves per SIMD.  attn.hip's kernel for split inputs is the round-1 shape (8 waves, 68 KB of
@@ -725,7 +725,7 @@ int launch_s(const AttnSArgs& a0, hipStream_t s) {
 
 // sequences of <= 4 steps at head_dim 128, inference (no log-sum-exp, no dropout), f32 q / k / v
 bool attention_small_supported(const AttnDesc& d) {
-    return !d.lse && !d.drop.enabled && !d.in_sp16 && d.Sq <= 4 && d.Sk <= 4 && d.DH == 128;
+    return !d.lse && !d.drop.enabled && d.in != Elem::SP16 && d.Sq <= 4 && d.Sk <= 4 && d.DH == 128;
 }
 
 static AttnSArgs make_sargs(const AttnDesc& d) {
@@ -756,23 +756,23 @@ int launch_attention_small(const AttnDesc& d, hipStream_t s) {
 // f32 q / k / v, more than 16 keys or queries; with a log-sum-exp output / dropout (training) the TR instantiation, f32 output only
 int g_attn_simple_train = 1;  // sola_tune "attn_simple_train": 0 = the training forward keeps attn.hip's kernels (A/B)
 bool attention_simple_supported(const AttnDesc& d) {
-    if ((d.lse || d.drop.enabled) && (!g_attn_simple_train || d.o_sp16)) return false;
-    return !d.in_sp16 && (d.Sq > 16 || d.Sk > 16) && (d.DH == 128 || d.DH == 64);
+    if ((d.lse || d.drop.enabled) && (!g_attn_simple_train || d.out == Elem::SP16)) return false;
+    return d.in != Elem::SP16 && (d.Sq > 16 || d.Sk > 16) && (d.DH == 128 || d.DH == 64);
 }
-// bfloat16 q / k / v (AttnDesc::in_bf16): this file's training instantiation takes them - f32 output or bf16 cast only, 8-value-aligned rows
+// bfloat16 q / k / v (AttnDesc::in BF16): this file's training instantiation takes them - f32 output or bf16 cast only, 8-value-aligned rows
 bool attention_in_bf16_supported(const AttnDesc& d) {
-    return g_attn_simple_train && !d.o_sp16 && !d.in_sp16 && !d.k_private && (d.Sq > 16 || d.Sk > 16) && (d.DH == 128 || d.DH == 64) &&
+    return g_attn_simple_train && d.out != Elem::SP16 && !d.k_private && (d.Sq > 16 || d.Sk > 16) && (d.DH == 128 || d.DH == 64) &&
            d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 8 == 0;
 }
 
 int launch_attention_simple(const AttnDesc& d, hipStream_t s) {
     AttnSArgs a = make_sargs(d);
-    if (d.o_cast && d.o_cast_done && (d.lse || d.drop.enabled || d.in_bf16) && !d.o_sp16 && d.ldo % 8 == 0) {  // the TR instantiation runs (launch_s)
-        a.o_cast = d.o_cast; a.o_side = d.o_cast_fmt == 1 ? d.o_side : nullptr; a.o_cast_fmt = d.o_cast_fmt;
+    if (d.o_cast && d.o_cast_done && (d.lse || d.drop.enabled || d.in == Elem::BF16) && d.out != Elem::SP16 && d.ldo % 8 == 0) {  // the TR instantiation runs (launch_s)
+        a.o_cast = d.o_cast; a.o_side = d.cast == Elem::SP16 ? d.o_side : nullptr; a.o_cast_fmt = (int)d.cast;  // (the kernel reads Elem's values)
         *d.o_cast_done = true;
     }
-    a.in_bf16 = d.in_bf16;
-    if (d.in_bf16) {
+    a.in_bf16 = d.in == Elem::BF16;
+    if (d.in == Elem::BF16) {
         SOLA_ARG(attention_in_bf16_supported(d), "attention: bf16 q / k / v need the high-occupancy training shape (more than 16 queries or keys, head_dim 64 / 128, pitches %% 8 == 0)");
         a.o_skip_f32 = d.o == nullptr;
         SOLA_ARG(d.o || a.o_cast, "attention: no output");
@@ -787,7 +787,7 @@ void sola_attn_set_spin(int v) { g_attn_spin = v != 0; g_attn_spin_db = v != 2; 
 bool attention_spin_supported(const AttnDesc& d) {
     // units of at most two 64-query blocks (the inter-object attention): with many q-blocks per unit (object -> language) every
     // block re-stages the unit's K / V and attn.hip's resident-K/V loop wins (158 vs 184 us at the headline shape)
-    return g_attn_spin && d.in_sp16 && !d.lse && !d.drop.enabled && d.DH == 128 && (d.Sq > 16 || d.Sk > 16) && (d.Sq <= 128 || d.q_units) &&
+    return g_attn_spin && d.in == Elem::SP16 && !d.lse && !d.drop.enabled && d.DH == 128 && (d.Sq > 16 || d.Sk > 16) && (d.Sq <= 128 || d.q_units) &&
            d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0;
 }
 int launch_attention_spin(const AttnDesc& d, hipStream_t s) {
@@ -798,7 +798,7 @@ int launch_attention_spin(const AttnDesc& d, hipStream_t s) {
 
 // f32 q / k / v with the products evaluated as split-f16 triples (AttnDesc::split_math; head_dim 128, inference)
 bool attention_splitm_supported(const AttnDesc& d) {
-    return d.split_math && !d.lse && !d.drop.enabled && !d.in_sp16 && (d.Sq > 4 || d.Sk > 4) && d.DH == 128;
+    return d.split_math && !d.lse && !d.drop.enabled && d.in != Elem::SP16 && (d.Sq > 4 || d.Sk > 4) && d.DH == 128;
 }
 int launch_attention_splitm(const AttnDesc& d, hipStream_t s) {
     const AttnSArgs a = make_sargs(d);

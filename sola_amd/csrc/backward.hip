@@ -234,18 +234,19 @@ struct BwdRun {
     const int BW = rt ? (int)rt->LW : B * Wn;             // text ++ negative rows
     const SiteShape shape = rt ? site_shape_samples(*rt) : site_shape_uniform(B, N, Tp, Wn);  // the layers' units (sites.h)
     // ---- modes
-    // split: every GEMM of the backward on f16 MFMAs - (hi, lo) operand pairs, three products (precision 1), or plain f16
-    // operands, one product (precision 2: "pure"; mixed precision - activations, gradients and accumulation stay f32)
-    const bool split = c->precision >= 1 && ar.present(S_DY_SP);
-    const bool pure = c->precision >= 2;
-    const int bf = c->precision == 3 ? 1 : 0;  // bfloat16 GEMM operands
-    const int lowp_arith = pure ? 2 : 1;
+    // split: every GEMM of the backward on 16-bit MFMAs - (hi, lo) operand pairs, three products (SP16), or plain f16 / bf16
+    // operands, one product (mixed precision - activations, gradients and accumulation stay f32)
+    const Elem opfmt = operand_format(c->precision);  // the step's GEMM operand format: forward and dX products
+    const bool op16 = is_row16(opfmt), is_bf = opfmt == Elem::BF16;
+    const int k_unit = op16 ? 64 : 32;  // reduction lengths are whole k-tiles of the operands' kernels
+    const bool split = opfmt != Elem::F32 && ar.present(S_DY_SP);
     // sola_tune "train_dw_f16": in the split-f16 step the weight-gradient products dW = dY^T X take PLAIN f16 operands (one MFMA per
     // product; a sum over all token rows, where the operand rounding averages out) while forward and dX keep the split pairs
-    const bool dw16 = !pure && g_train_dw_f16 != 0;
+    const bool dw16 = !op16 && g_train_dw_f16 != 0;
+    const Elem dw_fmt = dw16 ? Elem::F16 : opfmt;  // the dW products' operand format (split steps only)
     const bool lane_on = !split && g_bwd_side_rows > 0 && M <= g_bwd_side_rows;  // dW products on c->side_stream (g_bwd_side_rows)
     const bool group = !split && !lane_on && ar.present(S_DWKEEP);  // deferred, grouped dW of the linear layers (g_bwd_group_rows)
-    const bool gn16 = split && pure && bf && g_train_bf16_store && g_bwd_fused_bf16_cast && g_bwd_dual_cast && D % 8 == 0;  // norms write their bf16 dx
+    const bool gn16 = split && is_bf && g_train_bf16_store && g_bwd_fused_bf16_cast && g_bwd_dual_cast && D % 8 == 0;  // norms write their bf16 dx
     // ---- fixed scratch
     float* const tn = ar.get(S_TN);  // the dW kernels' slab scratch: touched by the side stream only (lane_on)
     float* const wt = ar.get(S_WT);
@@ -321,13 +322,13 @@ struct BwdRun {
     }
 
     int cast_scaled(const float* in, int ld, float* out, long long rows, int K, float* sc) const {
-        return pure ? launch_cast_f16_scaled(in, ld, out, K, rows, K, sc, s, bf) : launch_cast_sp16_scaled(in, ld, out, K, rows, K, sc, s);
+        return op16 ? launch_cast_f16_scaled(in, ld, out, K, rows, K, sc, opfmt, s) : launch_cast_sp16_scaled(in, ld, out, K, rows, K, sc, s);
     }
     int cast_auto(const float* in, int ld, float* out, long long rows, int K, float* sc) const {
-        return pure ? launch_cast_f16(in, ld, out, K, rows, K, 0.f, sc, s, 13, nullptr, bf) : launch_cast_sp16_auto(in, ld, out, K, rows, K, sc, s);
+        return op16 ? launch_cast_f16(in, ld, out, K, rows, K, 0.f, sc, opfmt, s) : launch_cast_sp16_auto(in, ld, out, K, rows, K, sc, s);
     }
     int cast_fixed(const float* in, int ld, float* out, long long rows, int K, float scale) const {
-        return pure ? launch_cast_f16(in, ld, out, K, rows, K, scale, nullptr, s, 13, nullptr, bf) : launch_cast_sp16(in, ld, out, K, rows, K, scale, s);
+        return op16 ? launch_cast_f16(in, ld, out, K, rows, K, scale, nullptr, opfmt, s) : launch_cast_sp16(in, ld, out, K, rows, K, scale, s);
     }
     // the 16-bit dW kernel takes the product and its scratch fits
     bool tns_fits(int rows, int n_out, int k_in, int nprob) const {
@@ -420,7 +421,7 @@ struct BwdRun {
             SOLA_TRY(launch_colsum_slabs_bf16(ready16, ld, rows, cols, sc, cpart, s));
             if (ready16 == dy16) { cast.src = dY; cast.ld = ld; cast.cols = cols; }
             else cast.kv_src = dY;
-        } else if (may_cast && pure && bf && g_bwd_fused_bf16_cast && g_bwd_dual_cast && ld % 8 == 0 && (size_t)rows * ld <= dy_sp_halfs) {
+        } else if (may_cast && is_bf && g_bwd_fused_bf16_cast && g_bwd_dual_cast && ld % 8 == 0 && (size_t)rows * ld <= dy_sp_halfs) {
             SOLA_TRY(launch_cast_bf16_colsum(dY, ld, ar.get(S_DY_SP), ld, rows, cols, sc, cpart, s));
             cast.src = dY; cast.ld = ld; cast.cols = cols;
         } else {
@@ -469,7 +470,7 @@ struct BwdRun {
             return SOLA_OK;
         }
         GemmTnSplitDesc d{};
-        d.scal = sc; d.pure = pure ? 1 + bf : (dw16 ? 1 : 0); d.rm_split = dw16 ? 1 : 0;
+        d.scal = sc; d.ab = d.b16_fmt = dw_fmt; d.rm_fmt = opfmt;
         if (dy_rm_done && sc && g_bwd_dual_cast) {
             d.a_rm = ar.get(S_DY_SP); d.a_rm_ld = ldy;
             d.a_rm_ready = cast.src && cast.src == g[0].dY && cast.ld == ldy && (g[n - 1].dY - g[0].dY) + n_out <= cast.cols;
@@ -480,7 +481,7 @@ struct BwdRun {
         d.nprob = n; d.M = rows; d.N = n_out; d.K = k_in; d.lda = ldy; d.ldb = ldx;
         for (int j = 0; j < n; ++j) {
             d.A[j] = g[j].dY; d.B[j] = g[j].X; d.C[j] = g[j].dW;
-            if ((pure || dw16) && ldx == k_in) d.B16[j] = c->x16_find(g[j].X, k_in, pure ? 1 + bf : 1);
+            if (is_row16(dw_fmt) && ldx == k_in) d.B16[j] = c->x16_find(g[j].X, k_in, dw_fmt);
         }
         d.scratch = ar.get(S_TNS); d.scratch_bytes = ar.bytes_from(S_TNS);
         // ... and of launch_gemm_tn_split's two routes only the row-major 16-bit kernel does
@@ -515,7 +516,7 @@ struct BwdRun {
                 d.p[0].W = wt;
             }
         }
-        if (split && n_cat % (pure ? 64 : 32) == 0 && ldy % 4 == 0) {
+        if (split && n_cat % k_unit == 0 && ldy % 4 == 0) {
             // dY is cast with a data-dependent power-of-two scale (gradients sit mostly below the f16 normal range), the
             // transposed weights with the fixed 2^6; the epilogue undoes both
             float* sl = sc ? sc : scal;
@@ -524,7 +525,7 @@ struct BwdRun {
                 d.p[0].A = reinterpret_cast<const float*>(kv16 + col_off);
                 d.lda = ldy;
             } else if (cast_done && sc) {
-                d.p[0].A = pure ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(dy_sp) + col_off) : dy_sp + col_off;
+                d.p[0].A = op16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(dy_sp) + col_off) : dy_sp + col_off;
                 d.lda = ldy;
             } else {
                 SOLA_TRY(need16(!dy16_only, "the gradient rows of an input gradient"));
@@ -537,8 +538,8 @@ struct BwdRun {
             if (!cast.wt_sp_ready) SOLA_TRY(cast_fixed(wt, n_cat, ar.get(S_WT_SP), k_in, n_cat, kLinScale));  // else transpose_into wrote the operand itself
             cast.wt_sp_ready = false;
             d.p[0].W = ar.get(S_WT_SP);
-            d.arith = lowp_arith; d.bf16 = bf; d.out_scale = 1.f / kLinScale; d.out_scale_dev = sl + 1;
-            if (c16) d.c_f16 = 1;
+            d.ab = opfmt; d.out_scale = 1.f / kLinScale; d.out_scale_dev = sl + 1;
+            if (c16) d.c = opfmt;
         } else {
             SOLA_TRY(need16(!dy16_only, "the gradient rows of an input gradient"));
             SOLA_ARG(!c16, "backward: a bf16 input gradient needs the 16-bit GEMM");
@@ -553,9 +554,9 @@ struct BwdRun {
             nn_rows = n_out;
             return SOLA_OK;
         }
-        if (split && n_cat % (pure ? 64 : 32) == 0) {  // grad_x's condition for the reduced-precision GEMM: the operand is written directly
+        if (split && n_cat % k_unit == 0) {  // grad_x's condition for the reduced-precision GEMM: the operand is written directly
             cast.wt_sp_ready = true;
-            return launch_transpose_cast(w, ar.get(S_WT_SP), n_out, k_in, k_in, n_cat, col_off, kLinScale, pure ? 1 + bf : 0, s);
+            return launch_transpose_cast(w, ar.get(S_WT_SP), n_out, k_in, k_in, n_cat, col_off, kLinScale, opfmt, s);
         }
         return launch_transpose(w, wt, n_out, k_in, k_in, n_cat, col_off, s);
     }
@@ -622,11 +623,11 @@ struct BwdRun {
         d.C = D; d.groups = c->cfg.n_groups_module;
         site_fill_norm(d, shape.fam[a]);
         if (a == 2 && c->gn2_stats[l]) d.stats_in = fb("l" + std::to_string(l) + "_gn2st");
-        if (a == 0) { d.dy2 = egrad; d.dy2_bf16 = egrad_bf16 ? 1 : 0; }
+        if (a == 0) { d.dy2 = egrad; d.dy2_fmt = egrad_bf16 ? Elem::BF16 : Elem::F32; }
         // dx16 (round 6, bf16 steps): the norm's input gradient once more as bfloat16 rows - the consumer GEMMs' operand, written here instead of
         // by a statistics-and-cast pass that read the f32 matrix back (launch_cast_bf16_colsum); the f32 rows stay (residual stream)
         if (gn16) d.dx16 = dy16;
-        d.x_bf16 = c->site(l, a).res16 ? 1 : 0;
+        d.x_fmt = c->site(l, a).res16 ? Elem::BF16 : Elem::F32;
         return gn_bwd(d, layer_prefix(l) + "norm." + std::to_string(a));
     }
 
@@ -634,8 +635,8 @@ struct BwdRun {
     // *g16_out (bf16 steps, train_bf16_store 3): d(attention output) left the GEMM as bfloat16 rows, which the attention backward reads - the
     // site's q / k / v are bf16 rows, its backward kernels take a bf16 dO, and the GEMM can write it
     int out_proj_bwd(int l, int a, bool* g16_out) {
-        const bool g16 = *g16_out = split && pure && bf && g_train_bf16_store >= 3 && c->site(l, a).qkv16 && attention_bwd_dout_bf16_enabled() &&
-                                    D % 8 == 0 && D % (pure ? 64 : 32) == 0;
+        const bool g16 = *g16_out = split && is_bf && g_train_bf16_store >= 3 && c->site(l, a).qkv16 && attention_bwd_dout_bf16_enabled() &&
+                                    D % 8 == 0 && D % k_unit == 0;
         SOLA_ARG(g16 || !c->site(l, a).o16,
                  "backward: attention output %d of layer %d exists as bf16 rows only, but this backward takes the f32 rows (a switch changed between the forward and the backward)", a, l);
         const std::string an = layer_prefix(l) + kAttnLong[a];
@@ -661,16 +662,16 @@ struct BwdRun {
         ad.drop = c->attn_drop(l, a);
         const bool s16 = *s16_out = split && c->site(l, a).qkv16;
         if (s16) {
-            ad.io_bf16 = 1; ad.dq16 = dy16;
+            ad.io_fmt = Elem::BF16; ad.dq16 = dy16;
             if (a == 2) { ad.dk16 = kv16; ad.dv16 = kv16 + D; cast.kv_src = nullptr; }
             else { ad.dk16 = dy16 + D; ad.dv16 = dy16 + 2 * D; }
             cast.src = nullptr;
-            ad.dout_bf16 = g16 ? 1 : 0;
+            ad.dout_fmt = g16 ? Elem::BF16 : Elem::F32;
             // the forward asked this of the same record (site16); "attn_bwd_fused" / "attn_bwd_small" may have changed since
             SOLA_TRY(need16(attention_bwd_bf16_supported(ad), "q / k / v of an attention site (the attention backward now takes another kernel)"));
             if (g16 && c->site(l, a).o16) {
-                ad.o = static_cast<const float*>(c->x16_find(ab(l, a, "attn"), D, 2));
-                ad.o_bf16 = 1;
+                ad.o = static_cast<const float*>(c->x16_find(ab(l, a, "attn"), D, Elem::BF16));
+                ad.o_fmt = Elem::BF16;
                 SOLA_ARG(ad.o, "backward: the forward kept only the bf16 rows of attention output %d of layer %d, and they are not in the arena", a, l);
             }
         }
@@ -738,7 +739,7 @@ struct BwdRun {
         SOLA_TRY(transpose_into(W(an + ".q_proj.weight"), D, D, 2 * D, 0));
         SOLA_TRY(transpose_into(W(an + ".k_proj.weight"), D, D, 2 * D, D));
         // (bf16 steps, train_bf16_store 3: this branch gradient leaves its GEMM as bfloat16 rows; the inter-object norm's backward adds it as dy2)
-        egrad_bf16 = split && pure && bf && g_train_bf16_store >= 3 && D % 8 == 0 && group_norm_bwd_dy2_bf16_supported(N, D, c->cfg.n_groups_module);
+        egrad_bf16 = split && is_bf && g_train_bf16_store >= 3 && D % 8 == 0 && group_norm_bwd_dy2_bf16_supported(N, D, c->cfg.n_groups_module);
         SOLA_TRY(grad_x(dqkv, 3 * D, M, 2 * D, D, nullptr, egrad, sc3, rm3, 0, egrad_bf16));  // d(x_obj + pe) = dq Wq + dk Wk
         SOLA_TRY(transpose_into(W(an + ".v_proj.weight"), D, D, D, 0));
         SOLA_TRY(grad_x(dqkv + 2 * D, 3 * D, M, D, D, dres, gbuf[1 - cur], sc3, rm3, 2 * D));  // d x_obj (direct) = dres + dv Wv
@@ -818,12 +819,12 @@ struct BwdRun {
         if (tns_fits(e.rows, g.cout, g.k * g.cin, 1)) {
             SOLA_TRY(stats(dy, g.cout, e.rows, g.cout, &e.scc, true, enc_dy16 ? dy16 : nullptr));
             GemmTnSplitDesc d{};
-            d.scal = e.scc; d.pure = pure ? 1 + bf : (dw16 ? 1 : 0); d.rm_split = dw16 ? 1 : 0;
+            d.scal = e.scc; d.ab = d.b16_fmt = dw_fmt; d.rm_fmt = opfmt;
             d.nprob = 1; d.A[0] = dy; d.B[0] = e.x; d.C[0] = dW;
             conv_dw_geom(d, e, p.Tl[i]);
             d.B_rows = e.rows_in;
             if (cast.holds(dy, g.cout, g.cout)) { d.a_rm = ar.get(S_DY_SP); d.a_rm_ld = g.cout; d.a_rm_ready = 1; }
-            if ((pure || dw16) && (i > 0 || (pure && bf))) d.B16[0] = c->x16_find(e.x, g.cin, pure ? 1 + bf : 1);
+            if (is_row16(dw_fmt) && (i > 0 || is_bf)) d.B16[0] = c->x16_find(e.x, g.cin, dw_fmt);
             d.scratch = ar.get(S_TNS); d.scratch_bytes = ar.bytes_from(S_TNS);
             SOLA_TRY(launch_gemm_tn_split(d, s));
             if (e.scc) return bias_from_stats(0, g.cout, db);
@@ -850,9 +851,9 @@ struct BwdRun {
         const ConvGeom& g = e.g;
         const int i = e.i, rows = e.rows;
         const float* const w_std = c->ws_buf + c->ws_off[i];  // [cout][k*cin], where the forward left them
-        auto col2im = [&](const float* zc, int z16 = 0) -> int {
-            if (rt) return launch_col2im_ragged(zc, dact, e.rows_in, rt->imap[i - 1], g.cin, g.k, g.stride, g.pad, s, z16);
-            return launch_col2im(zc, dact, R, e.t_in, p.Tl[i], g.cin, g.k, g.stride, g.pad, s, z16);
+        auto col2im = [&](const float* zc, Elem z_fmt) -> int {
+            if (rt) return launch_col2im_ragged(zc, dact, e.rows_in, rt->imap[i - 1], g.cin, g.k, g.stride, g.pad, z_fmt, s);
+            return launch_col2im(zc, dact, R, e.t_in, p.Tl[i], g.cin, g.k, g.stride, g.pad, z_fmt, s);
         };
         // z = dY W over the OUTPUT rows in one GEMM (every tap's contribution; a strided conv's gather form would multiply zeros for every
         // skipped step), then the k taps are gathered into dX; a k = 1 conv's z is dX
@@ -868,30 +869,29 @@ struct BwdRun {
         nn.w_nn[0] = w_std; nn.w_nn_rows = g.cout;
         if (group && gemm_nn_supported(nn)) {
             SOLA_TRY(launch_gemm(nn, s));
-            return g.k > 1 ? col2im(zcol) : SOLA_OK;
+            return g.k > 1 ? col2im(zcol, Elem::F32) : SOLA_OK;
         }
         if (split && g.cout % 128 == 0 && g.cin % 8 == 0 && (size_t)rows * g.cout <= std::max((size_t)M, (size_t)BW) * 3 * D) {
             float* sl = e.scc ? e.scc : scal;
             if (e.scc && cast.holds(dy, g.cout, g.cout)) {}  // the statistics pass left the cast (bf16)
             else if (e.scc) SOLA_TRY(cast_scaled(dy, g.cout, ar.get(S_DY_SP), rows, g.cout, sl));
             else SOLA_TRY(cast_auto(dy, g.cout, ar.get(S_DY_SP), rows, g.cout, sl));
-            if (pure) SOLA_TRY(launch_cast_f16_t(w_std, g.k * g.cin, ar.get(S_WT_SP), g.cout, g.cout, g.k * g.cin, nullptr, s, bf));
+            if (op16) SOLA_TRY(launch_cast_f16_t(w_std, g.k * g.cin, ar.get(S_WT_SP), g.cout, g.cout, g.k * g.cin, nullptr, opfmt, s));
             else SOLA_TRY(launch_cast_sp16_t(w_std, g.k * g.cin, ar.get(S_WT_SP), g.cout, g.cout, g.k * g.cin, nullptr, s));
             zd.p[0].A = ar.get(S_DY_SP); zd.p[0].W = ar.get(S_WT_SP);
-            zd.arith = lowp_arith; zd.bf16 = bf; zd.out_scale = 1.f; zd.out_scale_dev = sl + 1;
+            zd.ab = opfmt; zd.out_scale = 1.f; zd.out_scale_dev = sl + 1;
             // bf16 steps (train_bf16_store): the per-tap contributions leave the GEMM as bfloat16 rows - the input gradient of a bf16 conv as
             // autocast computes it - and the gather sums the taps in f32: half the bytes written and read between the two launches
-            const int z16 = (pure && bf && g_train_bf16_store >= 3 && g.k > 1 && (g.k * g.cin) % 8 == 0) ? 1 : 0;
-            zd.c_f16 = z16;
+            zd.c = (is_bf && g_train_bf16_store >= 3 && g.k > 1 && (g.k * g.cin) % 8 == 0) ? Elem::BF16 : Elem::F32;
             SOLA_TRY(launch_gemm(zd, s));
-            return g.k > 1 ? col2im(zcol, z16) : SOLA_OK;
+            return g.k > 1 ? col2im(zcol, zd.c) : SOLA_OK;
         }
         if (rt) {  // ragged, exact f32: a plain GEMM on the concatenated rows, then the taps are gathered per sequence
             SOLA_TRY(launch_transpose(w_std, wt, g.cout, g.k * g.cin, g.k * g.cin, g.cout, 0, s));  // wt [k*cin][cout]
             zd.p[0].W = wt;
             zd.splitk_ws = splitk_ws; zd.splitk_bytes = splitk_bytes;
             SOLA_TRY(launch_gemm(zd, s));
-            return g.k > 1 ? col2im(zcol) : SOLA_OK;
+            return g.k > 1 ? col2im(zcol, Elem::F32) : SOLA_OK;
         }
         // uniform, exact f32: the NT kernel with the transposed-conv gather over dY and the weights re-laid-out to [cin][kk*cout + co]
         for (int kk = 0; kk < g.k; ++kk)

@@ -734,9 +734,10 @@ int launch_group_norm_bwd(const GroupNormBwdDesc& d, hipStream_t s) {
     a.inner = d.inner; a.outer_stride = d.outer_stride; a.inner_stride = d.inner_stride; a.tok_stride = d.tok_stride;
     a.ntok = d.ntok; a.C = d.C; a.cg = cg; a.eps = d.eps; a.slope = d.slope; a.leaky = d.leaky; a.drop = d.drop; a.units = d.units;
     a.dx16 = static_cast<unsigned short*>(d.dx16);
-    a.x_bf16 = d.x_bf16;
+    SOLA_ARG(group_norm_bwd_formats_ok(d.x_fmt, d.dy2_fmt), "group_norm_bwd: x and dy2 are f32 or bfloat16 rows (%s, %s)", elem_name(d.x_fmt), elem_name(d.dy2_fmt));
+    a.x_bf16 = d.x_fmt == Elem::BF16;
     a.stats = static_cast<const float2*>(d.stats_in);
-    a.dy2_bf16 = (d.dy2 && d.dy2_bf16) ? 1 : 0;
+    a.dy2_bf16 = (d.dy2 && d.dy2_fmt == Elem::BF16) ? 1 : 0;
     SOLA_ARG(!a.dy2_bf16 || group_norm_bwd_dy2_bf16_supported(d.ntok, d.C, d.groups), "group_norm_bwd: a bfloat16 dy2 is not read by this shape's kernel");
     const double elems = (double)d.n_inst * d.ntok * d.C;
     SolaProfScope prof(SOLA_PROF_NORM, s, 20.0 * elems, (d.dy2 ? 16.0 : 12.0) * elems);

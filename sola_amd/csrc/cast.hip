@@ -347,9 +347,10 @@ static void amax_shape(long long& rows, int& K, int& ld) {
     }
 }
 
-int launch_cast_f16(const float* in, int ld_in, void* out, int ld_out, long long rows, int K, float scale, float* scal, hipStream_t s,
-                    int target_exp, float* scale_out, int bf16) {
-    SOLA_ARG(in && out && rows > 0 && K > 0 && K % 8 == 0 && ld_in % 4 == 0 && ld_out % 8 == 0, "cast_f16: K=%d ld_in=%d ld_out=%d", K, ld_in, ld_out);
+int launch_cast_f16(const float* in, int ld_in, void* out, int ld_out, long long rows, int K, float scale, float* scal, Elem fmt, hipStream_t s,
+                    int target_exp, float* scale_out) {
+    SOLA_ARG(in && out && rows > 0 && K > 0 && K % 8 == 0 && ld_in % 4 == 0 && ld_out % 8 == 0 && is_row16(fmt), "cast_f16: K=%d ld_in=%d ld_out=%d (%s)", K, ld_in, ld_out, elem_name(fmt));
+    const int bf16 = fmt == Elem::BF16;
     const long long n = rows * (K / 8);
     SolaProfScope prof(SOLA_PROF_MISC, s, 0, (scal ? 10.0 : 6.0) * rows * K);
     if (scal) {
@@ -374,8 +375,9 @@ int launch_cast_f16(const float* in, int ld_in, void* out, int ld_out, long long
 }
 
 // the cast half of launch_cast_f16 with a data-dependent scale: scal[0] already holds max|in| (launch_amax_colsum)
-int launch_cast_f16_scaled(const float* in, int ld_in, void* out, int ld_out, long long rows, int K, float* scal, hipStream_t s, int bf16) {
-    SOLA_ARG(in && out && scal && rows > 0 && K > 0 && K % 8 == 0 && ld_in % 4 == 0 && ld_out % 8 == 0, "cast_f16_scaled: K=%d ld_in=%d ld_out=%d", K, ld_in, ld_out);
+int launch_cast_f16_scaled(const float* in, int ld_in, void* out, int ld_out, long long rows, int K, float* scal, Elem fmt, hipStream_t s) {
+    SOLA_ARG(in && out && scal && rows > 0 && K > 0 && K % 8 == 0 && ld_in % 4 == 0 && ld_out % 8 == 0 && is_row16(fmt), "cast_f16_scaled: K=%d ld_in=%d ld_out=%d (%s)", K, ld_in, ld_out, elem_name(fmt));
+    const int bf16 = fmt == Elem::BF16;
     const long long n = rows * (K / 8);
     SolaProfScope prof(SOLA_PROF_MISC, s, 0, 6.0 * rows * K);
     hipLaunchKernelGGL(cast_f16_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, static_cast<_Float16*>(out), rows, K / 8, ld_in, ld_out,
@@ -384,8 +386,9 @@ int launch_cast_f16_scaled(const float* in, int ld_in, void* out, int ld_out, lo
     return SOLA_OK;
 }
 
-int launch_cast_f16_auto_multi(const float* const* in, void* const* out, int n, int rows, int K, float* scal, hipStream_t s, int bf16) {
-    SOLA_ARG(in && out && scal && n > 0 && rows > 0 && K > 0 && K % 8 == 0, "cast_f16_auto_multi: n=%d rows=%d K=%d", n, rows, K);
+int launch_cast_f16_auto_multi(const float* const* in, void* const* out, int n, int rows, int K, float* scal, Elem fmt, hipStream_t s) {
+    SOLA_ARG(in && out && scal && n > 0 && rows > 0 && K > 0 && K % 8 == 0 && is_row16(fmt), "cast_f16_auto_multi: n=%d rows=%d K=%d (%s)", n, rows, K, elem_name(fmt));
+    const int bf16 = fmt == Elem::BF16;
     SolaProfScope prof(SOLA_PROF_MISC, s, 0, 10.0 * n * rows * K);
     SOLA_HIP(hipMemsetAsync(scal, 0, (size_t)2 * n * sizeof(float), s));
     const long long elems = (long long)rows * K;

@@ -31,6 +31,20 @@ void sola_set_error(const char* fmt, ...);
         if (_s != SOLA_OK) return _s; \
     } while (0)
 
+// ---- element formats --------------------------------------------------------------------------------------------------------------
+// The format of a matrix's values, on the HOST side: every descriptor field, launcher parameter and context field that names a format
+// is one of these.  A launcher turns it into its kernel's own flags where it fills the kernel's argument struct; no kernel sees it.
+// SP16 = split-f16 pairs (hi = f16(x), lo = f16(x - hi); [hi8 | lo8] blocks, 4 bytes per value).
+enum class Elem : int { F32 = 0, SP16 = 1, F16 = 2, BF16 = 3 };
+// the values are sola_set_precision's codes (sola_hip.h): the arithmetic of precision p runs on GEMM operands of format Elem(p)
+static_assert((int)Elem::F32 == 0 && (int)Elem::SP16 == 1 && (int)Elem::F16 == 2 && (int)Elem::BF16 == 3, "Elem restates sola_set_precision's codes");
+constexpr Elem operand_format(int precision) { return static_cast<Elem>(precision); }
+constexpr bool is_row16(Elem e) { return e == Elem::F16 || e == Elem::BF16; }  // plain 16-bit rows (pitches count 2-byte values)
+constexpr int elem_bytes(Elem e) { return is_row16(e) ? 2 : 4; }
+constexpr const char* elem_name(Elem e) {
+    return e == Elem::F32 ? "f32" : e == Elem::SP16 ? "split-f16" : e == Elem::F16 ? "f16" : e == Elem::BF16 ? "bf16" : "?";
+}
+
 // ---- in-library event profiler (profile.cpp) -------------------------------------------------------------------
 struct SolaProfScope {
     int cat;

@@ -52,7 +52,7 @@ GemmDesc frame_launch(const GemmDesc& conv, const ConvFrameLaunch& L, const Conv
 bool takes_persist256(const GemmDesc& d) {
     const long long t128 = (long long)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.nprob;
     const bool big = t128 >= 512;
-    return d.arith == 1 && d.ksplit <= 1 && (big || g_gemm_glds_force) && g_gemm_glds && gemm_split_glds_supported(d) &&
+    return d.ab == Elem::SP16 && d.ksplit <= 1 && (big || g_gemm_glds_force) && g_gemm_glds && gemm_split_glds_supported(d) &&
            gemm_split_glds_shape(d) == 4 && g_gemm_persist && d.K / KTILE >= 2;
 }
 
@@ -66,7 +66,7 @@ long long rounds_256(const GemmDesc& d) {
 
 bool conv_frames_plan(const GemmDesc& conv, ConvFramePlan& plan) {
     plan.n = 0;
-    if (conv.conv != 1 || conv.rowmap || conv.arith != 1 || conv.nprob != 1 || conv.p[0].R || conv.ksplit > 1 || conv.gn_gamma) return false;
+    if (conv.conv != 1 || conv.rowmap || conv.ab != Elem::SP16 || conv.nprob != 1 || conv.p[0].R || conv.ksplit > 1 || conv.gn_gamma) return false;
     if (conv.Cin <= 0 || conv.Cin % KTILE != 0 || conv.K % conv.Cin != 0) return false;
     if (conv.T_out < 1 || conv.T_out > 5 || conv.T_in < 1 || conv.stride < 1 || conv.M % conv.T_out != 0) return false;
     const int k = conv.K / conv.Cin;

@@ -68,8 +68,8 @@ struct SolaCtx {
     float* ws_buf = nullptr;  // standardised conv weights [cout][k*cin], all six layers, ctx-owned
     size_t ws_off[6];
     bool ws_dirty = true;
-    int ws16_fmt = 0;         // what ws16_buf holds for the CURRENT ws_buf: 0 nothing / stale, 1 split-f16 pairs, 2 f16, 3 bf16 (a forward in another
-                              // arithmetic clears ws_dirty without writing this copy: round 4, few-row calls routed to exact f32)
+    Elem ws16_fmt = Elem::F32;  // what ws16_buf holds for the CURRENT ws_buf; F32: nothing / stale (a forward in another arithmetic clears
+                                // ws_dirty without writing this copy: round 4, few-row calls routed to exact f32)
     bool ws_every_forward = true;
     Plan last;                // plan of the last forward (taps, backward)
     const float* last_obj = nullptr;  // input of the last training forward (conv0's weight gradient reads it)
@@ -112,7 +112,7 @@ struct SolaCtx {
     // 16-bit operand modes, training: the row-major casts of the forward's GEMM inputs are KEPT (one arena slot each instead of two
     // shared buffers) and listed by their f32 source, so that the backward's weight-gradient products take them as their X operand
     // instead of casting the same activations again (sola_tune "train_x16_keep").  The arena grows between steps to the last need.
-    struct X16Entry { const float* src; const void* p16; int cols; int fmt; };
+    struct X16Entry { const float* src; const void* p16; int cols; Elem fmt; };
     std::vector<X16Entry> x16;
     char* x16_arena = nullptr;  // BORROWED from the caller (sola_set_x16_arena); null = nothing is kept, the backward casts as before
     size_t x16_cap = 0, x16_used = 0, x16_need = 0;  // x16_need: what the last training forward asked for in total (fitting or not)
@@ -124,7 +124,7 @@ struct SolaCtx {
         x16_used += bytes;
         return r;
     }
-    const void* x16_find(const float* src, int cols, int fmt) const {
+    const void* x16_find(const float* src, int cols, Elem fmt) const {
         for (const X16Entry& e : x16)
             if (e.src == src && e.cols == cols && e.fmt == fmt) return e.p16;
         return nullptr;
@@ -186,9 +186,9 @@ constexpr float kLinScale = 64.f;  // backward only (transposed weight casts): l
 // (re)builds the split-f16 copies of the projection weights with a per-matrix power-of-two scale and runs the weight-time
 // range check; no-op unless the copies are stale
 int sola_refresh_lin16(SolaCtx* c, hipStream_t s);
-// (re)standardises the conv weights and casts them into ws16_buf in operand format `fmt` (SolaCtx::ws16_fmt codes) when they
+// (re)standardises the conv weights and casts them into ws16_buf in operand format `fmt` (SP16, F16 or BF16) when they
 // changed, when the policy says every forward, when ws16_buf holds another format, or when `force` is set
-int sola_refresh_conv_weights(SolaCtx* c, int fmt, bool force, hipStream_t s);
+int sola_refresh_conv_weights(SolaCtx* c, Elem fmt, bool force, hipStream_t s);
 // every forward's preamble: all weights set, workspace of at least `need` bytes, 256-byte aligned; `who` prefixes the messages
 int sola_check_forward_args(const SolaCtx* c, const char* who, size_t need, const void* workspace, size_t ws_bytes);
 

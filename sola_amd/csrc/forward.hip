@@ -151,21 +151,21 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     // training forward in the split-f16 mode (sola_set_precision 1): the same GEMM kernels as the inference forward on casts of
     // the f32 activations, everything the backward reads stays f32
     // (from ~1024 token rows on: below that the step is launch-bound and the extra cast launches cost more than the GEMMs gain)
-    // precision 2 ("pure"): the same structure with plain f16 GEMM operands, ONE MFMA per product - mixed-precision training:
+    // precisions 2 / 3: the same structure with plain 16-bit GEMM operands, ONE MFMA per product - mixed-precision training:
     // activations, statistics, softmax, accumulation and everything the backward reads stay f32
-    const bool pure = c->precision >= 2;
-    const int bf = c->precision == 3 ? 1 : 0;  // precision 3: the 16-bit GEMM operands are bfloat16 (training only; BASELINE config C2)
-    const bool split = c->precision >= 1 && D % (pure ? 64 : 32) == 0 && c->cfg.object_token_dim % (pure ? 64 : 32) == 0 && p.M >= g_train_split_min_rows;
-    const int lowp_arith = pure ? 2 : 1;
+    const Elem opfmt = operand_format(c->precision);  // the step's GEMM operand format (BF16: training only; BASELINE config C2)
+    const bool op16 = is_row16(opfmt), is_bf = opfmt == Elem::BF16;
+    const int k_unit = op16 ? 64 : 32;  // reduction lengths are whole k-tiles of the operands' kernels
+    const bool split = opfmt != Elem::F32 && D % k_unit == 0 && c->cfg.object_token_dim % k_unit == 0 && p.M >= g_train_split_min_rows;
     auto cast_auto = [&](const float* in, int ld, float* out, long long rows, int K, float* scal) -> int {
-        return pure ? launch_cast_f16(in, ld, out, K, rows, K, 0.f, scal, s, 13, nullptr, bf) : launch_cast_sp16_auto(in, ld, out, K, rows, K, scal, s);
+        return op16 ? launch_cast_f16(in, ld, out, K, rows, K, 0.f, scal, opfmt, s) : launch_cast_sp16_auto(in, ld, out, K, rows, K, scal, s);
     };
     auto cast_fixed = [&](const float* in, int ld, float* out, long long rows, int K, float scale, void* side16 = nullptr) -> int {
-        return pure ? launch_cast_f16(in, ld, out, K, rows, K, scale, nullptr, s, 13, nullptr, bf) : launch_cast_sp16(in, ld, out, K, rows, K, scale, s, side16);
+        return op16 ? launch_cast_f16(in, ld, out, K, rows, K, scale, nullptr, opfmt, s) : launch_cast_sp16(in, ld, out, K, rows, K, scale, s, side16);
     };
 
     // a1: weight standardisation (module/ws.py:9-13), every training forward
-    SOLA_TRY(sola_refresh_conv_weights(c, split ? (pure ? 2 + bf : 1) : 0, true, s));
+    SOLA_TRY(sola_refresh_conv_weights(c, split ? opfmt : Elem::F32, true, s));
     auto lin_idx = [&](const std::string& attn, int proj) -> int {  // attn = "object_lang_align_layers.<l>.<name>"
         const int l = attn[attn.find('.') + 1] - '0';
         int a3 = 0;
@@ -174,7 +174,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
         return (l * 3 + a3) * 4 + proj;
     };
     auto lin16 = [&](const std::string& attn, int proj) -> const float* {  // split pairs: D*D floats per matrix; plain f16: D*D halfs
-        return pure ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->lin16_buf) + (size_t)lin_idx(attn, proj) * D * D)
+        return op16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->lin16_buf) + (size_t)lin_idx(attn, proj) * D * D)
                     : c->lin16_buf + (size_t)lin_idx(attn, proj) * D * D;
     };
     auto lin_inv = [&](const std::string& attn, int proj) -> const float* { return c->scal_buf + 2 * (2 + lin_idx(attn, proj)) + 1; };
@@ -186,8 +186,8 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     // The split-f16 step ("f16x3") keeps nothing of its split pairs (fetching their hi halves with every other 16-byte chunk slowed the
     // dW kernel's DMA by what the saved casts had cost); its operand casts instead write the hi halves ONCE MORE as plain f16 rows
     // into the arena (side16 below): 2 more bytes per value written here, 6 fewer moved by the backward's X cast.
-    const bool keep16 = split && pure && g_train_x16_keep != 0;
-    const bool side16_on = split && !pure && g_train_x16_keep != 0 && g_train_dw_f16 != 0;
+    const bool keep16 = split && op16 && g_train_x16_keep != 0;
+    const bool side16_on = split && !op16 && g_train_x16_keep != 0 && g_train_dw_f16 != 0;
     // the arena is the CALLER's (sola_set_x16_arena, round 4: an allocation of its own - half of the free device memory at most, grown with a
     // stream sync and a device-wide free inside the training forward - was memory torch's allocator could neither see nor reclaim);
     // what a forward asked for in total is read with sola_x16_arena_info; what does not fit is cast again by the backward as before
@@ -197,13 +197,13 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     auto side16 = [&](const float* src, long long rows, int cols) -> void* {  // f16x3: where the plain-f16 side copy of `src` goes
         if (!side16_on) return nullptr;
         void* q = c->x16_alloc((size_t)rows * cols * 2);
-        if (q) c->x16.push_back(SolaCtx::X16Entry{src, q, cols, 1});
+        if (q) c->x16.push_back(SolaCtx::X16Entry{src, q, cols, Elem::F16});
         return q;
     };
     auto slot16 = [&](int which, const float* src, long long rows, int cols) -> float* {  // the operand cast of `src` goes here
         if (keep16)
             if (void* q = c->x16_alloc((size_t)rows * cols * 2)) {
-                c->x16.push_back(SolaCtx::X16Entry{src, q, cols, 1 + bf});
+                c->x16.push_back(SolaCtx::X16Entry{src, q, cols, opfmt});
                 return static_cast<float*>(q);
             }
         return which ? sp_b : sp_a;
@@ -212,7 +212,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     // a2: encoder (module/module.py:74-96,137-140)
     // Operand casts written by the PRODUCING GroupNorm (GroupNormDesc::y_cast; sola_tune "train_gn_cast" 0 = separate cast launches):
     // the cast of a GEMM input was a launch of its own reading the f32 activation back - 24 of them per step
-    const int gn_fmt = (split && pure && g_train_gn_cast) ? 2 + bf : 0;  // 16-bit operand modes (split pairs: no gain, kernels.h)
+    const Elem gn_fmt = (split && op16 && g_train_gn_cast) ? opfmt : Elem::F32;  // 16-bit operand modes (split pairs: no gain, kernels.h)
     const float* pc_src[2] = {nullptr, nullptr};  // activations whose operand cast already sits in pc_dst (consumed by the next GEMM)
     float* pc_dst[2] = {nullptr, nullptr};
     const float* x = obj;
@@ -229,8 +229,8 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
         gd.T_in = t_in; gd.T_out = p.Tl[i]; gd.stride = g.stride; gd.pad = g.pad; gd.Cin = g.cin;
         if (rs && gd.conv) { gd.rowmap = rt.rowmap[i]; gd.T_in = 1; gd.T_out = 1; }
         gd.splitk_ws = splitk_ws; gd.splitk_bytes = splitk_bytes;
-        if (split && g.cin % (pure ? 64 : 32) == 0) {
-            if (i == 0 && !(pure && bf)) {  // the caller's tokens: data-dependent power-of-two scale (forward_fast.hip); bfloat16 has f32's range -
+        if (split && g.cin % k_unit == 0) {
+            if (i == 0 && !is_bf) {  // the caller's tokens: data-dependent power-of-two scale (forward_fast.hip); bfloat16 has f32's range -
                                             // its cast is the fixed-scale one below, kept for the backward's dW product like every other operand
                 SOLA_TRY(cast_auto(x, g.cin, sp_a, level_rows(i), g.cin, c->scal_pair(0)));
                 gd.out_scale_dev = c->scal_pair(0) + 1;
@@ -243,8 +243,8 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
                 gd.p[0].A = pc_dst[0];
             }
             pc_src[0] = nullptr;
-            gd.p[0].W = pure ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->ws16_buf) + c->ws_off[i]) : c->ws16_buf + c->ws_off[i];
-            gd.arith = lowp_arith; gd.out_scale = 1.f; gd.bf16 = bf;
+            gd.p[0].W = op16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->ws16_buf) + c->ws_off[i]) : c->ws16_buf + c->ws_off[i];
+            gd.ab = opfmt; gd.out_scale = 1.f;
         }
         SOLA_TRY(launch_gemm(gd, s));
         if (i < 5) {
@@ -256,9 +256,9 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
             site_fill_norm(nd, rs ? site_tracks(rt, i + 1) : site_tracks(R, p.Tl[i]));
             nd.C = g.cout; nd.groups = c->cfg.n_groups; nd.eps = 1e-5f; nd.slope = 0.01f; nd.leaky = 1;
             nd.drop = c->enc_drop(i);
-            if (gn_fmt && c->conv[i + 1].cin % 64 == 0) {  // conv i+1 takes the cast from here
+            if (gn_fmt != Elem::F32 && c->conv[i + 1].cin % 64 == 0) {  // conv i+1 takes the cast from here
                 float* dst = slot16(0, nd.y, level_rows(i + 1), g.cout);
-                nd.y_cast = dst; nd.cast_fmt = gn_fmt;
+                nd.y_cast = dst; nd.cast = gn_fmt;
                 pc_src[0] = nd.y; pc_dst[0] = dst;
             }
             SOLA_TRY(launch_group_norm(nd, s));
@@ -311,9 +311,9 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
                 gd.p[j].W = lin16(attn, first_proj + j);
                 gd.p[j].scale_dev = lin_inv(attn, first_proj + j);
             }
-            gd.arith = lowp_arith; gd.out_scale = 1.f; gd.bf16 = bf;
+            gd.ab = opfmt; gd.out_scale = 1.f;
             if (a_scal) gd.out_scale_dev = a_scal + 1;
-            if (c16) gd.c_f16 = 1;
+            if (c16) gd.c = opfmt;
             pc_src[0] = pc_src[1] = nullptr;
         }
         return launch_gemm(gd, s);
@@ -323,7 +323,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     c->reset_sites();
     auto site16 = [&](const AttnDesc& ad, int a) -> bool {
         const bool o2l = a == 2;
-        if (!(split && pure && bf && g_train_bf16_store)) return false;
+        if (!(split && is_bf && g_train_bf16_store)) return false;
         // the backward's dW products of these gradients must take the row-major 16-bit kernel (no f32 copy exists to transpose)
         if (!gemm_tn_tr_supported(M, D, D, D, D) || (o2l && !gemm_tn_tr_supported((int)text_rows, D, D, D, D))) return false;
         // ... and hand its row-major operand to the dX GEMMs: with sola_tune "bwd_dual_cast" 0 grad_w_many / grad_x cast the f32 matrix
@@ -331,8 +331,8 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
         // The backward checks again (BwdRun::need16): a switch may change behind this forward
         if (!g_bwd_dual_cast) return false;
         AttnDesc f = ad;
-        f.in_bf16 = 1;
-        f.o_cast = reinterpret_cast<void*>(1); f.o_cast_fmt = 3;  // (what attention() below hands the launch)
+        f.in = Elem::BF16;
+        f.o_cast = reinterpret_cast<void*>(1); f.cast = Elem::BF16;  // (what attention() below hands the launch)
         if (!attention_in_bf16_supported(f) && !attention_bf16_mfma_supported(f)) return false;
         // the backward's own record of the site (the chunked launch of site 2 gets its scratch there)
         return attention_bwd_bf16_supported(attn_bwd_site_desc(c, p, rs ? &rt : nullptr, a, reinterpret_cast<float*>(1)));
@@ -349,15 +349,15 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
         // measured on the 64-sample ragged mix (same box): f16 operands 22.67 -> 22.55 ms per step (attention +0.10 ms, cast launches -0.26 ms);
         // split pairs + side copy (10 instead of 4 bytes per element out of a latency-bound kernel) 31.76 -> 31.78 ms: no gain, so the
         // split-f16 step keeps its cast launches unless the key is 2
-        if (split && (pure ? g_train_attn_cast != 0 : g_train_attn_cast == 2) && ad.ldo == D) {
+        if (split && (op16 ? g_train_attn_cast != 0 : g_train_attn_cast == 2) && ad.ldo == D) {
             ac_src = ad.o;
             ac_dst = slot16(0, ad.o, M, D);
             ac_side = side16(ad.o, M, D);
-            ad.o_cast = ac_dst; ad.o_side = ac_side; ad.o_cast_fmt = pure ? 2 + bf : 1; ad.o_cast_done = &ac_done;
+            ad.o_cast = ac_dst; ad.o_side = ac_side; ad.cast = opfmt; ad.o_cast_done = &ac_done;
             // bf16 steps (train_bf16_store 3): where the bf16-MFMA kernel writes the out-projection's operand rows itself and they have an arena
             // slot of their own, the f32 rows are not written at all - the out-projection, its weight gradient and the attention backward
             // (D = dO . O) read the bfloat16 rows (4 of the launch's 12 bytes per element)
-            if (o16_site && ad.in_bf16 && g_train_bf16_store >= 3 && ac_dst != sp_a && ac_dst != sp_b && ad.o_cast_fmt == 3 &&
+            if (o16_site && ad.in == Elem::BF16 && g_train_bf16_store >= 3 && ac_dst != sp_a && ac_dst != sp_b && ad.cast == Elem::BF16 &&
                 attention_bf16_mfma_supported(ad) && attention_bwd_dout_bf16_enabled()) {
                 ad.o = nullptr;
                 o16_site->o16 = true;
@@ -375,7 +375,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
         gd.p[0] = GemmProblem{ao, W(attn + ".out_proj.weight"), W(attn + ".out_proj.bias"), resid, res};
         gd.M = M; gd.N = D; gd.K = D; gd.lda = D; gd.ldr = D; gd.ldc = D;
         gd.splitk_ws = splitk_ws; gd.splitk_bytes = splitk_bytes;
-        if (split && r16) { gd.p[0].R = static_cast<const float*>(r16); gd.r_f16 = 1; gd.c_f16 = 1; }
+        if (split && r16) { gd.p[0].R = static_cast<const float*>(r16); gd.r = gd.c = Elem::BF16; }
         if (split) {
             float* dst;
             if (ac_src == ao) {  // attention() reserved the operand's place; the attention kernel wrote it unless its shape cannot
@@ -387,7 +387,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
             }
             ac_src = nullptr;
             gd.p[0].A = dst; gd.p[0].W = lin16(attn, 3); gd.p[0].scale_dev = lin_inv(attn, 3);
-            gd.arith = lowp_arith; gd.out_scale = 1.f; gd.bf16 = bf;
+            gd.ab = opfmt; gd.out_scale = 1.f;
         }
         return launch_gemm(gd, s);
     };
@@ -396,8 +396,8 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     auto gn = [&](const std::string& lp, int l, int idx, const float* res, float* y, float* y2, const RowFamily& units, const float* next_src0,
                   const float* next_src1, bool res_bf16) -> int {
         GroupNormDesc nd{};
-        nd.in_f16 = res_bf16 ? 2 : 0;
-        if (gn_fmt) {
+        nd.in = res_bf16 ? Elem::BF16 : Elem::F32;
+        if (gn_fmt != Elem::F32) {
             const float* nxt[2] = {next_src0, next_src1};
             const long long y_rows = std::max<long long>(M, text_rows);  // the norm's token rows, bounded from above
             for (int e = 0; e < 2; ++e) {
@@ -405,7 +405,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
                 if (nxt[e] == y) { float* dst = slot16(e, y, y_rows, D); nd.y_cast = dst; pc_src[e] = y; pc_dst[e] = dst; }
                 else if (nxt[e] == y2) { float* dst = slot16(e, y2, y_rows, D); nd.y2_cast = dst; pc_src[e] = y2; pc_dst[e] = dst; }
             }
-            nd.cast_fmt = gn_fmt;
+            nd.cast = gn_fmt;
         }
         nd.slice_ws = buf("gn_slots"); nd.slice_ws_bytes = (size_t)p.bufs.at("gn_slots").rows * p.bufs.at("gn_slots").cols * sizeof(float);
         nd.x = res; nd.y = y; nd.y2 = y2; nd.pe = y2 ? buf("pe") : nullptr;
@@ -427,8 +427,8 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
     // the bf16 operand copy of a sub-block's input, if it sits in the kept-operand arena (a shared cast buffer is overwritten before the
     // out-projection runs) - then the sub-block's pre-norm rows are bfloat16 (out_proj / gn above)
     auto resid16 = [&](const float* resid) -> const void* {
-        if (!(split && pure && bf && g_train_bf16_store >= 2 && keep16 && D % 8 == 0)) return nullptr;
-        return c->x16_find(resid, D, 1 + bf);
+        if (!(split && is_bf && g_train_bf16_store >= 2 && keep16 && D % 8 == 0)) return nullptr;
+        return c->x16_find(resid, D, Elem::BF16);
     };
     const SiteShape shape = rs ? site_shape_samples(rt) : site_shape_uniform(B, N, Tp, Wn);
     const float* xin = buf("conv5");
@@ -466,7 +466,7 @@ int sola_forward_train_impl(SolaCtx* c, const float* obj, const float* lang, int
                 SOLA_TRY(linear3(io[a].xq, nullptr, nullptr, an, 1, M, ab(a, "q"), nullptr, nullptr, 0, nullptr, s16));
                 SOLA_TRY(linear3(buf("lang"), buf("lang"), nullptr, an, 2, (int)text_rows, k, v, nullptr, 1, split ? c->scal_pair(1) : nullptr, s16));
             }
-            ad.in_bf16 = s16 ? 1 : 0;
+            ad.in = s16 ? Elem::BF16 : Elem::F32;
             c->site(l, a).qkv16 = s16;
             o16_site = &c->site(l, a);
             SOLA_TRY(attention(ad));

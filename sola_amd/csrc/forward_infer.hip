@@ -52,10 +52,10 @@ int sola_refresh_lin16(SolaCtx* c, hipStream_t s) {
                 in.push_back(w);
                 out.push_back(c->lin16_buf + ((size_t)(l * 3 + a) * 4 + j) * D * D);
             }
-    if (c->precision >= 2) {  // 16-bit storage mode / 16-bit GEMM operands: plain f16 (precision 3: bfloat16) copies, same per-matrix
+    if (const Elem fmt = operand_format(c->precision); is_row16(fmt)) {  // 16-bit storage mode / 16-bit GEMM operands: plain f16 / bfloat16 copies, same per-matrix
         std::vector<void*> outh;  // scales, packed in the first half of the buffer
         for (size_t i = 0; i < out.size(); ++i) outh.push_back(reinterpret_cast<_Float16*>(c->lin16_buf) + i * (size_t)D * D);
-        SOLA_TRY(launch_cast_f16_auto_multi(in.data(), outh.data(), (int)in.size(), D, D, c->scal_pair(2), s, c->precision == 3 ? 1 : 0));
+        SOLA_TRY(launch_cast_f16_auto_multi(in.data(), outh.data(), (int)in.size(), D, D, c->scal_pair(2), fmt, s));
     } else {
         SOLA_TRY(launch_cast_sp16_auto_multi(in.data(), out.data(), (int)in.size(), D, D, c->scal_pair(2), s));
     }
@@ -82,19 +82,19 @@ int sola_refresh_lin16(SolaCtx* c, hipStream_t s) {
 }
 
 // Standardises the conv weights (module/ws.py:9-13) into ws_buf and casts them into ws16_buf in the GEMM operand format `fmt`
-// (the SolaCtx::ws16_fmt codes: 0 = none, 1 = split-f16 pairs, 2 = f16, 3 = bf16).  Runs when the weights changed, on every
-// forward under the reference's policy (ws_every_forward), when ws16_buf holds another format, and always with `force` (the
+// (Elem::F32 = none).  Runs when the weights changed, on every forward
+// under the reference's policy (ws_every_forward), when ws16_buf holds another format, and always with `force` (the
 // training forward).  Standardised rows are unit-variance by construction: the casts take the fixed scale 1.
-int sola_refresh_conv_weights(SolaCtx* c, int fmt, bool force, hipStream_t s) {
-    if (!force && !c->ws_dirty && !c->ws_every_forward && (fmt == 0 || c->ws16_fmt == fmt)) return SOLA_OK;
+int sola_refresh_conv_weights(SolaCtx* c, Elem fmt, bool force, hipStream_t s) {
+    if (!force && !c->ws_dirty && !c->ws_every_forward && (fmt == Elem::F32 || c->ws16_fmt == fmt)) return SOLA_OK;
     WsLayer layers[6];
     for (int i = 0; i < 6; ++i) {
         const std::string nm = "short_motion_encoder." + std::to_string(kConvIdx[i]) + ".weight";
         layers[i] = WsLayer{ctx_weight(c, nm), c->ws_buf + c->ws_off[i], c->conv[i].cout, c->conv[i].cin, c->conv[i].k};
     }
     SOLA_TRY(launch_ws_standardize(layers, 6, s));
-    c->ws16_fmt = 0;  // ws_buf is new: ws16_buf is current once the casts below have rewritten it
-    if (fmt == 1) {
+    c->ws16_fmt = Elem::F32;  // ws_buf is new: ws16_buf is current once the casts below have rewritten it
+    if (fmt == Elem::SP16) {
         // one launch for the six matrices and the packed tap ranges of the per-frame convs (ctx.h: ws_taps): the reference's policy
         // repeats this on every forward, at the head of the step where the queue is empty and each launch is paid in full.  A range
         // starts at a multiple of cin (a multiple of 8), so it is a whole number of 8-value pair groups: the packed copy is the
@@ -114,11 +114,10 @@ int sola_refresh_conv_weights(SolaCtx* c, int fmt, bool force, hipStream_t s) {
         for (size_t i0 = 0; i0 < jobs.size(); i0 += CAST_JOBS_MAX)  // (ten jobs with the default geometry)
             SOLA_TRY(launch_cast_sp16_multi(jobs.data() + i0, (int)std::min<size_t>(CAST_JOBS_MAX, jobs.size() - i0), 1.f, s));
     }
-    for (int i = 0; i < 6 && fmt >= 2; ++i) {
+    for (int i = 0; i < 6 && is_row16(fmt); ++i) {
         const int kc = c->conv[i].k * c->conv[i].cin;
         const float* w = c->ws_buf + c->ws_off[i];
-        SOLA_TRY(launch_cast_f16(w, kc, reinterpret_cast<_Float16*>(c->ws16_buf) + c->ws_off[i], kc, c->conv[i].cout, kc, 1.f, nullptr, s, 13,
-                                 nullptr, fmt == 3 ? 1 : 0));
+        SOLA_TRY(launch_cast_f16(w, kc, reinterpret_cast<_Float16*>(c->ws16_buf) + c->ws_off[i], kc, c->conv[i].cout, kc, 1.f, nullptr, fmt, s));
     }
     c->ws_dirty = false;
     c->ws16_fmt = fmt;
@@ -161,6 +160,7 @@ const char* const kProj[4] = {"q_proj", "k_proj", "v_proj", "out_proj"};
 struct InferBuilder {
     SolaCtx* c;
     hipStream_t s;
+    Elem opfmt;             // the call's operand format: SP16 under precision 1, F16 under precision 2, else F32 (bfloat16 operands are the training step's)
     bool sp, h16, op16;  // split-f16 operands; 16-bit storage; either (activations and weights in a 16-bit operand format)
     int* guard;
     int D, H, DH;
@@ -177,10 +177,12 @@ struct InferBuilder {
     float *lk = nullptr, *lv = nullptr;
 
     InferBuilder(SolaCtx* ctx, hipStream_t stream)
-        : c(ctx), s(stream), sp(ctx->precision == 1), h16(ctx->precision == 2), op16(sp || h16), guard(op16 ? ctx->guard : nullptr),
+        : c(ctx), s(stream), opfmt(ctx->precision == 1 || ctx->precision == 2 ? operand_format(ctx->precision) : Elem::F32), sp(opfmt == Elem::SP16), h16(opfmt == Elem::F16),
+          op16(sp || h16), guard(op16 ? ctx->guard : nullptr),
           D(ctx->cfg.lang_token_dim), H(ctx->cfg.num_heads), DH(D / H), scale(1.0f / sqrtf((float)DH)) {}
 
     const float* W(const std::string& name) const { return ctx_weight(c, name); }
+    Elem stored(bool on) const { return on ? opfmt : Elem::F32; }  // an activation kept in the mode's 16-bit storage, or f32 rows
 
     int check_mode() const {
         if (sp)
@@ -203,7 +205,7 @@ struct InferBuilder {
     // The projection weights are used as they are by the reference (no per-forward transform), so their 16-bit copies are
     // refreshed only when a weight pointer or value changed (sola_set_weight / sola_weights_changed).
     int prepare_weights() const {
-        SOLA_TRY(sola_refresh_conv_weights(c, sp ? 1 : (h16 ? 2 : 0), false, s));
+        SOLA_TRY(sola_refresh_conv_weights(c, opfmt, false, s));
         if (op16) {
             SOLA_TRY(sola_refresh_lin16(c, s));
             SOLA_HIP(hipMemsetAsync(c->guard, 0, sizeof(int), s));  // per-call range guard word (ctx.h)
@@ -239,11 +241,11 @@ struct InferBuilder {
     int cast_obj(const float* obj, float* obj_sp, long long rows) const {
         const int d_in = c->cfg.object_token_dim;
         if (sp) return launch_cast_sp16_auto(obj, d_in, obj_sp, d_in, rows, d_in, c->scal_pair(0), s);
-        return launch_cast_f16(obj, d_in, obj_sp, d_in, rows, d_in, 256.f, c->scal_pair(0), s, 6, c->scal_extra(0));
+        return launch_cast_f16(obj, d_in, obj_sp, d_in, rows, d_in, 256.f, c->scal_pair(0), opfmt, s, 6, c->scal_extra(0));
     }
     int cast_lang(const float* lang, float* lang_sp, long long rows) const {
         if (sp) return launch_cast_sp16_auto(lang, D, lang_sp, D, rows, D, c->scal_pair(1), s);
-        return launch_cast_f16(lang, D, lang_sp, D, rows, D, 1.f, c->scal_pair(1), s, 6);
+        return launch_cast_f16(lang, D, lang_sp, D, rows, D, 1.f, c->scal_pair(1), opfmt, s, 6);
     }
     const float* lang_inv_scale() const { return op16 ? c->scal_pair(1) + 1 : nullptr; }  // undone by the text-side projections
 
@@ -251,7 +253,8 @@ struct InferBuilder {
     GemmDesc gemm(long long rows, int N, int K) const {
         GemmDesc gd{};
         gd.M = (int)rows; gd.N = N; gd.K = K; gd.ldc = N;
-        if (op16) { gd.arith = sp ? 1 : 2; gd.out_scale = 1.f; }
+        gd.ab = opfmt;
+        if (op16) gd.out_scale = 1.f;
         gd.splitk_ws = splitk_ws; gd.splitk_bytes = splitk_bytes;
         return gd;
     }
@@ -269,11 +272,11 @@ struct InferBuilder {
         gd.stride = g.stride; gd.pad = g.pad; gd.Cin = g.cin;
         gd.guard = guard;
         if (sp) {
-            gd.c_sp16 = i == 5 ? 1 : 0;
+            gd.c = stored(i == 5);
             if (i == 0) gd.out_scale_dev = c->scal_pair(0) + 1;
         }
         if (h16) {
-            gd.c_f16 = 1;
+            gd.c = opfmt;
             if (i == 0) gd.bias_scale_dev = c->scal_extra(0);
         }
         return gd;
@@ -296,10 +299,10 @@ struct InferBuilder {
         }
         return launch_gemm(gd, s);
     }
-    // nprob projections first_proj.. of one attention in one launch.  out_sp16: split-f16 q/k/v for the split attention kernel
+    // nprob projections first_proj.. of one attention in one launch.  out_sp: split-f16 q/k/v for the split attention kernel
     // (the 16-bit storage mode writes f16 always, f32 ignores it)
     int linear3(const float* a0, const float* a1, const float* a2, int layer, int attn_i, int nprob, long long rows, float* o0, float* o1,
-                float* o2, int first_proj, int out_sp16, const float* a_inv_scale = nullptr) const {
+                float* o2, int first_proj, bool out_sp, const float* a_inv_scale = nullptr) const {
         const float* as[3] = {a0, a1, a2};
         float* os[3] = {o0, o1, o2};
         GemmDesc gd = gemm(rows, D, D);
@@ -308,8 +311,7 @@ struct InferBuilder {
         gd.lda = D;
         gd.guard = guard;
         if (op16) gd.out_scale_dev = a_inv_scale;
-        if (sp) gd.c_sp16 = out_sp16;
-        if (h16) gd.c_f16 = 1;
+        gd.c = h16 ? opfmt : stored(sp && out_sp);
         return launch_gemm(gd, s);
     }
     // res = attn * W_out^T + bias + resid; every residual of the path is in the mode's operand format
@@ -318,43 +320,43 @@ struct InferBuilder {
         gd.nprob = 1;
         gd.p[0] = lin_problem(attn, layer, attn_i, 3, resid, res);
         gd.lda = D; gd.ldr = D;
-        if (sp) gd.r_sp16 = 1;
-        if (h16) { gd.r_f16 = 1; gd.c_f16 = 1; gd.guard = guard; }
+        gd.r = opfmt;
+        if (h16) { gd.c = opfmt; gd.guard = guard; }
         return launch_gemm(gd, s);
     }
 
     // ---- GroupNorms.  out16: y / y2 in the mode's 16-bit storage (split pairs or f16); f32 ignores it
-    GroupNormDesc norm(const std::string& name, const float* x, float* y, int C, int groups, int out16) const {
+    GroupNormDesc norm(const std::string& name, const float* x, float* y, int C, int groups, bool out16) const {
         GroupNormDesc nd{};
         nd.slice_ws = gn_slots; nd.slice_ws_bytes = gn_slots_bytes;
         nd.x = x; nd.y = y;
         nd.gamma = W(name + ".weight"); nd.beta = W(name + ".bias");
         nd.C = C; nd.groups = groups; nd.eps = 1e-5f;
         nd.guard = guard;
-        if (sp) nd.out_sp16 = out16;
-        if (h16) { nd.in_f16 = 1; nd.out_f16 = out16; }
+        nd.out = stored(out16);
+        if (h16) nd.in = opfmt;
         return nd;
     }
     GroupNormDesc encoder_norm(int i, const float* x, float* y) const {
-        GroupNormDesc nd = norm("short_motion_encoder." + std::to_string(kNormIdx[i]), x, y, c->conv[i].cout, c->cfg.n_groups, 1);
+        GroupNormDesc nd = norm("short_motion_encoder." + std::to_string(kNormIdx[i]), x, y, c->conv[i].cout, c->cfg.n_groups, true);
         nd.slope = 0.01f; nd.leaky = 1;
         if (h16 && i == 0) nd.in_scale_dev = c->scal_pair(0) + 1;  // conv0's output is in the scaled units of the tokens
         return nd;
     }
-    GroupNormDesc layer_norm(int layer, int idx, float* y, float* y2, int out16) const {  // y2: optional y + positional encoding
+    GroupNormDesc layer_norm(int layer, int idx, float* y, float* y2, bool out16) const {  // y2: optional y + positional encoding
         GroupNormDesc nd = norm("object_lang_align_layers." + std::to_string(layer) + ".norm." + std::to_string(idx), res, y, D,
                                 c->cfg.n_groups_module, out16);
         nd.y2 = y2; nd.pe = y2 ? pe : nullptr;
         return nd;
     }
 
-    // ---- attention.  in_sp16: q/k/v left the projection GEMM as split pairs
-    AttnDesc attention(const float* q, const float* k, const float* v, int in_sp16) const {
+    // ---- attention.  in_sp: q/k/v left the projection GEMM as split pairs
+    AttnDesc attention(const float* q, const float* k, const float* v, bool in_sp) const {
         AttnDesc ad{};
         ad.q = q; ad.k = k; ad.v = v; ad.o = attn;
         ad.ldq = ad.ldk = ad.ldv = ad.ldo = D;
         ad.H = H; ad.DH = DH; ad.scale = scale;
-        ad.o_sp16 = sp ? 1 : 0; ad.in_sp16 = in_sp16; ad.split_math = sp ? 1 : 0;
+        ad.in = h16 ? opfmt : stored(sp && in_sp); ad.out = opfmt; ad.split_math = sp ? 1 : 0;
         ad.guard = guard;
         return ad;
     }
@@ -366,8 +368,8 @@ struct InferBuilder {
     // (tools/attn_probe.py): with <= 64 keys per unit the exact-f32 MFMA kernel is as fast or faster (bound by latency and LDS traffic, not
     // by the matrix pipe); with 65..128 keys the split shape wins by 14 %.  Never the packed short-sequence shape (uniform: > 16 keys).
     int sub_block(int layer, int a, const SiteGeom& g, long long rows, const float* xq, const float* xk, const float* xv, const float* resid,
-                  float* y, float* y2, int out16) const {
-        const int in_sp = (sp && g.k.len > g_attn_split_min_keys && (a == 2 || g.q.units || g.k.len > 16) && DH % 16 == 0) ? 1 : 0;
+                  float* y, float* y2, bool out16) const {
+        const bool in_sp = sp && g.k.len > g_attn_split_min_keys && (a == 2 || g.q.units || g.k.len > 16) && DH % 16 == 0;
         if (a < 2) {
             SOLA_TRY(linear3(xq, xk, xv, layer, a, 3, rows, q, k, v, 0, in_sp));
         } else {
@@ -433,10 +435,10 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
         bool fused_norm = false;
         if (sp && i < 5) {
             GemmDesc probe = gd;
-            probe.c_sp16 = 1;
+            probe.c = Elem::SP16;
             if (gemm_gn_fusable(probe, c->conv[i].cout / c->cfg.n_groups, p.Tl[i])) {
                 const std::string np = "short_motion_encoder." + std::to_string(kNormIdx[i]);
-                gd.c_sp16 = 1;
+                gd.c = Elem::SP16;
                 gd.p[0].C = buf("act" + is);
                 gd.gn_gamma = b.W(np + ".weight"); gd.gn_beta = b.W(np + ".bias");
                 gd.gn_tokens = p.Tl[i]; gd.gn_eps = 1e-5f; gd.gn_slope = 0.01f;

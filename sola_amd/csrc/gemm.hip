@@ -618,13 +618,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void gemm_nt_f32_small_ke
 int g_gemm_small_rows = 2048;  // sola_tune "gemm_small_rows": exact-f32 GEMMs of at most this many rows take the 32x32 in-block split-K shape (0 = never)
 namespace {
 static bool gemm_small_applies(const GemmDesc& d) {
-    if (d.r_sp16 || d.c_sp16 || d.gn_gamma) return false;  // the kernel reads R and writes C as plain f32 rows, no fused norm
+    if (d.r != Elem::F32 || d.c != Elem::F32 || d.gn_gamma) return false;  // the kernel reads R and writes C as plain f32 rows, no fused norm
     if (d.w_nn_rows) {  // NN form: one problem, plain rows, whole 32-row steps inside each stacked matrix, 16-byte aligned rows
         if (d.nprob != 1 || d.conv || d.w_nn_rows % 32 != 0 || d.K % d.w_nn_rows != 0 || d.K / d.w_nn_rows > 3 || d.N % 4 != 0) return false;
         for (int j = 0; j < d.K / d.w_nn_rows; ++j)
             if (!d.w_nn[j] || (reinterpret_cast<uintptr_t>(d.w_nn[j]) & 15)) return false;
     }
-    if (d.arith != 0 || d.conv > 1 || d.M > g_gemm_small_rows || d.N % 32 != 0 || d.K % 128 != 0 || d.ldc % 4 != 0) return false;
+    if (d.ab != Elem::F32 || d.conv > 1 || d.M > g_gemm_small_rows || d.N % 32 != 0 || d.K % 128 != 0 || d.ldc % 4 != 0) return false;
     if (d.conv ? (d.Cin % 32 != 0 || d.K % d.Cin != 0 || d.K / d.Cin > 8 || (!d.rowmap && (d.T_out <= 0 || d.T_in <= 0))) : d.lda % 4 != 0) return false;
     for (int j = 0; j < d.nprob; ++j) {
         if (d.p[j].R && d.ldr % 4 != 0) return false;
@@ -727,13 +727,14 @@ int launch_gemm(const GemmDesc& d, hipStream_t s) {
     } else {
         SOLA_ARG(d.lda % 4 == 0, "gemm: lda %d must be a multiple of 4", d.lda);
     }
+    SOLA_ARG(gemm_formats_ok(d.ab, d.r, d.c), "gemm: no kernel for %s operands with a %s residual and a %s output", elem_name(d.ab), elem_name(d.r), elem_name(d.c));
     GemmArgs a;
     gemm_fill_common(a, d);
     a.tiles_m = a.tiles_n = a.xcd_remap = 0;
-    a.out_scale = d.arith >= 1 && d.out_scale != 0.f ? d.out_scale : 1.f;
-    a.out_scale_dev = d.arith >= 1 ? d.out_scale_dev : nullptr;
-    a.r_sp16 = d.r_sp16;
-    a.c_sp16 = d.arith == 1 ? d.c_sp16 : 0;
+    a.out_scale = d.ab != Elem::F32 && d.out_scale != 0.f ? d.out_scale : 1.f;
+    a.out_scale_dev = d.ab != Elem::F32 ? d.out_scale_dev : nullptr;
+    a.r_sp16 = d.r == Elem::SP16;
+    a.c_sp16 = d.c == Elem::SP16;
     a.ksplit = 1; a.kt_per = 0; a.part = nullptr;
     a.guard = a.c_sp16 ? d.guard : nullptr;
     for (int j = 0; j < 3; ++j) a.w_nn[j] = d.w_nn_rows ? d.w_nn[j] : nullptr;
@@ -742,27 +743,27 @@ int launch_gemm(const GemmDesc& d, hipStream_t s) {
     SOLA_ARG(!a.c_sp16 || (d.N % 8 == 0 && d.ldc % 8 == 0), "gemm: split-f16 output needs N %% 8 == 0 and ldc %% 8 == 0");
     const long long t128 = (long long)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.nprob;
     const bool big = t128 >= 512;  // two 128x128 blocks per CU x 256 CUs
-    if (d.arith == 2) {  // plain f16 operands: direct-to-LDS kernels for every grid size
+    if (is_row16(d.ab)) {  // plain 16-bit operands: direct-to-LDS kernels for every grid size
         SOLA_ARG(gemm_split_glds_supported(d), "f16 gemm: K %% 64, row pitch %% 16 (Cin %% 64 for convs) required; K=%d lda=%d Cin=%d", d.K, d.lda, d.Cin);
-        SOLA_ARG(!d.c_f16 || (d.N % 4 == 0 && d.ldc % 4 == 0), "f16 gemm: f16 output needs N %% 4 == 0 and ldc %% 4 == 0");
-        SOLA_ARG(!d.p[0].R || !d.r_f16 || d.ldr % 4 == 0, "f16 gemm: f16 residual needs ldr %% 4 == 0");
+        SOLA_ARG(!is_row16(d.c) || (d.N % 4 == 0 && d.ldc % 4 == 0), "f16 gemm: f16 output needs N %% 4 == 0 and ldc %% 4 == 0");
+        SOLA_ARG(!d.p[0].R || !is_row16(d.r) || d.ldr % 4 == 0, "f16 gemm: f16 residual needs ldr %% 4 == 0");
         SolaProfScope prof(d.ksplit > 1 || gemm_split_glds_shape(d) == 4 ? SOLA_PROF_GEMM_SPLIT256 : SOLA_PROF_GEMM_SPLIT, s, 2.0 * d.M * d.N * (double)d.K * d.nprob,
                            2.0 * d.nprob * ((double)d.M * d.K + (double)d.N * d.K + (double)d.M * d.N));
         if (d.ksplit > 1) {  // weight gradients (gemm_tn_split.hip): K ranges as work items of the persistent kernel + ordered reduce
-            SOLA_ARG(d.splitk_ws && d.K % (64 * d.ksplit) == 0 && d.K / 64 / d.ksplit >= 2 && d.N % 4 == 0 && d.ldc % 4 == 0 && !d.c_f16 &&
+            SOLA_ARG(d.splitk_ws && d.K % (64 * d.ksplit) == 0 && d.K / 64 / d.ksplit >= 2 && d.N % 4 == 0 && d.ldc % 4 == 0 && !is_row16(d.c) &&
                          d.splitk_bytes >= (size_t)d.nprob * d.ksplit * d.M * d.N * sizeof(float),
                      "f16 gemm: split-K over %d ranges needs K %% (64 * ksplit) == 0 (K=%d) and a scratch of nprob*ksplit*M*N floats", d.ksplit, d.K);
             return launch_split_glds_reduce(a, d, s);
         }
         return launch_gemm_split_glds(d, s);
     }
-    const bool glds = d.arith == 1 && (big || g_gemm_glds_force || d.ksplit > 1) && g_gemm_glds && gemm_split_glds_supported(d);
-    const int cat = d.arith == 1 ? (glds && gemm_split_glds_shape(d) == 4 ? (d.gn_gamma ? SOLA_PROF_GEMM_SPLIT256_GN : SOLA_PROF_GEMM_SPLIT256) : SOLA_PROF_GEMM_SPLIT)
+    const bool glds = d.ab == Elem::SP16 && (big || g_gemm_glds_force || d.ksplit > 1) && g_gemm_glds && gemm_split_glds_supported(d);
+    const int cat = d.ab == Elem::SP16 ? (glds && gemm_split_glds_shape(d) == 4 ? (d.gn_gamma ? SOLA_PROF_GEMM_SPLIT256_GN : SOLA_PROF_GEMM_SPLIT256) : SOLA_PROF_GEMM_SPLIT)
                                  : (big ? SOLA_PROF_GEMM : SOLA_PROF_GEMM_SMALL);
     SolaProfScope prof(cat, s, 2.0 * d.M * d.N * (double)d.K * d.nprob,
                        4.0 * d.nprob * ((double)d.M * d.K + (double)d.N * d.K + (double)d.M * d.N));
     if (gemm_small_applies(d)) return launch_small(a, d.nprob, s);
-    if (d.arith == 0 && big && gemm_f32_persist_applies(d)) return launch_gemm_f32_persist(d, s);
+    if (d.ab == Elem::F32 && big && gemm_f32_persist_applies(d)) return launch_gemm_f32_persist(d, s);
     const int pipe = g_gemm_variant < 0 ? (big ? 0 : 1) : g_gemm_variant;
     // small grids (fewer 64x64 tiles than CUs, the single-sample regime): split K over up to 8 blocks per tile so the
     // serial k-loop gets ~8x shorter; partial sums go through the caller's scratch and are reduced in a fixed order
@@ -788,7 +789,7 @@ int launch_gemm(const GemmDesc& d, hipStream_t s) {
     }
     if (glds) return launch_gemm_split_glds(d, s);
     SOLA_ARG(!d.gn_gamma, "gemm: the fused GroupNorm epilogue needs the persistent direct-to-LDS kernel (check gemm_gn_fusable)");
-    if (d.arith == 1) {
+    if (d.ab == Elem::SP16) {
         SOLA_ARG(d.K % 16 == 0 && (d.conv ? d.Cin % 8 == 0 : d.lda % 8 == 0), "split-f16 gemm: K %% 16 and row pitch %% 8 required");
         if (big) return pipe ? launch_tile<128, 128, 1, 1>(a, d.nprob, s) : launch_tile<128, 128, 0, 1>(a, d.nprob, s);
         return pipe ? launch_tile<64, 64, 1, 1>(a, d.nprob, s) : launch_tile<64, 64, 0, 1>(a, d.nprob, s);

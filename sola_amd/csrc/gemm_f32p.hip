@@ -489,7 +489,7 @@ int g_gemm_f32_persist = 1;  // sola_tune "gemm_f32_persist": 0 = the 128x128 on
 // Shapes the persistent kernel takes: plain rows or the conv window gather (not the transposed-conv gather), 16-byte rows, whole k-tiles,
 // and a grid whose rounds of one 256x128 tile per CU are at least as full as the 128x128 kernel's rounds of two blocks per CU.
 bool gemm_f32_persist_applies(const GemmDesc& d) {
-    if (!g_gemm_f32_persist || d.arith != 0 || d.conv > 1 || d.K % (4 * PBK) != 0) return false;  // whole groups of four k-tiles
+    if (!g_gemm_f32_persist || d.ab != Elem::F32 || d.conv > 1 || d.K % (4 * PBK) != 0) return false;  // whole groups of four k-tiles
     if (d.conv == 1 ? (d.Cin % PBK != 0 || d.K % d.Cin != 0 || d.K / d.Cin > 8) : d.lda % 4 != 0) return false;
     for (int j = 0; j < d.nprob; ++j) {
         if ((reinterpret_cast<uintptr_t>(d.p[j].A) | reinterpret_cast<uintptr_t>(d.p[j].W) | reinterpret_cast<uintptr_t>(d.p[j].C) | reinterpret_cast<uintptr_t>(d.p[j].R)) & 15) return false;

@@ -38,7 +38,7 @@
 
 namespace {
 
-// PURE = plain f16 operands (GemmDesc::arith 2): the same 128-byte tile rows now hold 64 consecutive halfs instead of 32
+// PURE = plain 16-bit operands (GemmDesc::ab F16 / BF16): the same 128-byte tile rows now hold 64 consecutive halfs instead of 32
 // (hi, lo) pairs, so nothing about the DMA, the swizzle or the fragment reads changes - a "hi" chunk is simply halfs
 // 16j..16j+7 of the row and the "lo" chunk halfs 16j+8..16j+15 - and a product is hi*hi + lo*lo (two consecutive k-chunks,
 // the same permutation of k on both operands) instead of lo*hi + hi*lo + hi*hi: a third of the MFMAs for twice the k.
@@ -941,11 +941,11 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_split_glds_persist_kernel(con
 }  // namespace
 
 bool gemm_split_glds_supported(const GemmDesc& d) {
-    if (d.arith == 2) {  // plain f16 rows: sizes in halfs, two per 4-byte unit
+    if (is_row16(d.ab)) {  // plain 16-bit rows: sizes in halfs, two per 4-byte unit
         if (d.K % (2 * GBK) != 0 || d.conv == 2) return false;
         return d.conv == 1 ? d.Cin % (2 * GBK) == 0 : d.lda % 16 == 0;
     }
-    if (d.arith != 1 || d.K % GBK != 0 || d.conv == 2) return false;
+    if (d.ab != Elem::SP16 || d.K % GBK != 0 || d.conv == 2) return false;
     if (d.conv == 1) return d.Cin % GBK == 0;
     return d.lda % 8 == 0;
 }
@@ -1100,7 +1100,7 @@ bool gemm_gn_fusable(const GemmDesc& d, int channels_per_group, int tokens) {
 #ifndef SOLA_EXPERIMENTS
     return false;  // round 5: closed (bit-repeatable over 500 forwards, but no gain: the epilogue's arithmetic costs the power-bound launch what the norm's pass saved - profiles/r05_gnf_decision.txt)
 #endif
-    return g_gemm_gn_fuse && g_gemm_persist && d.arith == 1 && d.nprob == 1 && !d.p[0].R && d.ksplit <= 1 && d.M % 256 == 0 && d.N % 256 == 0 &&
+    return g_gemm_gn_fuse && g_gemm_persist && d.ab == Elem::SP16 && d.nprob == 1 && !d.p[0].R && d.ksplit <= 1 && d.M % 256 == 0 && d.N % 256 == 0 &&
            d.K / GBK >= 2 && channels_per_group == 64 && (tokens == 4 || tokens == 8 || tokens == 16) && (d.ldc & 7) == 0 &&
            gemm_split_glds_supported(d) && gemm_split_glds_shape(d) == 4;
 }
@@ -1111,28 +1111,27 @@ int launch_gemm_split_glds(const GemmDesc& d, hipStream_t s) {
     a.r_f16 = a.c_f16 = 0;
     a.bf16 = 0;
     a.bias_scale_dev = d.bias_scale_dev;
-    if (d.arith == 2) {  // plain f16 (or bf16) operand rows: the kernels address A and W in 4-byte units of two 16-bit values
+    if (is_row16(d.ab)) {  // plain f16 (or bf16) operand rows: the kernels address A and W in 4-byte units of two 16-bit values
         a.K = d.K / 2; a.lda = d.lda / 2; a.Cin = d.Cin / 2;
-        a.r_f16 = d.r_f16; a.c_f16 = d.c_f16;
-        a.bf16 = d.bf16 ? 1 : 0;
-        SOLA_ARG(!(a.bf16 && a.r_f16 && !a.c_f16), "gemm: a bf16 residual goes with a bf16 output");
+        a.r_f16 = is_row16(d.r); a.c_f16 = is_row16(d.c);  // (the operands' format: gemm_formats_ok)
+        a.bf16 = d.ab == Elem::BF16;
     }
     a.out_scale = d.out_scale != 0.f ? d.out_scale : 1.f;
     a.out_scale_dev = d.out_scale_dev;
-    a.r_sp16 = d.r_sp16;
-    a.c_sp16 = d.c_sp16;
+    a.r_sp16 = d.r == Elem::SP16;
+    a.c_sp16 = d.c == Elem::SP16;
     a.nprob = d.nprob;
     a.ablate = g_gemm_ablate;
     a.stagger = g_gemm_stagger; a.order = g_gemm_order; a.trace = nullptr;
-    if (a.stagger == 0 && d.arith == 2 && d.bf16 && g_gemm_slack_stagger > 0) a.stagger = -g_gemm_slack_stagger;
-    a.guard = (d.c_sp16 || d.c_f16) ? d.guard : nullptr;
+    if (a.stagger == 0 && d.ab == Elem::BF16 && g_gemm_slack_stagger > 0) a.stagger = -g_gemm_slack_stagger;
+    a.guard = d.c != Elem::F32 ? d.guard : nullptr;
     a.gn_gamma = d.gn_gamma; a.gn_beta = d.gn_beta; a.gn_tokens = d.gn_tokens; a.gn_eps = d.gn_eps; a.gn_slope = d.gn_slope;
     a.gn_icnt = d.gn_tokens > 0 ? 1.0f / (64.0f * (float)d.gn_tokens) : 0.f;
     a.ksplit = d.ksplit > 1 ? d.ksplit : 1;
     a.kper = a.K / GBK / a.ksplit;
     a.part = d.splitk_ws;
     const int shape = gemm_split_glds_shape(d);
-    if (d.arith == 2) return d.conv == 1 ? launch_shape_pure<true>(a, shape, d.M, d.N, d.nprob, s) : launch_shape_pure<false>(a, shape, d.M, d.N, d.nprob, s);
+    if (is_row16(d.ab)) return d.conv == 1 ? launch_shape_pure<true>(a, shape, d.M, d.N, d.nprob, s) : launch_shape_pure<false>(a, shape, d.M, d.N, d.nprob, s);
     return d.conv == 1 ? launch_shape<true>(a, shape, d.M, d.N, d.nprob, s) : launch_shape<false>(a, shape, d.M, d.N, d.nprob, s);
 }
 

@@ -556,12 +556,12 @@ int launch_transpose(const float* in, float* out, int rows, int cols, int ldi, i
     return SOLA_OK;
 }
 
-int launch_transpose_cast(const float* in, void* out, int rows, int cols, int ldi, int ldo, int col_off, float scale, int fmt, hipStream_t s) {
-    SOLA_ARG(in && out && rows > 0 && cols > 0 && fmt >= 0 && fmt <= 2 && (fmt != 0 || ldo % 8 == 0), "transpose_cast: bad arguments (fmt %d ldo %d)", fmt, ldo);
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, (fmt == 0 ? 8.0 : 6.0) * rows * cols);
+int launch_transpose_cast(const float* in, void* out, int rows, int cols, int ldi, int ldo, int col_off, float scale, Elem fmt, hipStream_t s) {
+    SOLA_ARG(in && out && rows > 0 && cols > 0 && fmt != Elem::F32 && (fmt != Elem::SP16 || ldo % 8 == 0), "transpose_cast: bad arguments (%s ldo %d)", elem_name(fmt), ldo);
+    SolaProfScope prof(SOLA_PROF_MISC, s, 0, (fmt == Elem::SP16 ? 8.0 : 6.0) * rows * cols);
     const dim3 grid((cols + 31) / 32, (rows + 31) / 32);
-    if (fmt == 0) hipLaunchKernelGGL(transpose_cast_kernel<0>, grid, dim3(256), 0, s, in, out, rows, cols, ldi, ldo, col_off, scale);
-    else if (fmt == 1) hipLaunchKernelGGL(transpose_cast_kernel<1>, grid, dim3(256), 0, s, in, out, rows, cols, ldi, ldo, col_off, scale);
+    if (fmt == Elem::SP16) hipLaunchKernelGGL(transpose_cast_kernel<0>, grid, dim3(256), 0, s, in, out, rows, cols, ldi, ldo, col_off, scale);
+    else if (fmt == Elem::F16) hipLaunchKernelGGL(transpose_cast_kernel<1>, grid, dim3(256), 0, s, in, out, rows, cols, ldi, ldo, col_off, scale);
     else hipLaunchKernelGGL(transpose_cast_kernel<2>, grid, dim3(256), 0, s, in, out, rows, cols, ldi, ldo, col_off, scale);
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;

@@ -6,7 +6,7 @@
 // one persistent-kernel work item each, and gemm.hip's splitk_reduce_kernel folds the partial sums in a fixed order.
 // dY is a gradient (entries ~1e-4..1e-9): it is scaled by a data-dependent power of two found on the device
 // (cast.hip's amax pass; all problems of a launch share the scale), undone by the GEMM's out_scale_dev.
-// Second route (round 3, the default for 16-bit operands - GemmTnSplitDesc::pure - when N and K are multiples of 256): NO transposed
+// Second route (round 3, the default for 16-bit operands - GemmTnSplitDesc::ab F16 / BF16 - when N and K are multiples of 256): NO transposed
 // copies.  The operands are cast ROW-MAJOR (dY's cast is the dX GEMM's operand anyway, X's comes from the training forward's kept
 // casts or one plain cast; convs: one cast of the conv input) and gemm_tn_tr.hip's gemm_tn_tr_kernel transposes them in its LDS reads.
 #include <algorithm>
@@ -27,7 +27,7 @@ __device__ __forceinline__ float auto_scale_t(unsigned amax_bits) {  // as cast.
 // With rowmap != null (ragged batches) row m reads source row rowmap[m].x + tap, zeros where bit `tap` of rowmap[m].y is clear.
 // With conv_T_out > 0 the input is the implicit im2col of a channels-last conv for ONE tap: row m = (r, to) reads source row
 // r * conv_T_in + to * conv_stride + conv_toff (tap - pad), zeros outside [0, conv_T_in).
-// PURE: the output is plain _Float16 ([cols][ld_out halfs]) for the one-MFMA-per-product GEMM (GemmDesc::arith 2); bf != 0: the
+// PURE: the output is plain _Float16 ([cols][ld_out halfs]) for the one-MFMA-per-product GEMM (GemmDesc::ab F16 / BF16); bf != 0: the
 // 16-bit values are bfloat16 bit patterns instead.
 // RMP: the format of the optional row-major copy (PURE = as the transposed output; false with PURE = true: the weight-gradient
 // product takes plain f16 operands while the dX GEMM of the same gradient matrix keeps split-f16 ones - sola_tune "train_dw_f16")
@@ -180,24 +180,26 @@ __global__ __launch_bounds__(256) void col2im_ragged_kernel(const float* __restr
     *reinterpret_cast<float4*>(dx + i * 4) = acc;
 }
 
-int cast_t(int pure, const float* in, int ld_in, float* out, long long ld_out, int rows, int cols, float* scal, hipStream_t s, int conv_T_in = 0,
+// ab: the transposed operand's format; rm_fmt: the row-major copy's (out_rm), `ab` or SP16
+int cast_t(Elem ab, const float* in, int ld_in, float* out, long long ld_out, int rows, int cols, float* scal, hipStream_t s, int conv_T_in = 0,
            int conv_T_out = 0, int conv_stride = 1, int conv_toff = 0, float* out_rm = nullptr, long long ld_rm = 0,
-           const int2* rowmap = nullptr, int tap = 0, int rm_split = 0) {
-    const int bf = pure == 2 ? 1 : 0;
-    const bool rmp = pure && !rm_split;
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, ((pure ? 6.0 : 8.0) + (out_rm ? (rmp ? 2.0 : 4.0) : 0.0)) * rows * cols);
+           const int2* rowmap = nullptr, int tap = 0, Elem rm_fmt = Elem::F32) {
+    const bool op16 = is_row16(ab), rm_sp = rm_fmt == Elem::SP16;
+    const int bf = ab == Elem::BF16;
+    const bool rmp = op16 && !rm_sp;
+    SolaProfScope prof(SOLA_PROF_MISC, s, 0, ((op16 ? 6.0 : 8.0) + (out_rm ? (rmp ? 2.0 : 4.0) : 0.0)) * rows * cols);
     const dim3 grid((unsigned)(ld_out / 128), (unsigned)((cols + 63) / 64));
-    if (pure && rm_split) hipLaunchKernelGGL((cast_sp16_t_kernel<true, false>), grid, dim3(256), 0, s, in, out, rows, cols, ld_in, ld_out, scal, conv_T_in, conv_T_out, conv_stride, conv_toff, out_rm, ld_rm, rowmap, tap, bf);
-    else if (pure) hipLaunchKernelGGL(cast_sp16_t_kernel<true>, grid, dim3(256), 0, s, in, out, rows, cols, ld_in, ld_out, scal, conv_T_in, conv_T_out, conv_stride, conv_toff, out_rm, ld_rm, rowmap, tap, bf);
+    if (op16 && rm_sp) hipLaunchKernelGGL((cast_sp16_t_kernel<true, false>), grid, dim3(256), 0, s, in, out, rows, cols, ld_in, ld_out, scal, conv_T_in, conv_T_out, conv_stride, conv_toff, out_rm, ld_rm, rowmap, tap, bf);
+    else if (op16) hipLaunchKernelGGL(cast_sp16_t_kernel<true>, grid, dim3(256), 0, s, in, out, rows, cols, ld_in, ld_out, scal, conv_T_in, conv_T_out, conv_stride, conv_toff, out_rm, ld_rm, rowmap, tap, bf);
     else hipLaunchKernelGGL(cast_sp16_t_kernel<false>, grid, dim3(256), 0, s, in, out, rows, cols, ld_in, ld_out, scal, conv_T_in, conv_T_out, conv_stride, conv_toff, out_rm, ld_rm, rowmap, tap, bf);
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
 }
 
-void geometry(int M, int& ksplit, long long& Mp, bool pure = false) {
+void geometry(int M, int& ksplit, long long& Mp, bool op16 = false) {
     ksplit = M >= 8192 ? 16 : (M >= 2048 ? 8 : (M >= 512 ? 4 : 2));
     // every range at least two k-tiles (32 pairs or 64 halfs wide); a multiple of the 128-row cast tile
-    const long long q = (pure ? 128LL : 64LL) * ksplit;
+    const long long q = (op16 ? 128LL : 64LL) * ksplit;
     Mp = (M + q - 1) / q * q;
 }
 
@@ -205,29 +207,31 @@ void geometry(int M, int& ksplit, long long& Mp, bool pure = false) {
 
 int launch_cast_sp16_t(const float* in, int ld_in, float* out, long long ld_out, int rows, int cols, float* scal, hipStream_t s) {
     SOLA_ARG(in && out && rows > 0 && cols > 0 && ld_out % 128 == 0 && ld_out >= rows, "cast_sp16_t: rows=%d ld_out=%lld", rows, ld_out);
-    return cast_t(0, in, ld_in, out, ld_out, rows, cols, scal, s);
+    return cast_t(Elem::SP16, in, ld_in, out, ld_out, rows, cols, scal, s);
 }
 
-int launch_cast_f16_t(const float* in, int ld_in, void* out, long long ld_out, int rows, int cols, float* scal, hipStream_t s, int bf16) {
-    SOLA_ARG(in && out && rows > 0 && cols > 0 && ld_out % 128 == 0 && ld_out >= rows, "cast_f16_t: rows=%d ld_out=%lld", rows, ld_out);
-    return cast_t(bf16 ? 2 : 1, in, ld_in, static_cast<float*>(out), ld_out, rows, cols, scal, s);
+int launch_cast_f16_t(const float* in, int ld_in, void* out, long long ld_out, int rows, int cols, float* scal, Elem fmt, hipStream_t s) {
+    SOLA_ARG(in && out && rows > 0 && cols > 0 && ld_out % 128 == 0 && ld_out >= rows && is_row16(fmt), "cast_f16_t: rows=%d ld_out=%lld (%s)", rows, ld_out, elem_name(fmt));
+    return cast_t(fmt, in, ld_in, static_cast<float*>(out), ld_out, rows, cols, scal, s);
 }
 
-int launch_col2im(const float* z, float* dx, long long R, int T_in, int T_out, int cin, int k, int stride, int pad, hipStream_t s, int z_bf16) {
-    SOLA_ARG(z && dx && cin % 4 == 0 && k >= 1 && stride >= 1, "col2im: cin=%d k=%d stride=%d", cin, k, stride);
+int launch_col2im(const float* z, float* dx, long long R, int T_in, int T_out, int cin, int k, int stride, int pad, Elem z_fmt, hipStream_t s) {
+    const bool z16 = z_fmt == Elem::BF16;
+    SOLA_ARG(z && dx && cin % 4 == 0 && k >= 1 && stride >= 1 && (z16 || z_fmt == Elem::F32), "col2im: cin=%d k=%d stride=%d", cin, k, stride);
     const long long n4 = R * T_in * (cin / 4);
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, (z_bf16 ? 2.0 : 4.0) * R * T_out * (double)k * cin + 4.0 * R * T_in * (double)cin);
-    if (z_bf16) hipLaunchKernelGGL(col2im_kernel<true>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, z, dx, n4, T_in, T_out, cin / 4, k, stride, pad);
+    SolaProfScope prof(SOLA_PROF_MISC, s, 0, (z16 ? 2.0 : 4.0) * R * T_out * (double)k * cin + 4.0 * R * T_in * (double)cin);
+    if (z16) hipLaunchKernelGGL(col2im_kernel<true>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, z, dx, n4, T_in, T_out, cin / 4, k, stride, pad);
     else hipLaunchKernelGGL(col2im_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, z, dx, n4, T_in, T_out, cin / 4, k, stride, pad);
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
 }
 
-int launch_col2im_ragged(const float* z, float* dx, long long rows_in, const int4* imap, int cin, int k, int stride, int pad, hipStream_t s, int z_bf16) {
-    SOLA_ARG(z && dx && imap && cin % 4 == 0 && k >= 1 && stride >= 1 && rows_in > 0, "col2im_ragged: cin=%d k=%d stride=%d", cin, k, stride);
+int launch_col2im_ragged(const float* z, float* dx, long long rows_in, const int4* imap, int cin, int k, int stride, int pad, Elem z_fmt, hipStream_t s) {
+    const bool z16 = z_fmt == Elem::BF16;
+    SOLA_ARG(z && dx && imap && cin % 4 == 0 && k >= 1 && stride >= 1 && rows_in > 0 && (z16 || z_fmt == Elem::F32), "col2im_ragged: cin=%d k=%d stride=%d", cin, k, stride);
     const long long n4 = rows_in * (cin / 4);
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, (z_bf16 ? 2.0 : 4.0) * rows_in * (double)k * cin / stride + 4.0 * rows_in * (double)cin);
-    if (z_bf16) hipLaunchKernelGGL(col2im_ragged_kernel<true>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, z, dx, n4, imap, cin / 4, k, stride, pad);
+    SolaProfScope prof(SOLA_PROF_MISC, s, 0, (z16 ? 2.0 : 4.0) * rows_in * (double)k * cin / stride + 4.0 * rows_in * (double)cin);
+    if (z16) hipLaunchKernelGGL(col2im_ragged_kernel<true>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, z, dx, n4, imap, cin / 4, k, stride, pad);
     else hipLaunchKernelGGL(col2im_ragged_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, z, dx, n4, imap, cin / 4, k, stride, pad);
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
@@ -248,7 +252,7 @@ bool gemm_tn_split_writes_rm(const GemmTnSplitDesc& d) {
 static long long conv_input_rows(const GemmTnSplitDesc& d) { return !d.conv ? 0 : (d.rowmap ? d.B_rows : (long long)d.M / d.T_out * d.T_in); }
 
 bool gemm_tn_split_takes_tr(const GemmTnSplitDesc& d) {
-    return d.pure != 0 && d.ldb % 4 == 0 && gemm_tn_tr_supported(d.M, d.N, d.K, 8, 8) &&
+    return is_row16(d.ab) && d.ldb % 4 == 0 && gemm_tn_tr_supported(d.M, d.N, d.K, 8, 8) &&
            (!d.conv || (d.Cin % 256 == 0 && d.ldb == d.Cin && conv_input_rows(d) > 0));
 }
 
@@ -264,12 +268,15 @@ int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s) {
     SOLA_ARG(gemm_tn_split_supported(d.M, d.N, d.K) && d.lda % 4 == 0, "gemm_tn_split: M=%d N=%d K=%d lda=%d", d.M, d.N, d.K, d.lda);
     SOLA_ARG(!d.conv || (d.Cin > 0 && d.K % d.Cin == 0 && (d.rowmap || (d.T_out > 0 && d.M % d.T_out == 0))), "gemm_tn_split: conv geometry K=%d Cin=%d", d.K, d.Cin);
     SOLA_ARG(d.scratch_bytes >= gemm_tn_split_scratch_bytes(d.M, d.N, d.K, d.nprob), "gemm_tn_split: scratch too small");
+    SOLA_ARG(gemm_tn_split_formats_ok(d.ab, d.rm_fmt, d.b16_fmt), "gemm_tn_split: %s operands with a %s row-major copy and %s kept rows", elem_name(d.ab),
+             elem_name(d.rm_fmt), elem_name(d.b16_fmt));
     int ks; long long Mp;
-    const bool pure = d.pure != 0;
-    const int pure_fmt = d.pure;  // 0 split-f16, 1 f16, 2 bf16
-    geometry(d.M, ks, Mp, pure);
+    const bool op16 = is_row16(d.ab);
+    const bool rm_sp = op16 && d.rm_fmt == Elem::SP16;  // the row-major copy stays split-f16 beside 16-bit operands
+    const bool bf = d.ab == Elem::BF16;
+    geometry(d.M, ks, Mp, op16);
     // transposed operands: rows of Mp split-f16 pairs (4 bytes per element) or Mp halfs (2 bytes); the buffers are sized for pairs
-    const long long rowf = pure ? Mp / 2 : Mp;  // floats per transposed row
+    const long long rowf = op16 ? Mp / 2 : Mp;  // floats per transposed row
     float* at = d.scratch;
     float* xt = at + (size_t)d.nprob * d.N * Mp;
     float* slabs = xt + (size_t)d.nprob * d.K * Mp;
@@ -283,29 +290,29 @@ int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s) {
     if (gemm_tn_split_takes_tr(d)) {
         // 16-bit operands, linear layers: NO transposed copies.  gemm_tn_tr.hip's gemm_tn_tr_kernel takes the ROW-MAJOR casts - dY's is the
         // dX GEMM's operand anyway - and transposes between LDS and the matrix pipe (ds_read_b64_tr_b16).
-        const int bf = pure_fmt == 2 ? 1 : 0;
         GemmTnTrDesc t{};
-        t.nprob = d.nprob; t.M = d.M; t.N = d.N; t.K = d.K; t.bf16 = bf;
+        t.nprob = d.nprob; t.M = d.M; t.N = d.N; t.K = d.K;
         _Float16* a16 = reinterpret_cast<_Float16*>(at);
         _Float16* x16 = reinterpret_cast<_Float16*>(xt);
-        const bool rm16 = rm && !d.rm_split;  // the caller's row-major copy has the operand's format: cast once, into it
+        const bool rm16 = rm && !rm_sp;  // the caller's row-major copy has the operand's format: cast once, into it
         // ... or it is the split-f16 copy (the dX GEMM of a split-f16 step): its hi halves ARE the plain f16 cast, the kernel fetches them
-        const bool rmsp = rm && d.rm_split && !bf;
+        const bool rmsp = rm && rm_sp && !bf;
         int n_x = 0;
-        bool b_kept = !d.scal_b && !(d.b16_split && bf);  // every problem's X comes from the forward's kept operand casts
+        const bool b16_sp = d.b16_fmt == Elem::SP16;
+        bool b_kept = !d.scal_b && !(b16_sp && bf);  // every problem's X comes from the forward's kept operand casts
         for (int j = 0; j < d.nprob; ++j) b_kept = b_kept && d.B16[j] != nullptr;
         for (int j = 0; j < d.nprob; ++j) {
             const long long off = d.A[j] - d.A[0];
             if (rm16) {
                 _Float16* dst = reinterpret_cast<_Float16*>(d.a_rm) + off;
-                if (!d.a_rm_ready) SOLA_TRY(launch_cast_f16_scaled(d.A[j], d.lda, dst, d.a_rm_ld, d.M, d.N, scal, s, bf));
+                if (!d.a_rm_ready) SOLA_TRY(launch_cast_f16_scaled(d.A[j], d.lda, dst, d.a_rm_ld, d.M, d.N, scal, d.ab, s));
                 t.A[j] = dst;
             } else if (rmsp) {
                 SOLA_TRY(launch_cast_sp16_scaled(d.A[j], d.lda, d.a_rm + off, d.a_rm_ld, d.M, d.N, scal, s));
                 t.A[j] = d.a_rm + off;
             } else {
                 _Float16* dst = a16 + (size_t)j * d.M * d.N;
-                SOLA_TRY(launch_cast_f16_scaled(d.A[j], d.lda, dst, d.N, d.M, d.N, scal, s, bf));
+                SOLA_TRY(launch_cast_f16_scaled(d.A[j], d.lda, dst, d.N, d.M, d.N, scal, d.ab, s));
                 t.A[j] = dst;
                 if (rm) SOLA_TRY(launch_cast_sp16_scaled(d.A[j], d.lda, d.a_rm + off, d.a_rm_ld, d.M, d.N, scal, s));  // the dX GEMM keeps split-f16 operands
             }
@@ -318,35 +325,35 @@ int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s) {
                 const long long b_rows = d.conv ? conv_rows_in : d.M;
                 const int b_cols = d.conv ? d.Cin : d.K;
                 _Float16* dst = x16 + (size_t)n_x++ * b_rows * b_cols;
-                if (d.scal_b) SOLA_TRY(launch_cast_f16_scaled(d.B[j], d.ldb, dst, b_cols, b_rows, b_cols, d.scal_b, s, bf));
-                else SOLA_TRY(launch_cast_f16(d.B[j], d.ldb, dst, b_cols, b_rows, b_cols, 1.f, nullptr, s, 13, nullptr, bf));
+                if (d.scal_b) SOLA_TRY(launch_cast_f16_scaled(d.B[j], d.ldb, dst, b_cols, b_rows, b_cols, d.scal_b, d.ab, s));
+                else SOLA_TRY(launch_cast_f16(d.B[j], d.ldb, dst, b_cols, b_rows, b_cols, 1.f, nullptr, d.ab, s));
                 t.B[j] = dst;
             }
         }
         t.lda = (rm16 || rmsp) ? d.a_rm_ld : d.N;
-        t.a_split = rmsp ? 1 : 0;
+        t.a_fmt = rmsp ? Elem::SP16 : d.ab;
         t.ldb = d.conv ? d.Cin : d.K;
-        t.b_split = b_kept && d.b16_split ? 1 : 0;
+        t.b_fmt = b_kept && b16_sp ? Elem::SP16 : d.ab;
         t.conv = d.conv; t.Cin = d.Cin; t.T_in = d.T_in; t.T_out = d.T_out; t.stride = d.stride; t.pad = d.pad; t.rowmap = d.rowmap;
         gemm_tn_tr_geometry(d.M, d.N, d.K, d.nprob, ks, t.ksplit, t.kper);
         t.part = slabs;
         // bf16 steps (train_bf16_store 3): the partial sums of the k ranges leave as bfloat16 slabs (half the bytes written by the 256 blocks
         // at once and read back by the fold); sixteen of them are summed in f32 - autocast's linear backward rounds the whole dW to bfloat16 once
         extern int g_train_bf16_store;
-        t.part_bf16 = (bf && g_train_bf16_store >= 3 && d.K % 4 == 0) ? 1 : 0;
+        t.part_fmt = (bf && g_train_bf16_store >= 3 && d.K % 4 == 0) ? Elem::BF16 : Elem::F32;
         SOLA_TRY(launch_gemm_tn_tr(t, s));
-        if (t.part_bf16) return launch_splitk_reduce_bf16(slabs, t.ksplit, d.nprob, d.C, d.N, d.K, d.K, scal + 1, d.scal_b ? d.scal_b + 1 : nullptr, s);
+        if (t.part_fmt == Elem::BF16) return launch_splitk_reduce_bf16(slabs, t.ksplit, d.nprob, d.C, d.N, d.K, d.K, scal + 1, d.scal_b ? d.scal_b + 1 : nullptr, s);
         return launch_splitk_reduce(slabs, t.ksplit, d.nprob, d.C, d.N, d.K, d.K, scal + 1, d.scal_b ? d.scal_b + 1 : nullptr, s);
     }
     const float* xt_of[3] = {nullptr, nullptr, nullptr};
     int n_xt = 0;
     for (int j = 0; j < d.nprob; ++j) {
-        if (rm && !(d.a_rm_ready && pure && !d.rm_split)) {  // + the row-major cast of the same gradient matrix (the dX GEMM's operand): one read of dY for both
+        if (rm && !(d.a_rm_ready && op16 && !rm_sp)) {  // + the row-major cast of the same gradient matrix (the dX GEMM's operand): one read of dY for both
             const long long off = d.A[j] - d.A[0];
-            float* dst = (pure && !d.rm_split) ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(d.a_rm) + off) : d.a_rm + off;
-            SOLA_TRY(cast_t(pure_fmt, d.A[j], d.lda, at + (size_t)j * d.N * rowf, Mp, d.M, d.N, scal, s, 0, 0, 1, 0, dst, d.a_rm_ld, nullptr, 0, d.rm_split));
+            float* dst = (op16 && !rm_sp) ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(d.a_rm) + off) : d.a_rm + off;
+            SOLA_TRY(cast_t(d.ab, d.A[j], d.lda, at + (size_t)j * d.N * rowf, Mp, d.M, d.N, scal, s, 0, 0, 1, 0, dst, d.a_rm_ld, nullptr, 0, d.rm_fmt));
         } else {
-            SOLA_TRY(cast_t(pure_fmt, d.A[j], d.lda, at + (size_t)j * d.N * rowf, Mp, d.M, d.N, scal, s));
+            SOLA_TRY(cast_t(d.ab, d.A[j], d.lda, at + (size_t)j * d.N * rowf, Mp, d.M, d.N, scal, s));
         }
         for (int e = 0; e < j; ++e)
             if (d.B[e] == d.B[j]) xt_of[j] = xt_of[e];
@@ -354,10 +361,10 @@ int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s) {
             float* dst = xt + (size_t)n_xt++ * d.K * rowf;
             if (d.conv) {  // rows [kk*Cin, (kk+1)*Cin) of X^T = tap kk of the implicit im2col
                 for (int kk = 0; kk < d.K / d.Cin; ++kk)
-                    SOLA_TRY(cast_t(pure_fmt, d.B[j], d.ldb, dst + (size_t)kk * d.Cin * rowf, Mp, d.M, d.Cin, d.scal_b, s, d.T_in, d.T_out, d.stride, kk - d.pad,
+                    SOLA_TRY(cast_t(d.ab, d.B[j], d.ldb, dst + (size_t)kk * d.Cin * rowf, Mp, d.M, d.Cin, d.scal_b, s, d.T_in, d.T_out, d.stride, kk - d.pad,
                                     nullptr, 0, d.rowmap, kk));
             } else {
-                SOLA_TRY(cast_t(pure_fmt, d.B[j], d.ldb, dst, Mp, d.M, d.K, d.scal_b, s));
+                SOLA_TRY(cast_t(d.ab, d.B[j], d.ldb, dst, Mp, d.M, d.K, d.scal_b, s));
             }
             xt_of[j] = dst;
         }
@@ -366,7 +373,7 @@ int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s) {
     g.nprob = d.nprob;
     for (int j = 0; j < d.nprob; ++j) g.p[j] = GemmProblem{at + (size_t)j * d.N * rowf, xt_of[j], nullptr, nullptr, d.C[j]};
     g.M = d.N; g.N = d.K; g.K = (int)Mp; g.lda = (int)Mp; g.ldr = 0; g.ldc = d.K;
-    g.arith = pure ? 2 : 1; g.bf16 = pure_fmt == 2 ? 1 : 0; g.out_scale = 1.f; g.out_scale_dev = scal + 1;
+    g.ab = d.ab; g.out_scale = 1.f; g.out_scale_dev = scal + 1;
     if (d.scal_b)  // the activations' own scale (the caller's tokens): every problem shares it
         for (int j = 0; j < d.nprob; ++j) g.p[j].scale_dev = d.scal_b + 1;
     g.ksplit = ks; g.splitk_ws = slabs; g.splitk_bytes = (size_t)d.nprob * ks * d.N * d.K * sizeof(float);

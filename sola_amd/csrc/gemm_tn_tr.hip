@@ -280,7 +280,7 @@ __global__ __launch_bounds__(512) void gemm_tn_tr_kernel(const TnTrArgs t) {
 
     GemmProblem pr{};
     const long long slab = ((long long)blockIdx.z * a.ksplit + range) * a.M * a.N;
-    // (c_f16: the partial sums leave as 16-bit rows - bfloat16 in the bf16 step: GemmTnTrDesc::part_bf16)
+    // (c_f16: the partial sums leave as 16-bit rows - bfloat16 in the bf16 step: GemmTnTrDesc::part_fmt)
     pr.C = a.c_f16 ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(a.part) + slab) : a.part + slab;
     glds_tile_epilogue<MI, WAVES_N>(a, pr, acc, lds, wave, lane, wr, wc, m0, n0);
 }
@@ -335,6 +335,9 @@ int launch_splitk_reduce_bf16(const void* part, int ksplit, int nprob, float* co
 int launch_gemm_tn_tr(const GemmTnTrDesc& d, hipStream_t s) {
     SOLA_ARG(d.nprob >= 1 && d.nprob <= 3 && d.part && d.ksplit >= 1 && d.kper >= 1, "gemm_tn_tr: nprob %d ksplit %d", d.nprob, d.ksplit);
     SOLA_ARG(gemm_tn_tr_supported(d.M, d.N, d.K, d.lda, d.ldb), "gemm_tn_tr: M=%d N=%d K=%d", d.M, d.N, d.K);
+    SOLA_ARG(gemm_tn_tr_formats_ok(d.a_fmt, d.b_fmt, d.part_fmt), "gemm_tn_tr: no kernel for %s x %s operands with %s partial sums (split-f16 operands are f16)",
+             elem_name(d.a_fmt), elem_name(d.b_fmt), elem_name(d.part_fmt));
+    const bool bf = d.a_fmt == Elem::BF16;
     SolaProfScope prof(SOLA_PROF_GEMM_SPLIT256, s, 2.0 * d.M * d.N * (double)d.K * d.nprob,
                        2.0 * d.nprob * ((double)d.M * d.N + (double)d.M * d.K) + 4.0 * d.nprob * d.ksplit * (double)d.N * d.K);
     TnTrArgs t{};
@@ -344,28 +347,27 @@ int launch_gemm_tn_tr(const GemmTnTrDesc& d, hipStream_t s) {
     a.out_scale = 1.f;
     a.ksplit = d.ksplit; a.part = d.part; a.nprob = d.nprob;
     a.ablate = g_gemm_ablate;
-    if (d.part_bf16) { SOLA_ARG(d.bf16 && d.K % 4 == 0, "gemm_tn_tr: bfloat16 partial sums go with bfloat16 operands"); a.c_f16 = 1; a.bf16 = 1; }
+    if (d.part_fmt == Elem::BF16) { SOLA_ARG(d.K % 4 == 0, "gemm_tn_tr: bfloat16 partial sums need K %% 4 == 0"); a.c_f16 = 1; a.bf16 = 1; }
     for (int j = 0; j < 3; ++j) {
         t.A[j] = static_cast<const char*>(d.A[j < d.nprob ? j : 0]);
         t.B[j] = static_cast<const char*>(d.B[j < d.nprob ? j : 0]);
         SOLA_ARG((reinterpret_cast<uintptr_t>(t.A[j]) & 15) == 0 && (reinterpret_cast<uintptr_t>(t.B[j]) & 15) == 0, "gemm_tn_tr: operands must be 16-byte aligned");
     }
-    t.a_sp = d.a_split ? 1 : 0; t.b_sp = d.b_split ? 1 : 0;
-    t.lda = d.lda * (d.a_split ? 4 : 2); t.ldb = d.ldb * (d.b_split ? 4 : 2); t.Mred = d.M; t.kper = d.kper; t.nkt = (d.M + 63) / 64;
+    t.a_sp = d.a_fmt == Elem::SP16; t.b_sp = d.b_fmt == Elem::SP16;
+    t.lda = d.lda * elem_bytes(d.a_fmt); t.ldb = d.ldb * elem_bytes(d.b_fmt); t.Mred = d.M; t.kper = d.kper; t.nkt = (d.M + 63) / 64;
     SOLA_ARG((long long)d.ksplit * d.kper >= t.nkt && (long long)(d.ksplit - 1) * d.kper < t.nkt, "gemm_tn_tr: ranges %d x %d k-tiles do not cover %d", d.ksplit, d.kper, t.nkt);
     constexpr size_t lds = 2 * 2 * 64 * 512;
     t.Cin = d.Cin; t.T_in = d.T_in; t.T_out = d.T_out; t.stride = d.stride; t.pad = d.pad; t.rowmap = d.rowmap;
     const int conv = !d.conv ? 0 : (d.rowmap ? 2 : 1);
     SOLA_ARG(!conv || (d.Cin % 256 == 0 && d.K % d.Cin == 0 && d.K / d.Cin <= 8 && (d.rowmap || (d.T_out > 0 && d.T_in > 0 && d.stride >= 1))),
              "gemm_tn_tr: conv geometry Cin=%d K=%d", d.Cin, d.K);
-    SOLA_ARG(!(d.bf16 && (d.a_split || d.b_split)), "gemm_tn_tr: split-f16 operands are f16");
-    if (conv) t.ldb = (long long)d.Cin * (d.b_split ? 4 : 2);
+    if (conv) t.ldb = (long long)d.Cin * elem_bytes(d.b_fmt);
     static DeviceOnce once[2][3];
     const dim3 grid(a.tiles_m * a.tiles_n * d.ksplit, 1, d.nprob);
     const void* fn = nullptr;
-#define TN_TR_PICK(BFV, CV) if ((d.bf16 ? 1 : 0) == BFV && conv == CV) fn = reinterpret_cast<const void*>(&gemm_tn_tr_kernel<BFV, CV>);
+#define TN_TR_PICK(BFV, CV) if ((bf ? 1 : 0) == BFV && conv == CV) fn = reinterpret_cast<const void*>(&gemm_tn_tr_kernel<BFV, CV>);
     TN_TR_PICK(0, 0) TN_TR_PICK(0, 1) TN_TR_PICK(0, 2) TN_TR_PICK(1, 0) TN_TR_PICK(1, 1) TN_TR_PICK(1, 2)
 #undef TN_TR_PICK
     void* kargs[] = {&t};
-    return launch_lds_fn(fn, once[d.bf16 ? 1 : 0][conv], grid, dim3(512), lds, s, kargs);
+    return launch_lds_fn(fn, once[bf ? 1 : 0][conv], grid, dim3(512), lds, s, kargs);
 }

@@ -9,7 +9,7 @@ struct GemmProblem {
     const float* bias;  // [N] or null
     const float* R;     // [M, N] residual or null
     float* C;           // [M, N]
-    const float* scale_dev;  // arith 1, optional: this problem's own result multiplier in device memory (the inverse of the
+    const float* scale_dev;  // split-f16 operands, optional: this problem's own result multiplier in device memory (the inverse of the
                              // data-dependent power-of-two scale its W operand was cast with); null = 1
 };
 struct GemmDesc {
@@ -24,40 +24,47 @@ struct GemmDesc {
     // source row rowmap[m].x (the row of tap 0, may lie outside the sequence) and bit kk of rowmap[m].y says whether tap kk
     // is inside the sequence (else it reads zeros).  T_in / T_out / stride / pad are then unused.
     const int2* rowmap;
-    int arith;        // 0: f32 operands (exact f32 MFMA); 1: split-f16 operands (3 x f16 MFMA, f32 accumulate);
-                      // 2: plain f16 operands (the 16-bit storage mode: ONE f16 MFMA per product, f32 accumulate).  A and W
-                      //    then hold _Float16 rows and K, lda, Cin count halfs (K % 64 == 0, lda % 16 == 0, Cin % 64 == 0);
-                      //    direct-to-LDS kernels only
-    float out_scale;  // arith 1: multiplier undoing the power-of-two weight pre-scale (0 = 1)
-    int ksplit;  // arith 1, direct-to-LDS kernels: > 1 cuts the reduction into that many ranges, one work item each (few output
+    Elem ab;          // A and W.  F32: exact f32 MFMA; SP16: 3 x f16 MFMA per product, f32 accumulate; F16 / BF16: ONE 16-bit MFMA per
+                      // product, f32 accumulate - A and W then hold 16-bit rows and K, lda, Cin count values (K % 64 == 0,
+                      // lda % 16 == 0, Cin % 64 == 0); direct-to-LDS kernels only
+    Elem r, c;        // the residual R and the output C: f32 rows, or the operands' own format (gemm_formats_ok).  SP16 C: N % 8 == 0;
+                      // 16-bit rows: ldr / ldc count values, N % 4 == 0, pitches % 4 == 0
+    float out_scale;  // 16-bit operands: multiplier undoing the power-of-two weight pre-scale (0 = 1)
+    int ksplit;  // 16-bit operands, direct-to-LDS kernels: > 1 cuts the reduction into that many ranges, one work item each (few output
                  // tiles, long K: weight gradients); needs splitk_ws of nprob * ksplit * M * N floats and K % (32 * ksplit) == 0
-    const float* out_scale_dev;  // arith 1, optional: a further multiplier read from device memory (the inverse of the
+    const float* out_scale_dev;  // 16-bit operands, optional: a further multiplier read from device memory (the inverse of the
                                  // data-dependent scale launch_cast_sp16_auto gave the A operand)
-    int r_sp16;       // arith 1: the residual R is split-f16
-    int c_sp16;       // arith 1: write C as split-f16 pairs (N % 8 == 0), e.g. q/k/v for the split attention kernel
-    int r_f16, c_f16; // arith 2: R / C are _Float16 matrices (ldr / ldc count halfs then; N % 4 == 0, pitches % 4 == 0)
-    int bf16;         // arith 2: A and W hold bfloat16 rows instead of f16 ones (v_mfma_f32_32x32x16_bf16; f32 C / R only): training with
-                      // bf16 GEMM operands (BASELINE config C2)
     const float* bias_scale_dev;  // direct-to-LDS kernels, optional: the bias is multiplied by this device scalar (an output kept in
                                   // the units of a scaled input: conv0 of the 16-bit storage mode)
     // optional scratch for the two-pass split-K of small grids (fewer 64x64 tiles than CUs): S partial sums per problem,
     // [nprob][S][M][N] f32, reduced in a fixed order (deterministic).  Null = never split.
     float* splitk_ws;
     size_t splitk_bytes;
-    // arith 1 with c_sp16, optional: device word that gets bit 0 set when a value written as split-f16 is not finite or
+    // SP16 (or F16) C, optional: device word that gets bit 0 set when a value written as split-f16 is not finite or
     // beyond the f16 range (|v| >= 65000): the inference forward then repeats the call on the exact-f32 kernels
     int* guard;
-    // arith 1, optional (check gemm_gn_fusable first): GroupNorm + LeakyReLU of the output applied in the epilogue - instances of
-    // gn_tokens (4 / 8 / 16) consecutive rows x 64 channels - and C written as split-f16 pairs (c_sp16 must be 1)
+    // SP16 operands, optional (check gemm_gn_fusable first): GroupNorm + LeakyReLU of the output applied in the epilogue - instances of
+    // gn_tokens (4 / 8 / 16) consecutive rows x 64 channels - and C written as split-f16 pairs (c must be SP16)
     const float *gn_gamma, *gn_beta;
     int gn_tokens;
     float gn_eps, gn_slope;
-    // arith 0, few-row shape only (gemm_nn_supported): the weights in their ROW-MAJOR [K][N] form instead of W[N][K] - the reduction index
+    // F32 operands, few-row shape only (gemm_nn_supported): the weights in their ROW-MAJOR [K][N] form instead of W[N][K] - the reduction index
     // runs over the rows of up to three matrices of w_nn_rows rows each, stacked (K = their total; pitch N; p[].W unused): a dX GEMM reads
     // the layer's weight matrices where they lie, no transposed copy.  One problem.  0 = off.
     const float* w_nn[3];
     int w_nn_rows;
 };
+// the format triples a kernel exists for: R and C are f32 rows or in the operands' own format, and a bfloat16 residual goes into a
+// bfloat16 output (launch_gemm checks it)
+constexpr bool gemm_formats_ok(Elem ab, Elem r, Elem c) {
+    return (r == Elem::F32 || (r == ab && ab != Elem::F32)) && (c == Elem::F32 || c == ab) && !(r == Elem::BF16 && c != Elem::BF16);
+}
+static_assert(gemm_formats_ok(Elem::BF16, Elem::F32, Elem::BF16) && gemm_formats_ok(Elem::SP16, Elem::SP16, Elem::F32) &&
+              gemm_formats_ok(Elem::F16, Elem::F16, Elem::F32), "operand-format residuals and outputs");
+static_assert(!gemm_formats_ok(Elem::F16, Elem::F32, Elem::BF16) && !gemm_formats_ok(Elem::F32, Elem::SP16, Elem::F32), "no mixed 16-bit formats");
+static_assert(!gemm_formats_ok(Elem::F16, Elem::BF16, Elem::F16) && !gemm_formats_ok(Elem::SP16, Elem::BF16, Elem::BF16),
+              "a bfloat16 residual needs bfloat16 operands");
+static_assert(!gemm_formats_ok(Elem::BF16, Elem::BF16, Elem::F32), "a bfloat16 residual goes with a bfloat16 output");
 bool gemm_nn_supported(const GemmDesc& d);  // the launch takes the w_nn form (else launch_gemm fails)
 int launch_gemm(const GemmDesc& d, hipStream_t s);
 bool gemm_gn_fusable(const GemmDesc& d, int channels_per_group, int tokens);
@@ -132,32 +139,39 @@ struct GemmTnSplitDesc {
     float* scal;  // optional device pair with scal[0] = max|A| over all problems already computed (else found here)
     float* scal_b;  // optional device pair with scal_b[0] = max|B| already computed: B is cast with that power-of-two scale too
                     // (activations whose magnitude the caller does not control: the object tokens); null = B is cast unscaled
-    int pure;     // 1: plain f16 transposed operands and ONE f16 MFMA per product (training with f16 GEMM operands), 2: the same in
-                  // bfloat16, else split-f16
+    Elem ab;      // the operands both matrices are cast to - SP16: split-f16 pairs; F16 / BF16: plain 16-bit values and ONE MFMA per
+                  // product (training with 16-bit GEMM operands)
     // optional: the transposing cast of A also writes the ROW-MAJOR cast of A (same scale, the format of launch_cast_f16_scaled /
     // launch_cast_sp16_scaled) - the operand of the dX GEMM that consumes the same gradient matrix - so dY is read once for both.
     // a_rm addresses the value (row 0, column of A[0]); problem j lands at column A[j] - A[0]; a_rm_ld = row pitch in values.
     // Needs N % 64 == 0 and column offsets % 8 == 0 (else ignored: check gemm_tn_split_writes_rm()).
     float* a_rm;
     int a_rm_ld;
-    int rm_split;  // pure != 0 only: the row-major copy stays split-f16 (the dX GEMM of a split-f16 step whose dW products run on plain f16)
-    int a_rm_ready;  // pure 16-bit, rm_split == 0: a_rm already holds the cast of every problem (launch_cast_bf16_colsum): no cast here
+    Elem rm_fmt;   // format of that copy: `ab`, or SP16 beside F16 operands (the dX GEMM of a split-f16 step whose dW products run on plain f16)
+    int a_rm_ready;  // 16-bit rows in the operands' format (rm_fmt == ab): a_rm already holds the cast of every problem (launch_cast_bf16_colsum): no cast here
     float* scratch;
     size_t scratch_bytes;
     const int2* rowmap;  // conv = 1, optional, ragged batches: as GemmDesc::rowmap
     long long B_rows;    // conv = 1 with rowmap: rows of the conv input B (the geometry gives M / T_out * T_in otherwise); 0 = unknown
-    const void* B16[3];  // optional, pure != 0: problem j's B already cast row-major in the operand format ([M][K], or the conv input
+    const void* B16[3];  // optional, F16 / BF16 operands: problem j's B already cast row-major in format `b16_fmt` ([M][K], or the conv input
                          // [rows_in][Cin]), unscaled - the training forward's own operand cast (SolaCtx::x16); used by the row-major route
                          // when every problem has one
-    int b16_split;       // ... as SPLIT-f16 pairs (the split-f16 step's forward operands; pure == 1): the kernel takes their hi halves
+    Elem b16_fmt;        // `ab`, or SP16 (the split-f16 step's forward operands, beside F16 products: the kernel takes their hi halves;
+                         // beside BF16 products such copies are not used)
 };
+// split-f16 or 16-bit operands; the row-major copy and the kept B rows are in the operands' format or split-f16 pairs
+constexpr bool gemm_tn_split_formats_ok(Elem ab, Elem rm, Elem b16) {
+    return ab != Elem::F32 && (rm == ab || rm == Elem::SP16) && (b16 == ab || b16 == Elem::SP16);
+}
+static_assert(gemm_tn_split_formats_ok(Elem::F16, Elem::SP16, Elem::SP16) && gemm_tn_split_formats_ok(Elem::BF16, Elem::BF16, Elem::BF16));
+static_assert(!gemm_tn_split_formats_ok(Elem::F32, Elem::F32, Elem::F32) && !gemm_tn_split_formats_ok(Elem::BF16, Elem::F16, Elem::BF16));
 // in [rows][cols] f32 -> out [cols][ld_out] split-f16 (rows rows..ld_out zero-filled; ld_out % 128 == 0); scal: optional
 // device pair as for launch_cast_sp16_auto with scal[0] = max|in| already there
 int launch_cast_sp16_t(const float* in, int ld_in, float* out, long long ld_out, int rows, int cols, float* scal, hipStream_t s);
 // dx[(r, ti)][ci] = sum over taps of z[(r, to)][kk*cin + ci] (the scatter of a transposed conv, as a gather)
-int launch_col2im(const float* z, float* dx, long long R, int T_in, int T_out, int cin, int k, int stride, int pad, hipStream_t s, int z_bf16 = 0);  // z_bf16: z is a bfloat16 matrix (round 6)
+int launch_col2im(const float* z, float* dx, long long R, int T_in, int T_out, int cin, int k, int stride, int pad, Elem z_fmt, hipStream_t s);  // z: F32 or BF16 rows
 // ragged batches: input row i has imap[i] = (first output row of its sequence, T_out, step ti inside the sequence, -)
-int launch_col2im_ragged(const float* z, float* dx, long long rows_in, const int4* imap, int cin, int k, int stride, int pad, hipStream_t s, int z_bf16 = 0);
+int launch_col2im_ragged(const float* z, float* dx, long long rows_in, const int4* imap, int cin, int k, int stride, int pad, Elem z_fmt, hipStream_t s);
 bool gemm_tn_split_supported(int M, int N, int K);
 bool gemm_tn_split_writes_rm(const GemmTnSplitDesc& d);
 // the launch takes gemm_tn_tr.hip's kernel on ROW-MAJOR 16-bit operands (no transposed copies; the only route that reads a_rm_ready / B16 rows)
@@ -173,17 +187,23 @@ struct GemmTnTrDesc {
     const void* B[3];  // 16-bit rows [M][ldb]
     int nprob, M, N, K;
     long long lda, ldb;  // row pitch in VALUES, multiples of 8
-    int a_split, b_split;  // the operand is a split-f16 row-major matrix ([hi8 | lo8] blocks, 4 bytes per value; f16 only): its hi halves
-                           // are the plain f16 cast of the same values and are what the kernel fetches
-    int bf16;
+    Elem a_fmt, b_fmt;  // F16 / BF16 rows, or - f16 products only - SP16: a split-f16 row-major matrix, whose hi halves are the plain f16
+                        // cast of the same values and are what the kernel fetches
     int ksplit, kper;    // gemm_tn_tr_geometry()
     float* part;
     // conv = 1: B is the channels-last conv input [rows_in][Cin] as 16-bit rows, K = k * Cin (implicit im2col, Cin % 256 == 0); the
     // geometry or the ragged rowmap as in GemmDesc
     int conv, Cin, T_in, T_out, stride, pad;
     const int2* rowmap;
-    int part_bf16 = 0;  // round 6 (bf16 operands): the split-K partial sums are written as bfloat16 slabs (same element order) - launch_splitk_reduce_bf16 folds them
+    Elem part_fmt;  // F32, or with bf16 operands BF16 (round 6): the split-K partial sums are written as bfloat16 slabs (same element order) -
+                    // launch_splitk_reduce_bf16 folds them
 };
+// f16 products on f16 or split-f16 rows, or bf16 products on bf16 rows; bfloat16 partial sums with the latter only
+constexpr bool gemm_tn_tr_formats_ok(Elem a, Elem b, Elem part) {
+    return a != Elem::F32 && b != Elem::F32 && (a == Elem::BF16) == (b == Elem::BF16) && (part == Elem::F32 || (part == Elem::BF16 && a == Elem::BF16));
+}
+static_assert(gemm_tn_tr_formats_ok(Elem::SP16, Elem::F16, Elem::F32) && gemm_tn_tr_formats_ok(Elem::BF16, Elem::BF16, Elem::BF16));
+static_assert(!gemm_tn_tr_formats_ok(Elem::SP16, Elem::BF16, Elem::F32) && !gemm_tn_tr_formats_ok(Elem::F16, Elem::F16, Elem::BF16));
 int launch_splitk_reduce_bf16(const void* part, int ksplit, int nprob, float* const* C, int M, int N, int ldc, const float* out_scale_dev,
                               const float* scale_dev, hipStream_t s);
 bool gemm_tn_tr_supported(int M, int N, int K, long long lda, long long ldb);
@@ -194,8 +214,8 @@ int launch_splitk_reduce(const float* part, int ksplit, int nprob, float* const*
                          const float* scale_dev, hipStream_t s);
 
 int launch_transpose(const float* in, float* out, int rows, int cols, int ldi, int ldo, int col_off, hipStream_t s);
-// out row c (pitch ldo values), column col_off + r = scale * in[r][c], written as a GEMM operand: fmt 0 = split-f16 pairs, 1 = f16, 2 = bf16
-int launch_transpose_cast(const float* in, void* out, int rows, int cols, int ldi, int ldo, int col_off, float scale, int fmt, hipStream_t s);
+// out row c (pitch ldo values), column col_off + r = scale * in[r][c], written as a GEMM operand of format fmt (SP16, F16 or BF16)
+int launch_transpose_cast(const float* in, void* out, int rows, int cols, int ldi, int ldo, int col_off, float scale, Elem fmt, hipStream_t s);
 size_t colsum_scratch_bytes(int segments, int seg_rows, int cols);
 int launch_colsum(const float* in, float* out, int segments, int seg_rows, int cols, int ld, float scale, int accumulate,
                   float* scratch, size_t scratch_bytes, hipStream_t s);
@@ -232,11 +252,11 @@ struct AttnDesc {
     float scale;
     float* lse;  // optional [q rows][H]
     DropoutCfg drop;  // on the probabilities (tools/attention.py:71)
-    int o_sp16;       // output as split-f16 pairs
-    int in_sp16;      // q, k, v are split-f16 rows (written by a GEMM with c_sp16); not for sequences of <= 16 steps
-    int in_bf16 = 0;  // round 6: q, k, v are BFLOAT16 rows (ldq / ldk / ldv in values; a GEMM with bf16 + c_f16 wrote them) - the training
-                      // step's bf16 storage; check attention_in_bf16_supported().  o may then be null: only the o_cast copy is written
-    int* guard;       // o_sp16, optional: range guard word (see GemmDesc::guard)
+    Elem in;          // q, k, v.  SP16: rows a GEMM with an SP16 output wrote; not for sequences of <= 16 steps.  BF16 (round 6; ldq / ldk /
+                      // ldv in values): the training step's bf16 storage; check attention_in_bf16_supported().  o may then be null: only the
+                      // o_cast copy is written.  F16: launch_attention_f16 only
+    Elem out;         // o: F32 or SP16 (F16 in launch_attention_f16)
+    int* guard;       // SP16 / F16 o, optional: range guard word (see GemmDesc::guard)
     // optional, ragged batches: group g attends q_units[g] = (first row, row stride, Sq_g, -) over k_units[g] = (first row,
     // row stride, Sk_g, -); Sq / Sk are then the LARGEST lengths (they select the kernel shape and size the LDS)
     const int4 *q_units, *k_units;
@@ -245,8 +265,8 @@ struct AttnDesc {
     int split_math;
     // training forward, optional (round 4): the operand cast of the output that the out-projection GEMM behind this launch takes, written by
     // the attention kernel next to the f32 output (the cast launch read the f32 output back: 62 us per attention on the ragged mix).
-    // o_cast_fmt 1: split-f16 pairs (rows of ldo floats) + optionally o_side = the hi halves once more as plain f16 rows (ldo halfs; the
-    // backward's dW operand); 2 / 3: plain f16 / bfloat16 rows (ldo halfs).  Unscaled, bit-identical to launch_cast_sp16 / launch_cast_f16.
+    // cast SP16: split-f16 pairs (rows of ldo floats) + optionally o_side = the hi halves once more as plain f16 rows (ldo halfs; the
+    // backward's dW operand); F16 / BF16: plain 16-bit rows (ldo values).  Unscaled, bit-identical to launch_cast_sp16 / launch_cast_f16.
     // Only some shapes write it: the launch that did sets *o_cast_done (else the caller casts as before).
     // optional (round 5, the few-keys shape of attn_res.hip only - check attention_shared_keys_supported): the keys j >= k_private of EVERY
     // group are shared rows k_shared_row + (j - k_private) of k / v instead of rows of the group's own range - the object -> language
@@ -255,11 +275,19 @@ struct AttnDesc {
     long long k_shared_row = 0;
     void* o_cast = nullptr;
     void* o_side = nullptr;
-    int o_cast_fmt = 0;
+    Elem cast = Elem::F32;  // format of o_cast (F32: there is none)
     bool* o_cast_done = nullptr;
 };
+// f32 or split-f16 q / k / v with an f32 or split-f16 output; bfloat16 q / k / v with an f32 output (and / or the o_cast copy); f16 q / k /
+// v / o all together (launch_attention_f16).  Which shapes write an o_cast copy is a matter of the kernels (o_cast_done).
+constexpr bool attn_formats_ok(Elem in, Elem out, Elem cast) {
+    return in == Elem::F16 ? (out == Elem::F16 && cast == Elem::F32) : (out == Elem::F32 || (out == Elem::SP16 && in != Elem::BF16));
+}
+static_assert(attn_formats_ok(Elem::SP16, Elem::SP16, Elem::F32) && attn_formats_ok(Elem::BF16, Elem::F32, Elem::BF16) &&
+              attn_formats_ok(Elem::F16, Elem::F16, Elem::F32));
+static_assert(!attn_formats_ok(Elem::F32, Elem::F16, Elem::F32) && !attn_formats_ok(Elem::BF16, Elem::SP16, Elem::F32));
 int launch_attention(const AttnDesc& d, hipStream_t s);
-int launch_attention_f16(const AttnDesc& d, hipStream_t s);  // the 16-bit storage mode's kernels (attn_f16.hip): q / k / v / o are _Float16 rows
+int launch_attention_f16(const AttnDesc& d, hipStream_t s);  // the 16-bit storage mode's kernels (attn_f16.hip): in = out = F16
 bool attention_in_bf16_supported(const AttnDesc& d);   // attn_simple.hip's f32-MFMA kernel on bfloat16 rows
 bool attention_bf16_mfma_supported(const AttnDesc& d);  // attn_f16.hip's bf16-MFMA training kernel (the default where it applies)
 bool attention_shared_keys_supported(const AttnDesc& d);  // d.k_private / k_shared_row can be honoured (the launch then takes attn_res.hip's shape)
@@ -287,13 +315,21 @@ struct AttnBwdDesc {
     // round 6, the training step's bf16 storage (check attention_bwd_bf16_supported): q, k, v are BFLOAT16 rows (ldq / ldk / ldv in values)
     // and the gradients leave as bfloat16 rows dq16 / dk16 / dv16 (pitches ld_dq / ld_dk / ld_dv, in values); dq (f32, same pitch) is
     // scratch for units whose keys exceed one key group
-    int io_bf16 = 0;
+    Elem io_fmt = Elem::F32;
     void *dq16 = nullptr, *dk16 = nullptr, *dv16 = nullptr;
-    // ... and dout is a BFLOAT16 matrix (pitch ldo, in values; ldo % 8 == 0): with io_bf16 and the bf16 products only
+    // ... and dout is a BFLOAT16 matrix (pitch ldo, in values; ldo % 8 == 0): with BF16 q / k / v and the bf16 products only
     // (attention_bwd_dout_bf16_enabled())
-    int dout_bf16 = 0;
-    int o_bf16 = 0;  // ... and o as well (with dout_bf16): the forward kept only the bfloat16 output rows
+    Elem dout_fmt = Elem::F32;
+    Elem o_fmt = Elem::F32;  // ... and o as well (with a BF16 dout): the forward kept only the bfloat16 output rows
 };
+// all f32, or bfloat16 q / k / v / gradients; then dout may be bfloat16 too, and with it o
+constexpr bool attn_bwd_formats_ok(Elem io, Elem dout, Elem o) {
+    return (io == Elem::F32 || io == Elem::BF16) && (dout == Elem::F32 || (dout == Elem::BF16 && io == Elem::BF16)) &&
+           (o == Elem::F32 || (o == Elem::BF16 && dout == Elem::BF16));
+}
+static_assert(attn_bwd_formats_ok(Elem::F32, Elem::F32, Elem::F32) && attn_bwd_formats_ok(Elem::BF16, Elem::BF16, Elem::BF16));
+static_assert(!attn_bwd_formats_ok(Elem::F32, Elem::BF16, Elem::F32) && !attn_bwd_formats_ok(Elem::BF16, Elem::F32, Elem::BF16) &&
+              !attn_bwd_formats_ok(Elem::F16, Elem::F32, Elem::F32));
 bool attention_bwd_dout_bf16_enabled();
 int launch_attention_bwd(const AttnBwdDesc& d, hipStream_t s);
 bool attention_bwd_bf16_supported(const AttnBwdDesc& d);
@@ -318,12 +354,16 @@ struct GroupNormBwdDesc {
     // ntok is then the LARGEST token count (it selects the kernel shape)
     const int4* units;
     void* dx16 = nullptr;  // optional (round 6, bf16 steps): dx once more as bfloat16 rows, same pitch (C values)
-    int x_bf16 = 0;        // round 6: x is a bfloat16 matrix (the bf16 step's pre-norm rows), same pitch
+    Elem x_fmt = Elem::F32;    // BF16 (round 6): x is a bfloat16 matrix (the bf16 step's pre-norm rows), same pitch
     // optional (round 6): (mean, rstd) of every (instance, group) unit as the forward computed them (GroupNormDesc::stats_out) - the
     // three-pass kernel of the largest units then skips its two statistics walks over x (the register shapes recompute: x is in registers)
     const void* stats_in = nullptr;
-    int dy2_bf16 = 0;  // round 6: dy2 is a bfloat16 matrix (same pitch)
+    Elem dy2_fmt = Elem::F32;  // BF16 (round 6): dy2 is a bfloat16 matrix (same pitch)
 };
+constexpr bool group_norm_bwd_formats_ok(Elem x_fmt, Elem dy2_fmt) {
+    return (x_fmt == Elem::F32 || x_fmt == Elem::BF16) && (dy2_fmt == Elem::F32 || dy2_fmt == Elem::BF16);
+}
+static_assert(group_norm_bwd_formats_ok(Elem::BF16, Elem::F32) && !group_norm_bwd_formats_ok(Elem::F16, Elem::F32));
 int launch_group_norm_bwd(const GroupNormBwdDesc& d, hipStream_t s);
 bool group_norm_bwd_dy2_bf16_supported(int ntok, int C, int groups);  // the shapes whose kernels read a bfloat16 dy2 (all but the 1024-thread register shape)
 struct WsBwdLayer {
@@ -396,12 +436,11 @@ struct GroupNormDesc {
     float eps, slope;
     int leaky;
     DropoutCfg drop;
-    int out_sp16;  // y / y2 written as split-f16 pairs
-    int* guard;    // out_sp16, optional: range guard word (see GemmDesc::guard)
+    Elem in, out;  // x: F32, F16 (16-bit storage mode) or BF16 (round 6) rows; y / y2: F32, SP16 or F16.  Statistics stay f32
+    int* guard;    // SP16 / F16 out, optional: range guard word (see GemmDesc::guard)
     // optional, ragged batches: instance i covers the tokens units[i] = (first row, row stride, token count, pe row) instead
     // of the strided pattern above; ntok is then the LARGEST token count (it selects the kernel shape)
     const int4* units;
-    int in_f16, out_f16;  // 16-bit storage mode: x / (y, y2) are _Float16 matrices (statistics stay f32); in_f16 == 2: x is a BFLOAT16 matrix (round 6)
     const float* in_scale_dev;  // optional: x is multiplied by this device scalar while it is read (an input stored in scaled units)
     // optional scratch of the sliced shape (units beyond the register shapes): 8 bytes per (unit, 256-token slice); the forward
     // orchestrators pass a piece of the caller's workspace (concurrent calls on one device must not share it); null = a
@@ -409,18 +448,26 @@ struct GroupNormDesc {
     void* slice_ws;
     size_t slice_ws_bytes;
     // optional, f32 outputs only (training forward with 16-bit GEMM operands): besides y / y2 the kernel also writes their casts in
-    // the format the NEXT GEMM takes as its operand, unscaled - cast_fmt 2: plain f16, 3: bfloat16 - so the operand cast launch (a
+    // the format the NEXT GEMM takes as its operand, unscaled - cast F16 or BF16 - so the operand cast launch (a
     // read of y and a write of the cast) disappears.  Same row pitch C as y.  (Split-f16 pairs were tried too: the pair shuffles and
     // 16 more bytes per lane cost the norm what the cast launch saved - 34.2 vs 34.3 ms per ragged step.)
     void* y_cast = nullptr;
     void* y2_cast = nullptr;
-    int cast_fmt = 0;
+    Elem cast = Elem::F32;  // format of y_cast / y2_cast (F32: there are none)
     // optional (round 6, training forward of the largest units): where the sliced shape leaves (mean, rstd) of every (instance, group) unit
     // - [n_inst * groups] pairs - for the backward (GroupNormBwdDesc::stats_in); *stats_written (host) is set to 1 when the launch took
     // that shape and wrote them, left alone otherwise
     void* stats_out = nullptr;
     int* stats_written = nullptr;
 };
+// operand casts are plain 16-bit rows beside f32 outputs
+constexpr bool group_norm_formats_ok(Elem in, Elem out, Elem cast) {
+    return in != Elem::SP16 && out != Elem::BF16 && (cast == Elem::F32 || (is_row16(cast) && out == Elem::F32));
+}
+static_assert(group_norm_formats_ok(Elem::BF16, Elem::F32, Elem::BF16) && group_norm_formats_ok(Elem::F16, Elem::F16, Elem::F32));
+static_assert(!group_norm_formats_ok(Elem::F32, Elem::BF16, Elem::F32), "no bfloat16 output");
+static_assert(!group_norm_formats_ok(Elem::F32, Elem::F32, Elem::SP16) && !group_norm_formats_ok(Elem::F32, Elem::SP16, Elem::F16),
+              "operand casts are F16 or BF16 and go with f32 outputs");
 int launch_group_norm(const GroupNormDesc& d, hipStream_t s);
 // side16 (optional): also the plain f16 cast of the same values, contiguous [rows][K] halfs (= the hi halves)
 int launch_cast_sp16(const float* in, int ld_in, float* out, int ld_out, long long rows, int K, float scale, hipStream_t s, void* side16 = nullptr);
@@ -454,14 +501,14 @@ int launch_cast_sp16_multi(const CastJob* jobs, int n, float scale, hipStream_t 
 // f32 rows -> plain _Float16 rows (16-bit storage mode).  scal != null: data-dependent power-of-two scale as above (scal[1]
 // receives its inverse), else the fixed `scale`.  ld_out counts halfs.
 // target_exp: the largest magnitude lands in [2^target_exp, 2^(target_exp+1)); scale_out (optional, device): receives the scale itself
-// bf16 = 1 (every launcher of this group): the 16-bit values are bfloat16 (round to nearest even) instead of f16 - same bytes, same
-// layouts; the GEMM that consumes them gets GemmDesc::bf16
-int launch_cast_f16(const float* in, int ld_in, void* out, int ld_out, long long rows, int K, float scale, float* scal, hipStream_t s,
-                    int target_exp = 13, float* scale_out = nullptr, int bf16 = 0);
-int launch_cast_f16_auto_multi(const float* const* in, void* const* out, int n, int rows, int K, float* scal, hipStream_t s, int bf16 = 0);
-int launch_cast_f16_scaled(const float* in, int ld_in, void* out, int ld_out, long long rows, int K, float* scal, hipStream_t s, int bf16 = 0);
-// transposing cast to plain f16: in [rows][cols] f32 -> out [cols][ld_out halfs] (ld_out % 128 == 0, zero-filled past rows)
-int launch_cast_f16_t(const float* in, int ld_in, void* out, long long ld_out, int rows, int cols, float* scal, hipStream_t s, int bf16 = 0);
+// fmt (every launcher of this group): F16, or BF16 - the 16-bit values are bfloat16 (round to nearest even) instead of f16: same bytes,
+// same layouts
+int launch_cast_f16(const float* in, int ld_in, void* out, int ld_out, long long rows, int K, float scale, float* scal, Elem fmt, hipStream_t s,
+                    int target_exp = 13, float* scale_out = nullptr);
+int launch_cast_f16_auto_multi(const float* const* in, void* const* out, int n, int rows, int K, float* scal, Elem fmt, hipStream_t s);
+int launch_cast_f16_scaled(const float* in, int ld_in, void* out, int ld_out, long long rows, int K, float* scal, Elem fmt, hipStream_t s);
+// transposing cast to plain 16-bit values: in [rows][cols] f32 -> out [cols][ld_out values] (ld_out % 128 == 0, zero-filled past rows)
+int launch_cast_f16_t(const float* in, int ld_in, void* out, long long ld_out, int rows, int cols, float* scal, Elem fmt, hipStream_t s);
 // Weight-time range check of the split-f16 activations: a GroupNorm output has E[y^2] = gamma^2 + beta^2 per channel (its
 // input is normalised), so the magnitude of every tensor the norms emit is known from the weights alone.  Sets bit 1 of
 // *guard when the rms of any (gamma, beta) pair lies outside [2^-6, 2^9] - where the fixed-scale split-f16 activations would

@@ -375,7 +375,7 @@ int g_attn_ring = 0;  // sola_tune "attn_ring": 1 = this shape where attn_simple
 // f32 q / k / v, head_dim 128, inference (no log-sum-exp, no dropout), more than 16 keys or queries; the byte offsets inside a unit fit
 // the buffer instructions' 32-bit offsets
 bool attention_ring_supported(const AttnDesc& d) {
-    if (!g_attn_ring || d.lse || d.drop.enabled || d.in_sp16 || d.split_math || d.DH != 128 || d.k_private > 0) return false;
+    if (!g_attn_ring || d.lse || d.drop.enabled || d.in == Elem::SP16 || d.split_math || d.DH != 128 || d.k_private > 0) return false;
     if (!(d.Sq > 16 || d.Sk > 16)) return false;
     const long long k_rs = d.q_units ? 64 : d.k_rs, q_rs = d.q_units ? 64 : d.q_rs;  // unit tables: row strides are at most T' (<= 64)
     const long long kb = ((long long)d.Sk + 16) * k_rs * std::max(d.ldk, d.ldv) * 4, qb = 80 * q_rs * d.ldq * 4;

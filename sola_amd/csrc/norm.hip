@@ -742,14 +742,14 @@ int launch_group_norm(const GroupNormDesc& d, hipStream_t s) {
     GnArgs a;
     a.x = d.x; a.y = d.y; a.y2 = d.y2; a.pe = d.pe; a.gamma = d.gamma; a.beta = d.beta;
     a.inner = d.inner; a.outer_stride = d.outer_stride; a.inner_stride = d.inner_stride; a.tok_stride = d.tok_stride;
-    a.ntok = d.ntok; a.C = d.C; a.cg = cg; a.groups = d.groups; a.eps = d.eps; a.slope = d.slope; a.leaky = d.leaky; a.drop = d.drop; a.out_sp16 = d.out_sp16; a.guard = (d.out_sp16 || d.out_f16) ? d.guard : nullptr; a.units = d.units;
-    a.in_f16 = d.in_f16; a.out_f16 = d.out_f16; a.in_scale_dev = d.in_scale_dev;
-    a.y_cast = d.y_cast; a.y2_cast = d.y2_cast; a.cast_fmt = (d.y_cast || d.y2_cast) ? d.cast_fmt : 0;
+    a.ntok = d.ntok; a.C = d.C; a.cg = cg; a.groups = d.groups; a.eps = d.eps; a.slope = d.slope; a.leaky = d.leaky; a.drop = d.drop; a.out_sp16 = d.out == Elem::SP16; a.guard = d.out != Elem::F32 ? d.guard : nullptr; a.units = d.units;
+    a.in_f16 = d.in == Elem::BF16 ? 2 : (d.in == Elem::F16 ? 1 : 0); a.out_f16 = d.out == Elem::F16; a.in_scale_dev = d.in_scale_dev;
+    a.y_cast = d.y_cast; a.y2_cast = d.y2_cast; a.cast_fmt = (d.y_cast || d.y2_cast) ? (int)d.cast : 0;  // (the kernel's own codes: 2 f16, 3 bf16)
     a.stats_out = static_cast<float2*>(d.stats_out);
-    SOLA_ARG(a.cast_fmt == 0 || (!d.out_sp16 && !d.out_f16 && a.cast_fmt >= 2 && a.cast_fmt <= 3 && (!d.y2_cast || d.y2)),
-             "group_norm: operand casts go with f32 outputs (format 2 = f16, 3 = bf16)");
-    SOLA_ARG(!(d.out_f16 && d.out_sp16), "group_norm: one output format at a time");
-    SOLA_ARG(!d.out_sp16 || cg % 8 == 0, "group_norm: split-f16 output needs channels per group %% 8 == 0");
+    SOLA_ARG(group_norm_formats_ok(d.in, d.out, a.cast_fmt ? d.cast : Elem::F32), "group_norm: no kernel for %s rows in, %s rows out and %s operand casts (f16 / bf16 beside f32 outputs)",
+             elem_name(d.in), elem_name(d.out), elem_name(d.cast));
+    SOLA_ARG(a.cast_fmt == 0 || !d.y2_cast || d.y2, "group_norm: y2_cast needs y2");
+    SOLA_ARG(d.out != Elem::SP16 || cg % 8 == 0, "group_norm: split-f16 output needs channels per group %% 8 == 0");
     const double elems = (double)d.n_inst * d.ntok * d.C;
     SolaProfScope prof(SOLA_PROF_NORM, s, 8.0 * elems, (d.y2 ? 12.0 : 8.0) * elems);
     const int f4 = cg / 4;
@@ -759,7 +759,7 @@ int launch_group_norm(const GroupNormDesc& d, hipStream_t s) {
     const int rb = 256 % f4 == 0 ? (d.ntok + 256 / f4 - 1) / (256 / f4) : 1 << 30;  // ... one block per unit
     // 16-bit storage mode: eight channels (16 bytes) per lane where the unit fits the register shapes
     const int f8 = cg / 8;
-    const bool h8 = g_gn_variant != 0 && g_gn_h8 && d.in_f16 && d.out_f16 && !d.drop.enabled && cg % 8 == 0 && n_units < (1ll << 31);
+    const bool h8 = g_gn_variant != 0 && g_gn_h8 && d.in != Elem::F32 && d.out == Elem::F16 && !d.drop.enabled && cg % 8 == 0 && n_units < (1ll << 31);
     const int rw8 = (h8 && 64 % f8 == 0) ? (d.ntok + 64 / f8 - 1) / (64 / f8) : 1 << 30;
     const int rb8 = (h8 && 256 % f8 == 0) ? (d.ntok + 256 / f8 - 1) / (256 / f8) : 1 << 30;
     const int rk8 = (h8 && 1024 % f8 == 0) ? (d.ntok + 1024 / f8 - 1) / (1024 / f8) : 1 << 30;

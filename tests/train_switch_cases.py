@@ -122,7 +122,7 @@ NOT_TRAINING = {
     "attn_f16_small": "attn_f16.hip launch_h<.., TRAIN = false>: the plain-f16 inference forward's streaming shape",
     "lang_shared_neg": "forward_infer.hip: the negative tokens' text-side projections of the split-f16 inference forward",
     "infer_f32_rows": "api.hip few_rows_f32: sola_forward / sola_forward_ragged only",
-    "gn_h8": "norm.hip: needs 16-bit input AND output rows (GroupNormDesc::out_f16), which only the plain-f16 inference forward sets",
+    "gn_h8": "norm.hip: needs 16-bit input AND output rows (GroupNormDesc::out F16), which only the plain-f16 inference forward sets",
     "bilinear_staged": "masklet.hip: mask resampling",
     "iou_fused": "iou.hip: sola_mask_iou_matrix",
     "iou_shape": "iou.hip: block shape of the one-launch IoU kernel",

@@ -86,6 +86,21 @@ static void put_arrays(const ColsumPairGroupDesc& d) {
 static void put_arrays(const ColsumJobsDesc& d) {
     for (int j = 0; j < d.n; ++j) printf("  [%d] %s %s %d %d %d\n", j, ptr_str(d.in[j]).c_str(), ptr_str(d.out[j]).c_str(), d.rows[j], d.cols[j], d.ld[j]);
 }
+// the element formats a descriptor or a launcher call carries, as one canonical line behind it (the struct dump shows Elem fields as integers)
+static int fmt_line(const char* k0, Elem e0, const char* k1 = nullptr, Elem e1 = Elem::F32, const char* k2 = nullptr, Elem e2 = Elem::F32) {
+    printf("fmt %s=%s", k0, elem_name(e0));
+    if (k1) printf(" %s=%s", k1, elem_name(e1));
+    if (k2) printf(" %s=%s", k2, elem_name(e2));
+    fputc('\n', stdout);
+    return SOLA_OK;
+}
+template <class T> void put_formats(const T&) {}
+static void put_formats(const GemmDesc& d) { fmt_line("ab", d.ab, "r", d.r, "c", d.c); }
+static void put_formats(const GemmTnSplitDesc& d) { fmt_line("ab", d.ab, "rm", d.rm_fmt, "b16", d.b16_fmt); }
+static void put_formats(const AttnDesc& d) { fmt_line("in", d.in, "out", d.out, "cast", d.cast); }
+static void put_formats(const AttnBwdDesc& d) { fmt_line("io", d.io_fmt, "dout", d.dout_fmt, "o", d.o_fmt); }
+static void put_formats(const GroupNormDesc& d) { fmt_line("in", d.in, "out", d.out, "cast", d.cast); }
+static void put_formats(const GroupNormBwdDesc& d) { fmt_line("x", d.x_fmt, "dy2", d.dy2_fmt); }
 template <class T> void put(const T& v) {
     if constexpr (std::is_pointer<T>::value) printf(" %s", ptr_str(reinterpret_cast<const void*>(v)).c_str());
     else if constexpr (std::is_floating_point<T>::value) printf(" %.9g", (double)v);
@@ -94,6 +109,7 @@ template <class T> void put(const T& v) {
         fputc('\n', stdout);
         __builtin_dump_struct(&v, rec_printf);
         put_arrays(v);
+        put_formats(v);
     }
 }
 template <class... A> int rec(const char* name, const A&... a) {
@@ -111,18 +127,18 @@ int launch_attention(AttnDesc const& a0, hipStream_t a1) { int r = rec("launch_a
 int launch_attention_bwd(AttnBwdDesc const& a0, hipStream_t a1) { return rec("launch_attention_bwd",  a0, a1); }
 int launch_attention_f16(AttnDesc const& a0, hipStream_t a1) { return rec("launch_attention_f16",  a0, a1); }
 int launch_cast_bf16_colsum(float const* a0, int a1, void* a2, int a3, long long a4, int a5, float* a6, float* a7, hipStream_t a8) { return rec("launch_cast_bf16_colsum",  a0, a1, a2, a3, a4, a5, a6, a7, a8); }
-int launch_cast_f16(float const* a0, int a1, void* a2, int a3, long long a4, int a5, float a6, float* a7, hipStream_t a8, int a9, float* a10, int a11) { return rec("launch_cast_f16",  a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, a10, a11); }
-int launch_cast_f16_auto_multi(float const* const* a0, void* const* a1, int a2, int a3, int a4, float* a5, hipStream_t a6, int a7) { rec("launch_cast_f16_auto_multi", a2,a3,a4,a5,a6,a7); put_list(a0, a2); put_list(a1, a2); fputc(10, stdout); return SOLA_OK; }
-int launch_cast_f16_scaled(float const* a0, int a1, void* a2, int a3, long long a4, int a5, float* a6, hipStream_t a7, int a8) { return rec("launch_cast_f16_scaled",  a0, a1, a2, a3, a4, a5, a6, a7, a8); }
-int launch_cast_f16_t(float const* a0, int a1, void* a2, long long a3, int a4, int a5, float* a6, hipStream_t a7, int a8) { return rec("launch_cast_f16_t",  a0, a1, a2, a3, a4, a5, a6, a7, a8); }
+int launch_cast_f16(float const* a0, int a1, void* a2, int a3, long long a4, int a5, float a6, float* a7, Elem fmt, hipStream_t a8, int a9, float* a10) { rec("launch_cast_f16",  a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, a10); return fmt_line("out", fmt); }
+int launch_cast_f16_auto_multi(float const* const* a0, void* const* a1, int a2, int a3, int a4, float* a5, Elem fmt, hipStream_t a6) { rec("launch_cast_f16_auto_multi", a2,a3,a4,a5,a6); put_list(a0, a2); put_list(a1, a2); fputc(10, stdout); return fmt_line("out", fmt); }
+int launch_cast_f16_scaled(float const* a0, int a1, void* a2, int a3, long long a4, int a5, float* a6, Elem fmt, hipStream_t a7) { rec("launch_cast_f16_scaled",  a0, a1, a2, a3, a4, a5, a6, a7); return fmt_line("out", fmt); }
+int launch_cast_f16_t(float const* a0, int a1, void* a2, long long a3, int a4, int a5, float* a6, Elem fmt, hipStream_t a7) { rec("launch_cast_f16_t",  a0, a1, a2, a3, a4, a5, a6, a7); return fmt_line("out", fmt); }
 int launch_cast_sp16(float const* a0, int a1, float* a2, int a3, long long a4, int a5, float a6, hipStream_t a7, void* a8) { return rec("launch_cast_sp16",  a0, a1, a2, a3, a4, a5, a6, a7, a8); }
 int launch_cast_sp16_auto(float const* a0, int a1, float* a2, int a3, long long a4, int a5, float* a6, hipStream_t a7) { return rec("launch_cast_sp16_auto",  a0, a1, a2, a3, a4, a5, a6, a7); }
 int launch_cast_sp16_auto_multi(float const* const* a0, float* const* a1, int a2, int a3, int a4, float* a5, hipStream_t a6) { rec("launch_cast_sp16_auto_multi", a2,a3,a4,a5,a6); put_list(a0, a2); put_list(a1, a2); fputc(10, stdout); return SOLA_OK; }
 int launch_cast_sp16_multi(CastJob const* a0, int a1, float a2, hipStream_t a3) { rec("launch_cast_sp16_multi", a1,a2,a3); put_list(a0, a1); return SOLA_OK; }
 int launch_cast_sp16_scaled(float const* a0, int a1, float* a2, int a3, long long a4, int a5, float* a6, hipStream_t a7) { return rec("launch_cast_sp16_scaled",  a0, a1, a2, a3, a4, a5, a6, a7); }
 int launch_cast_sp16_t(float const* a0, int a1, float* a2, long long a3, int a4, int a5, float* a6, hipStream_t a7) { return rec("launch_cast_sp16_t",  a0, a1, a2, a3, a4, a5, a6, a7); }
-int launch_col2im(float const* a0, float* a1, long long a2, int a3, int a4, int a5, int a6, int a7, int a8, hipStream_t a9, int a10) { return rec("launch_col2im",  a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, a10); }
-int launch_col2im_ragged(float const* a0, float* a1, long long a2, int4 const* a3, int a4, int a5, int a6, int a7, hipStream_t a8, int a9) { return rec("launch_col2im_ragged",  a0, a1, a2, a3, a4, a5, a6, a7, a8, a9); }
+int launch_col2im(float const* a0, float* a1, long long a2, int a3, int a4, int a5, int a6, int a7, int a8, Elem z_fmt, hipStream_t a9) { rec("launch_col2im",  a0, a1, a2, a3, a4, a5, a6, a7, a8, a9); return fmt_line("z", z_fmt); }
+int launch_col2im_ragged(float const* a0, float* a1, long long a2, int4 const* a3, int a4, int a5, int a6, int a7, Elem z_fmt, hipStream_t a8) { rec("launch_col2im_ragged",  a0, a1, a2, a3, a4, a5, a6, a7, a8); return fmt_line("z", z_fmt); }
 int launch_colsum(float const* a0, float* a1, int a2, int a3, int a4, int a5, float a6, int a7, float* a8, size_t a9, hipStream_t a10) { return rec("launch_colsum",  a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, a10); }
 int launch_colsum_jobs(ColsumJobsDesc const& a0, hipStream_t a1) { return rec("launch_colsum_jobs",  a0, a1); }
 int launch_colsum_pair(float const* a0, float const* a1, float* a2, float* a3, int a4, int a5, int a6, float* a7, size_t a8, hipStream_t a9) { return rec("launch_colsum_pair",  a0, a1, a2, a3, a4, a5, a6, a7, a8, a9); }
@@ -146,7 +162,7 @@ int launch_score_head(HeadDesc const& a0, hipStream_t a1) { return rec("launch_s
 int launch_score_head_bwd(HeadBwdDesc const& a0, hipStream_t a1) { return rec("launch_score_head_bwd",  a0, a1); }
 int launch_segsum_rows(float const* a0, float* a1, int const* a2, int a3, int a4, hipStream_t a5) { return rec("launch_segsum_rows",  a0, a1, a2, a3, a4, a5); }
 int launch_transpose(float const* a0, float* a1, int a2, int a3, int a4, int a5, int a6, hipStream_t a7) { return rec("launch_transpose",  a0, a1, a2, a3, a4, a5, a6, a7); }
-int launch_transpose_cast(float const* a0, void* a1, int a2, int a3, int a4, int a5, int a6, float a7, int a8, hipStream_t a9) { return rec("launch_transpose_cast",  a0, a1, a2, a3, a4, a5, a6, a7, a8, a9); }
+int launch_transpose_cast(float const* a0, void* a1, int a2, int a3, int a4, int a5, int a6, float a7, Elem fmt, hipStream_t a9) { rec("launch_transpose_cast",  a0, a1, a2, a3, a4, a5, a6, a7, a9); return fmt_line("out", fmt); }
 int launch_ws_backward(WsBwdLayer const* a0, int a1, hipStream_t a2) { rec("launch_ws_backward", a1,a2); put_list(a0, a1); return SOLA_OK; }
 int launch_ws_standardize(WsLayer const* a0, int a1, hipStream_t a2) { rec("launch_ws_standardize", a1,a2); put_list(a0, a1); return SOLA_OK; }
 
