@@ -1,6 +1,7 @@
 // Backward of the HBM-bound stages (autograd of module/module.py:76-92,34-49,152-160, module/ws.py:9-13,
 // train.py:98-113, tools/loss.py:29-56).  Same decomposition and deterministic reductions as the forward kernels.
 #include "kernels.h"
+#include "gn_common.h"
 #include <type_traits>
 
 namespace {
@@ -25,15 +26,10 @@ struct GnBwdArgs {
     const float2* stats;   // round 6, three-pass kernel: the forward's (mean, rstd) per (instance, group) - no statistics walks (GroupNormBwdDesc::stats_in)
     int dy2_bf16;          // round 6: dy2 is a bfloat16 matrix of the same pitch (a branch gradient written by its GEMM as bfloat16 rows)
 };
-__device__ __forceinline__ float4 gnb_widen(const uint2 w) {
-    return make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                       __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
-}
 __device__ __forceinline__ float4 gnb_load_x(const GnBwdArgs& a, long long off) {
     if (a.x_bf16) {
         const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.x) + off);
-        return make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                           __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
+        return bf16x4_to_f32(w);
     }
     return *reinterpret_cast<const float4*>(a.x + off);
 }
@@ -47,32 +43,6 @@ __device__ __forceinline__ void gn_store_dx(const GnBwdArgs& a, long long off, f
     }
 }
 
-// token set of instance `inst` (norm.hip: gn_unit)
-struct GnBwdUnit { long long row0, tok_stride; int ntok; };
-__device__ __forceinline__ GnBwdUnit gn_bwd_unit(const GnBwdArgs& a, int inst) {
-    GnBwdUnit u;
-    if (a.units) {
-        const int4 d = a.units[inst];
-        u.row0 = d.x; u.tok_stride = d.y; u.ntok = d.z;
-    } else {
-        u.row0 = (long long)(inst / a.inner) * a.outer_stride + (long long)(inst % a.inner) * a.inner_stride;
-        u.tok_stride = a.tok_stride; u.ntok = a.ntok;
-    }
-    return u;
-}
-
-template <int NTHR>
-__device__ __forceinline__ float bwd_block_sum(float v, float* red) {
-    if (NTHR == 256) return block_sum_256(v, red);
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < NTHR / 64; ++i) t += red[i];
-    return t;
-}
 // NTHR = 1024 (round 3): units beyond the register shapes are the object->language norm's (a sample's N*T' tokens x 128 channels: up
 // to 1 MB per (sample, group)); a launch has only samples x groups blocks and its time is the longest block's four walks over
 // its unit - four times the threads move the unit four times as fast (515 -> ~200 us per launch on the MeViS-like mix).
@@ -88,7 +58,7 @@ __global__ __launch_bounds__(NTHR) void group_norm_bwd_kernel(const GnBwdArgs a)
     const int tpp = NTHR / lpt;
     const int tl = threadIdx.x / lpt;
     const int c4 = threadIdx.x - tl * lpt;
-    const GnBwdUnit un = gn_bwd_unit(a, inst);
+    const GnUnit un = gn_unit(a, inst);
     const long long row0 = un.row0, tok_stride = un.tok_stride;
     const int ntok = un.ntok;
     const int ch = g * a.cg + c4 * 4;
@@ -106,7 +76,7 @@ __global__ __launch_bounds__(NTHR) void group_norm_bwd_kernel(const GnBwdArgs a)
                 const float4 v = gnb_load_x(a, (row0 + (long long)t * tok_stride) * a.C + ch);
                 s += (v.x + v.y) + (v.z + v.w);
             }
-        mean = bwd_block_sum<NTHR>(s, red) / cnt;
+        mean = block_sum_n<NTHR>(s, red) / cnt;
         float q = 0.f;
         if (active)
             for (int t = tl; t < ntok; t += tpp) {
@@ -114,7 +84,7 @@ __global__ __launch_bounds__(NTHR) void group_norm_bwd_kernel(const GnBwdArgs a)
                 const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
                 q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
             }
-        const float var = bwd_block_sum<NTHR>(q, red) / cnt;
+        const float var = block_sum_n<NTHR>(q, red) / cnt;
         rstd = 1.0f / sqrtf(var + a.eps);
     }
 
@@ -154,8 +124,7 @@ __global__ __launch_bounds__(NTHR) void group_norm_bwd_kernel(const GnBwdArgs a)
                 offs[u] = (row0 + (long long)(t < ntok ? t : tl) * tok_stride) * a.C + ch;
                 if constexpr (XB) {
                     const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.x) + offs[u]);
-                    xr[u] = make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                                        __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
+                    xr[u] = bf16x4_to_f32(w);
                 } else {
                     xr[u] = *reinterpret_cast<const float4*>(a.x + offs[u]);
                 }
@@ -164,7 +133,7 @@ __global__ __launch_bounds__(NTHR) void group_norm_bwd_kernel(const GnBwdArgs a)
             if (a.dy2 && a.dy2_bf16) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const float4 e = gnb_widen(*reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.dy2) + offs[u]));
+                    const float4 e = bf16x4_to_f32(*reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.dy2) + offs[u]));
                     dr[u].x += e.x; dr[u].y += e.y; dr[u].z += e.z; dr[u].w += e.w;
                 }
             } else if (a.dy2) {
@@ -194,8 +163,8 @@ __global__ __launch_bounds__(NTHR) void group_norm_bwd_kernel(const GnBwdArgs a)
         if (a.x_bf16) walk(std::true_type{}, sums);
         else walk(std::false_type{}, sums);
     }
-    const float m1 = bwd_block_sum<NTHR>(s1, red) / cnt;
-    const float m2 = bwd_block_sum<NTHR>(s2, red) / cnt;
+    const float m1 = block_sum_n<NTHR>(s1, red) / cnt;
+    const float m2 = block_sum_n<NTHR>(s2, red) / cnt;
     // per-channel partials: reduce the token slots that share a channel quad
     float* pp = &part[threadIdx.x * 8];
     pp[0] = dgam.x; pp[1] = dgam.y; pp[2] = dgam.z; pp[3] = dgam.w;
@@ -246,7 +215,7 @@ __global__ __launch_bounds__(NTHR, (NTHR == 256 && !WAVE) ? (R <= 2 ? 8 : (R == 
     const int inst = (int)(unit / groups), g = (int)(unit - (long long)inst * groups);
     const int tpp = nthr / f4;
     const int tl = tid / f4, c4 = tid - tl * f4;
-    const GnBwdUnit un = gn_bwd_unit(a, inst);
+    const GnUnit un = gn_unit(a, inst);
     const long long row0 = un.row0, tok_stride = un.tok_stride;
     const int ntok = un.ntok;
     const int ch = g * a.cg + c4 * 4;
@@ -277,8 +246,7 @@ __global__ __launch_bounds__(NTHR, (NTHR == 256 && !WAVE) ? (R <= 2 ? 8 : (R == 
             float4 xr;
             if constexpr (XB) {
                 const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.x) + off);
-                xr = make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                                 __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
+                xr = bf16x4_to_f32(w);
             } else {
                 xr = *reinterpret_cast<const float4*>(a.x + off);
             }
@@ -298,7 +266,7 @@ __global__ __launch_bounds__(NTHR, (NTHR == 256 && !WAVE) ? (R <= 2 ? 8 : (R == 
             const int t = tl + r * tpp;
             const bool ok = t < ntok;
             const long long off = (row0 + (long long)(ok ? t : 0) * tok_stride) * a.C + ch;
-            const float4 e = gnb_widen(*reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.dy2) + off));
+            const float4 e = bf16x4_to_f32(*reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.dy2) + off));
             dv[r].x += ok ? e.x : 0.f; dv[r].y += ok ? e.y : 0.f; dv[r].z += ok ? e.z : 0.f; dv[r].w += ok ? e.w : 0.f;
         }
     } else if (a.dy2) {  // block-uniform: the second gradient of the inter-object norm (x_obj feeds x_obj + pe too)
@@ -311,7 +279,7 @@ __global__ __launch_bounds__(NTHR, (NTHR == 256 && !WAVE) ? (R <= 2 ? 8 : (R == 
             dv[r].x += ok ? e.x : 0.f; dv[r].y += ok ? e.y : 0.f; dv[r].z += ok ? e.z : 0.f; dv[r].w += ok ? e.w : 0.f;
         }
     }
-    const float mean = (WAVE ? wave_sum(s) : bwd_block_sum<NTHR>(s, red)) / cnt;
+    const float mean = (WAVE ? wave_sum(s) : block_sum_n<NTHR>(s, red)) / cnt;
     float q = 0.f;
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -319,7 +287,7 @@ __global__ __launch_bounds__(NTHR, (NTHR == 256 && !WAVE) ? (R <= 2 ? 8 : (R == 
             const float d0 = xv[r].x - mean, d1 = xv[r].y - mean, d2 = xv[r].z - mean, d3 = xv[r].w - mean;
             q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
         }
-    const float var = (WAVE ? wave_sum(q) : bwd_block_sum<NTHR>(q, red)) / cnt;
+    const float var = (WAVE ? wave_sum(q) : block_sum_n<NTHR>(q, red)) / cnt;
     const float rstd = 1.0f / sqrtf(var + a.eps);
     if constexpr (R > 4) {
         ga = *reinterpret_cast<const float4*>(a.gamma + ch);
@@ -355,8 +323,8 @@ __global__ __launch_bounds__(NTHR, (NTHR == 256 && !WAVE) ? (R <= 2 ? 8 : (R == 
             dv[r] = make_float4(g0, g1, g2, g3);   // dy' * gamma
         }
     }
-    const float m1 = (WAVE ? wave_sum(s1) : bwd_block_sum<NTHR>(s1, red)) / cnt;
-    const float m2 = (WAVE ? wave_sum(s2) : bwd_block_sum<NTHR>(s2, red)) / cnt;
+    const float m1 = (WAVE ? wave_sum(s1) : block_sum_n<NTHR>(s1, red)) / cnt;
+    const float m2 = (WAVE ? wave_sum(s2) : block_sum_n<NTHR>(s2, red)) / cnt;
     // per-channel partials: add up the token lanes that share a channel quad (fixed order)
     const long long po = (long long)inst * a.C + g * a.cg + c4 * 4;
     if (WAVE) {
@@ -708,20 +676,8 @@ int launch_segsum_rows(const float* in, float* out, const int32_t* off, int segm
 
 int g_gn_bwd_reg = 1;  // sola_tune "gn_bwd_reg": 0 = three-pass kernel for every shape (A/B)
 
-// which kernel launch_group_norm_bwd picks for units of at most `ntok` tokens: the 1024-thread register shape (17..32 float4 per lane of a
-// 256-thread block) has no bfloat16-dy2 code
-static bool gn_bwd_takes_reg1024(int ntok, int cg) {
-    const int f4 = cg / 4;
-    const bool pow2 = (f4 & (f4 - 1)) == 0;
-    if (!g_gn_bwd_reg || !pow2 || f4 > 256) return false;
-    const int rw = f4 <= 64 ? (ntok + 64 / f4 - 1) / (64 / f4) : 1 << 30;
-    const int rb = (ntok + 256 / f4 - 1) / (256 / f4);
-    if (rw <= 4 || rb <= 8) return false;
-    if (rb <= 16 && 512 % f4 == 0) return false;
-    return rb <= 32 && 1024 % f4 == 0;
-}
 bool group_norm_bwd_dy2_bf16_supported(int ntok, int C, int groups) {
-    return groups > 0 && C % groups == 0 && (C / groups) % 4 == 0 && !gn_bwd_takes_reg1024(ntok, C / groups);
+    return groups > 0 && C % groups == 0 && (C / groups) % 4 == 0 && gn_bwd_reads_bf16_dy2(gn_bwd_shape(ntok, C / groups, g_gn_bwd_reg));
 }
 
 int launch_group_norm_bwd(const GroupNormBwdDesc& d, hipStream_t s) {
@@ -738,36 +694,28 @@ int launch_group_norm_bwd(const GroupNormBwdDesc& d, hipStream_t s) {
     a.x_bf16 = d.x_fmt == Elem::BF16;
     a.stats = static_cast<const float2*>(d.stats_in);
     a.dy2_bf16 = (d.dy2 && d.dy2_fmt == Elem::BF16) ? 1 : 0;
-    SOLA_ARG(!a.dy2_bf16 || group_norm_bwd_dy2_bf16_supported(d.ntok, d.C, d.groups), "group_norm_bwd: a bfloat16 dy2 is not read by this shape's kernel");
+    const GnShape sh = gn_bwd_shape(d.ntok, cg, g_gn_bwd_reg);
+    SOLA_ARG(!a.dy2_bf16 || gn_bwd_reads_bf16_dy2(sh), "group_norm_bwd: a bfloat16 dy2 is not read by this shape's kernel");
     const double elems = (double)d.n_inst * d.ntok * d.C;
     SolaProfScope prof(SOLA_PROF_NORM, s, 20.0 * elems, (d.dy2 ? 16.0 : 12.0) * elems);
-    const int f4 = cg / 4;
-    const bool pow2 = (f4 & (f4 - 1)) == 0;
     const long long n_units = (long long)d.n_inst * d.groups;
     SOLA_ARG(n_units < (1ll << 31), "group_norm_bwd: %lld (instance, group) units exceed the grid", n_units);
-    const int rw = pow2 && f4 <= 64 ? (d.ntok + 64 / f4 - 1) / (64 / f4) : 1 << 30;    // float4 per lane and tensor, one wave per unit
-    const int rb = pow2 && f4 <= 256 ? (d.ntok + 256 / f4 - 1) / (256 / f4) : 1 << 30;  // ... one block per unit
-    if (g_gn_bwd_reg && rw <= 4 && n_units < (1ll << 31)) {
-        const dim3 grid((unsigned)((n_units + 3) / 4));
-        if (rw == 1) hipLaunchKernelGGL((group_norm_bwd_reg_kernel<1, true>), grid, dim3(256), 0, s, a, n_units, d.groups);
-        else if (rw == 2) hipLaunchKernelGGL((group_norm_bwd_reg_kernel<2, true>), grid, dim3(256), 0, s, a, n_units, d.groups);
-        else hipLaunchKernelGGL((group_norm_bwd_reg_kernel<4, true>), grid, dim3(256), 0, s, a, n_units, d.groups);
-    } else if (g_gn_bwd_reg && rb <= 8 && n_units < (1ll << 31)) {
-        const dim3 grid((unsigned)n_units);
-        if (rb <= 2) hipLaunchKernelGGL((group_norm_bwd_reg_kernel<2, false>), grid, dim3(256), 0, s, a, n_units, d.groups);
-        else if (rb <= 4) hipLaunchKernelGGL((group_norm_bwd_reg_kernel<4, false>), grid, dim3(256), 0, s, a, n_units, d.groups);
-        else hipLaunchKernelGGL((group_norm_bwd_reg_kernel<8, false>), grid, dim3(256), 0, s, a, n_units, d.groups);
-    } else if (g_gn_bwd_reg && rb <= 16 && pow2 && f4 <= 256 && 512 % f4 == 0 && n_units < (1ll << 31)) {
-        // units of up to twice the 256-thread shape (ragged batches: the inter-object norm over up to 128 tracks): 512 threads at 8
-        // float4 per lane and tensor - the 1024-thread shape leaves most of its lanes idle on them (407 -> ~220 us per launch)
-        hipLaunchKernelGGL((group_norm_bwd_reg_kernel<8, false, 512>), dim3((unsigned)n_units), dim3(512), 0, s, a, n_units, d.groups);
-    } else if (g_gn_bwd_reg && rb <= 32 && pow2 && f4 <= 256 && 1024 % f4 == 0 && n_units < (1ll << 31)) {
-        hipLaunchKernelGGL((group_norm_bwd_reg_kernel<8, false, 1024>), dim3((unsigned)n_units), dim3(1024), 0, s, a, n_units, d.groups);
-    } else if (g_gn_bwd_reg && (1024 % f4) == 0 && f4 <= 256) {
-        hipLaunchKernelGGL(group_norm_bwd_kernel<1024>, dim3((unsigned)n_units), dim3(1024), 0, s, a);
+    const dim3 grid((unsigned)(sh.kind == GnKind::Wave ? (n_units + 3) / 4 : n_units)), block((unsigned)sh.nthr);
+    const int key = sh.R * 10000 + sh.nthr * 2 + (sh.kind == GnKind::Wave);  // (R, threads per block, WAVE) of the register shapes
+#define GN_REG(R_, WAVE_, NTHR_) \
+    case R_ * 10000 + NTHR_ * 2 + WAVE_: hipLaunchKernelGGL((group_norm_bwd_reg_kernel<R_, WAVE_, NTHR_>), grid, block, 0, s, a, n_units, d.groups); break
+    if (sh.kind == GnKind::ThreePass) {
+        if (sh.nthr == 1024) hipLaunchKernelGGL(group_norm_bwd_kernel<1024>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(group_norm_bwd_kernel<256>, grid, block, 0, s, a);
     } else {
-        hipLaunchKernelGGL(group_norm_bwd_kernel<256>, dim3((unsigned)n_units), dim3(256), 0, s, a);
+        switch (key) {
+            GN_REG(1, true, 256); GN_REG(2, true, 256); GN_REG(4, true, 256);
+            GN_REG(2, false, 256); GN_REG(4, false, 256); GN_REG(8, false, 256);
+            GN_REG(8, false, 512); GN_REG(8, false, 1024);
+            default: SOLA_ARG(false, "group_norm_bwd: no kernel of %d slots at %d threads", sh.R, sh.nthr);
+        }
     }
+#undef GN_REG
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
 }

@@ -11,6 +11,7 @@
 #include <utility>
 
 #include "kernels.h"
+#include "gn_common.h"
 
 namespace {
 
@@ -88,14 +89,12 @@ struct GnArgs {
     float2* stats_out;          // sliced shape only: (mean, rstd) per unit for the backward (GroupNormDesc::stats_out)
 };
 
-typedef _Float16 half4n __attribute__((ext_vector_type(4)));
 // four consecutive channels starting at element offset `off` of x
 __device__ __forceinline__ float4 gn_load(const GnArgs& a, long long off) {
     float4 v;
     if (a.in_f16 == 2) {  // bfloat16 rows (round 6: the bf16 training step's pre-norm activations)
         const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.x) + off);
-        v = make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                        __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
+        v = bf16x4_to_f32(w);
     } else if (a.in_f16) {
         const half4n h = *reinterpret_cast<const half4n*>(reinterpret_cast<const _Float16*>(a.x) + off);
         v = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
@@ -128,8 +127,8 @@ __device__ __forceinline__ void gn_load_slots(const GnArgs& a, float4 (&v)[R], l
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const bool ok = t_first + r * tpp < ntok;
-            v[r] = make_float4(ok ? __builtin_bit_cast(float, h[r].x << 16) * sc : 0.f, ok ? __builtin_bit_cast(float, h[r].x & 0xffff0000u) * sc : 0.f,
-                               ok ? __builtin_bit_cast(float, h[r].y << 16) * sc : 0.f, ok ? __builtin_bit_cast(float, h[r].y & 0xffff0000u) * sc : 0.f);
+            // (widened element by element: behind one widened quad the selects of the register kernels are scheduled differently)
+            v[r] = make_float4(ok ? bf16x4_to_f32(h[r]).x * sc : 0.f, ok ? bf16x4_to_f32(h[r]).y * sc : 0.f, ok ? bf16x4_to_f32(h[r]).z * sc : 0.f, ok ? bf16x4_to_f32(h[r]).w * sc : 0.f);
         }
     } else if (a.in_f16) {
         const _Float16* x = reinterpret_cast<const _Float16*>(a.x);
@@ -156,20 +155,6 @@ __device__ __forceinline__ void gn_load_slots(const GnArgs& a, float4 (&v)[R], l
             v[r] = make_float4(ok ? v[r].x * sc : 0.f, ok ? v[r].y * sc : 0.f, ok ? v[r].z * sc : 0.f, ok ? v[r].w * sc : 0.f);
         }
     }
-}
-
-// The token set of instance `inst`: first row, row stride, token count and the positional-encoding row of the y + pe output.
-struct GnUnit { long long row0, tok_stride; int ntok, pe_row; };
-__device__ __forceinline__ GnUnit gn_unit(const GnArgs& a, int inst) {
-    GnUnit u;
-    if (a.units) {
-        const int4 d = a.units[inst];
-        u.row0 = d.x; u.tok_stride = d.y; u.ntok = d.z; u.pe_row = d.w;
-    } else {
-        u.row0 = (long long)(inst / a.inner) * a.outer_stride + (long long)(inst % a.inner) * a.inner_stride;
-        u.tok_stride = a.tok_stride; u.ntok = a.ntok; u.pe_row = inst % a.inner;
-    }
-    return u;
 }
 
 // normalise + affine (+ LeakyReLU, dropout, the y + pe side output, split-f16 emission) of one float4 and its store
@@ -294,20 +279,6 @@ __global__ __launch_bounds__(256) void group_norm_kernel(const GnArgs a) {
         const long long off = (row0 + (long long)t * tok_stride) * a.C + ch;
         gn_apply_store(a, off, gn_load(a, off), mean, rstd, ga, be, pe, c4);
     }
-}
-
-// Sum over a block of NTHR threads (NTHR / 64 waves); every thread gets the result; fixed combination order.
-template <int NTHR>
-__device__ __forceinline__ float block_sum_n(float v, float* red) {
-    if (NTHR == 256) return block_sum_256(v, red);
-    v = wave_sum(v);
-    __syncthreads();  // protect `red` from a previous use
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < NTHR / 64; ++i) t += red[i];
-    return t;
 }
 
 // Register-resident shape: the whole unit is read ONCE into R float4 per lane, mean and the centred second moment are
@@ -459,7 +430,7 @@ __global__ __launch_bounds__(NTHR) void group_norm_reg_h8_kernel(const GnArgs a,
 //   apply : the slots of the unit are combined in slice order (Chan: M2 = sum M2_i + sum n_i (mean_i - mean)^2), then the
 //           slice is read again, normalised and stored (same epilogue as every other shape).
 // No inter-block waiting.  Traffic 2 reads + 1 write, from (units x slices) blocks.
-constexpr int GNC_R = 32;
+constexpr int GNC_R = GN_SLICE_R;
 struct GncGeo { long long row0, tok_stride, unit; int ntok, pe_row, g, inst, t0, tl, c4, tpp, nslice, sl; };
 __device__ __forceinline__ GncGeo gnc_geo(const GnArgs& a, int S) {
     GncGeo q;
@@ -743,7 +714,7 @@ int launch_group_norm(const GroupNormDesc& d, hipStream_t s) {
     a.x = d.x; a.y = d.y; a.y2 = d.y2; a.pe = d.pe; a.gamma = d.gamma; a.beta = d.beta;
     a.inner = d.inner; a.outer_stride = d.outer_stride; a.inner_stride = d.inner_stride; a.tok_stride = d.tok_stride;
     a.ntok = d.ntok; a.C = d.C; a.cg = cg; a.groups = d.groups; a.eps = d.eps; a.slope = d.slope; a.leaky = d.leaky; a.drop = d.drop; a.out_sp16 = d.out == Elem::SP16; a.guard = d.out != Elem::F32 ? d.guard : nullptr; a.units = d.units;
-    a.in_f16 = d.in == Elem::BF16 ? 2 : (d.in == Elem::F16 ? 1 : 0); a.out_f16 = d.out == Elem::F16; a.in_scale_dev = d.in_scale_dev;
+    a.in_f16 = d.in == Elem::BF16 ? GN_BF16 : (d.in == Elem::F16 ? GN_F16 : GN_F32); a.out_f16 = d.out == Elem::F16; a.in_scale_dev = d.in_scale_dev;
     a.y_cast = d.y_cast; a.y2_cast = d.y2_cast; a.cast_fmt = (d.y_cast || d.y2_cast) ? (int)d.cast : 0;  // (the kernel's own codes: 2 f16, 3 bf16)
     a.stats_out = static_cast<float2*>(d.stats_out);
     SOLA_ARG(group_norm_formats_ok(d.in, d.out, a.cast_fmt ? d.cast : Elem::F32), "group_norm: no kernel for %s rows in, %s rows out and %s operand casts (f16 / bf16 beside f32 outputs)",
@@ -752,50 +723,20 @@ int launch_group_norm(const GroupNormDesc& d, hipStream_t s) {
     SOLA_ARG(d.out != Elem::SP16 || cg % 8 == 0, "group_norm: split-f16 output needs channels per group %% 8 == 0");
     const double elems = (double)d.n_inst * d.ntok * d.C;
     SolaProfScope prof(SOLA_PROF_NORM, s, 8.0 * elems, (d.y2 ? 12.0 : 8.0) * elems);
-    const int f4 = cg / 4;
     const long long n_units = (long long)d.n_inst * d.groups;
     SOLA_ARG(n_units < (1ll << 31), "group_norm: %lld (instance, group) units exceed the grid", n_units);
-    const int rw = 64 % f4 == 0 ? (d.ntok + 64 / f4 - 1) / (64 / f4) : 1 << 30;     // float4 per lane, one wave per unit
-    const int rb = 256 % f4 == 0 ? (d.ntok + 256 / f4 - 1) / (256 / f4) : 1 << 30;  // ... one block per unit
-    // 16-bit storage mode: eight channels (16 bytes) per lane where the unit fits the register shapes
-    const int f8 = cg / 8;
-    const bool h8 = g_gn_variant != 0 && g_gn_h8 && d.in != Elem::F32 && d.out == Elem::F16 && !d.drop.enabled && cg % 8 == 0 && n_units < (1ll << 31);
-    const int rw8 = (h8 && 64 % f8 == 0) ? (d.ntok + 64 / f8 - 1) / (64 / f8) : 1 << 30;
-    const int rb8 = (h8 && 256 % f8 == 0) ? (d.ntok + 256 / f8 - 1) / (256 / f8) : 1 << 30;
-    const int rk8 = (h8 && 1024 % f8 == 0) ? (d.ntok + 1024 / f8 - 1) / (1024 / f8) : 1 << 30;
-    if (rw8 <= 2) {
-        const dim3 grid((unsigned)((n_units + 3) / 4));
-        if (rw8 == 1) hipLaunchKernelGGL((group_norm_reg_h8_kernel<1, true>), grid, dim3(256), 0, s, a, n_units);
-        else hipLaunchKernelGGL((group_norm_reg_h8_kernel<2, true>), grid, dim3(256), 0, s, a, n_units);
-    } else if (rb8 <= 4) {
-        const dim3 grid((unsigned)n_units);
-        if (rb8 <= 2) hipLaunchKernelGGL((group_norm_reg_h8_kernel<2, false>), grid, dim3(256), 0, s, a, n_units);
-        else hipLaunchKernelGGL((group_norm_reg_h8_kernel<4, false>), grid, dim3(256), 0, s, a, n_units);
-    } else if (rk8 <= 4) {
-        hipLaunchKernelGGL((group_norm_reg_h8_kernel<4, false, 1024>), dim3((unsigned)n_units), dim3(1024), 0, s, a, n_units);
-    } else if (g_gn_variant != 0 && rw <= 4 && n_units < (1ll << 31)) {
-        const dim3 grid((unsigned)((n_units + 3) / 4));
-        if (rw == 1) hipLaunchKernelGGL((group_norm_reg_kernel<1, true>), grid, dim3(256), 0, s, a, n_units);
-        else if (rw == 2) hipLaunchKernelGGL((group_norm_reg_kernel<2, true>), grid, dim3(256), 0, s, a, n_units);
-        else hipLaunchKernelGGL((group_norm_reg_kernel<4, true>), grid, dim3(256), 0, s, a, n_units);
-    } else if (g_gn_variant != 0 && rb <= 32 && n_units < (1ll << 31)) {
-        const dim3 grid((unsigned)n_units);
-        if (rb <= 2) hipLaunchKernelGGL((group_norm_reg_kernel<2, false>), grid, dim3(256), 0, s, a, n_units);
-        else if (rb <= 4) hipLaunchKernelGGL((group_norm_reg_kernel<4, false>), grid, dim3(256), 0, s, a, n_units);
-        else if (rb <= 8) hipLaunchKernelGGL((group_norm_reg_kernel<8, false>), grid, dim3(256), 0, s, a, n_units);
-        else if (rb <= 16 || !g_gn_wide || 1024 % f4 != 0) {
-            if (rb <= 16) hipLaunchKernelGGL((group_norm_reg_kernel<16, false>), grid, dim3(256), 0, s, a, n_units);
-            else hipLaunchKernelGGL((group_norm_reg_kernel<32, false>), grid, dim3(256), 0, s, a, n_units);
-        } else {
-            hipLaunchKernelGGL((group_norm_reg_kernel<8, false, 1024>), grid, dim3(1024), 0, s, a, n_units);  // rb in (16, 32]: 8 per lane at 1024 threads
-        }
-    } else if (g_gn_variant != 0 && g_gn_slices && 256 % f4 == 0 && n_units < (1ll << 24)) {
-        // units of more than 32 float4 per thread: (unit, slice) blocks, two launches (stats, apply)
-        const int ts = (256 / f4) * GNC_R;
-        const int S = (d.ntok + ts - 1) / ts;
+    const GnShape sh = gn_fwd_shape(d.ntok, cg, d.in, d.out, d.drop.enabled != 0, g_gn_variant, g_gn_wide, g_gn_slices, g_gn_h8);
+    const dim3 grid((unsigned)(sh.kind == GnKind::Wave ? (n_units + 3) / 4 : n_units)), block((unsigned)sh.nthr);
+    const int key = sh.R * 10000 + sh.nthr * 2 + (sh.kind == GnKind::Wave);  // (R, threads per block, WAVE) of the register shapes
+#define GN_REG(K, R_, WAVE_, NTHR_) \
+    case R_ * 10000 + NTHR_ * 2 + WAVE_: hipLaunchKernelGGL((K<R_, WAVE_, NTHR_>), grid, block, 0, s, a, n_units); break
+    if (sh.kind == GnKind::Sliced) {
+        // (unit, slice) blocks, two launches (stats, apply); without scratch for the slots, or beyond the grid, the three-pass kernel
+        const int S = sh.slices;
         const long long blocks = n_units * S;
-        float2* slots = (d.slice_ws && d.slice_ws_bytes >= (size_t)blocks * sizeof(float2)) ? static_cast<float2*>(d.slice_ws)
-                                                                                         : gn_slice_scratch((size_t)blocks * sizeof(float2), s);
+        float2* slots = n_units >= (1ll << 24) ? nullptr
+                        : (d.slice_ws && d.slice_ws_bytes >= (size_t)blocks * sizeof(float2)) ? static_cast<float2*>(d.slice_ws)
+                                                                                            : gn_slice_scratch((size_t)blocks * sizeof(float2), s);
         if (slots && blocks < (1ll << 31)) {
             hipLaunchKernelGGL(group_norm_slice_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, S, slots);
             SOLA_LAUNCH_CHECK();
@@ -804,9 +745,25 @@ int launch_group_norm(const GroupNormDesc& d, hipStream_t s) {
         } else {
             hipLaunchKernelGGL(group_norm_kernel, dim3((unsigned)n_units), dim3(256), 0, s, a);
         }
+    } else if (sh.kind == GnKind::ThreePass) {
+        hipLaunchKernelGGL(group_norm_kernel, grid, block, 0, s, a);
+    } else if (sh.cpl == 8) {
+        switch (key) {
+            GN_REG(group_norm_reg_h8_kernel, 1, true, 256); GN_REG(group_norm_reg_h8_kernel, 2, true, 256);
+            GN_REG(group_norm_reg_h8_kernel, 2, false, 256); GN_REG(group_norm_reg_h8_kernel, 4, false, 256);
+            GN_REG(group_norm_reg_h8_kernel, 4, false, 1024);
+            default: SOLA_ARG(false, "group_norm: no eight-channel kernel of %d slots at %d threads", sh.R, sh.nthr);
+        }
     } else {
-        hipLaunchKernelGGL(group_norm_kernel, dim3((unsigned)n_units), dim3(256), 0, s, a);
+        switch (key) {
+            GN_REG(group_norm_reg_kernel, 1, true, 256); GN_REG(group_norm_reg_kernel, 2, true, 256); GN_REG(group_norm_reg_kernel, 4, true, 256);
+            GN_REG(group_norm_reg_kernel, 2, false, 256); GN_REG(group_norm_reg_kernel, 4, false, 256); GN_REG(group_norm_reg_kernel, 8, false, 256);
+            GN_REG(group_norm_reg_kernel, 16, false, 256); GN_REG(group_norm_reg_kernel, 32, false, 256);
+            GN_REG(group_norm_reg_kernel, 8, false, 1024);
+            default: SOLA_ARG(false, "group_norm: no kernel of %d slots at %d threads", sh.R, sh.nthr);
+        }
     }
+#undef GN_REG
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
 }

@@ -4,7 +4,7 @@
 // (forward_infer.hip) and the backward (backward.hip).  A site is projection GEMM -> attention -> out-projection (+ residual) ->
 // GroupNorm; the attention's query units and the norm's instances are the SAME family of row sets, which the attention backward, the
 // norm backward and - for the track family - the score head walk too: strided over the one [B, N, T', D] layout, or a unit table of
-// ragged.hip.  Under a table the strides are dead (attn_common.h: attn_unit, norm.hip: gn_unit, bwd.hip: gn_bwd_unit take first row,
+// ragged.hip.  Under a table the strides are dead (attn_common.h: attn_unit, gn_common.h: gn_unit take first row,
 // row stride and length from the entry; the host predicates test the table first) and every caller gets inner 1, row stride 1, rest 0.
 #pragma once
 #include <type_traits>

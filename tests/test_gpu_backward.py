@@ -109,7 +109,14 @@ def test_conv1d_backward_split(R, T, cin, cout, k, s, p, mag):
     assert_close(db, bt.grad, name="conv db")
 
 
-@pytest.mark.parametrize("B,N,Tp,C", [(2, 5, 3, 128), (1, 64, 4, 1024), (2, 3, 1, 64), (1, 7, 25, 512)])
+@pytest.mark.parametrize("B,N,Tp,C", [(2, 5, 3, 128), (1, 64, 4, 1024), (2, 3, 1, 64), (1, 7, 25, 512),
+                                      # shape edges, tokens per track / per (b, t') / per sample:
+                                      (1, 17, 1, 128),   # 1 / 17 / 17: wave R1, R2 with a partial last pass
+                                      (1, 43, 3, 128),   # 3 / 43 / 129: wave R4; block R4 one token past the edge
+                                      (1, 257, 2, 128),  # 2 / 257 / 514: block R8; 512 threads
+                                      (1, 205, 5, 128),  # 5 / 205 / 1025: the 1024-thread register shape, one token past the edge
+                                      (1, 683, 3, 128),  # 3 / 683 / 2049: three passes with 1024 threads
+                                      (1, 5, 14, 384)])  # 48 channels per group: three passes with 256 threads, lanes with tl >= tpp idle
 def test_group_norm_backward(B, N, Tp, C):
     rng = np.random.default_rng(C + N)
     x = rnd(rng, B, N, Tp, C) * 2 + 0.3

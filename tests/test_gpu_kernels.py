@@ -218,7 +218,14 @@ def _gn_ref(x, gamma, beta, groups):
 
 
 @pytest.mark.parametrize("B,N,Tp,C", [(2, 5, 3, 128), (1, 64, 4, 1024), (2, 3, 1, 64), (1, 7, 25, 512), (2, 75, 8, 1024), (1, 300, 7, 512),
-                                      (1, 128, 16, 1024)])  # the last three: units beyond the register shapes (sliced, two launches)
+                                      (1, 128, 16, 1024),  # the last three: units beyond the register shapes (sliced, two launches)
+                                      # shape edges, tokens per track / per (b, t') / per sample:
+                                      (1, 17, 1, 128),   # 1 / 17 / 17: wave R1, R2 with a partial last pass
+                                      (1, 43, 3, 128),   # 3 / 43 / 129: wave R4; block R4 one token past the edge
+                                      (1, 257, 2, 128),  # 2 / 257 / 514: block R8; R16
+                                      (1, 205, 5, 128),  # 5 / 205 / 1025: the 1024-thread shape, one token past the edge
+                                      (1, 683, 3, 128),  # 3 / 683 / 2049: sliced with a one-token second slice
+                                      (1, 5, 14, 384)])  # 48 channels per group: three passes, lanes with tl >= tpp idle
 def test_group_norm_addressing(B, N, Tp, C):
     """The four instance layouts used by the path, all on an [B,N,T',C] tensor."""
     rng = np.random.default_rng(C + N)
