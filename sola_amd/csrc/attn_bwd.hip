@@ -9,6 +9,9 @@
 // forward kernel - probabilities never move across lanes.  Every wave stages the streamed side through its own LDS
 // slice (16 rows at a time); all waves of a launch run the same trip count, so block barriers are uniform.
 // Addressing is the forward kernels' (attn_unit, attn_common.h), so no permuted copies exist in the backward either.
+// The steps of a pass (prologues, tile products, tile steps, stores) are written once below; the kernels keep what differs between
+// them: unit decoding, trip counts, staging and launch bounds.  profiles/attn_bwd_bodies_isa.txt: what the compiler makes of the
+// shared steps against the written-out copies, kernel by kernel.
 #include "attn_common.h"
 
 namespace {
@@ -66,6 +69,144 @@ __device__ __forceinline__ void stage_sync() {
     }
 }
 
+// ---- the steps of a pass, each written once ------------------------------------------------------------------------------
+// Four values of an f32 (B16 = false) or bfloat16 (true) row at element offset off of its matrix, as f32.
+template <bool B16>
+__device__ __forceinline__ float4 ld4(const float* base, long long off) {
+    if constexpr (B16) return bf16x4_to_f32(*reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + off));
+    else return *reinterpret_cast<const float4*>(base + off);
+}
+
+// S and dP of a 16 x 16 tile, one 16-column chunk: sv / pv = four values of this lane's row of the two STAGED matrices (K and V rows in
+// the dQ pass, Q and dO rows in the dK / dV pass and in the one-pass kernel), sf / pf = the register fragments of the other side.
+__device__ __forceinline__ void bwd_chunk_products(const float4 sv, const float4 pv, const float4& sf, const float4& pf, f32x4& ss, f32x4& ps) {
+    ss = __builtin_amdgcn_mfma_f32_16x16x4f32(sv.x, sf.x, ss, 0, 0, 0);
+    ps = __builtin_amdgcn_mfma_f32_16x16x4f32(pv.x, pf.x, ps, 0, 0, 0);
+    ss = __builtin_amdgcn_mfma_f32_16x16x4f32(sv.y, sf.y, ss, 0, 0, 0);
+    ps = __builtin_amdgcn_mfma_f32_16x16x4f32(pv.y, pf.y, ps, 0, 0, 0);
+    ss = __builtin_amdgcn_mfma_f32_16x16x4f32(sv.z, sf.z, ss, 0, 0, 0);
+    ps = __builtin_amdgcn_mfma_f32_16x16x4f32(pv.z, pf.z, ps, 0, 0, 0);
+    ss = __builtin_amdgcn_mfma_f32_16x16x4f32(sv.w, sf.w, ss, 0, 0, 0);
+    ps = __builtin_amdgcn_mfma_f32_16x16x4f32(pv.w, pf.w, ps, 0, 0, 0);
+}
+// ... all chunks, read as b128 from LDS: sp / pp = the lane's row (c16) at column 4 * g4.  Two accumulators a product (even / odd
+// chunks): s0 + s1 and p0 + p1 are the tile.
+template <int NC>
+__device__ __forceinline__ void bwd_tile_products(const float* sp, const float* pp, const float4 (&sf)[NC], const float4 (&pf)[NC],
+                                                  f32x4& s0, f32x4& s1, f32x4& p0, f32x4& p1) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        bwd_chunk_products(*reinterpret_cast<const float4*>(sp + c * 16), *reinterpret_cast<const float4*>(pp + c * 16), sf[c], pf[c],
+                           (c & 1) ? s1 : s0, (c & 1) ? p1 : p0);
+}
+
+// Query side of the dQ pass: the lane's q * scale and dO fragments of row qrow (clamped; zero where !q_ok), the row's log-sum-exp, and
+// D[q] = dO[q] . O[q] for the lane's column, returned and written to dvec (the dK / dV pass reads it).  (Its three loads keep the
+// conditional form the dQ kernels have always had, not bwd_key_side's load-then-zero: changing it would change their code.)
+template <int DH>
+__device__ __forceinline__ float bwd_query_side(const AttnBwdArgs& a, long long qrow, int h, int g4, bool q_ok,
+                                                float4 (&qf)[DH / 16], float4 (&dof)[DH / 16], float& lse_q) {
+    float dsum = 0.f;
+    const float* qp = a.q + qrow * a.ldq + h * DH + 4 * g4;
+    const float* op = a.o + qrow * a.ldo + h * DH + 4 * g4;
+    const float* gp = a.dout + qrow * a.ldo + h * DH + 4 * g4;
+#pragma unroll
+    for (int c = 0; c < DH / 16; ++c) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 qv = q_ok ? *reinterpret_cast<const float4*>(qp + c * 16) : z;
+        const float4 ov = q_ok ? *reinterpret_cast<const float4*>(op + c * 16) : z;
+        const float4 gv = q_ok ? *reinterpret_cast<const float4*>(gp + c * 16) : z;
+        qf[c] = make_float4(qv.x * a.scale, qv.y * a.scale, qv.z * a.scale, qv.w * a.scale);
+        dof[c] = gv;
+        dsum += (ov.x * gv.x + ov.y * gv.y) + (ov.z * gv.z + ov.w * gv.w);
+    }
+    dsum += __shfl_xor(dsum, 16, 64);  // xor16_32_sum (attn_common.h) written out: through it the dQ kernels of head_dim 64 / 128
+    dsum += __shfl_xor(dsum, 32, 64);  // come out with other register names (profiles/attn_common_isa.txt).  D[q] for the lane's column
+    lse_q = q_ok ? a.lse[qrow * a.H + h] : 0.f;
+    if (q_ok && g4 == 0) a.dvec[qrow * a.H + h] = dsum;
+    return dsum;
+}
+
+// Key side of the dK / dV pass and of the one-pass kernel's f32 products: the lane's k * scale and v fragments of a key row at element
+// offsets koff / voff.  The rule of every load in this file of a row that may lie past its unit's length: the caller CLAMPS the row, the
+// load is unconditional and the VALUE is zeroed.  A select of POINTERS (`cond ? *p : z`) goes through a scratch copy of z and a flat load
+// (attn_simple.hip).
+template <int NC, bool B16 = false>
+__device__ __forceinline__ void bwd_key_side(const float* k, long long koff, const float* v, long long voff, bool k_ok, float scale,
+                                             float4 (&kf)[NC], float4 (&vf)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 kl = ld4<B16>(k, koff + c * 16);
+        const float4 kv = k_ok ? kl : z;
+        kf[c] = make_float4(kv.x * scale, kv.y * scale, kv.z * scale, kv.w * scale);
+        const float4 vl = ld4<B16>(v, voff + c * 16);
+        vf[c] = k_ok ? vl : z;
+    }
+}
+
+// (The dQ pass's tile step - dS^T = P^T o (dP^T - D) with dropout, dQ^T += K^T dS^T - stays written out in attn_bwd_dq_kernel and
+// attn_bwd_dq_blk_kernel: as a shared function attn_bwd_dq_blk_kernel loses a scalar register or the per-wave kernels gain four vector
+// registers, whichever way its arguments travel - profiles/attn_bwd_bodies_isa.txt.)
+
+// One 16-query tile of the dK / dV pass, staged in Qs / Gs (dO rows): S[q][key] and dP[q][key] (A = Q / dO rows, B = k / v fragments;
+// the lane gets q = 4 * g4 + r, key = c16), lse / D fetched per register slot (rows qrow0 + q * q_rs), P, dS, the keep factor, then
+// dV^T[d][key] += sum_q dO[q][d] P[q][key] and dK^T[d][key] += sum_q Q[q][d] dS[q][key].  kj = the lane's key, qt0 = the tile's first query.
+// (dS is an unconditional product here and `ok ? ... : 0` in the one-pass kernel: the same value, P being zero where !ok and every
+// other factor finite - left as the two kernels had it, no arithmetic is touched by sharing the steps.)
+template <int NC, int LD>
+__device__ __forceinline__ void bwd_dkv_tile(const float* Qs, const float* Gs, const float4 (&kf)[NC], const float4 (&vf)[NC], const DropoutCfg& drop,
+                                             const float* lse_all, const float* dvec, bool k_ok, int unit_h, int H, int h, long long qrow0, long long q_rs,
+                                             int Sq, int Sk, int kj, int qt0, int g4, int c16, f32x4 (&dkacc)[NC], f32x4 (&dvacc)[NC]) {
+    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
+    bwd_tile_products<NC>(&Qs[c16 * LD + 4 * g4], &Gs[c16 * LD + 4 * g4], kf, vf, s0, s1, p0, p1);
+    float pr[4], ds[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int q = qt0 + 4 * g4 + r;
+        const bool ok = k_ok && q < Sq;
+        float lse = 0.f, dv = 0.f;
+        if (ok) {
+            const long long row = qrow0 + (long long)q * q_rs;
+            lse = lse_all[row * H + h];
+            dv = dvec[row * H + h];
+        }
+        pr[r] = ok ? __expf((s0[r] + s1[r]) - lse) : 0.f;
+        const float dp = p0[r] + p1[r];
+        float keep = 1.f;
+        if (drop.enabled)
+            keep = dropout_keep(drop, ((unsigned long long)unit_h * Sq + q) * Sk + kj) ? drop.scale : 0.f;
+        ds[r] = pr[r] * (dp * keep - dv);
+        pr[r] *= keep;  // dV uses the dropped probabilities
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float* gr = &Gs[(4 * g4 + r) * LD + c16];
+        const float* qr = &Qs[(4 * g4 + r) * LD + c16];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            dvacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(gr[c * 16], pr[r], dvacc[c], 0, 0, 0);
+            dkacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(qr[c * 16], ds[r], dkacc[c], 0, 0, 0);
+        }
+    }
+}
+
+// The lane's four columns (at 4 * g4) of every 16-column chunk of a gradient row: dQ and dK leave times scale, dV as it is.
+template <int NC>
+__device__ __forceinline__ void bwd_store_dq(float* dp, const f32x4 (&dqacc)[NC], float scale) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        *reinterpret_cast<float4*>(dp + c * 16) = make_float4(dqacc[c][0] * scale, dqacc[c][1] * scale, dqacc[c][2] * scale, dqacc[c][3] * scale);
+}
+template <int NC>
+__device__ __forceinline__ void bwd_store_dkv(float* dkp, float* dvp, const f32x4 (&dkacc)[NC], const f32x4 (&dvacc)[NC], float scale) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        *reinterpret_cast<float4*>(dkp + c * 16) = make_float4(dkacc[c][0] * scale, dkacc[c][1] * scale, dkacc[c][2] * scale, dkacc[c][3] * scale);
+        *reinterpret_cast<float4*>(dvp + c * 16) = make_float4(dvacc[c][0], dvacc[c][1], dvacc[c][2], dvacc[c][3]);
+    }
+}
+
 template <int DH, bool RAG = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnBwdArgs a) {
     constexpr int NC = DH / 16, LD = DH + 4, F4 = DH / 4;
@@ -91,26 +232,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnBwdArgs a) {
     const long long qrow = qrow0 + (long long)(q_ok ? qi : 0) * geo.q_rs;
 
     float4 qf[NC], dof[NC];
-    float dsum = 0.f;
-    {
-        const float* qp = a.q + qrow * a.ldq + h * DH + 4 * g4;
-        const float* op = a.o + qrow * a.ldo + h * DH + 4 * g4;
-        const float* gp = a.dout + qrow * a.ldo + h * DH + 4 * g4;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 qv = q_ok ? *reinterpret_cast<const float4*>(qp + c * 16) : z;
-            const float4 ov = q_ok ? *reinterpret_cast<const float4*>(op + c * 16) : z;
-            const float4 gv = q_ok ? *reinterpret_cast<const float4*>(gp + c * 16) : z;
-            qf[c] = make_float4(qv.x * a.scale, qv.y * a.scale, qv.z * a.scale, qv.w * a.scale);
-            dof[c] = gv;
-            dsum += (ov.x * gv.x + ov.y * gv.y) + (ov.z * gv.z + ov.w * gv.w);
-        }
-    }
-    dsum += __shfl_xor(dsum, 16, 64);  // xor16_32_sum (attn_common.h) written out: through it the dQ kernels of head_dim 64 / 128
-    dsum += __shfl_xor(dsum, 32, 64);  // come out with other register names (profiles/attn_common_isa.txt).  D[q] for the lane's column
-    const float lse_q = q_ok ? a.lse[qrow * a.H + h] : 0.f;
-    if (q_ok && g4 == 0) a.dvec[qrow * a.H + h] = dsum;
+    float lse_q;
+    const float dsum = bwd_query_side<DH>(a, qrow, h, g4, q_ok, qf, dof, lse_q);
 
     f32x4 dqacc[NC];
 #pragma unroll
@@ -135,32 +258,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnBwdArgs a) {
         stage_sync<RAG>();
         // S^T[key][q] and dP^T[key][q]: A = K / V rows (b128), B = q / dO fragments
         f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
-        const float* kp = &Ks[c16 * LD + 4 * g4];
-        const float* vp = &Vs[c16 * LD + 4 * g4];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float4 kf = *reinterpret_cast<const float4*>(kp + c * 16);
-            const float4 vf = *reinterpret_cast<const float4*>(vp + c * 16);
-            if (c & 1) {
-                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[c].x, s1, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.x, dof[c].x, p1, 0, 0, 0);
-                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[c].y, s1, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.y, dof[c].y, p1, 0, 0, 0);
-                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[c].z, s1, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.z, dof[c].z, p1, 0, 0, 0);
-                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[c].w, s1, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.w, dof[c].w, p1, 0, 0, 0);
-            } else {
-                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[c].x, s0, 0, 0, 0);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.x, dof[c].x, p0, 0, 0, 0);
-                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[c].y, s0, 0, 0, 0);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.y, dof[c].y, p0, 0, 0, 0);
-                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[c].z, s0, 0, 0, 0);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.z, dof[c].z, p0, 0, 0, 0);
-                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[c].w, s0, 0, 0, 0);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.w, dof[c].w, p0, 0, 0, 0);
-            }
-        }
+        bwd_tile_products<NC>(&Ks[c16 * LD + 4 * g4], &Vs[c16 * LD + 4 * g4], qf, dof, s0, s1, p0, p1);
         float ds[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -172,7 +270,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnBwdArgs a) {
                          ? dp * a.drop.scale : 0.f;
             ds[r] = p * (dp - dsum);
         }
-        // dQ^T[d][q] += sum_key K[key][d] * dS^T[key][q]
+        // dQ^T[d][q] += sum_key K[key][d] * dS^T[key][q]   (this step is written out in both dQ kernels: the note above bwd_dkv_tile)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float* kr = &Ks[(4 * g4 + r) * LD + c16];
@@ -180,13 +278,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnBwdArgs a) {
             for (int c = 0; c < NC; ++c) dqacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[c * 16], ds[r], dqacc[c], 0, 0, 0);
         }
     }
-    if (q_ok) {
-        float* dp = a.dq + qrow * a.ld_dq + h * DH + 4 * g4;
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            *reinterpret_cast<float4*>(dp + c * 16) = make_float4(dqacc[c][0] * a.scale, dqacc[c][1] * a.scale,
-                                                                  dqacc[c][2] * a.scale, dqacc[c][3] * a.scale);
-    }
+    if (q_ok) bwd_store_dq<NC>(a.dq + qrow * a.ld_dq + h * DH + 4 * g4, dqacc, a.scale);
 }
 
 template <int DH, bool RAG = false>
@@ -214,19 +306,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdArgs a) 
     const long long krow = krow0 + (long long)(k_ok ? kj : 0) * geo.k_rs;
 
     float4 kf[NC], vf[NC];
-    {
-        const float* kp = a.k + krow * a.ldk + h * DH + 4 * g4;
-        const float* vp = a.v + krow * a.ldv + h * DH + 4 * g4;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 kl = *reinterpret_cast<const float4*>(kp + c * 16);  // the row is clamped: load, then zero the VALUE (a select
-            const float4 kv = k_ok ? kl : z;                                  // of POINTERS goes through a scratch copy of z + a flat load)
-            kf[c] = make_float4(kv.x * a.scale, kv.y * a.scale, kv.z * a.scale, kv.w * a.scale);
-            const float4 vl = *reinterpret_cast<const float4*>(vp + c * 16);
-            vf[c] = k_ok ? vl : z;
-        }
-    }
+    bwd_key_side<NC>(a.k, krow * a.ldk + h * DH + 4 * g4, a.v, krow * a.ldv + h * DH + 4 * g4, k_ok, a.scale, kf, vf);
     f32x4 dkacc[NC], dvacc[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) dkacc[c] = dvacc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -248,75 +328,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdArgs a) 
             }
         }
         stage_sync<RAG>();
-        // S[q][key] and dP[q][key]: A = Q / dO rows (b128), B = k / v fragments; lane gets q = 4*g4 + r, key = c16
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
-        const float* qp = &Qs[c16 * LD + 4 * g4];
-        const float* gp = &Gs[c16 * LD + 4 * g4];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float4 qv = *reinterpret_cast<const float4*>(qp + c * 16);
-            const float4 gv = *reinterpret_cast<const float4*>(gp + c * 16);
-            if (c & 1) {
-                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.x, kf[c].x, s1, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.x, vf[c].x, p1, 0, 0, 0);
-                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.y, kf[c].y, s1, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.y, vf[c].y, p1, 0, 0, 0);
-                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.z, kf[c].z, s1, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.z, vf[c].z, p1, 0, 0, 0);
-                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.w, kf[c].w, s1, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.w, vf[c].w, p1, 0, 0, 0);
-            } else {
-                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.x, kf[c].x, s0, 0, 0, 0);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.x, vf[c].x, p0, 0, 0, 0);
-                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.y, kf[c].y, s0, 0, 0, 0);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.y, vf[c].y, p0, 0, 0, 0);
-                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.z, kf[c].z, s0, 0, 0, 0);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.z, vf[c].z, p0, 0, 0, 0);
-                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.w, kf[c].w, s0, 0, 0, 0);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.w, vf[c].w, p0, 0, 0, 0);
-            }
-        }
-        float pr[4], ds[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int q = qt0 + 4 * g4 + r;
-            const bool ok = k_ok && q < geo.Sq;
-            float lse = 0.f, dv = 0.f;
-            if (ok) {
-                const long long row = qrow0 + (long long)q * geo.q_rs;
-                lse = a.lse[row * a.H + h];
-                dv = a.dvec[row * a.H + h];
-            }
-            pr[r] = ok ? __expf((s0[r] + s1[r]) - lse) : 0.f;
-            float dp = p0[r] + p1[r];
-            float keep = 1.f;
-            if (a.drop.enabled)
-                keep = dropout_keep(a.drop, ((unsigned long long)(grp * a.H + h) * geo.Sq + q) * geo.Sk + kj) ? a.drop.scale : 0.f;
-            ds[r] = pr[r] * (dp * keep - dv);
-            pr[r] *= keep;  // dV uses the dropped probabilities
-        }
-        // dV^T[d][key] += sum_q dO[q][d] P[q][key];  dK^T[d][key] += sum_q Q[q][d] dS[q][key]
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* gr = &Gs[(4 * g4 + r) * LD + c16];
-            const float* qr = &Qs[(4 * g4 + r) * LD + c16];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                dvacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(gr[c * 16], pr[r], dvacc[c], 0, 0, 0);
-                dkacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(qr[c * 16], ds[r], dkacc[c], 0, 0, 0);
-            }
-        }
+        bwd_dkv_tile<NC, LD>(Qs, Gs, kf, vf, a.drop, a.lse, a.dvec, k_ok, grp * a.H + h, a.H, h, qrow0, geo.q_rs, geo.Sq, geo.Sk, kj, qt0, g4, c16,
+                             dkacc, dvacc);
     }
-    if (k_ok) {
-        float* dkp = a.dk + krow * a.ld_dk + h * DH + 4 * g4;
-        float* dvp = a.dv + krow * a.ld_dv + h * DH + 4 * g4;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            *reinterpret_cast<float4*>(dkp + c * 16) = make_float4(dkacc[c][0] * a.scale, dkacc[c][1] * a.scale,
-                                                                   dkacc[c][2] * a.scale, dkacc[c][3] * a.scale);
-            *reinterpret_cast<float4*>(dvp + c * 16) = make_float4(dvacc[c][0], dvacc[c][1], dvacc[c][2], dvacc[c][3]);
-        }
-    }
+    if (k_ok) bwd_store_dkv<NC>(a.dk + krow * a.ld_dk + h * DH + 4 * g4, a.dv + krow * a.ld_dv + h * DH + 4 * g4, dkacc, dvacc, a.scale);
 }
 
 // ---- block-shared staging (round 2) --------------------------------------------------------------------------------------
@@ -325,6 +340,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdArgs a) 
 // Q and dO) through L2, and no load overlaps a MFMA.  Here a BLOCK owns (unit, 64 queries) for dQ or (unit, 64 keys) for
 // dK/dV: the 16-row tile of the streamed side is staged ONCE per block by all 256 threads into one of two LDS buffers, the
 // next tile travels in registers while the current one is multiplied (one barrier per tile), the arithmetic is unchanged.
+// (Each of the two keeps its own fetch / stash pair: as one function of the two streamed tensors both kernels lose scalar registers
+// and come out 40 lines shorter, i.e. as other kernels - profiles/attn_bwd_bodies_isa.txt.)
 template <int DH>
 __global__ __launch_bounds__(256) void attn_bwd_dq_blk_kernel(const AttnBwdArgs a) {
     constexpr int NC = DH / 16, LD = DH + 4, F4 = DH / 4, PT = 2 * 16 * F4 / 256;  // float4 per thread and tile (K + V)
@@ -343,26 +360,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_blk_kernel(const AttnBwdArgs 
     const long long qrow = qrow0 + (long long)(q_ok ? qi : 0) * geo.q_rs;
 
     float4 qf[NC], dof[NC];
-    float dsum = 0.f;
-    {
-        const float* qp = a.q + qrow * a.ldq + h * DH + 4 * g4;
-        const float* op = a.o + qrow * a.ldo + h * DH + 4 * g4;
-        const float* gp = a.dout + qrow * a.ldo + h * DH + 4 * g4;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 qv = q_ok ? *reinterpret_cast<const float4*>(qp + c * 16) : z;
-            const float4 ov = q_ok ? *reinterpret_cast<const float4*>(op + c * 16) : z;
-            const float4 gv = q_ok ? *reinterpret_cast<const float4*>(gp + c * 16) : z;
-            qf[c] = make_float4(qv.x * a.scale, qv.y * a.scale, qv.z * a.scale, qv.w * a.scale);
-            dof[c] = gv;
-            dsum += (ov.x * gv.x + ov.y * gv.y) + (ov.z * gv.z + ov.w * gv.w);
-        }
-    }
-    dsum += __shfl_xor(dsum, 16, 64);  // xor16_32_sum (attn_common.h) written out: through it the dQ kernels of head_dim 64 / 128
-    dsum += __shfl_xor(dsum, 32, 64);  // come out with other register names (profiles/attn_common_isa.txt).  D[q] for the lane's column
-    const float lse_q = q_ok ? a.lse[qrow * a.H + h] : 0.f;
-    if (q_ok && g4 == 0) a.dvec[qrow * a.H + h] = dsum;
+    float lse_q;
+    const float dsum = bwd_query_side<DH>(a, qrow, h, g4, q_ok, qf, dof, lse_q);
 
     f32x4 dqacc[NC];
 #pragma unroll
@@ -399,23 +398,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_blk_kernel(const AttnBwdArgs 
         if (kt0 + 16 < geo.Sk) fetch(kt0 + 16);
         // S^T[key][q] and dP^T[key][q]: A = K / V rows (b128), B = q / dO fragments
         f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
-        const float* kp = &Ks[c16 * LD + 4 * g4];
-        const float* vp = &Vs[c16 * LD + 4 * g4];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float4 kf = *reinterpret_cast<const float4*>(kp + c * 16);
-            const float4 vf = *reinterpret_cast<const float4*>(vp + c * 16);
-            f32x4& ss = (c & 1) ? s1 : s0;
-            f32x4& pp = (c & 1) ? p1 : p0;
-            ss = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[c].x, ss, 0, 0, 0);
-            pp = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.x, dof[c].x, pp, 0, 0, 0);
-            ss = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[c].y, ss, 0, 0, 0);
-            pp = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.y, dof[c].y, pp, 0, 0, 0);
-            ss = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[c].z, ss, 0, 0, 0);
-            pp = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.z, dof[c].z, pp, 0, 0, 0);
-            ss = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[c].w, ss, 0, 0, 0);
-            pp = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.w, dof[c].w, pp, 0, 0, 0);
-        }
+        bwd_tile_products<NC>(&Ks[c16 * LD + 4 * g4], &Vs[c16 * LD + 4 * g4], qf, dof, s0, s1, p0, p1);
         float ds[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -427,7 +410,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_blk_kernel(const AttnBwdArgs 
                          ? dp * a.drop.scale : 0.f;
             ds[r] = p * (dp - dsum);
         }
-        // dQ^T[d][q] += sum_key K[key][d] * dS^T[key][q]
+        // dQ^T[d][q] += sum_key K[key][d] * dS^T[key][q]   (this step is written out in both dQ kernels: the note above bwd_dkv_tile)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float* kr = &Ks[(4 * g4 + r) * LD + c16];
@@ -435,18 +418,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_blk_kernel(const AttnBwdArgs 
             for (int c = 0; c < NC; ++c) dqacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[c * 16], ds[r], dqacc[c], 0, 0, 0);
         }
     }
-    if (q_ok) {
-        float* dp = a.dq + qrow * a.ld_dq + h * DH + 4 * g4;
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            *reinterpret_cast<float4*>(dp + c * 16) = make_float4(dqacc[c][0] * a.scale, dqacc[c][1] * a.scale,
-                                                                  dqacc[c][2] * a.scale, dqacc[c][3] * a.scale);
-    }
+    if (q_ok) bwd_store_dq<NC>(a.dq + qrow * a.ld_dq + h * DH + 4 * g4, dqacc, a.scale);
 }
 
 template <int DH>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_blk_kernel(const AttnBwdArgs a) {
-    constexpr int NC = DH / 16, LD = DH + 4, F4 = DH / 4, PT = 2 * 16 * F4 / 256;
+    constexpr int NC = DH / 16, LD = DH + 4, F4 = DH / 4, PT = 2 * 16 * F4 / 256;  // float4 per thread and tile (Q + dO)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c16 = lane & 15, g4 = lane >> 4;
@@ -462,19 +439,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_blk_kernel(const AttnBwdA
     const long long krow = krow0 + (long long)(k_ok ? kj : 0) * geo.k_rs;
 
     float4 kf[NC], vf[NC];
-    {
-        const float* kp = a.k + krow * a.ldk + h * DH + 4 * g4;
-        const float* vp = a.v + krow * a.ldv + h * DH + 4 * g4;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 kl = *reinterpret_cast<const float4*>(kp + c * 16);  // the row is clamped: load, then zero the VALUE (a select
-            const float4 kv = k_ok ? kl : z;                                  // of POINTERS goes through a scratch copy of z + a flat load)
-            kf[c] = make_float4(kv.x * a.scale, kv.y * a.scale, kv.z * a.scale, kv.w * a.scale);
-            const float4 vl = *reinterpret_cast<const float4*>(vp + c * 16);
-            vf[c] = k_ok ? vl : z;
-        }
-    }
+    bwd_key_side<NC>(a.k, krow * a.ldk + h * DH + 4 * g4, a.v, krow * a.ldv + h * DH + 4 * g4, k_ok, a.scale, kf, vf);
     f32x4 dkacc[NC], dvacc[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) dkacc[c] = dvacc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -507,66 +472,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_blk_kernel(const AttnBwdA
         stash(Qs);
         __syncthreads();
         if (qt0 + 16 < geo.Sq) fetch(qt0 + 16);
-        // S[q][key] and dP[q][key]: A = Q / dO rows (b128), B = k / v fragments; lane gets q = 4*g4 + r, key = c16
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
-        const float* qp = &Qs[c16 * LD + 4 * g4];
-        const float* gp = &Gs[c16 * LD + 4 * g4];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float4 qv = *reinterpret_cast<const float4*>(qp + c * 16);
-            const float4 gv = *reinterpret_cast<const float4*>(gp + c * 16);
-            f32x4& ss = (c & 1) ? s1 : s0;
-            f32x4& pp = (c & 1) ? p1 : p0;
-            ss = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.x, kf[c].x, ss, 0, 0, 0);
-            pp = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.x, vf[c].x, pp, 0, 0, 0);
-            ss = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.y, kf[c].y, ss, 0, 0, 0);
-            pp = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.y, vf[c].y, pp, 0, 0, 0);
-            ss = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.z, kf[c].z, ss, 0, 0, 0);
-            pp = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.z, vf[c].z, pp, 0, 0, 0);
-            ss = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.w, kf[c].w, ss, 0, 0, 0);
-            pp = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.w, vf[c].w, pp, 0, 0, 0);
-        }
-        float pr[4], ds[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int q = qt0 + 4 * g4 + r;
-            const bool ok = k_ok && q < geo.Sq;
-            float lse = 0.f, dv = 0.f;
-            if (ok) {
-                const long long row = qrow0 + (long long)q * geo.q_rs;
-                lse = a.lse[row * a.H + h];
-                dv = a.dvec[row * a.H + h];
-            }
-            pr[r] = ok ? __expf((s0[r] + s1[r]) - lse) : 0.f;
-            const float dp = p0[r] + p1[r];
-            float keep = 1.f;
-            if (a.drop.enabled)
-                keep = dropout_keep(a.drop, ((unsigned long long)(grp * a.H + h) * geo.Sq + q) * geo.Sk + kj) ? a.drop.scale : 0.f;
-            ds[r] = pr[r] * (dp * keep - dv);
-            pr[r] *= keep;  // dV uses the dropped probabilities
-        }
-        // dV^T[d][key] += sum_q dO[q][d] P[q][key];  dK^T[d][key] += sum_q Q[q][d] dS[q][key]
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* gr = &Gs[(4 * g4 + r) * LD + c16];
-            const float* qr = &Qs[(4 * g4 + r) * LD + c16];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                dvacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(gr[c * 16], pr[r], dvacc[c], 0, 0, 0);
-                dkacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(qr[c * 16], ds[r], dkacc[c], 0, 0, 0);
-            }
-        }
+        bwd_dkv_tile<NC, LD>(Qs, Gs, kf, vf, a.drop, a.lse, a.dvec, k_ok, grp * a.H + h, a.H, h, qrow0, geo.q_rs, geo.Sq, geo.Sk, kj, qt0, g4, c16,
+                             dkacc, dvacc);
     }
-    if (k_ok) {
-        float* dkp = a.dk + krow * a.ld_dk + h * DH + 4 * g4;
-        float* dvp = a.dv + krow * a.ld_dv + h * DH + 4 * g4;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            *reinterpret_cast<float4*>(dkp + c * 16) = make_float4(dkacc[c][0] * a.scale, dkacc[c][1] * a.scale,
-                                                                   dkacc[c][2] * a.scale, dkacc[c][3] * a.scale);
-            *reinterpret_cast<float4*>(dvp + c * 16) = make_float4(dvacc[c][0], dvacc[c][1], dvacc[c][2], dvacc[c][3]);
-        }
-    }
+    if (k_ok) bwd_store_dkv<NC>(a.dk + krow * a.ld_dk + h * DH + 4 * g4, a.dv + krow * a.ld_dv + h * DH + 4 * g4, dkacc, dvacc, a.scale);
 }
 
 // ---- sequences of at most 4 steps (motion attention over T' = 4 at the headline shape): ONE pass -------------------------
@@ -596,8 +505,9 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(const AttnBwdArgs a
     float dsum[TT], lse[TT];
 #pragma unroll
     for (int t = 0; t < TT; ++t) {
-        // rows past the unit's length: a CLAMPED row is loaded and the VALUE zeroed (a `cond ? *p : z` makes the compiler select
-        // between the global pointer and a scratch copy of z and load through a flat address - attn_simple.hip)
+        // rows past the unit's length: a CLAMPED row is loaded and the VALUE zeroed (the rule at bwd_key_side).  (ld / ld16 stay lambdas
+        // of this kernel: as one load function templated on the format ten of the twelve instantiations change their register rows -
+        // profiles/attn_bwd_bodies_isa.txt)
         const long long qr = q0 + (long long)(t < Sq ? t : 0) * geo.q_rs, kr = k0 + (long long)(t < Sk ? t : 0) * geo.k_rs;
         auto ld = [&](const float* p, bool ok) {
             const float4 v = *reinterpret_cast<const float4*>(p);
@@ -772,7 +682,7 @@ __global__ __launch_bounds__(64 * NWU, 2) void attn_bwd_fused_kernel(const AttnB
                 if constexpr (G16) gv[u] = bf16x4_to_f32(*reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.dout) + row * a.ldo + h * DH + c4 * 4));
                 else gv[u] = *reinterpret_cast<const float4*>(a.dout + row * a.ldo + h * DH + c4 * 4);
                 if constexpr (O16) ov[u] = bf16x4_to_f32(*reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.o) + row * a.ldo + h * DH + c4 * 4));
-                else ov[u] = *reinterpret_cast<const float4*>(a.o + row * a.ldo + h * DH + c4 * 4);
+                else ov[u] = *reinterpret_cast<const float4*>(a.o + row * a.ldo + h * DH + c4 * 4);  // (written out, not ld4: the sgpr spills move otherwise)
                 ls[u] = a.lse[row * a.H + h];
             }
 #pragma unroll
@@ -904,25 +814,7 @@ __global__ __launch_bounds__(64 * NWU, 2) void attn_bwd_fused_kernel(const AttnB
             for (int c = 0; c < NC; ++c)
                 kTh[c] = __builtin_bit_cast(short4m, make_uint2((unsigned)kr[c][0] | ((unsigned)kr[c][1] << 16), (unsigned)kr[c][2] | ((unsigned)kr[c][3] << 16)));
         } else {
-            const float* kp = a.k + krow * a.ldk + h * DH + 4 * g4;
-            const float* vp = a.v + krow * a.ldv + h * DH + 4 * g4;
-            const unsigned short* kp16 = reinterpret_cast<const unsigned short*>(a.k) + krow * a.ldk + h * DH + 4 * g4;
-            const unsigned short* vp16 = reinterpret_cast<const unsigned short*>(a.v) + krow * a.ldv + h * DH + 4 * g4;
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                float4 kl, vl;  // clamped row, VALUE select (see attn_bwd_dkv_kernel)
-                if constexpr (IO16) {
-                    kl = bf16x4_to_f32(*reinterpret_cast<const uint2*>(kp16 + c * 16));
-                    vl = bf16x4_to_f32(*reinterpret_cast<const uint2*>(vp16 + c * 16));
-                } else {
-                    kl = *reinterpret_cast<const float4*>(kp + c * 16);
-                    vl = *reinterpret_cast<const float4*>(vp + c * 16);
-                }
-                const float4 kv = k_ok ? kl : z;
-                kf[c] = make_float4(kv.x * a.scale, kv.y * a.scale, kv.z * a.scale, kv.w * a.scale);
-                vf[c] = k_ok ? vl : z;
-            }
+            bwd_key_side<NC, IO16>(a.k, krow * a.ldk + h * DH + 4 * g4, a.v, krow * a.ldv + h * DH + 4 * g4, k_ok, a.scale, kf, vf);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {  // the same tile with the key on the contraction slots: K[key = 4*g4 + r][d = 16*c + c16]
                 const int kk = kt * 16 + 4 * g4 + r;
@@ -978,24 +870,8 @@ __global__ __launch_bounds__(64 * NWU, 2) void attn_bwd_fused_kernel(const AttnB
                         const short4m qh = pk4(qv.x, qv.y, qv.z, qv.w), gh = pk4(gv.x, gv.y, gv.z, gv.w);
                         if (c & 1) { s1 = mf16(qh, kfh[c], s1); p1 = mf16(gh, vfh[c], p1); }
                         else { s0 = mf16(qh, kfh[c], s0); p0 = mf16(gh, vfh[c], p0); }
-                    } else if (c & 1) {
-                        s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.x, kf[c].x, s1, 0, 0, 0);
-                        p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.x, vf[c].x, p1, 0, 0, 0);
-                        s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.y, kf[c].y, s1, 0, 0, 0);
-                        p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.y, vf[c].y, p1, 0, 0, 0);
-                        s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.z, kf[c].z, s1, 0, 0, 0);
-                        p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.z, vf[c].z, p1, 0, 0, 0);
-                        s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.w, kf[c].w, s1, 0, 0, 0);
-                        p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.w, vf[c].w, p1, 0, 0, 0);
-                    } else {
-                        s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.x, kf[c].x, s0, 0, 0, 0);
-                        p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.x, vf[c].x, p0, 0, 0, 0);
-                        s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.y, kf[c].y, s0, 0, 0, 0);
-                        p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.y, vf[c].y, p0, 0, 0, 0);
-                        s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.z, kf[c].z, s0, 0, 0, 0);
-                        p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.z, vf[c].z, p0, 0, 0, 0);
-                        s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.w, kf[c].w, s0, 0, 0, 0);
-                        p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.w, vf[c].w, p0, 0, 0, 0);
+                    } else {  // (chunk by chunk inside this loop: as bwd_tile_products the four-wave shapes spill 2 / 6 registers)
+                        bwd_chunk_products(qv, gv, kf[c], vf[c], (c & 1) ? s1 : s0, (c & 1) ? p1 : p0);
                     }
                 }
                 const float4 lse4 = *reinterpret_cast<const float4*>(&lsh[cur * 16 + 4 * g4]);
@@ -1157,7 +1033,7 @@ __global__ __launch_bounds__(64 * NWU, 2) void attn_bwd_fused_kernel(const AttnB
                     *reinterpret_cast<uint2*>(dk16 + c * 16) = f32x4_to_bf16(dkacc[c][0] * a.scale, dkacc[c][1] * a.scale, dkacc[c][2] * a.scale, dkacc[c][3] * a.scale);
                     *reinterpret_cast<uint2*>(dv16 + c * 16) = f32x4_to_bf16(dvacc[c][0], dvacc[c][1], dvacc[c][2], dvacc[c][3]);
                 }
-            } else {
+            } else {  // bwd_store_dkv written out: through the call the f32 shapes change their register rows (the four-wave one to 256)
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 *reinterpret_cast<float4*>(dkp + c * 16) = make_float4(dkacc[c][0] * a.scale, dkacc[c][1] * a.scale,
@@ -1208,17 +1084,76 @@ int g_attn_bwd_fused = 1;  // sola_tune "attn_bwd_fused": 0 = two-pass kernels f
 
 int g_attn_bwd_bf16_mfma = 1;  // sola_tune "attn_bwd_bf16_mfma": 0 = the bf16-row launches keep the f32 products (bit-identical to the f32 kernel on the widened values)
 namespace {
-template <int NWU, bool IO16, bool MF = false, bool G16 = false, bool O16 = false>
-static int launch_bwd_fused_n(const AttnBwdArgs& a, int chunks, hipStream_t s) {
-    constexpr int LD = 128 + 4;
-    constexpr bool DMA = NWU == 4;  // as in the kernel
-    constexpr size_t lds = ((size_t)(DMA ? 5 : 2) * 16 * LD + (NWU > 1 ? NWU * 16 * LD : 0) + NWU * 16 * 17 + (DMA ? 64 : 32)) * sizeof(float);
+// ---- which kernel serves which shape: the limits, each named once ------------------------------------------------------------
+constexpr int kBwdSmallSteps = 4;   // attn_bwd_small_kernel: units of at most this many queries and keys (head dim 128)
+constexpr int kBwdFusedRows = 128;  // attn_bwd_fused_kernel: units of at most this many queries and keys (head dim 128), or
+constexpr int kBwdChunkKeys = 64;   // of at most this many keys - one key group of four waves - against longer query ranges:
+// queries per chunk of a chunked launch (object -> language: up to N * T' = 2048 queries against <= 64 keys): 16 tiles = 256.  One
+// chunk's worth of queries needs no scratch; more takes a block per chunk and the caller's scratch for the dK / dV partial sums
+constexpr int kBwdChunkTiles = 16;
+// few-sample launches (at most kBwdFewRows query rows in total - one sample per step is 256-2000): chunks of 4 tiles = 64 queries, so that
+// a single unit's eight (unit, head) blocks become 8 x Sq/64 (one sample of 256 queries: 75 -> ~25 us per launch)
+constexpr int kBwdFewRows = 4096, kBwdFewChunkTiles = 4;
+constexpr int bwd_chunk_tiles(long long q_rows) { return q_rows <= kBwdFewRows ? kBwdFewChunkTiles : kBwdChunkTiles; }
+
+// The one-pass kernel's plan for a launch.  Chunked launches address their partial sums by the unit's first row: units of row stride 1
+// in unit order (the caller's promise when it hands over `part`), sized by attention_bwd_part_floats().
+struct BwdPlan {
+    bool fused, can_chunk;  // the one-pass kernel serves the shape; the scratch and the layout allow chunks
+    int qc_tiles, chunks;   // 16-query tiles per chunk (0 = every tile of a unit in one block) and chunks per unit (grid y)
+};
+BwdPlan bwd_plan(const AttnBwdDesc& d) {
+    BwdPlan p{false, false, 0, 1};
+    p.can_chunk = d.part && d.Sk <= kBwdChunkKeys && d.part_floats >= attention_bwd_part_floats(d.part_rows, d.G, d.H, d.Sk) &&
+                  (d.q_units || (d.q_rs == 1 && d.inner == 1));
+    p.fused = g_attn_bwd_fused && d.DH == 128 && d.Sk <= kBwdFusedRows &&
+              (d.Sq <= kBwdFusedRows || (d.Sk <= kBwdChunkKeys && (d.Sq <= 16 * kBwdChunkTiles || p.can_chunk)));
+    const int qc = bwd_chunk_tiles(d.part_rows);
+    if (p.can_chunk && d.Sq > 16 * qc) {
+        p.qc_tiles = qc;
+        p.chunks = ((d.Sq + 15) / 16 + qc - 1) / qc;
+    }
+    return p;
+}
+bool bwd_small_shape(const AttnBwdDesc& d) { return g_attn_bwd_small && d.DH == 128 && d.Sq <= kBwdSmallSteps && d.Sk <= kBwdSmallSteps; }
+
+// ---- launches ---------------------------------------------------------------------------------------------------------------
+// more than the default 64 KB of dynamic LDS: asked for once per device and kernel
+template <auto KERNEL>
+int bwd_max_lds_once(size_t lds) {
     static DeviceOnce once;
     int dev;
     if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_fused_kernel<NWU, IO16, MF, G16, O16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         once.done(dev);
     }
+    return SOLA_OK;
+}
+
+// f(integral_constant N, integral_constant FORM) for N = 1 | 2 | 4, the smallest that holds n (waves of the one-pass kernel, steps of the
+// register kernel), and FORM = form < NFORM (the format combination: bwd_io_form)
+template <int NFORM, int FORM = 0, class F>
+int bwd_dispatch(int n, int form, F&& f) {
+    if constexpr (FORM < NFORM) {
+        if (form != FORM) return bwd_dispatch<NFORM, FORM + 1>(n, form, f);
+        constexpr std::integral_constant<int, FORM> fm{};
+        if (n <= 1) return f(std::integral_constant<int, 1>{}, fm);
+        if (n <= 2) return f(std::integral_constant<int, 2>{}, fm);
+        return f(std::integral_constant<int, 4>{}, fm);
+    } else {
+        sola_set_error("attention backward: no kernel for format combination %d", form);
+        return SOLA_ERR_ARG;
+    }
+}
+// 0 = f32 rows; bf16 q / k / v and gradients: 1, with a bf16 dO: 2, with a bf16 O too: 3 (attn_bwd_formats_ok allows no other)
+int bwd_io_form(const AttnBwdArgs& a) { return !a.io16 ? 0 : (a.g16 && a.o16) ? 3 : a.g16 ? 2 : 1; }
+
+template <int NWU, bool IO16, bool MF, bool G16, bool O16>
+int launch_bwd_fused_n(const AttnBwdArgs& a, int chunks, hipStream_t s) {
+    constexpr int LD = 128 + 4;
+    constexpr bool DMA = NWU == 4;  // as in the kernel
+    constexpr size_t lds = ((size_t)(DMA ? 5 : 2) * 16 * LD + (NWU > 1 ? NWU * 16 * LD : 0) + NWU * 16 * 17 + (DMA ? 64 : 32)) * sizeof(float);
+    SOLA_TRY((bwd_max_lds_once<&attn_bwd_fused_kernel<NWU, IO16, MF, G16, O16>>(lds)));
     const long long blocks = (long long)a.G * a.H;
     SOLA_ARG(blocks < (1ll << 31) && chunks < 65536, "attention backward: grid too large");
     hipLaunchKernelGGL((attn_bwd_fused_kernel<NWU, IO16, MF, G16, O16>), dim3((unsigned)blocks, (unsigned)chunks), dim3(64 * NWU), lds, s, a);
@@ -1231,170 +1166,95 @@ static int launch_bwd_fused_n(const AttnBwdArgs& a, int chunks, hipStream_t s) {
     }
     return SOLA_OK;
 }
-// queries per chunk of a chunked launch (object -> language: up to N * T' = 2048 queries against <= 64 keys): 16 tiles = 256
-constexpr int kBwdChunkTiles = 16;
-static bool bwd_fused_supported(const AttnBwdArgs& a, int DH, bool can_chunk) {
-    if (!g_attn_bwd_fused || DH != 128 || a.Sk > 128) return false;
-    return a.Sq <= 128 || (a.Sk <= 64 && (a.Sq <= 16 * kBwdChunkTiles || can_chunk));
-}
-// few-sample launches (at most kBwdFewRows query rows in total - one sample per step is 256-2000): chunks of 4 tiles = 64 queries, so that
-// a single unit's eight (unit, head) blocks become 8 x Sq/64 (one sample of 256 queries: 75 -> ~25 us per launch)
-constexpr int kBwdFewRows = 4096, kBwdFewChunkTiles = 4;
-static int launch_bwd_fused(AttnBwdArgs a, bool can_chunk, long long part_rows, hipStream_t s) {
-    // waves per (unit, head) = key tiles held in registers at a time, sized by the LONGEST unit of the launch
-    int chunks = 1;
-    a.qc_tiles = 0;
+// waves per (unit, head) = key tiles held in registers at a time, sized by the LONGEST unit of the launch; the bf16 forms take the bf16
+// products unless sola_tune "attn_bwd_bf16_mfma" is 0 (a bf16 dO comes with them on only: launch_attention_bwd)
+int launch_bwd_fused(AttnBwdArgs a, const BwdPlan& plan, hipStream_t s) {
+    a.qc_tiles = plan.qc_tiles;
     a.ntile = g_attn_bwd_ablate;
-    const int qc = (can_chunk && part_rows <= kBwdFewRows) ? kBwdFewChunkTiles : kBwdChunkTiles;
-    if (a.Sq > 16 * qc && can_chunk) {
-        a.qc_tiles = qc;
-        chunks = ((a.Sq + 15) / 16 + qc - 1) / qc;
-    }
-    if (a.io16 && a.g16 && a.o16) {
-        if (a.Sk <= 16) return launch_bwd_fused_n<1, true, true, true, true>(a, chunks, s);
-        if (a.Sk <= 32) return launch_bwd_fused_n<2, true, true, true, true>(a, chunks, s);
-        return launch_bwd_fused_n<4, true, true, true, true>(a, chunks, s);
-    }
-    if (a.io16 && a.g16) {  // (launch_attention_bwd: only with the bf16 products on)
-        if (a.Sk <= 16) return launch_bwd_fused_n<1, true, true, true>(a, chunks, s);
-        if (a.Sk <= 32) return launch_bwd_fused_n<2, true, true, true>(a, chunks, s);
-        return launch_bwd_fused_n<4, true, true, true>(a, chunks, s);
-    }
-    if (a.io16 && g_attn_bwd_bf16_mfma) {
-        if (a.Sk <= 16) return launch_bwd_fused_n<1, true, true>(a, chunks, s);
-        if (a.Sk <= 32) return launch_bwd_fused_n<2, true, true>(a, chunks, s);
-        return launch_bwd_fused_n<4, true, true>(a, chunks, s);
-    }
-    if (a.io16) {
-        if (a.Sk <= 16) return launch_bwd_fused_n<1, true>(a, chunks, s);
-        if (a.Sk <= 32) return launch_bwd_fused_n<2, true>(a, chunks, s);
-        return launch_bwd_fused_n<4, true>(a, chunks, s);
-    }
-    if (a.Sk <= 16) return launch_bwd_fused_n<1, false>(a, chunks, s);
-    if (a.Sk <= 32) return launch_bwd_fused_n<2, false>(a, chunks, s);
-    return launch_bwd_fused_n<4, false>(a, chunks, s);
+    const int io = bwd_io_form(a);
+    const int form = io == 0 ? 0 : io == 1 ? (g_attn_bwd_bf16_mfma ? 2 : 1) : io + 1;  // f32 | bf16 rows | + bf16 products | + bf16 dO | + bf16 O
+    return bwd_dispatch<5>((a.Sk + 15) / 16, form, [&](auto n, auto fm) -> int {
+        constexpr int FM = decltype(fm)::value;
+        return launch_bwd_fused_n<decltype(n)::value, (FM >= 1), (FM >= 2), (FM >= 3), (FM >= 4)>(a, plan.chunks, s);
+    });
 }
 
-static int launch_bwd_small(const AttnBwdArgs& a, hipStream_t s) {
+int launch_bwd_small(const AttnBwdArgs& a, hipStream_t s) {
     const long long units = (long long)a.G * a.H;
     const unsigned blocks = (unsigned)((units + 7) / 8);
-    const int need = a.Sq > a.Sk ? a.Sq : a.Sk;
-    if (a.io16 && a.g16 && a.o16) {
-        if (need <= 1) hipLaunchKernelGGL((attn_bwd_small_kernel<1, true, true, true>), dim3(blocks), dim3(256), 0, s, a);
-        else if (need <= 2) hipLaunchKernelGGL((attn_bwd_small_kernel<2, true, true, true>), dim3(blocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((attn_bwd_small_kernel<4, true, true, true>), dim3(blocks), dim3(256), 0, s, a);
-    } else if (a.io16 && a.g16) {
-        if (need <= 1) hipLaunchKernelGGL((attn_bwd_small_kernel<1, true, true>), dim3(blocks), dim3(256), 0, s, a);
-        else if (need <= 2) hipLaunchKernelGGL((attn_bwd_small_kernel<2, true, true>), dim3(blocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((attn_bwd_small_kernel<4, true, true>), dim3(blocks), dim3(256), 0, s, a);
-    } else if (a.io16) {
-        if (need <= 1) hipLaunchKernelGGL((attn_bwd_small_kernel<1, true>), dim3(blocks), dim3(256), 0, s, a);
-        else if (need <= 2) hipLaunchKernelGGL((attn_bwd_small_kernel<2, true>), dim3(blocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((attn_bwd_small_kernel<4, true>), dim3(blocks), dim3(256), 0, s, a);
-    } else if (need <= 1) hipLaunchKernelGGL((attn_bwd_small_kernel<1>), dim3(blocks), dim3(256), 0, s, a);
-    else if (need <= 2) hipLaunchKernelGGL((attn_bwd_small_kernel<2>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_bwd_small_kernel<4>), dim3(blocks), dim3(256), 0, s, a);
+    return bwd_dispatch<4>(a.Sq > a.Sk ? a.Sq : a.Sk, bwd_io_form(a), [&](auto n, auto fm) -> int {
+        constexpr int FM = decltype(fm)::value;
+        hipLaunchKernelGGL((attn_bwd_small_kernel<decltype(n)::value, (FM >= 1), (FM >= 2), (FM >= 3)>), dim3(blocks), dim3(256), 0, s, a);
+        SOLA_LAUNCH_CHECK();
+        return SOLA_OK;
+    });
+}
+
+// One pass of the per-wave kernels: four 16-row tiles a block, `rows` = the longest unit's rows on the pass's own side
+template <auto KERNEL, int DH>
+int launch_bwd_wave_pass(AttnBwdArgs a, int rows, hipStream_t s) {
+    constexpr size_t lds = (size_t)4 * 2 * 16 * (DH + 4) * sizeof(float);
+    a.ntile = (rows + 15) / 16;
+    const long long blocks = ((long long)a.G * a.H * a.ntile + 3) / 4;
+    SOLA_TRY(attn_grid_ok(blocks, "attention backward"));
+    SOLA_TRY(bwd_max_lds_once<KERNEL>(lds));
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(256), lds, s, a);
+    SOLA_LAUNCH_CHECK();
+    return SOLA_OK;
+}
+template <int DH, bool RAG>
+int launch_bwd_wave_dq(const AttnBwdArgs& a, hipStream_t s) { return launch_bwd_wave_pass<&attn_bwd_dq_kernel<DH, RAG>, DH>(a, a.Sq, s); }
+template <int DH, bool RAG>
+int launch_bwd_wave_dkv(const AttnBwdArgs& a, hipStream_t s) { return launch_bwd_wave_pass<&attn_bwd_dkv_kernel<DH, RAG>, DH>(a, a.Sk, s); }
+// ... of the block-shared kernels: 64 rows of one unit a block
+template <auto KERNEL, int DH>
+int launch_bwd_blk_pass(const AttnBwdArgs& a, int rows, hipStream_t s) {
+    constexpr size_t lds = (size_t)2 * 2 * 16 * (DH + 4) * sizeof(float);
+    const long long blocks = (long long)a.G * a.H * ((rows + 63) / 64);
+    SOLA_TRY(attn_grid_ok(blocks, "attention backward"));
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(256), lds, s, a);
     SOLA_LAUNCH_CHECK();
     return SOLA_OK;
 }
 
+// The two-pass kernels.  In every branch the dQ pass runs first: it writes dvec = dO . O, which the dK / dV pass reads.
 template <int DH>
-int launch_bwd_dh(const AttnBwdArgs& a0, hipStream_t s) {
-    constexpr size_t lds = (size_t)4 * 2 * 16 * (DH + 4) * sizeof(float);
-    static DeviceOnce once;
-    int dev;
-    if (once.needed(&dev)) {
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<DH>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<DH>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        once.done(dev);
-    }
-    AttnBwdArgs a = a0;
-    bool done_dq = false;
+int launch_bwd_dh(const AttnBwdArgs& a, hipStream_t s) {
     if (a.q_units && a.Sq <= g_attn_bwd_rag_wave && a.Sk <= g_attn_bwd_rag_wave) {
         // ragged batch of short units (motion attention over T' <= 25 steps, inter-object attention over N <= 80 tracks): one wave
         // per 16-row tile, no block-level sync, every wave runs its own unit's trip count.  A 64-row block of the shared-staging
         // shape would serve one unit of 3..80 rows with one to five of its tiles idle and all of them at the longest unit's pace.
-        static DeviceOnce once_r;
-        int dev_r;
-        if (once_r.needed(&dev_r)) {
-            SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<DH, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<DH, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            once_r.done(dev_r);
-        }
-        a.ntile = (a.Sq + 15) / 16;
-        long long u = (long long)a.G * a.H * a.ntile;
-        SOLA_TRY(attn_grid_ok((u + 3) / 4, "attention backward"));
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, true>), dim3((unsigned)((u + 3) / 4)), dim3(256), lds, s, a);
-        SOLA_LAUNCH_CHECK();
-        a.ntile = (a.Sk + 15) / 16;
-        u = (long long)a.G * a.H * a.ntile;
-        SOLA_TRY(attn_grid_ok((u + 3) / 4, "attention backward"));
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH, true>), dim3((unsigned)((u + 3) / 4)), dim3(256), lds, s, a);
-        SOLA_LAUNCH_CHECK();
-        return SOLA_OK;
+        SOLA_TRY((launch_bwd_wave_dq<DH, true>(a, s)));
+        return launch_bwd_wave_dkv<DH, true>(a, s);
     }
-    if constexpr (DH == 128) if (g_attn_bwd_blk) {  // block-shared double-buffered staging (dvec is written by the dQ pass, read by the dK/dV pass)
-        constexpr size_t lds2 = (size_t)2 * 2 * 16 * (DH + 4) * sizeof(float);
-        const long long bq = (long long)a.G * a.H * ((a.Sq + 63) / 64), bk = (long long)a.G * a.H * ((a.Sk + 63) / 64);
-        SOLA_ARG(bq < (1ll << 31) && bk < (1ll << 31), "attention backward: grid too large");
-        // a block of the shared-staging shape serves 64 queries (dQ) / 64 keys (dK, dV) of one unit: with one 16-row tile per
-        // unit three of its four waves would idle (16-step motion attention: 278 us per-wave vs 369 us), so those keep the
-        // per-wave kernels, where a block is four units
-        if (a.Sq > 16) {
-            hipLaunchKernelGGL((attn_bwd_dq_blk_kernel<DH>), dim3((unsigned)bq), dim3(256), lds2, s, a);
-            SOLA_LAUNCH_CHECK();
-            done_dq = true;
-        }
-        if (a.Sk > 16) {
-            if (!done_dq) {  // the dK/dV pass reads dvec = dO . O, which the dQ pass writes
-                a.ntile = (a.Sq + 15) / 16;
-                const long long u = (long long)a.G * a.H * a.ntile;
-                hipLaunchKernelGGL((attn_bwd_dq_kernel<DH>), dim3((unsigned)((u + 3) / 4)), dim3(256), lds, s, a);
-                SOLA_LAUNCH_CHECK();
-                done_dq = true;
-            }
-            hipLaunchKernelGGL((attn_bwd_dkv_blk_kernel<DH>), dim3((unsigned)bk), dim3(256), lds2, s, a);
-            SOLA_LAUNCH_CHECK();
-            return SOLA_OK;
+    // block-shared double-buffered staging (head dim 128) where a side has more than one 16-row tile: a block of that shape serves 64
+    // queries (dQ) / 64 keys (dK, dV) of one unit, and with one tile per unit three of its four waves would idle (16-step motion
+    // attention: 278 us per-wave vs 369 us), so those sides keep the per-wave kernels, where a block is four units
+    if constexpr (DH == 128) {
+        if (g_attn_bwd_blk && (a.Sq > 16 || a.Sk > 16)) {
+            if (a.Sq > 16) SOLA_TRY((launch_bwd_blk_pass<&attn_bwd_dq_blk_kernel<DH>, DH>(a, a.Sq, s)));
+            else SOLA_TRY((launch_bwd_wave_dq<DH, false>(a, s)));
+            if (a.Sk > 16) return launch_bwd_blk_pass<&attn_bwd_dkv_blk_kernel<DH>, DH>(a, a.Sk, s);
+            return launch_bwd_wave_dkv<DH, false>(a, s);
         }
     }
-    long long units;
-    if (!done_dq) {
-        a.ntile = (a.Sq + 15) / 16;
-        units = (long long)a.G * a.H * a.ntile;
-        SOLA_TRY(attn_grid_ok((units + 3) / 4, "attention backward"));
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<DH>), dim3((unsigned)((units + 3) / 4)), dim3(256), lds, s, a);
-        SOLA_LAUNCH_CHECK();
-    }
-    a.ntile = (a.Sk + 15) / 16;
-    units = (long long)a.G * a.H * a.ntile;
-    SOLA_TRY(attn_grid_ok((units + 3) / 4, "attention backward"));
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH>), dim3((unsigned)((units + 3) / 4)), dim3(256), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
+    SOLA_TRY((launch_bwd_wave_dq<DH, false>(a, s)));
+    return launch_bwd_wave_dkv<DH, false>(a, s);
 }
 
 }  // namespace
 
 size_t attention_bwd_part_floats(long long q_rows, int G, int H, int Sk) {
-    if (Sk > 64) return 0;
-    const int qc = q_rows <= 4096 ? 4 : 16;  // kBwdFewRows / kBwdFewChunkTiles / kBwdChunkTiles (launch_bwd_fused)
-    return (size_t)(q_rows / (16 * qc) + G + 1) * H * 2 * 64 * 128;
+    if (Sk > kBwdChunkKeys) return 0;
+    return (size_t)(q_rows / (16 * bwd_chunk_tiles(q_rows)) + G + 1) * H * 2 * kBwdChunkKeys * 128;
 }
 
 bool attention_bwd_dout_bf16_enabled() { return g_attn_bwd_bf16_mfma != 0; }
 
-// bf16 q / k / v in and bf16 dQ / dK / dV out (AttnBwdDesc::io_fmt BF16): the one-pass kernel's shapes, 8-value-aligned rows
+// bf16 q / k / v in and bf16 dQ / dK / dV out (AttnBwdDesc::io_fmt BF16): the one-pass kernel's shapes (or the register kernel's), 8-value-aligned rows
 bool attention_bwd_bf16_supported(const AttnBwdDesc& d) {
     if (d.DH != 128 || d.ldq % 8 || d.ldk % 8 || d.ldv % 8 || d.ld_dq % 4 || d.ld_dk % 4 || d.ld_dv % 4) return false;
-    if (g_attn_bwd_small && d.Sq <= 4 && d.Sk <= 4) return true;  // the register kernel of sequences of <= 4 steps
-    if (!g_attn_bwd_fused || d.Sk > 128) return false;
-    const bool can_chunk = d.part && d.Sk <= 64 && d.part_floats >= attention_bwd_part_floats(d.part_rows, d.G, d.H, d.Sk) && (d.q_units || (d.q_rs == 1 && d.inner == 1));
-    return d.Sq <= 128 || (d.Sk <= 64 && (d.Sq <= 16 * 16 || can_chunk));
+    return bwd_small_shape(d) || bwd_plan(d).fused;
 }
 
 int launch_attention_bwd(const AttnBwdDesc& d, hipStream_t s) {
@@ -1418,13 +1278,10 @@ int launch_attention_bwd(const AttnBwdDesc& d, hipStream_t s) {
     if (io16) SOLA_ARG(attention_bwd_bf16_supported(d) && d.dq16 && d.dk16 && d.dv16 && d.dq, "attention backward: bf16 q / k / v and gradients need the one-pass kernel's shapes");
     const double elems = (double)d.G * d.H * d.DH;
     SolaProfScope prof(SOLA_PROF_ATTN_BWD, s, 14.0 * elems * d.Sq * d.Sk, 4.0 * elems * (5.0 * d.Sq + 4.0 * d.Sk));
-    if (g_attn_bwd_small && d.DH == 128 && d.Sq <= 4 && d.Sk <= 4) return launch_bwd_small(a, s);
-    // chunked launches address their partial sums by the unit's first row: units of row stride 1 in unit order (the caller's promise
-    // when it hands over `part`), sized by attention_bwd_part_floats()
+    if (bwd_small_shape(d)) return launch_bwd_small(a, s);
     a.qc_tiles = 0;
     a.part = d.part;
-    const bool can_chunk = d.part && d.Sk <= 64 && d.part_floats >= attention_bwd_part_floats(d.part_rows, d.G, d.H, d.Sk) &&
-                           (d.q_units || (d.q_rs == 1 && d.inner == 1));
-    if (bwd_fused_supported(a, d.DH, can_chunk)) return launch_bwd_fused(a, can_chunk, d.part_rows, s);
+    const BwdPlan plan = bwd_plan(d);
+    if (plan.fused) return launch_bwd_fused(a, plan, s);
     return attn_dispatch_dh(d.DH, "attention backward: head_dim %d unsupported", [&](auto dh) { return launch_bwd_dh<decltype(dh)::value>(a, s); });
 }

@@ -95,17 +95,17 @@ def unit_rows(case):
 
 def expected_branch(case, switches=None):
     """The kernels a launch of ``case`` runs under the sola_tune ``switches``.  A restatement of launch_attention_bwd,
-    bwd_fused_supported, launch_bwd_fused, launch_bwd_small and launch_bwd_dh (attn_bwd.hip): whoever edits one of those edits this."""
+    bwd_small_shape, bwd_plan, launch_bwd_fused, launch_bwd_small and launch_bwd_dh (attn_bwd.hip): whoever edits one of those edits this."""
     sw = dict(SWITCHES, **(switches or {}))
     Sq, Sk = case.Sq, case.Sk
-    if sw["attn_bwd_small"] and case.DH == 128 and Sq <= 4 and Sk <= 4:  # launch_attention_bwd -> launch_bwd_small
+    if sw["attn_bwd_small"] and case.DH == 128 and Sq <= 4 and Sk <= 4:  # bwd_small_shape -> launch_bwd_small
         need = max(Sq, Sk)
         return "small1" if need <= 1 else "small2" if need <= 2 else "small4"
     q_rows = addressing(case)[3]
     # can_chunk: the scratch is there and large enough (the tests size it with the library's own function), rows consecutive
     can_chunk = case.scratch and Sk <= 64 and case.layout != "strided"
     fused = bool(sw["attn_bwd_fused"]) and case.DH == 128 and Sk <= 128 and (Sq <= 128 or (Sk <= 64 and (Sq <= 256 or can_chunk)))
-    if fused:  # launch_bwd_fused
+    if fused:  # bwd_plan -> launch_bwd_fused
         qc = 4 if can_chunk and q_rows <= 4096 else 16
         chunk = ("chunk64" if qc == 4 else "chunk256") if Sq > 16 * qc and can_chunk else "nochunk"
         return f"fused{1 if Sk <= 16 else 2 if Sk <= 32 else 4}/{chunk}"
