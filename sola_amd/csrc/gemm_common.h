@@ -1,4 +1,4 @@
-// What the GEMM kernels (gemm.hip, gemm_f32p.hip, gemm_glds.hip, gemm_tn.hip, gemm_tn_f32p.hip, gemm_tn_split.hip, gemm_tn_tr.hip and the
+// What the GEMM kernels (gemm.hip, gemm_f32p.hip, gemm_glds.hip, gemm_tn.hip, gemm_tn_f32p.hip, gemm_tn_tr.hip and the
 // closed experiments lab/gemm_k16.hip, lab/gemm_pp.hip) share, stated once: the conv window of an output row, the order in which block or
 // tile ids walk the output, the piece layout of the direct-to-LDS kernels and their zero page, and on the host the XCD-remap rule and the
 // GemmDesc -> kernel-argument fill.  Every args struct keeps its own members and order (the kernarg layout is the kernel's); the templates

@@ -1,14 +1,12 @@
-// Weight-gradient GEMM and its helpers (backward of F.linear / F.conv1d at tools/attention.py:63-73, module/ws.py:14-22):
+// Exact-f32 weight-gradient GEMM (backward of F.linear / F.conv1d at tools/attention.py:63-73, module/ws.py:14-22):
 //   gemm_tn_f32_kernel : P[s][n][k] = sum_{m in split s} A[m][n] * B[m][k]   ("TN": both operands reduce over ROWS)
 //                        A = dY [M, N]; B = X [M, K] or the implicit im2col of the channels-last conv input.
-//   sum_slabs_kernel   : C[n][k] = sum_s P[s][n][k]  (fixed order: deterministic, no float atomics)
-//   transpose_kernel   : out[c][r] = in[r][c]  (W -> W^T so that dX = dY * W runs on the NT kernel)
-//   colsum_kernel      : out[seg][c] = sum_{r in segment} in[r][c]  (bias gradients, GroupNorm dgamma/dbeta, dlbar)
+//   gemm_tn_f32_group_kernel : the same tile for up to 32 problems in one launch, every block over all rows of its problem
+// The splits' partial sums are folded in index order by reduce.hip's sum_slabs_kernel (deterministic, no float atomics).
 // Exact f32 on v_mfma_f32_32x32x2_f32.  The reduction index m is the slow (row) index of both operands, so tiles are
 // staged [32 m][128 cols] with coalesced float4 row loads and the MFMA fragments are ds_read_b32 across the columns
 // (lanes 0-31 take row m, lanes 32-63 row m+1: consecutive addresses, conflict-free).
 #include <algorithm>
-#include <utility>
 
 #include "gemm_common.h"
 
@@ -228,210 +226,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_tn_f32_group_kernel(const TnG
 // (round 4's grouped weight transposition - W -> W^T for the dX GEMMs of a few-sample backward, 49 matrices in one launch - left with round 5:
 // those GEMMs read the weights where they lie, gemm.hip's NN form)
 
-__global__ void sum_slabs_kernel(const float* __restrict__ P, float* __restrict__ C, long long n4, int splits) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    float4 acc = reinterpret_cast<const float4*>(P)[i];
-    for (int s = 1; s < splits; ++s) {
-        const float4 v = reinterpret_cast<const float4*>(P)[i + (long long)s * n4];
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    reinterpret_cast<float4*>(C)[i] = acc;
-}
-
-// out[c * ldo + col_off + r] = in[r * ldi + c], 32x32 tiles through LDS
-__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int rows,
-                                                        int cols, int ldi, int ldo, int col_off) {
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = r0 + ty + 8 * i, c = c0 + tx;
-        if (r < rows && c < cols) tile[ty + 8 * i][tx] = in[(long long)r * ldi + c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = c0 + ty + 8 * i, r = r0 + tx;
-        if (r < rows && c < cols) out[(long long)c * ldo + col_off + r] = tile[tx][ty + 8 * i];
-    }
-}
-
-// The same transposition written straight in a GEMM operand format (FMT 0 = split-f16 pairs in 8-value blocks [hi8 | lo8], 1 = f16,
-// 2 = bfloat16), scaled: out row c (pitch ldo VALUES) column col_off + r = scale * in[r][c].  One launch where the backward's dX GEMMs
-// ran a transposition into an f32 buffer and a cast of that buffer (two launches per weight matrix and step).
-template <int FMT>
-__global__ __launch_bounds__(256) void transpose_cast_kernel(const float* __restrict__ in, void* __restrict__ out, int rows, int cols, int ldi,
-                                                             int ldo, int col_off, float scale) {
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = r0 + ty + 8 * i, c = c0 + tx;
-        if (r < rows && c < cols) tile[ty + 8 * i][tx] = in[(long long)r * ldi + c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = c0 + ty + 8 * i, r = r0 + tx;
-        if (r >= rows || c >= cols) continue;
-        const float v = tile[tx][ty + 8 * i] * scale;
-        const long long n = col_off + r;
-        if (FMT == 0) {
-            _Float16 hi, lo;
-            split_f16(v, hi, lo);
-            _Float16* blk = reinterpret_cast<_Float16*>(static_cast<float*>(out) + (long long)c * ldo + (n & ~7LL)) + (n & 7);
-            blk[0] = hi;
-            blk[8] = lo;
-        } else if (FMT == 1) {
-            static_cast<_Float16*>(out)[(long long)c * ldo + n] = (_Float16)v;
-        } else {
-            static_cast<__bf16*>(out)[(long long)c * ldo + n] = (__bf16)v;
-        }
-    }
-}
-
-// out[(chunk * segments + seg)][c] (+)= scale * sum_{r in chunk of segment} in[(seg * seg_rows + r)][c]
-// block = 64 columns x 4 row lanes; grid.z splits long segments into row chunks (second launch adds the chunks up)
-// seg_stride: elements between the first rows of consecutive segments (seg_rows * ld for back-to-back segments).  out1 / split: output
-// index >= split goes to out1[index - split] instead (two reductions with separate destinations in one launch: launch_colsum_pair).
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ in, float* __restrict__ out, int seg_rows,
-                                                     int cols, int ld, int chunk_rows, float scale, int accumulate, long long seg_stride,
-                                                     float* __restrict__ out1, long long split) {
-    __shared__ float red[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int rl = threadIdx.x >> 6;
-    const int seg = blockIdx.y;
-    const int r_begin = blockIdx.z * chunk_rows;
-    const int r_end = min(seg_rows, r_begin + chunk_rows);
-    // four independent partial sums, fixed combination order: a thread's loads pipeline instead of queueing behind one add
-    // chain (a [256][1024] bias pass took 16 us for 1 MB: 64 dependent load-add steps per thread)
-    // (round 3: eight - the 70 second-stage bias / norm-parameter reductions of a training step are ~200 dependent rows each)
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f, s6 = 0.f, s7 = 0.f;
-    if (c < cols) {
-        const float* p = in + (long long)seg * seg_stride + c;
-        int r = r_begin + rl;
-        for (; r + 28 < r_end; r += 32) {
-            s0 += p[(long long)r * ld]; s1 += p[(long long)(r + 4) * ld]; s2 += p[(long long)(r + 8) * ld]; s3 += p[(long long)(r + 12) * ld];
-            s4 += p[(long long)(r + 16) * ld]; s5 += p[(long long)(r + 20) * ld]; s6 += p[(long long)(r + 24) * ld]; s7 += p[(long long)(r + 28) * ld];
-        }
-        for (; r < r_end; r += 4) s0 += p[(long long)r * ld];
-    }
-    const float s = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
-    red[rl][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (rl == 0 && c < cols) {
-        const float v = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x])) * scale;
-        const long long oi = ((long long)blockIdx.z * gridDim.y + seg) * cols + c;
-        float* o = (out1 && oi >= split) ? out1 + (oi - split) : out + oi;
-        *o = accumulate ? *o + v : v;
-    }
-}
-
-
-// up to 16 (dgamma, dbeta) pairs of column sums in ONE launch (round 5, few-sample backward: the 11 GroupNorm backwards of a one-sample step
-// each ended in a launch_colsum_pair of ~5 us; deferred - every norm keeps private partial buffers - they are one launch per bucket).  Same
-// per-column arithmetic as colsum_kernel with one chunk (rows r = lane, lane + 4, ... in eight partial sums, the four row lanes combined in
-// a fixed order): the same bits as launch_colsum_pair on <= 256 rows.
-constexpr int CSG_MAX = 16;
-struct ColsumGroupArgs {
-    const float* in0[CSG_MAX];
-    const float* in1[CSG_MAX];
-    float* out0[CSG_MAX];
-    float* out1[CSG_MAX];
-    int rows[CSG_MAX], cols[CSG_MAX], first_block[CSG_MAX + 1];
-    int n;
-};
-__global__ __launch_bounds__(256) void colsum_pair_group_kernel(const ColsumGroupArgs a) {
-    __shared__ float red[4][64];
-    int e = 0;
-    for (int j = 1; j < a.n; ++j)
-        if ((int)blockIdx.x >= a.first_block[j]) e = j;
-    const int lb = (int)blockIdx.x - a.first_block[e];
-    const int cb = (a.cols[e] + 63) / 64;
-    const int which = lb / cb;
-    const int c = (lb - which * cb) * 64 + (threadIdx.x & 63);
-    const int rl = threadIdx.x >> 6;
-    const int cols = a.cols[e], ld = cols, r_end = a.rows[e];
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f, s6 = 0.f, s7 = 0.f;
-    if (c < cols) {
-        const float* p = (which ? a.in1[e] : a.in0[e]) + c;
-        int r = rl;
-        for (; r + 28 < r_end; r += 32) {
-            s0 += p[(long long)r * ld]; s1 += p[(long long)(r + 4) * ld]; s2 += p[(long long)(r + 8) * ld]; s3 += p[(long long)(r + 12) * ld];
-            s4 += p[(long long)(r + 16) * ld]; s5 += p[(long long)(r + 20) * ld]; s6 += p[(long long)(r + 24) * ld]; s7 += p[(long long)(r + 28) * ld];
-        }
-        for (; r < r_end; r += 4) s0 += p[(long long)r * ld];
-    }
-    const float s = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
-    red[rl][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (rl == 0 && c < cols) {
-        const float v = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x])) * 1.0f;
-        (which ? a.out1[e] : a.out0[e])[c] = v;
-    }
-}
-
-// Up to 48 single column sums in ONE launch (round 6: the ~30 bias gradients of a reduced-precision training step were one ~9-us launch each
-// over the slab sums their statistics pass left; every statistics pass keeps its slab table now and a bucket's bias sums leave together).
-// Per-column arithmetic = colsum_kernel with one chunk (eight partial sums per row lane, four row lanes combined in a fixed order): the same bits.
-constexpr int CSJ_MAX = 48;
-struct ColsumJobsArgs {
-    const float* in[CSJ_MAX];
-    float* out[CSJ_MAX];
-    int rows[CSJ_MAX], cols[CSJ_MAX], ld[CSJ_MAX], first_block[CSJ_MAX + 1];
-    int n;
-};
-__global__ __launch_bounds__(256) void colsum_jobs_kernel(const ColsumJobsArgs a) {
-    __shared__ float red[4][64];
-    int lo = 0, hi = a.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.first_block[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int e = lo;
-    const int c = ((int)blockIdx.x - a.first_block[e]) * 64 + (threadIdx.x & 63);
-    const int rl = threadIdx.x >> 6;
-    const int cols = a.cols[e], ld = a.ld[e], r_end = a.rows[e];
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f, s6 = 0.f, s7 = 0.f;
-    if (c < cols) {
-        const float* p = a.in[e] + c;
-        int r = rl;
-        for (; r + 28 < r_end; r += 32) {
-            s0 += p[(long long)r * ld]; s1 += p[(long long)(r + 4) * ld]; s2 += p[(long long)(r + 8) * ld]; s3 += p[(long long)(r + 12) * ld];
-            s4 += p[(long long)(r + 16) * ld]; s5 += p[(long long)(r + 20) * ld]; s6 += p[(long long)(r + 24) * ld]; s7 += p[(long long)(r + 28) * ld];
-        }
-        for (; r < r_end; r += 4) s0 += p[(long long)r * ld];
-    }
-    const float s = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
-    red[rl][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (rl == 0 && c < cols) a.out[e][c] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x])) * 1.0f;
-}
-
 }  // namespace
-
-int launch_colsum_jobs(const ColsumJobsDesc& d, hipStream_t s) {
-    SOLA_ARG(d.n >= 1 && d.n <= CSJ_MAX, "colsum_jobs: %d jobs", d.n);
-    ColsumJobsArgs a;
-    a.n = d.n;
-    int blocks = 0;
-    double bytes = 0;
-    for (int e = 0; e < d.n; ++e) {
-        SOLA_ARG(d.in[e] && d.out[e] && d.rows[e] > 0 && d.cols[e] > 0 && d.ld[e] >= d.cols[e], "colsum_jobs: job %d", e);
-        a.in[e] = d.in[e]; a.out[e] = d.out[e]; a.rows[e] = d.rows[e]; a.cols[e] = d.cols[e]; a.ld[e] = d.ld[e];
-        a.first_block[e] = blocks;
-        blocks += (d.cols[e] + 63) / 64;
-        bytes += 4.0 * d.rows[e] * d.cols[e];
-    }
-    a.first_block[d.n] = blocks;
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, bytes);
-    hipLaunchKernelGGL(colsum_jobs_kernel, dim3(blocks), dim3(256), 0, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
 
 int g_gemm_tn_nw8 = 1;  // sola_tune "gemm_tn_nw8": the exact-f32 weight-gradient kernels with eight waves per block (0 = four; A/B)
 static int tn_splits(int M, int N, int K) {
@@ -443,8 +238,6 @@ static int tn_splits(int M, int N, int K) {
     return splits;
 }
 
-int gemm_tn_persist_plan(int M, int N, int K);  // gemm_tn_f32p.hip
-size_t colsum_scratch_bytes(int segments, int seg_rows, int cols);
 size_t gemm_tn_scratch_bytes(int M, int N, int K) {
     const int splits = tn_splits(M, N, K);
     const size_t one_tile = (size_t)splits * ((size_t)N * K + N) * sizeof(float);
@@ -452,9 +245,6 @@ size_t gemm_tn_scratch_bytes(int M, int N, int K) {
     const size_t persist = ps > 0 ? (size_t)ps * N * K * sizeof(float) + colsum_scratch_bytes(1, M, N) : 0;
     return std::max(one_tile, persist);
 }
-
-int gemm_tn_persist_splits(const GemmTnDesc& d, int max_splits);  // gemm_tn_f32p.hip: the persistent direct-to-LDS form (0 = not its shape)
-int launch_gemm_tn_f32_persist(const GemmTnDesc& d, int splits, float* P, int* splits_out, hipStream_t s);
 
 int launch_gemm_tn(const GemmTnDesc& d, hipStream_t s) {
     SOLA_ARG(d.M > 0 && d.N > 0 && d.K > 0 && d.N % 4 == 0 && d.K % 4 == 0, "gemm_tn: bad dims M=%d N=%d K=%d", d.M, d.N, d.K);
@@ -487,8 +277,7 @@ int launch_gemm_tn(const GemmTnDesc& d, hipStream_t s) {
             const long long n4 = (long long)d.N * d.K / 4;
             {
                 SolaProfScope prof(SOLA_PROF_MISC, s, 0, 4.0 * (used + 1.0) * d.N * d.K);
-                hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, d.scratch, d.C, n4, used);
-                SOLA_LAUNCH_CHECK();
+                SOLA_TRY(sum_slabs(d.scratch, d.C, n4, used, s));
             }
             if (d.bias_grad) {
                 float* cs = d.scratch + (size_t)used * d.N * d.K;
@@ -510,13 +299,8 @@ int launch_gemm_tn(const GemmTnDesc& d, hipStream_t s) {
     {
         const long long n4 = (long long)d.N * d.K / 4;
         SolaProfScope prof(SOLA_PROF_MISC, s, 0, 4.0 * (splits + 1.0) * d.N * d.K);
-        hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, d.scratch, d.C, n4, splits);
-        SOLA_LAUNCH_CHECK();
-        if (d.bias_grad) {
-            const long long b4 = d.N / 4;
-            hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)((b4 + 255) / 256)), dim3(256), 0, s, a.Pb, d.bias_grad, b4, splits);
-            SOLA_LAUNCH_CHECK();
-        }
+        SOLA_TRY(sum_slabs(d.scratch, d.C, n4, splits, s));
+        if (d.bias_grad) SOLA_TRY(sum_slabs(a.Pb, d.bias_grad, d.N / 4, splits, s));
     }
     return SOLA_OK;
 }
@@ -546,100 +330,4 @@ int launch_gemm_tn_group(const GemmTnGroupDesc& d, hipStream_t s) {
     SolaProfScope prof(SOLA_PROF_GEMM_TN, s, flops, bytes);
     if (g_gemm_tn_nw8) return launch_lds<gemm_tn_f32_group_kernel<8>>(dim3((unsigned)tiles), dim3(512), lds, s, g);
     return launch_lds<gemm_tn_f32_group_kernel<4>>(dim3((unsigned)tiles), dim3(256), lds, s, g);
-}
-
-int launch_transpose(const float* in, float* out, int rows, int cols, int ldi, int ldo, int col_off, hipStream_t s) {
-    SOLA_ARG(rows > 0 && cols > 0, "transpose: bad dims");
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, 8.0 * rows * cols);
-    hipLaunchKernelGGL(transpose_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0, s, in, out, rows, cols, ldi, ldo, col_off);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-
-int launch_transpose_cast(const float* in, void* out, int rows, int cols, int ldi, int ldo, int col_off, float scale, Elem fmt, hipStream_t s) {
-    SOLA_ARG(in && out && rows > 0 && cols > 0 && fmt != Elem::F32 && (fmt != Elem::SP16 || ldo % 8 == 0), "transpose_cast: bad arguments (%s ldo %d)", elem_name(fmt), ldo);
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, (fmt == Elem::SP16 ? 8.0 : 6.0) * rows * cols);
-    const dim3 grid((cols + 31) / 32, (rows + 31) / 32);
-    if (fmt == Elem::SP16) hipLaunchKernelGGL(transpose_cast_kernel<0>, grid, dim3(256), 0, s, in, out, rows, cols, ldi, ldo, col_off, scale);
-    else if (fmt == Elem::F16) hipLaunchKernelGGL(transpose_cast_kernel<1>, grid, dim3(256), 0, s, in, out, rows, cols, ldi, ldo, col_off, scale);
-    else hipLaunchKernelGGL(transpose_cast_kernel<2>, grid, dim3(256), 0, s, in, out, rows, cols, ldi, ldo, col_off, scale);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-
-size_t colsum_scratch_bytes(int segments, int seg_rows, int cols) {
-    if (seg_rows <= 256) return 0;
-    const int chunks = min(64, (seg_rows + 127) / 128);
-    return (size_t)chunks * segments * cols * sizeof(float);
-}
-
-int launch_colsum(const float* in, float* out, int segments, int seg_rows, int cols, int ld, float scale, int accumulate,
-                  float* scratch, size_t scratch_bytes, hipStream_t s) {
-    SOLA_ARG(segments > 0 && seg_rows > 0 && cols > 0 && segments <= 65535, "colsum: bad dims");
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, 4.0 * segments * (double)seg_rows * cols);
-    const size_t need = colsum_scratch_bytes(segments, seg_rows, cols);
-    if (need == 0 || scratch == nullptr || scratch_bytes < need) {
-        hipLaunchKernelGGL(colsum_kernel, dim3((cols + 63) / 64, segments, 1), dim3(256), 0, s, in, out, seg_rows, cols, ld,
-                           seg_rows, scale, accumulate, (long long)seg_rows * ld, (float*)nullptr, 0LL);
-        SOLA_LAUNCH_CHECK();
-        return SOLA_OK;
-    }
-    const int chunks = (int)(need / ((size_t)segments * cols * sizeof(float)));
-    const int chunk_rows = (seg_rows + chunks - 1) / chunks;
-    hipLaunchKernelGGL(colsum_kernel, dim3((cols + 63) / 64, segments, chunks), dim3(256), 0, s, in, scratch, seg_rows, cols,
-                       ld, chunk_rows, 1.0f, 0, (long long)seg_rows * ld, (float*)nullptr, 0LL);
-    SOLA_LAUNCH_CHECK();
-    const int wide = segments * cols;  // second pass: [chunks][segments*cols] -> [segments*cols]
-    hipLaunchKernelGGL(colsum_kernel, dim3((wide + 63) / 64, 1, 1), dim3(256), 0, s, scratch, out, chunks, wide, wide, chunks,
-                       scale, accumulate, (long long)chunks * wide, (float*)nullptr, 0LL);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-
-// Two column sums of equally shaped matrices with separate destinations (GroupNorm's dgamma / dbeta partials) in the launches of one:
-// the same chunking and summation order as two launch_colsum calls, so the same bits.
-int launch_colsum_pair(const float* in0, const float* in1, float* out0, float* out1, int seg_rows, int cols, int ld, float* scratch,
-                       size_t scratch_bytes, hipStream_t s) {
-    SOLA_ARG(in0 && in1 && out0 && out1 && seg_rows > 0 && cols > 0, "colsum_pair: bad arguments");
-    if (in1 < in0) { std::swap(in0, in1); std::swap(out0, out1); }
-    const long long stride = in1 - in0;
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, 8.0 * (double)seg_rows * cols);
-    const size_t need = colsum_scratch_bytes(2, seg_rows, cols);
-    if (need == 0 || scratch == nullptr || scratch_bytes < need) {
-        hipLaunchKernelGGL(colsum_kernel, dim3((cols + 63) / 64, 2, 1), dim3(256), 0, s, in0, out0, seg_rows, cols, ld, seg_rows, 1.0f, 0, stride, out1,
-                           (long long)cols);
-        SOLA_LAUNCH_CHECK();
-        return SOLA_OK;
-    }
-    const int chunks = (int)(need / ((size_t)2 * cols * sizeof(float)));
-    const int chunk_rows = (seg_rows + chunks - 1) / chunks;
-    hipLaunchKernelGGL(colsum_kernel, dim3((cols + 63) / 64, 2, chunks), dim3(256), 0, s, in0, scratch, seg_rows, cols, ld, chunk_rows, 1.0f, 0, stride,
-                       (float*)nullptr, 0LL);
-    SOLA_LAUNCH_CHECK();
-    const int wide = 2 * cols;
-    hipLaunchKernelGGL(colsum_kernel, dim3((wide + 63) / 64, 1, 1), dim3(256), 0, s, scratch, out0, chunks, wide, wide, chunks, 1.0f, 0,
-                       (long long)chunks * wide, out1, (long long)cols);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-
-
-int launch_colsum_pair_group(const ColsumPairGroupDesc& d, hipStream_t s) {
-    SOLA_ARG(d.n >= 1 && d.n <= CSG_MAX, "colsum_pair_group: %d pairs", d.n);
-    ColsumGroupArgs a;
-    a.n = d.n;
-    int blocks = 0;
-    double bytes = 0;
-    for (int e = 0; e < d.n; ++e) {
-        SOLA_ARG(d.in0[e] && d.in1[e] && d.out0[e] && d.out1[e] && d.rows[e] > 0 && d.rows[e] <= 256 && d.cols[e] > 0, "colsum_pair_group: pair %d (rows %d)", e, d.rows[e]);
-        a.in0[e] = d.in0[e]; a.in1[e] = d.in1[e]; a.out0[e] = d.out0[e]; a.out1[e] = d.out1[e]; a.rows[e] = d.rows[e]; a.cols[e] = d.cols[e];
-        a.first_block[e] = blocks;
-        blocks += 2 * ((d.cols[e] + 63) / 64);
-        bytes += 8.0 * d.rows[e] * d.cols[e];
-    }
-    a.first_block[d.n] = blocks;
-    SolaProfScope prof(SOLA_PROF_MISC, s, 0, bytes);
-    hipLaunchKernelGGL(colsum_pair_group_kernel, dim3(blocks), dim3(256), 0, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
 }

@@ -1,6 +1,6 @@
 // Exact-f32 weight-gradient GEMM, persistent direct-to-LDS form (round 5): P[s][n][k] = sum over the rows m of split s of A[m][n] * B[m][k]
 // (A = dY [M, N]; B = X [M, K] or the implicit im2col of the channels-last conv input) - the backward of F.linear / F.conv1d at
-// tools/attention.py:63-73, module/ws.py:14-22.  gemm_tn.hip's sum_slabs_kernel folds the splits in index order (deterministic).
+// tools/attention.py:63-73, module/ws.py:14-22.  reduce.hip's sum_slabs_kernel folds the splits in index order (deterministic).
 //
 // Same arithmetic as gemm_tn_f32_kernel (v_mfma_f32_32x32x2_f32, one accumulator per output element, rows in ascending pairs inside a
 // split); built like gemm_f32p.hip's NT kernel, for the same reason - on gfx950 a VALU instruction does not overlap with the f32 MFMA

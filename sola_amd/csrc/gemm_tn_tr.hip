@@ -295,9 +295,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_bf16_kernel(const unsigned 
     const unsigned short* p = part + (long long)z * ksplit * mn + i * 4;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int k = 0; k < ksplit; ++k) {
-        const uint2 w = *reinterpret_cast<const uint2*>(p + (long long)k * mn);
-        acc.x += __builtin_bit_cast(float, w.x << 16); acc.y += __builtin_bit_cast(float, w.x & 0xffff0000u);
-        acc.z += __builtin_bit_cast(float, w.y << 16); acc.w += __builtin_bit_cast(float, w.y & 0xffff0000u);
+        const float4 v = bf16x4_to_f32(*reinterpret_cast<const uint2*>(p + (long long)k * mn));
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     }
     const float osc = (s0 ? *s0 : 1.f) * (s1 ? *s1 : 1.f);
     float* c = z == 0 ? c0 : (z == 1 ? c1 : c2);

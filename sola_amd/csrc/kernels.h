@@ -102,7 +102,8 @@ bool conv_frames_pays(const GemmDesc& conv, const ConvFramePlan& plan);
 bool conv_frames_has_weights(const GemmDesc& conv, const ConvFramePlan& plan, const ConvTapWeights& w);  // a packed copy for every partial range
 int launch_conv_frames(const GemmDesc& conv, const ConvFramePlan& plan, const ConvTapWeights& w, hipStream_t s);
 
-// ---- weight-gradient GEMM + helpers (gemm_tn.hip) ----------------------------------------------------------------
+// ---- weight-gradient GEMMs (gemm_tn.hip, gemm_tn_f32p.hip, gemm_tn_split.hip, gemm_tn_tr.hip), the transposes (cast.hip) and the
+//      fixed-order sums (reduce.hip) ------------------------------------------------------------------------------------
 struct GemmTnDesc {
     const float* A;   // dY [M, N]
     const float* B;   // X [M, K] (or conv source when conv = 1)
@@ -168,6 +169,29 @@ static_assert(!gemm_tn_split_formats_ok(Elem::F32, Elem::F32, Elem::F32) && !gem
 // in [rows][cols] f32 -> out [cols][ld_out] split-f16 (rows rows..ld_out zero-filled; ld_out % 128 == 0); scal: optional
 // device pair as for launch_cast_sp16_auto with scal[0] = max|in| already there
 int launch_cast_sp16_t(const float* in, int ld_in, float* out, long long ld_out, int rows, int cols, float* scal, hipStream_t s);
+// The transposing cast behind launch_cast_sp16_t / launch_cast_f16_t with everything launch_gemm_tn_split asks of it (cast.hip; no argument
+// checks: the launchers' and that route's own)
+struct CastTDesc {
+    Elem ab;             // the transposed output's format: SP16 pairs ([cols][ld_out] floats) or F16 / BF16 values ([cols][ld_out] halfs)
+    const float* in;     // [rows][cols], pitch ld_in
+    int ld_in;
+    float* out;
+    long long ld_out;    // % 128 == 0, >= rows; rows past `rows` are written as zeros
+    int rows, cols;
+    float* scal;         // optional device pair, scal[0] = max|in|: the power-of-two scale of launch_cast_sp16_auto
+    // conv_T_out > 0: `in` is the channels-last conv input and the rows are ONE tap of its implicit im2col: row m = (r, to) reads source
+    // row r * conv_T_in + to * conv_stride + conv_toff (tap - pad), zeros outside [0, conv_T_in)
+    int conv_T_in = 0, conv_T_out = 0, conv_stride = 1, conv_toff = 0;
+    // optional row-major cast of the same values in format rm_fmt (`ab` or SP16), pitch ld_rm values; whole 64-column tiles and
+    // ld_in % 4 == 0 (gemm_tn_split_writes_rm)
+    float* out_rm = nullptr;
+    long long ld_rm = 0;
+    Elem rm_fmt = Elem::F32;
+    // ragged batches: row m reads source row rowmap[m].x + tap, zeros where bit `tap` of rowmap[m].y is clear
+    const int2* rowmap = nullptr;
+    int tap = 0;
+};
+int cast_t(const CastTDesc& d, hipStream_t s);
 // dx[(r, ti)][ci] = sum over taps of z[(r, to)][kk*cin + ci] (the scatter of a transposed conv, as a gather)
 int launch_col2im(const float* z, float* dx, long long R, int T_in, int T_out, int cin, int k, int stride, int pad, Elem z_fmt, hipStream_t s);  // z: F32 or BF16 rows
 // ragged batches: input row i has imap[i] = (first output row of its sequence, T_out, step ti inside the sequence, -)
@@ -180,6 +204,13 @@ size_t gemm_tn_split_scratch_bytes(int M, int N, int K, int nprob);
 int launch_gemm_tn_split(const GemmTnSplitDesc& d, hipStream_t s);
 size_t gemm_tn_scratch_bytes(int M, int N, int K);
 int launch_gemm_tn(const GemmTnDesc& d, hipStream_t s);
+// gemm_tn_f32p.hip, the persistent direct-to-LDS form behind launch_gemm_tn: the splits its shape plan wants (0 = not its shape), the
+// splits of one problem within max_splits slabs of scratch, and the launch (partial sums P[*splits_out][N][K]; the caller folds them)
+int gemm_tn_persist_plan(int M, int N, int K);
+int gemm_tn_persist_splits(const GemmTnDesc& d, int max_splits);
+int launch_gemm_tn_f32_persist(const GemmTnDesc& d, int splits, float* P, int* splits_out, hipStream_t s);
+// C[i] = sum_s P[s * n4 + i] over float4s, in index order (reduce.hip); inside the caller's profiler scope
+int sum_slabs(const float* P, float* C, long long n4, int splits, hipStream_t s);
 // dW_j[n][k] = sum_m A_j[m][n] B_j[m][k] on ROW-MAJOR 16-bit operands (gemm_tn_tr.hip's gemm_tn_tr_kernel: transposing LDS reads,
 // no transposed copies): raw partial sums of `ksplit` row ranges of `kper` 64-row k-tiles into part[(j * ksplit + range)][N][K]
 struct GemmTnTrDesc {
