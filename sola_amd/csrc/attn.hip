@@ -20,7 +20,7 @@
 //   packed : sequences of <= 16 steps (motion attention over T').  16 / pow2(T') independent (group, head) units share
 //            ONE 16x16 MFMA tile as a block-diagonal problem (cross-unit scores masked to -inf), so a T'=4 launch
 //            issues a quarter of the waves and MFMAs and each wave moves 4x the bytes per tile.
-#include "attn_common.h"
+#include "attn_fwd_steps.h"
 
 namespace {
 
@@ -148,24 +148,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
         }
         __syncthreads();
         f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-        {
-            const float* kp = &Ks[c16 * LDK + 4 * g4];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const float4 kf = *reinterpret_cast<const float4*>(kp + c * 16);
-                if (c & 1) {
-                    a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[c].x, a1, 0, 0, 0);
-                    a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[c].y, a1, 0, 0, 0);
-                    a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[c].z, a1, 0, 0, 0);
-                    a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[c].w, a1, 0, 0, 0);
-                } else {
-                    a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[c].x, a0, 0, 0, 0);
-                    a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[c].y, a0, 0, 0, 0);
-                    a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[c].z, a0, 0, 0, 0);
-                    a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[c].w, a0, 0, 0, 0);
-                }
-            }
-        }
+        attn_qk_f32<NC>(&Ks[c16 * LDK + 4 * g4], qf, a0, a1);
         // block-diagonal mask: key slot (4*g4 + r) is visible to query row c16 only inside the same unit
         float sc[4];
         float mx = -INFINITY;
@@ -194,6 +177,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
         f32x4 oacc[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) oacc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // PV loop written out: a shared body costs the packed kernels of head_dim 16 / 64 two / one VGPR (profiles/attn_fwd_bodies_isa.txt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float* vp = &Vs[(4 * g4 + r) * LDV + c16];
@@ -263,18 +247,10 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
         };
         long long u = blockIdx.x;
         Unit cur = decode(u);
-        auto stage = [&](int kt0, int nrows, int nrows16) {  // multi-tile path: straight to LDS
-            for (int idx = tid; idx < nrows16 * F4; idx += NT) {
-                const int r = idx / F4, c4 = idx - r * F4;
-                float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
-                if (r < nrows) {
-                    const long long row = cur.krow0 + (long long)(kt0 + r) * cur.k_rs;
-                    kv = *reinterpret_cast<const float4*>(a.k + row * a.ldk + cur.h * DH + c4 * 4);
-                    vv = *reinterpret_cast<const float4*>(a.v + row * a.ldv + cur.h * DH + c4 * 4);
-                }
-                put_k(r, c4, kv);
-                put_v(r, c4, vv);
-            }
+        // multi-tile path: straight to LDS.  (The call stays inside this lambda: made where the tile loop stages, the head-dim-32 kernels
+        // spill 106 SGPRs instead of 94.)
+        auto stage = [&](int kt0, int nrows, int nrows16) {
+            attn_stage_rows<float4, DH, NT>(a.k, a.v, a.ldk, a.ldv, cur.krow0, cur.k_rs, kt0, cur.h, nrows, nrows16, tid, Ks, Vs, LDK, LDV);
         };
         auto load_q = [&](const Unit& c, int qb, float4 (&dst)[NC]) {
             const int qi = qb * (NW * 16) + wave * 16 + c16;
@@ -353,34 +329,15 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
                         if constexpr (SPLIT) {
                             // A = K rows as (hi4, lo4) of head dims 16c + 4*g4 .. +3: two 8-byte reads of block 2c + (g4 >> 1)
                             const char* kb = reinterpret_cast<const char*>(&Ks[(kbase + t * 16 + c16) * LDK]) + (g4 >> 1) * 32 + (g4 & 1) * 8;
+                            HL4 qq[NC];
 #pragma unroll
-                            for (int c = 0; c < NC; ++c) {
-                                const HL4 kf = as_hl4(*reinterpret_cast<const float2*>(kb + c * 64), *reinterpret_cast<const float2*>(kb + c * 64 + 16));
-                                const HL4 qq = as_hl4(make_float2(qf[c].x, qf[c].y), make_float2(qf[c].z, qf[c].w));
-                                if (c & 1) a1 = mfma3(kf, qq, a1);
-                                else a0 = mfma3(kf, qq, a0);
-                            }
+                            for (int c = 0; c < NC; ++c) qq[c] = as_hl4(make_float2(qf[c].x, qf[c].y), make_float2(qf[c].z, qf[c].w));
+                            attn_qk_split<NC>(kb, kb + 16, 64, qq, a0, a1);
                         } else
-#pragma unroll
-                        for (int c = 0; c < NC; ++c) {
-                            const float4 kf = *reinterpret_cast<const float4*>(kp + c * 16);
-                            if (c & 1) {
-                                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[c].x, a1, 0, 0, 0);
-                                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[c].y, a1, 0, 0, 0);
-                                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[c].z, a1, 0, 0, 0);
-                                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[c].w, a1, 0, 0, 0);
-                            } else {
-                                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[c].x, a0, 0, 0, 0);
-                                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[c].y, a0, 0, 0, 0);
-                                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[c].z, a0, 0, 0, 0);
-                                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[c].w, a0, 0, 0, 0);
-                            }
-                        }
-                        const int key0 = kt0 + t * 16 + 4 * g4;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) sc[t][r] = (key0 + r < cur.Sk) ? (a0[r] + a1[r]) * a.scale : -INFINITY;
+                            attn_qk_f32<NC>(kp, qf, a0, a1);
+                        sc[t] = attn_mask_scale(a0, a1, kt0 + t * 16 + 4 * g4, cur.Sk, a.scale);
                     } else {
-                        sc[t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                        sc[t] = attn_mask_scale();
                     }
                 }
                 if (kt0 + a.tile_rows >= cur.Sk) {  // q is dead for this q-block: fetch the next fragment into the same registers
@@ -388,34 +345,11 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
                     else if (has_next) load_q(nxt, nxt.qs, qf);
                 }
                 // ---- online softmax over this key tile (row = 16-lane column c16; key slots spread over g4 and r)
-                float mx = -INFINITY;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[t][r]);
-                mx = xor16_32_max(mx);
-                const float m_new = fmaxf(m_run, mx);
-                const float alpha = __expf(m_run - m_new);  // exp(-inf) = 0 on the first tile
-                float rs = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        sc[t][r] = __expf(sc[t][r] - m_new);
-                        rs += sc[t][r];
-                    }
-                rs = xor16_32_sum(rs);
-                l_run = l_run * alpha + rs;
-                m_run = m_new;
+                const float alpha = attn_softmax_tile<4, false>(sc, m_run, l_run);
 #pragma unroll
                 for (int c = 0; c < NC; ++c) oacc[c] *= alpha;
                 if (a.drop.enabled) {  // dropout acts on the normalised probabilities: the row sum above stays undropped
-                    const unsigned long long rbase = ((unsigned long long)(grp * a.H + h) * cur.Sq + qi) * cur.Sk;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            sc[t][r] = dropout_keep(a.drop, rbase + kt0 + t * 16 + 4 * g4 + r) ? sc[t][r] * a.drop.scale : 0.f;
+                    attn_dropout_tile<4>(sc, a.drop, ((unsigned long long)(grp * a.H + h) * cur.Sq + qi) * cur.Sk, kt0, g4);
                 }
                 if (single_tile && has_next && qb + a.qsplit >= cur.nqb && kt0 + a.tile_rows >= cur.Sk) {
                     // last QK^T of this unit is done: Ks can take the next unit's K, and its V starts to travel
@@ -443,6 +377,8 @@ __global__ __launch_bounds__(NW * 64, MINB) void attn_fwd_f32_kernel(const AttnA
                                 oacc[c] = mfma3(vf, ps, oacc[c]);
                             }
                         } else
+                        // PV loop written out: a shared body makes other, smaller kernels (head_dim 128: 256 -> 242 VGPRs, no scratch), untimed so
+                        // far - store_o's finding above; worth revisiting with timings (profiles/attn_fwd_bodies_isa.txt)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const float* vp = &Vs[(kbase + t * 16 + 4 * g4 + r) * LDV + c16];

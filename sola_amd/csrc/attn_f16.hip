@@ -17,7 +17,7 @@
 // per block at head_dim 128, so four 4-wave blocks share a CU and cover each other's memory latency; longer key sequences
 // take further tiles with an online softmax.  Sequences of at most 16 steps (motion attention over T') use one wave per
 // (group, head) unit with a private 16-row tile, four units per block, no block-level synchronisation.
-#include "attn_common.h"
+#include "attn_fwd_steps.h"
 
 namespace {
 
@@ -177,6 +177,7 @@ __global__ __launch_bounds__(256, WPU ? 2 : 4) void attn_fwd_f16_kernel(const At
                 }
             }
             // online softmax over this key tile (row = 16-lane column c16; key slots spread over g4 and r)
+            // (written out, as mask-and-scale and the staging above: the shared forms made other kernels; profiles/attn_fwd_bodies_bench.txt)
             float mx = -INFINITY;
 #pragma unroll
             for (int t = 0; t < TROWS / 16; ++t)
@@ -200,12 +201,7 @@ __global__ __launch_bounds__(256, WPU ? 2 : 4) void attn_fwd_f16_kernel(const At
             for (int c = 0; c < NC; ++c) oacc[c] *= alpha;
             if constexpr (TR) {
                 if (a.drop.enabled) {  // dropout acts on the normalised probabilities: the row sum above stays undropped (attn.hip)
-                    const unsigned long long rbase = ((unsigned long long)(grp * a.H + h) * g.Sq + qi) * g.Sk;
-#pragma unroll
-                    for (int t = 0; t < TROWS / 16; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            sc[t][r] = dropout_keep(a.drop, rbase + kt0 + t * 16 + 4 * g4 + r) ? sc[t][r] * a.drop.scale : 0.f;
+                    attn_dropout_tile<TROWS / 16>(sc, a.drop, ((unsigned long long)(grp * a.H + h) * g.Sq + qi) * g.Sk, kt0, g4);
                 }
             }
             // O^T += V^T P^T

@@ -7,7 +7,7 @@
 // VGPRs, so four to five blocks share a CU and cover each other's latency; longer key sequences take further tiles with
 // the online softmax.  Same arithmetic (v_mfma_f32_16x16x4_f32, S^T = K Q^T / O^T = V^T P^T register layout), same
 // addressing (strided groups or unit tables), f32 or split-f16 output.
-#include "attn_common.h"
+#include "attn_fwd_steps.h"
 
 namespace {
 
@@ -45,7 +45,6 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_f32_simple_kernel(const AttnS
     static_assert(!IN16 || (DB && TR), "bf16 inputs: the double-buffered training instantiation");
     constexpr int NC = DH / 16;
     constexpr int LDK = DH + 4, LDV = DH + 4;
-    constexpr int F4 = DH / 4;
     extern __shared__ __attribute__((aligned(16))) float smem_s[];
     float* Ks = smem_s;
     float* Vs = smem_s + TK * LDK;
@@ -136,17 +135,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_f32_simple_kernel(const AttnS
             if (kt0 + TK < Sk) fetch(kt0 + TK);
         } else {
         if (kt0 > 0) __syncthreads();
-        for (int idx = tid; idx < nrows16 * F4; idx += 256) {
-            const int r = idx / F4, c4 = idx - r * F4;
-            float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
-            if (r < nrows) {
-                const long long row = k0 + (long long)(kt0 + r) * k_rs;
-                kv = *reinterpret_cast<const float4*>(a.k + row * a.ldk + h * DH + c4 * 4);
-                vv = *reinterpret_cast<const float4*>(a.v + row * a.ldv + h * DH + c4 * 4);
-            }
-            *reinterpret_cast<float4*>(&Ks[r * LDK + c4 * 4]) = kv;
-            *reinterpret_cast<float4*>(&Vs[r * LDV + c4 * 4]) = vv;
-        }
+        attn_stage_rows<float4, DH, 256>(a.k, a.v, a.ldk, a.ldv, k0, k_rs, kt0, h, nrows, nrows16, tid, Ks, Vs, LDK, LDV);
         __syncthreads();
         }
         const int ntile = nrows16 >> 4;
@@ -155,22 +144,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_f32_simple_kernel(const AttnS
         for (int t = 0; t < TK / 16; ++t) {
             if (t < ntile) {
                 f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-                const float* kp = &Ks[(t * 16 + c16) * LDK + 4 * g4];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const float4 kf = *reinterpret_cast<const float4*>(kp + c * 16);
-                    if (c & 1) {
-                        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[c].x, a1, 0, 0, 0);
-                        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[c].y, a1, 0, 0, 0);
-                        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[c].z, a1, 0, 0, 0);
-                        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[c].w, a1, 0, 0, 0);
-                    } else {
-                        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[c].x, a0, 0, 0, 0);
-                        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[c].y, a0, 0, 0, 0);
-                        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[c].z, a0, 0, 0, 0);
-                        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[c].w, a0, 0, 0, 0);
-                    }
-                }
+                attn_qk_f32<NC>(&Ks[(t * 16 + c16) * LDK + 4 * g4], qf, a0, a1);
                 const int key0 = kt0 + t * 16 + 4 * g4;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sc[t][r] = (key0 + r < Sk) ? (a0[r] + a1[r]) * a.scale : -INFINITY;
@@ -178,6 +152,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_f32_simple_kernel(const AttnS
                 sc[t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
             }
         }
+        // mask-and-scale, the softmax step and the PV loop stay written out: profiles/attn_fwd_bodies_isa.txt, attn_fwd_bodies_bench.txt
         float mx = -INFINITY;
 #pragma unroll
         for (int t = 0; t < TK / 16; ++t)
@@ -381,6 +356,16 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(const AttnSArgs a) 
 // converted to (hi, lo) halfs while it is staged - K row-major, V TRANSPOSED ([d][key]) so that both MFMA A-fragments are
 // single 8-byte LDS reads - Q and P are split in registers, and a product costs 3 x 8 cycles instead of 4 x 32.  The halved
 // tile (38 KB for 32 keys) keeps four blocks per CU.  Same block decomposition, addressing and online softmax as above.
+// block -> (unit, 64-query block) -> (group, head) for the two split kernels below.  The f32 kernel keeps its own lines (with the XCD
+// remap), and the unit's rows and the lane's query stay in the kernels: either way moved a register row (profiles/attn_fwd_bodies_isa.txt).
+struct SimpleBlock { int grp, h, qb; };
+__device__ __forceinline__ SimpleBlock simple_block(const AttnSArgs& a) {
+    SimpleBlock b;
+    const long long unit = blockIdx.x / a.nqb;
+    b.qb = (int)(blockIdx.x - unit * a.nqb);
+    b.grp = (int)(unit / a.H); b.h = (int)(unit - (long long)b.grp * a.H);
+    return b;
+}
 template <int DH, int TK>
 __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs a) {
     constexpr int NC = DH / 16;
@@ -394,9 +379,8 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs
     _Float16* Vl = Vh + DH * LDT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c16 = lane & 15, g4 = lane >> 4;
-    const long long unit = blockIdx.x / a.nqb;
-    const int qb = blockIdx.x - (int)unit * a.nqb;
-    const int grp = (int)(unit / a.H), h = (int)(unit - (long long)grp * a.H);
+    const SimpleBlock b = simple_block(a);
+    const int qb = b.qb, grp = b.grp, h = b.h;
     const AttnUnit u = attn_unit<true>(a, grp);  // a block serves one unit
     const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
     const int Sq = u.Sq, Sk = u.Sk;
@@ -445,12 +429,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs
             if (t < ntile) {
                 f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
                 const int ko = (t * 16 + c16) * LDK + 4 * g4;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const HL4 kf = {*reinterpret_cast<const half4v*>(&Kh[ko + c * 16]), *reinterpret_cast<const half4v*>(&Kl[ko + c * 16])};
-                    if (c & 1) a1 = mfma3(kf, qs[c], a1);
-                    else a0 = mfma3(kf, qs[c], a0);
-                }
+                attn_qk_split<NC>(reinterpret_cast<const char*>(&Kh[ko]), reinterpret_cast<const char*>(&Kl[ko]), 32, qs, a0, a1);
                 const int key0 = kt0 + t * 16 + 4 * g4;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sc[t][r] = (key0 + r < Sk) ? (a0[r] + a1[r]) * a.scale : -INFINITY;
@@ -458,6 +437,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_splitm_kernel(const AttnSArgs
                 sc[t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
             }
         }
+        // mask-and-scale and the softmax step stay written out: either shared form costs the single-buffered shape 2 - 4 SGPRs
         float mx = -INFINITY;
 #pragma unroll
         for (int t = 0; t < TK / 16; ++t)
@@ -523,9 +503,8 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
     char* Vs = smem_p + TK * RB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c16 = lane & 15, g4 = lane >> 4;
-    const long long unit = blockIdx.x / a.nqb;
-    const int qb = blockIdx.x - (int)unit * a.nqb;
-    const int grp = (int)(unit / a.H), h = (int)(unit - (long long)grp * a.H);
+    const SimpleBlock b = simple_block(a);
+    const int qb = b.qb, grp = b.grp, h = b.h;
     const AttnUnit u = attn_unit<true>(a, grp);  // a block serves one unit
     const long long q0 = u.q0, k0 = u.k0, q_rs = u.q_rs, k_rs = u.k_rs;
     const int Sq = u.Sq, Sk = u.Sk;
@@ -586,17 +565,8 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
             if (kt0 + TK < Sk) fetch(kt0 + TK);
         } else {
         if (kt0 > 0) __syncthreads();
-        for (int idx = tid; idx < nrows16 * P16; idx += 256) {
-            const int r = idx / P16, c4 = idx - r * P16;
-            float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
-            if (r < nrows) {
-                const long long row = k0 + (long long)(kt0 + r) * k_rs;
-                kv = *reinterpret_cast<const float4*>(a.k + row * a.ldk + h * DH + c4 * 4);
-                vv = *reinterpret_cast<const float4*>(a.v + row * a.ldv + h * DH + c4 * 4);
-            }
-            *reinterpret_cast<float4*>(Ks + r * RB + c4 * 16) = kv;
-            *reinterpret_cast<float4*>(Vs + r * RB + c4 * 16) = vv;
-        }
+        attn_stage_rows<float4, DH, 256>(a.k, a.v, a.ldk, a.ldv, k0, k_rs, kt0, h, nrows, nrows16, tid, reinterpret_cast<float*>(Ks),
+                                         reinterpret_cast<float*>(Vs), RB / 4, RB / 4);
         __syncthreads();
         }
         const int ntile = nrows16 >> 4;
@@ -606,12 +576,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
             if (t < ntile) {
                 f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
                 const char* kp = Ks + (t * 16 + c16) * RB + frag;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const HL4 kf = {*reinterpret_cast<const half4v*>(kp + c * 64), *reinterpret_cast<const half4v*>(kp + c * 64 + 16)};
-                    if (c & 1) a1 = mfma3(kf, qs[c], a1);
-                    else a0 = mfma3(kf, qs[c], a0);
-                }
+                attn_qk_split<NC>(kp, kp + 16, 64, qs, a0, a1);
                 const int key0 = kt0 + t * 16 + 4 * g4;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sc[t][r] = (key0 + r < Sk) ? (a0[r] + a1[r]) * a.scale : -INFINITY;
@@ -619,6 +584,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
                 sc[t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
             }
         }
+        // mask-and-scale and the softmax step stay written out: either shared form costs the single-buffered shape 2 - 4 SGPRs
         float mx = -INFINITY;
 #pragma unroll
         for (int t = 0; t < TK / 16; ++t)
@@ -662,48 +628,23 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_spin_kernel(const AttnSArgs a
 
 }  // namespace: sola_tune switches are extern (tune.h)
 int g_attn_spin_db = 1;  // sola_tune "attn_spin" 2 = single-buffered 32-key stages (A/B)
-namespace {
-int launch_spin(const AttnSArgs& a0, hipStream_t s) {
-    AttnSArgs a = a0;
-    constexpr int TK = 32;
-    a.nqb = (a.Sq + 63) / 64;
-    const long long blocks = (long long)a.G * a.H * a.nqb;
-    SOLA_TRY(attn_grid_ok(blocks, "attention"));
-    if (g_attn_spin_db) {  // two stages of 16 keys (the same 35.8 KB), next tile prefetched in registers
-        hipLaunchKernelGGL((attn_fwd_spin_kernel<16, true>), dim3((unsigned)blocks), dim3(256), (size_t)2 * 2 * 16 * 560, s, a);
-        SOLA_LAUNCH_CHECK();
-        return SOLA_OK;
-    }
-    const size_t lds = (size_t)2 * TK * 560;
-    hipLaunchKernelGGL((attn_fwd_spin_kernel<TK>), dim3((unsigned)blocks), dim3(256), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-
-int launch_splitm(const AttnSArgs& a0, hipStream_t s) {
-    AttnSArgs a = a0;
-    constexpr int DH = 128, TK = 32;
-    a.nqb = (a.Sq + 63) / 64;
-    const long long blocks = (long long)a.G * a.H * a.nqb;
-    SOLA_TRY(attn_grid_ok(blocks, "attention"));
-    const size_t lds = ((size_t)2 * TK * (DH + 8) + (size_t)2 * DH * (TK + 8)) * sizeof(_Float16);
-    hipLaunchKernelGGL((attn_fwd_splitm_kernel<DH, TK>), dim3((unsigned)blocks), dim3(256), lds, s, a);
-    SOLA_LAUNCH_CHECK();
-    return SOLA_OK;
-}
-
-}  // namespace: sola_tune switches are extern (tune.h)
 int g_attn_simple_db = 1;  // sola_tune "attn_simple_db": 1 = double-buffered 16-key stages with register prefetch
 int g_attn_simple_remap = 0;  // sola_tune "attn_simple_remap": XCD-contiguous block order; measured no gain (273.8 vs 275.8 us at 64 tracks, 392 vs 400 at 128)
 namespace {
+
+// the grid of the three MFMA kernels: one block per (group, head, 64-query block)
+int simple_grid(AttnSArgs& a, long long* blocks) {
+    a.nqb = (a.Sq + 63) / 64;
+    *blocks = (long long)a.G * a.H * a.nqb;
+    return attn_grid_ok(*blocks, "attention");
+}
 
 template <int DH>
 int launch_s(const AttnSArgs& a0, hipStream_t s) {
     AttnSArgs a = a0;
     constexpr int TK = 32;
-    a.nqb = (a.Sq + 63) / 64;
-    const long long blocks = (long long)a.G * a.H * a.nqb;
-    SOLA_TRY(attn_grid_ok(blocks, "attention"));
+    long long blocks;
+    SOLA_TRY(simple_grid(a, &blocks));
     a.xcd_remap = (g_attn_simple_remap && blocks % 8 == 0) ? 1 : 0;
     // two stages of 16 keys: the LDS footprint of one 32-key stage (34 KB), the next tile prefetched in registers
     const size_t lds_db = (size_t)2 * 2 * 16 * (DH + 4) * sizeof(float);
@@ -732,20 +673,19 @@ static AttnSArgs make_sargs(const AttnDesc& d) {
     AttnSArgs a;
     a.q = d.q; a.k = d.k; a.v = d.v; a.o = d.o;
     attn_fill_common(a, d);
-    a.nqb = 1; a.xcd_remap = 0;
     a.lse = d.lse;
     a.drop = d.drop;
-    a.o_cast = nullptr; a.o_side = nullptr; a.o_cast_fmt = 0;  // launch_attention_simple's training instantiation takes them
-    a.in_bf16 = 0; a.o_skip_f32 = 0;
+    a.nqb = 1; a.xcd_remap = 0;  // the launchers of the MFMA kernels set them (simple_grid, launch_s)
+    a.in_bf16 = 0; a.o_skip_f32 = 0;  // f32 rows in, f32 rows out ...
+    a.o_cast = nullptr; a.o_side = nullptr; a.o_cast_fmt = 0;  // ... and no operand cast: launch_attention_simple decides otherwise
     return a;
 }
 
 int launch_attention_small(const AttnDesc& d, hipStream_t s) {
     const AttnSArgs a = make_sargs(d);
     const SolaProfScope prof = attn_prof_scope(d, s);
-    const long long units = (long long)d.G * d.H;
-    const unsigned blocks = (unsigned)((units + 7) / 8);
-    const int need = d.Sq > d.Sk ? d.Sq : d.Sk;
+    const unsigned blocks = (unsigned)(((long long)d.G * d.H + 7) / 8);  // half a wave per (group, head) unit
+    const int need = d.Sq > d.Sk ? d.Sq : d.Sk;                          // steps the instantiation holds: 1, 2 or 4
     if (need <= 1) hipLaunchKernelGGL((attn_fwd_small_kernel<1>), dim3(blocks), dim3(256), 0, s, a);
     else if (need <= 2) hipLaunchKernelGGL((attn_fwd_small_kernel<2>), dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((attn_fwd_small_kernel<4>), dim3(blocks), dim3(256), 0, s, a);
@@ -791,9 +731,16 @@ bool attention_spin_supported(const AttnDesc& d) {
            d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0;
 }
 int launch_attention_spin(const AttnDesc& d, hipStream_t s) {
-    const AttnSArgs a = make_sargs(d);
+    AttnSArgs a = make_sargs(d);
     const SolaProfScope prof = attn_prof_scope(d, s);
-    return launch_spin(a, s);
+    long long blocks;
+    SOLA_TRY(simple_grid(a, &blocks));
+    // two stages of 16 keys with the next tile prefetched in registers, or one stage of 32 (sola_tune "attn_spin" 2): 35.8 KB either way
+    const size_t lds = (size_t)2 * 32 * 560;
+    if (g_attn_spin_db) hipLaunchKernelGGL((attn_fwd_spin_kernel<16, true>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((attn_fwd_spin_kernel<32>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+    SOLA_LAUNCH_CHECK();
+    return SOLA_OK;
 }
 
 // f32 q / k / v with the products evaluated as split-f16 triples (AttnDesc::split_math; head_dim 128, inference)
@@ -801,7 +748,13 @@ bool attention_splitm_supported(const AttnDesc& d) {
     return d.split_math && !d.lse && !d.drop.enabled && d.in != Elem::SP16 && (d.Sq > 4 || d.Sk > 4) && d.DH == 128;
 }
 int launch_attention_splitm(const AttnDesc& d, hipStream_t s) {
-    const AttnSArgs a = make_sargs(d);
+    AttnSArgs a = make_sargs(d);
     const SolaProfScope prof = attn_prof_scope(d, s);
-    return launch_splitm(a, s);
+    long long blocks;
+    SOLA_TRY(simple_grid(a, &blocks));
+    constexpr int DH = 128, TK = 32;  // K rows as (hi, lo) halfs at pitch DH + 8, V^T rows at pitch TK + 8
+    const size_t lds = ((size_t)2 * TK * (DH + 8) + (size_t)2 * DH * (TK + 8)) * sizeof(_Float16);
+    hipLaunchKernelGGL((attn_fwd_splitm_kernel<DH, TK>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+    SOLA_LAUNCH_CHECK();
+    return SOLA_OK;
 }

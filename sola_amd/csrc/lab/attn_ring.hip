@@ -27,7 +27,7 @@
 // softmax per 16-key tile): the outputs are bit-identical to that kernel's.
 #include <type_traits>
 
-#include "../attn_common.h"
+#include "../attn_fwd_steps.h"
 
 #ifdef SOLA_EXPERIMENTS
 namespace {
@@ -273,25 +273,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_ring_kernel(const AttnRAr
         for (int r = 2; r < 4; ++r)
 #pragma unroll
             for (int cl = 0; cl < 4; ++cl) RING_RD2(vf[r][cl], va[r][cl], (ST * RSTAGE + RKV) / 256);
-        f32x4 sc;
-        const int key0 = c_kt + 4 * g4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sc[r] = (key0 + r < cur.Sk) ? (a0[r] + a1[r]) * a.scale : -INFINITY;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[r]);
-        mx = max_xor32(max_xor16(mx));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = __expf(m_run - m_new);
-        float rs = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            sc[r] = __expf(sc[r] - m_new);
-            rs += sc[r];
-        }
-        rs = sum_xor32(sum_xor16(rs));
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
+        f32x4 sc[1] = {attn_mask_scale(a0, a1, c_kt + 4 * g4, cur.Sk, a.scale)};  // one 16-key tile per step
+        const float alpha = attn_softmax_tile<1, true>(sc, m_run, l_run);
 #pragma unroll
         for (int c = 0; c < 8; ++c) oacc[c] *= alpha;
         asm volatile("s_waitcnt lgkmcnt(0)"
@@ -300,7 +283,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_ring_kernel(const AttnRAr
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int c = 0; c < 8; ++c) oacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[r][c & 3][c >> 2], sc[r], oacc[c], 0, 0, 0);
+            for (int c = 0; c < 8; ++c) oacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[r][c & 3][c >> 2], sc[0][r], oacc[c], 0, 0, 0);
 
         }
         c_kt += 16;

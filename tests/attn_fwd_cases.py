@@ -61,7 +61,7 @@ def reg_offsets_fit(Sk, k_rs, ld):
 def expected_launch(case, switches=None, dropout=False, lse=None, ld=None):
     """(branch, launch parameters) of a sola_attention call of ``case`` under the sola_tune ``switches``: the kernel family and
     instantiation, and the grid and loop parameters the launcher derives.  A restatement of launch_attention, launch_dh (attn.hip),
-    attention_small_supported, attention_simple_supported, launch_attention_small, launch_s (attn_simple.hip), attention_reg_supported
+    attention_small_supported, attention_simple_supported, launch_attention_small, launch_s with simple_grid (attn_simple.hip), attention_reg_supported
     (attn_reg.hip), attention_res_supported, launch_res and launch_attention_res (attn_res.hip): whoever edits one of those edits this.
     ``lse``: overrides case.lse; ``ld``: the larger of the k and v pitches (default: rows of D values)."""
     sw = dict(SWITCHES, **(switches or {}))
@@ -93,7 +93,7 @@ def expected_launch(case, switches=None, dropout=False, lse=None, ld=None):
             {"blocks": _ceil(units * nchunk, 8) * 8, "nchunk": nchunk, "tiles_per_wave": tiles, "key_tile": 16}
     simple = (Sq > 16 or Sk > 16) and DH in (64, 128) and not ((lse or dropout) and not sw["attn_simple_train"])  # attention_simple_supported
     if simple and (variant == 2 or (variant == 1 and Sq <= 128 and Sk <= 128)):  # launch_attention_simple -> launch_s
-        nqb = _ceil(Sq, 64)
+        nqb = _ceil(Sq, 64)  # simple_grid
         blocks = units * nqb
         kind = "train" if lse or dropout else "db" if sw["attn_simple_db"] else "single"
         remap = bool(sw["attn_simple_remap"]) and blocks % 8 == 0

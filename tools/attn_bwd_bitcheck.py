@@ -16,8 +16,6 @@ records hold the same launches and arrays and that every digest is equal; exit s
 """
 import argparse
 import ctypes as C
-import hashlib
-import json
 import math
 import os
 import sys
@@ -25,23 +23,13 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from bitcheck_common import compare, digest, switch_name, write_record  # noqa: E402
 
 P_DROP, SEED = 0.1, 777
 BF16_CASES = ("motion_17x12", "motion_24", "inter_object", "inter_object_80", "motion_4", "object_to_language")
 BF16_FORMS = (("f32_products", {"attn_bwd_bf16_mfma": 0}, False, False), ("bf16_products", {}, False, False),
               ("bf16_dout", {}, True, False), ("bf16_dout_o", {}, True, True))
-
-
-def digest(t):
-    import torch
-
-    t = t.detach().contiguous().cpu()
-    raw = t.view(torch.int16) if t.dtype == torch.bfloat16 else t
-    return hashlib.sha256(raw.numpy().tobytes()).hexdigest()
-
-
-def switch_name(sw):
-    return ",".join(f"{k}={v}" for k, v in sw.items()) or "default"
 
 
 def record(out):
@@ -89,23 +77,7 @@ def record(out):
                     ptr(dq_scr), ptr(dvec), G, H, 128, Sq, Sk, inner, qa[0], qa[1], qa[2], ka[0], ka[1], ka[2], 1.0 / math.sqrt(128), qrows,
                     ptr(scr) if n_scr else None, n_scr, current_stream(q16.device)), "sola_attention_backward_bf16")
             keep(f"bf16 {name} {form}", (gq, gk[:, D:2 * D], gk[:, 2 * D:]))  # (gq whole: the columns behind dq must stay 7)
-    os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, "record.json"), "w") as f:
-        json.dump(rec, f, indent=0, sort_keys=True)
-    print(f"{len(rec)} launches recorded in {out}/record.json")
-
-
-def compare(a, b):
-    ra, rb = (json.load(open(os.path.join(d, "record.json"))) for d in (a, b))
-    bad = sorted(set(ra) ^ set(rb))
-    if bad:
-        print("launches in one record only:", bad)
-    diff = [(k, n) for k in sorted(set(ra) & set(rb)) for n in sorted(set(ra[k]) | set(rb[k])) if ra[k].get(n) != rb[k].get(n)]
-    for k, n in diff:
-        print(f"DIFFERENT: {k}: {n}")
-    n_arrays = sum(len(v) for v in rb.values())
-    print(f"{len(rb)} launches, {n_arrays} arrays: " + ("every array bit-equal" if not bad and not diff else f"{len(diff)} arrays differ, {len(bad)} launches unmatched"))
-    return len(bad) + len(diff)
+    write_record(out, rec)
 
 
 if __name__ == "__main__":
