@@ -104,9 +104,13 @@ int sola_set_precision(SolaCtx* ctx, int precision);
  *   - the activations between the stages use a fixed scale; every kernel that writes one checks the value against the f16
  *     range (non-finite or |v| >= 65000 sets a guard word), and when the weights change the rms each GroupNorm will emit,
  *     sqrt(mean(gamma^2 + beta^2)), is checked against [2^-6, 2^9].
- * With the guard enabled (default) the forward reads the guard words (a 4-byte copy and ONE stream synchronisation per
- * call) and, when one is set, repeats the call on the exact-f32 kernels in the same workspace, so the caller never sees a
- * result computed outside the format's range.  enable = 0 keeps the call fully asynchronous (also while the stream is
+ * With the guard enabled (default) the forward reads the guard words (an 8-byte copy and ONE host wait per call) and, when
+ * one is set, repeats the call on the exact-f32 kernels in the same workspace, so the caller never sees a result computed
+ * outside the format's range.  The wait is for an EVENT behind the last launch of the sequence that can set a guard bit
+ * (precision 1: the last object -> language attention; precision 2: the out-projection behind it), not for the stream: a
+ * guarded call may return while its tail - that out-projection, the last GroupNorm, the score head - is still running, so
+ * its outputs are complete ON THE STREAM, as those of an unguarded call, not on return.  The repeat is enqueued on the same
+ * stream behind that tail and overwrites the outputs in stream order.  enable = 0 keeps the call fully asynchronous (also while the stream is
  * being captured into a graph, where the check is skipped automatically); the words can then be read with
  * sola_split_fallback_count: *count = calls repeated in f32 so far, *last_guard = guard bits of the last checked call
  * (bit 0: a value left the f16 range, bit 1: GroupNorm weights outside the covered magnitude).  Once bit 1 has been seen for the

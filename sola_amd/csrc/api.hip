@@ -189,6 +189,7 @@ extern "C" int sola_ctx_destroy(SolaCtx* c) {
     if (c->lin16_buf) (void)hipFree(c->lin16_buf);
     if (c->scal_buf) (void)hipFree(c->scal_buf);
     if (c->guard_host) (void)hipHostFree(c->guard_host);
+    if (c->guard_ev) (void)hipEventDestroy(c->guard_ev);
     sola_rag_stage_free(c->rag_stage);
     for (hipEvent_t e : c->bucket_ev) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -436,6 +437,7 @@ extern "C" int sola_set_precision(SolaCtx* c, int precision) {
         c->guard = reinterpret_cast<int*>(c->scal_buf + 2 * n_pairs);
         SOLA_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->guard_host), 2 * sizeof(int), hipHostMallocDefault));
         c->guard_host[0] = c->guard_host[1] = 0;
+        SOLA_HIP(hipEventCreateWithFlags(&c->guard_ev, hipEventDisableTiming));
     }
     c->precision = precision;
     c->ws_dirty = true;
@@ -598,14 +600,22 @@ extern "C" int sola_gemm_nt_split_scaled(const float* a_sp, int lda, const float
 }
 
 // Reads the guard words the split-f16 forward left (ctx.h) and reports whether the call must be repeated in exact f32.
-// Synchronises the stream (4 bytes back to the host), so it is skipped while the stream is being captured into a graph.
+// Where the sequence has copied the words back behind its last guarded launch (ctx.h: guard_ev) only that event is waited for: the
+// sequence's tail - which cannot set a bit - is still running or queued when this returns.  Otherwise (a sequence without such a point)
+// the copy is made here and the stream synchronised (8 bytes back to the host).  Skipped while the stream is being captured into a graph.
 int sola_split_guard_tripped(SolaCtx* c, hipStream_t s, bool* tripped) {
     *tripped = false;
+    const bool recorded = c->guard_ev_recorded;
+    c->guard_ev_recorded = false;
     if (!c->split_guard || !c->guard) return SOLA_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return SOLA_OK;
-    SOLA_HIP(hipMemcpyAsync(c->guard_host, c->guard, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    SOLA_HIP(hipStreamSynchronize(s));
+    if (recorded) {
+        SOLA_HIP(hipEventSynchronize(c->guard_ev));
+    } else {
+        SOLA_HIP(hipMemcpyAsync(c->guard_host, c->guard, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+        SOLA_HIP(hipStreamSynchronize(s));
+    }
     *tripped = (c->guard_host[0] | c->guard_host[1]) != 0;
     if (!c->guard_host[1]) c->weight_range_bad = false;  // the current weights are fine (again)
     if (c->guard_host[1] && !c->weight_range_bad) {
@@ -641,6 +651,8 @@ static bool few_rows_f32(const SolaCtx* c, long long rows0) { return c->precisio
 // over at most infer_f32_rows object-token rows (`rows0`; kRowsUnknown = never) or with weights known to be out of range runs once, on the
 // exact-f32 kernels; every other 16-bit call runs, reads the guard words and, when one is set - a value left the range the 16-bit formats
 // cover, or the weights say it would - runs again on the exact-f32 kernels (the f32 plan fits the workspace of the 16-bit one).
+// The words are read behind the sequence's last guarded launch (sola_split_guard_tripped), so a clean call returns with its tail still
+// queued, and the repeat of a tripped one is enqueued behind that tail on the same stream: it overwrites the outputs in stream order.
 // The host-side plans allocate: nothing may throw across the ABI.
 constexpr long long kRowsUnknown = 1ll << 62;
 template <class Run>
@@ -654,6 +666,7 @@ static int guarded_inference(SolaCtx* c, const char* who, long long rows0, hipSt
             exact = true;
         }
         if (!exact) {
+            c->guard_ev_recorded = false;  // (a sequence that failed behind its read-back point left it set)
             SOLA_TRY(run());
             bool tripped = false;
             SOLA_TRY(sola_split_guard_tripped(c, s, &tripped));

@@ -138,6 +138,11 @@ struct SolaCtx {
     float* scal_buf = nullptr;
     int* guard = nullptr;
     int* guard_host = nullptr;      // pinned, 2 ints
+    // Early read-back (forward_infer.hip: InferBuilder::read_guard): behind the LAST launch that can set guard[0] the sequence copies both
+    // words into guard_host and records guard_ev (timing disabled, created with the guard words), then enqueues its tail; the caller
+    // waits for the event, not for the stream (api.hip: sola_split_guard_tripped).  guard_ev_recorded: this call recorded one.
+    hipEvent_t guard_ev = nullptr;
+    bool guard_ev_recorded = false;
     bool split_guard = true;        // sola_set_split_guard
     long long split_fallbacks = 0;  // calls that were repeated in exact f32
     bool weight_range_bad = false;  // the weight-time guard bit was seen set for the current weights: precision 1 goes straight to f32

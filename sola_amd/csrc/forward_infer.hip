@@ -212,6 +212,20 @@ struct InferBuilder {
         }
         return SOLA_OK;
     }
+    // The guard words travel to the host HERE, behind the last launch of the sequence that can set guard[0] (sub_block: `tail`), and the
+    // ctx's event marks the copy: the caller waits for that event only (api.hip: sola_split_guard_tripped) and enqueues its next launches
+    // while the tail of this sequence - launches that write f32 rows or carry no guard pointer - still runs.  guard[1], the weight-time
+    // word, is final since prepare_weights and rides along.  Not with the guard switched off (nobody reads the words) and not while the
+    // stream is being captured (the read-back is skipped there altogether).
+    int read_guard() const {
+        if (!op16 || !c->split_guard || !c->guard_ev) return SOLA_OK;
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return SOLA_OK;
+        SOLA_HIP(hipMemcpyAsync(c->guard_host, c->guard, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+        SOLA_HIP(hipEventRecord(c->guard_ev, s));
+        c->guard_ev_recorded = true;
+        return SOLA_OK;
+    }
 
     // ---- the weights in the mode's operand format: f32 as set, split-f16 pairs (D*D floats per matrix) or plain f16 (D*D halfs)
     const float* ws_w(int i) const {
@@ -332,7 +346,7 @@ struct InferBuilder {
         nd.x = x; nd.y = y;
         nd.gamma = W(name + ".weight"); nd.beta = W(name + ".bias");
         nd.C = C; nd.groups = groups; nd.eps = 1e-5f;
-        nd.guard = guard;
+        nd.guard = out16 ? guard : nullptr;  // f32 rows are never range-checked (norm.hip: launch_group_norm drops the pointer for them)
         nd.out = stored(out16);
         if (h16) nd.in = opfmt;
         return nd;
@@ -367,8 +381,12 @@ struct InferBuilder {
     // Split-f16: q/k/v leave the projection GEMM already split when the attention that reads them runs the split-f16 MFMA shape.  Measured
     // (tools/attn_probe.py): with <= 64 keys per unit the exact-f32 MFMA kernel is as fast or faster (bound by latency and LDS traffic, not
     // by the matrix pipe); with 65..128 keys the split shape wins by 14 %.  Never the packed short-sequence shape (uniform: > 16 keys).
+    // `tail`: the sequence's last sub-block, whose norm writes the f32 rows the score head reads (out16 = 0).  The last launch that can
+    // set the guard word lies in it - split-f16: the attention (split-pair output; the out-projection writes f32 rows and carries no
+    // guard pointer); 16-bit storage: the out-projection (f16 rows) - and the words are read back behind that launch (read_guard).
     int sub_block(int layer, int a, const SiteGeom& g, long long rows, const float* xq, const float* xk, const float* xv, const float* resid,
-                  float* y, float* y2, bool out16) const {
+                  float* y, float* y2, bool out16, bool tail = false) const {
+        SOLA_ARG(!tail || !out16, "forward: the tail sub-block's norm must write f32 rows (a 16-bit output could set the guard behind its read-back)");
         const bool in_sp = sp && g.k.len > g_attn_split_min_keys && (a == 2 || g.q.units || g.k.len > 16) && DH % 16 == 0;
         if (a < 2) {
             SOLA_TRY(linear3(xq, xk, xv, layer, a, 3, rows, q, k, v, 0, in_sp));
@@ -379,7 +397,9 @@ struct InferBuilder {
         AttnDesc ad = attention(q, a < 2 ? k : lk, a < 2 ? v : lv, in_sp);
         site_fill_attn(ad, g);
         SOLA_TRY(launch(ad));
+        if (tail && !h16) SOLA_TRY(read_guard());
         SOLA_TRY(out_proj(layer, a, rows, resid));
+        if (tail && h16) SOLA_TRY(read_guard());
         GroupNormDesc nd = layer_norm(layer, a, y, y2, out16);
         site_fill_norm(nd, g.q);
         return launch_group_norm(nd, s);
@@ -493,7 +513,7 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
         // (ii) motion attention over T' per track, PE on q and k only: module.py:38-43
         SOLA_TRY(b.sub_block(l, 1, site_geom(shape, 1), M, x_pe, x_pe, x_obj, x_obj, x_mot, nullptr, 1));
         // (iii) object -> language cross attention: module.py:46-50 (the score head reads f32)
-        SOLA_TRY(b.sub_block(l, 2, site_geom(shape, 2), M, x_mot, nullptr, nullptr, x_mot, x_o2l, nullptr, last ? 0 : 1));
+        SOLA_TRY(b.sub_block(l, 2, site_geom(shape, 2), M, x_mot, nullptr, nullptr, x_mot, x_o2l, nullptr, last ? 0 : 1, last));
         xin = x_o2l;
     }
 
@@ -658,7 +678,7 @@ int sola_forward_ragged_impl(SolaCtx* c, const float* obj, const float* lang, co
         }
         // object -> language attention (module/module.py:46-50; the score head reads f32)
         float* x_o2l = buf(ls + "_o2l");
-        SOLA_TRY(b.sub_block(l, 2, site_geom(samples, 2), M, x_mot, nullptr, nullptr, x_mot, x_o2l, nullptr, last ? 0 : 1));
+        SOLA_TRY(b.sub_block(l, 2, site_geom(samples, 2), M, x_mot, nullptr, nullptr, x_mot, x_o2l, nullptr, last ? 0 : 1, last));
         xin = x_o2l;
     }
     HeadDesc hd{xin, buf("lbar"), score_map, score_tokens};

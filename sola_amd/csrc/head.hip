@@ -196,14 +196,33 @@ __global__ __launch_bounds__(256) void loss_terms_rows_kernel(const LossArgs a) 
 }
 
 // The same block shape with the token rows in REGISTERS: the LDS version above reads 8 token float4s from LDS per negative
-// float4 it loads (1056 ds_read_b128 per lane, 8.8 GB of LDS traffic at the headline batch: LDS-bound at ~130 us); here
-// every wave keeps its lanes' slices of the 8 rows (NI float4 per row) and only the n_neg + 1 vectors stream through.
-// Same per-lane summation order, so the logits are bit-identical to the LDS version's.
+// float4 it loads (1056 ds_read_b128 per lane, 8.8 GB of LDS traffic at the headline batch: LDS-bound at ~130 us).  Here a
+// wave keeps only the LOSS_RPW rows it reduces (its lanes' slices, NI float4 per row) and all n_neg + 1 vectors stream
+// through it: every token row is fetched once, by one wave, and the wave's 8 * NI registers of rows plus 8 * NI of the
+// two vectors in flight leave room for four waves per SIMD.  (With all 8 rows in every wave - 128 registers, every row
+// fetched four times, two blocks per CU - and every fourth vector per wave the launch took 125 us at the headline batch;
+// this shape with the old tail 110 us, with the tail below 80 us: profiles/step_boundary.txt.)  The vectors are one
+// shared 4 KB x (n_neg + 1) set that the four waves of a block walk together: cache traffic, not memory traffic (staging
+// them through LDS once per block, 4 at a time under a barrier, measured no faster).
+// Per lane every logit is summed as before: i = 0 .. NI - 1 in turn, each step adding (x.x + y.y) + (z.z + w.w).  How the
+// four products of a step are ROUNDED is stated here and no longer left to the compiler: the 8-rows-per-wave form came out
+// of hipcc with the products of rows 1..7 of a block packed (v_pk_mul_f32: each product rounded, then added) and row 0's
+// left scalar and contracted (x.x and z.z fused into the rounded y.y and w.w).  Both are valid readings of the expression
+// under -ffp-contract=fast; which row got which was the vectoriser's choice, and another block shape moves it - so the two
+// forms are written out (loss_dot4) and row 0 of a block keeps the contracted one: every logit keeps its bits.
+constexpr int LOSS_RPW = LOSS_RPB / 4;  // rows per wave
+template <bool CONTRACTED>
+__device__ __forceinline__ float loss_dot4(const float4& t, const float4& v) {
+    if (CONTRACTED) return __builtin_fmaf(t.x, v.x, t.y * v.y) + __builtin_fmaf(t.z, v.z, t.w * v.w);
+    {
+#pragma clang fp contract(off)
+        return (t.x * v.x + t.y * v.y) + (t.z * v.z + t.w * v.w);
+    }
+}
 template <int NI>
 __global__ __launch_bounds__(256) void loss_terms_regs_kernel(const LossArgs a) {
     extern __shared__ float sh[];
     float* logit = sh;  // [RPB][n_neg + 1], pos last
-    const int d4n = a.D >> 2;
     const int b = blockIdx.y, n0 = blockIdx.x * LOSS_RPB;
     long long first;
     int count;
@@ -211,49 +230,69 @@ __global__ __launch_bounds__(256) void loss_terms_regs_kernel(const LossArgs a) 
     if (n0 >= count) return;  // ragged: the grid is sized by the largest sample
     const int rows = min(LOSS_RPB, count - n0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float4 tk[LOSS_RPB][NI];
-#pragma unroll
-    for (int r = 0; r < LOSS_RPB; ++r)
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            tk[r][i] = r < rows ? reinterpret_cast<const float4*>(a.score_tokens + (first + n0 + r) * a.D)[lane + 64 * i]
-                                : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* negb = a.neg + (long long)b * a.neg_batch_stride;
+    const int r0 = wave * LOSS_RPW;
     const int stride = a.n_neg + 1;
-    // the next vector travels while this one is reduced (at one sample per call a wave's nine iterations each waited for their own load;
-    // the loop holds cross-lane operations, so the compiler will not unroll it over a runtime trip count)
-    auto vec_of = [&](int m) { return reinterpret_cast<const float4*>(m < a.n_neg ? negb + (long long)m * a.D : a.pos + (long long)b * a.D); };
-    float4 vcur[NI], vnext[NI];
-    if (wave <= a.n_neg) {
+    if (r0 < rows) {  // (the whole wave: a tail block's waves without a row have nothing to reduce)
+        float4 tk[LOSS_RPW][NI];
 #pragma unroll
-        for (int i = 0; i < NI; ++i) vcur[i] = vec_of(wave)[lane + 64 * i];
-    }
-    for (int m = wave; m <= a.n_neg; m += 4) {
-        if (m + 4 <= a.n_neg) {
+        for (int r = 0; r < LOSS_RPW; ++r)
 #pragma unroll
-            for (int i = 0; i < NI; ++i) vnext[i] = vec_of(m + 4)[lane + 64 * i];
-        }
-        float s[LOSS_RPB];
+            for (int i = 0; i < NI; ++i)
+                tk[r][i] = r0 + r < rows ? reinterpret_cast<const float4*>(a.score_tokens + (first + n0 + r0 + r) * a.D)[lane + 64 * i]
+                                         : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float* negb = a.neg + (long long)b * a.neg_batch_stride;
+        // the next vector travels while this one is reduced (the loop holds cross-lane operations, so the compiler will not unroll it
+        // over a runtime trip count)
+        auto vec_of = [&](int m) { return reinterpret_cast<const float4*>(m < a.n_neg ? negb + (long long)m * a.D : a.pos + (long long)b * a.D); };
+        float4 vcur[NI], vnext[NI];
 #pragma unroll
-        for (int r = 0; r < LOSS_RPB; ++r) s[r] = 0.f;
+        for (int i = 0; i < NI; ++i) vcur[i] = vec_of(0)[lane + 64 * i];
+        for (int m = 0; m <= a.n_neg; ++m) {
+            if (m + 1 <= a.n_neg) {
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const float4 v = vcur[i];
+                for (int i = 0; i < NI; ++i) vnext[i] = vec_of(m + 1)[lane + 64 * i];
+            }
+            float s[LOSS_RPW];
 #pragma unroll
-            for (int r = 0; r < LOSS_RPB; ++r) {
-                const float4 tv = tk[r][i];
-                s[r] += (tv.x * v.x + tv.y * v.y) + (tv.z * v.z + tv.w * v.w);
+            for (int r = 0; r < LOSS_RPW; ++r) {
+                s[r] = 0.f;
+                if (r0 + r == 0) {  // row 0 of the block (wave 0 only)
+#pragma unroll
+                    for (int i = 0; i < NI; ++i) s[r] += loss_dot4<true>(tk[r][i], vcur[i]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < NI; ++i) s[r] += loss_dot4<false>(tk[r][i], vcur[i]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NI; ++i) vcur[i] = vnext[i];
+#pragma unroll
+            for (int r = 0; r < LOSS_RPW; ++r) {
+                const float t = wave_sum(s[r]);
+                if (lane == 0) logit[(r0 + r) * stride + m] = t * a.temp_scale;  // tools/loss.py:29-36
             }
         }
-#pragma unroll
-        for (int i = 0; i < NI; ++i) vcur[i] = vnext[i];
-#pragma unroll
-        for (int r = 0; r < LOSS_RPB; ++r) {
-            const float t = wave_sum(s[r]);
-            if (lane == 0) logit[r * stride + m] = t * a.temp_scale;  // tools/loss.py:29-36
-        }
     }
-    (void)d4n;
+    __syncthreads();
+    // The terms.  One lane per row finds the row's hardest negative; then the rows' (n_neg + 1) cross-entropy terms - ~150 instructions
+    // each - are evaluated by ALL lanes of the block, in place, and the lane of a row adds its row's up in the order m = 0 .. n_neg - 1.
+    // (With 8 lanes of wave 0 evaluating their rows' 33 terms one after the other a block spent ~5000 instructions at 8 of 64 lanes, and
+    // wave 0 of every resident block sits on the same SIMD: that tail, not the dot products, set the launch's time.)
+    int* argl = reinterpret_cast<int*>(logit + LOSS_RPB * stride);  // [RPB]
+    if (threadIdx.x < rows) {
+        const float* negl = logit + threadIdx.x * stride;
+        int arg = 0;
+        float best = negl[0];
+        for (int m = 1; m < a.n_neg; ++m)  // torch.argmax: first maximum (tools/loss.py:40)
+            if (negl[m] > best) { best = negl[m]; arg = m; }
+        argl[threadIdx.x] = arg;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < rows * stride; e += 256) {
+        const int r = e / stride, m = e - r * stride;
+        const float y = a.labels[first + n0 + r];
+        logit[e] = bce_logits(logit[e], m == a.n_neg ? y : m == argl[r] ? (1.f - y) : 0.f);
+    }
     __syncthreads();
     if (threadIdx.x < rows) {
         const int r = threadIdx.x;
@@ -262,32 +301,42 @@ __global__ __launch_bounds__(256) void loss_terms_regs_kernel(const LossArgs a) 
         const float y = a.labels[bn];
         const float x = a.score_map[bn];
         const float w = y > 0.f ? a.pos_w : 1.f;  // train.py:98-99
-        int arg = 0;
-        float best = negl[0];
-        for (int m = 1; m < a.n_neg; ++m)  // torch.argmax: first maximum (tools/loss.py:40)
-            if (negl[m] > best) { best = negl[m]; arg = m; }
         float neg_sum = 0.f;
-        for (int m = 0; m < a.n_neg; ++m) neg_sum += bce_logits(negl[m], m == arg ? (1.f - y) : 0.f);
+        for (int m = 0; m < a.n_neg; ++m) neg_sum += negl[m];
         a.terms[bn * 3 + 0] = w * bce_logits(x, y);
-        a.terms[bn * 3 + 1] = bce_logits(negl[a.n_neg], y);
+        a.terms[bn * 3 + 1] = negl[a.n_neg];
         a.terms[bn * 3 + 2] = neg_sum;
-        if (a.neg_argmax) a.neg_argmax[bn] = arg;
+        if (a.neg_argmax) a.neg_argmax[bn] = argl[r];
     }
 }
 
-__global__ __launch_bounds__(256) void loss_reduce_kernel(const float* terms, int n, int n_neg, float pos_w,
-                                                          float align_w, float* loss3) {
-    __shared__ float red[4];
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        s0 += terms[(long long)i * 3 + 0];
-        s1 += terms[(long long)i * 3 + 1];
-        s2 += terms[(long long)i * 3 + 2];
+// The mean over B*N: ONE block, a fixed order.  Term k (0..2) is summed by threads 256 k .. 256 k + 255: thread t of them adds
+// terms i = t, t + 256, t + 512, ... one after the other, then wave_sum, then (w0 + w1) + (w2 + w3) over the group's four waves -
+// the order of a 256-thread block that walks the three terms side by side and calls block_sum_256 three times, with a third of
+// the loads per thread and eight of them in flight (that block took 18 us over 49 152 floats, waiting for one load after the other).
+constexpr int LOSS_RED_THREADS = 768;
+__global__ __launch_bounds__(LOSS_RED_THREADS) void loss_reduce_kernel(const float* terms, int n, int n_neg, float pos_w,
+                                                                       float align_w, float* loss3) {
+    __shared__ float red[3][4];
+    const int k = threadIdx.x >> 8, t = threadIdx.x & 255;
+    const float* tk = terms + k;
+    float s = 0.f;
+    int i = t;
+    for (; i + 7 * 256 < n; i += 8 * 256) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = tk[(long long)(i + j * 256) * 3];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += v[j];
     }
-    s0 = block_sum_256(s0, red);
-    s1 = block_sum_256(s1, red);
-    s2 = block_sum_256(s2, red);
+    for (; i < n; i += 256) s += tk[(long long)i * 3];
+    s = wave_sum(s);
+    if ((t & 63) == 0) red[k][t >> 6] = s;
+    __syncthreads();
     if (threadIdx.x == 0) {
+        const float s0 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        const float s1 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        const float s2 = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
         const float bce = s0 / (float)n;                                               // mean over B*N (train.py:100)
         const float align = pos_w * (s1 / (float)n) + s2 / ((float)n * (float)n_neg);  // tools/loss.py:45-56
         loss3[0] = bce + align_w * align;                                              // train.py:113
@@ -352,11 +401,13 @@ int launch_loss(const LossDesc& d, hipStream_t s) {
                            4.0 * d.B * d.N * (double)d.D);
         const size_t lds_rows = ((size_t)LOSS_RPB * d.D + (size_t)LOSS_RPB * (d.n_neg + 1)) * 4;
         const size_t lds_logits = (size_t)LOSS_RPB * (d.n_neg + 1) * 4;
-        if (d.D == 1024 && lds_logits <= 64 * 1024)
-            hipLaunchKernelGGL(loss_terms_regs_kernel<4>, dim3((d.N + LOSS_RPB - 1) / LOSS_RPB, d.B), dim3(256), lds_logits, s, a);
-        else if (d.D == 512 && lds_logits <= 64 * 1024)
-            hipLaunchKernelGGL(loss_terms_regs_kernel<2>, dim3((d.N + LOSS_RPB - 1) / LOSS_RPB, d.B), dim3(256), lds_logits, s, a);
-        else if (lds_rows <= 64 * 1024)
+        const size_t lds_regs = lds_logits + LOSS_RPB * 4;  // + the rows' hardest-negative indices
+        if ((d.D == 1024 || d.D == 512) && lds_logits <= 64 * 1024) {
+            const auto kern = d.D == 1024 ? loss_terms_regs_kernel<4> : loss_terms_regs_kernel<2>;
+            if (lds_regs > 64 * 1024)  // (2047 negatives: the indices pass the 64 KB a launch may ask for without saying so)
+                SOLA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_regs));
+            hipLaunchKernelGGL(kern, dim3((d.N + LOSS_RPB - 1) / LOSS_RPB, d.B), dim3(256), lds_regs, s, a);
+        } else if (lds_rows <= 64 * 1024)
             hipLaunchKernelGGL(loss_terms_rows_kernel, dim3((d.N + LOSS_RPB - 1) / LOSS_RPB, d.B), dim3(256), lds_rows, s, a);
         else {
             SOLA_ARG(!d.trk_off, "loss: ragged batches need D and n_neg that fit the row kernels' LDS");
@@ -369,7 +420,7 @@ int launch_loss(const LossDesc& d, hipStream_t s) {
         if (d.trk_off)
             hipLaunchKernelGGL(loss_reduce_ragged_kernel, dim3(d.B), dim3(256), 0, s, d.terms, d.trk_off, d.n_neg, d.pos_w, d.align_w, d.loss3);
         else
-            hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, s, d.terms, d.B * d.N, d.n_neg, d.pos_w, d.align_w, d.loss3);
+            hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LOSS_RED_THREADS), 0, s, d.terms, d.B * d.N, d.n_neg, d.pos_w, d.align_w, d.loss3);
         SOLA_LAUNCH_CHECK();
     }
     return SOLA_OK;
