@@ -238,6 +238,7 @@ struct BwdRun {
     // operands, one product (mixed precision - activations, gradients and accumulation stay f32)
     const Elem opfmt = operand_format(c->precision);  // the step's GEMM operand format: forward and dX products
     const bool op16 = is_row16(opfmt), is_bf = opfmt == Elem::BF16;
+    const OperandCast ocast{opfmt, s};  // the row-major casts into that format (ctx.h)
     const int k_unit = op16 ? 64 : 32;  // reduction lengths are whole k-tiles of the operands' kernels
     const bool split = opfmt != Elem::F32 && ar.present(S_DY_SP);
     // sola_tune "train_dw_f16": in the split-f16 step the weight-gradient products dW = dY^T X take PLAIN f16 operands (one MFMA per
@@ -316,20 +317,10 @@ struct BwdRun {
     const float* W(const std::string& name) const { return ctx_weight(c, name); }
     float* G(const std::string& name) const { return ctx_grad(c, name); }
     const float* ab(int l, int a, const char* what) const { return fb(abuf(true, l, kAttnShort[a], what)); }
-    static std::string layer_prefix(int l) { return "object_lang_align_layers." + std::to_string(l) + "."; }
     WG wg(const std::string& an, const char* proj, const float* dY, const float* X) const {
         return WG{dY, X, G(an + "." + proj + ".weight"), G(an + "." + proj + ".bias")};
     }
 
-    int cast_scaled(const float* in, int ld, float* out, long long rows, int K, float* sc) const {
-        return op16 ? launch_cast_f16_scaled(in, ld, out, K, rows, K, sc, opfmt, s) : launch_cast_sp16_scaled(in, ld, out, K, rows, K, sc, s);
-    }
-    int cast_auto(const float* in, int ld, float* out, long long rows, int K, float* sc) const {
-        return op16 ? launch_cast_f16(in, ld, out, K, rows, K, 0.f, sc, opfmt, s) : launch_cast_sp16_auto(in, ld, out, K, rows, K, sc, s);
-    }
-    int cast_fixed(const float* in, int ld, float* out, long long rows, int K, float scale) const {
-        return op16 ? launch_cast_f16(in, ld, out, K, rows, K, scale, nullptr, opfmt, s) : launch_cast_sp16(in, ld, out, K, rows, K, scale, s);
-    }
     // the 16-bit dW kernel takes the product and its scratch fits
     bool tns_fits(int rows, int n_out, int k_in, int nprob) const {
         return split && ar.present(S_TNS) && gemm_tn_split_supported(rows, n_out, k_in) &&
@@ -530,12 +521,12 @@ struct BwdRun {
             } else {
                 SOLA_TRY(need16(!dy16_only, "the gradient rows of an input gradient"));
                 cast.src = nullptr;  // "dy_sp" is rewritten
-                if (sc) SOLA_TRY(cast_scaled(dY, ldy, dy_sp, rows, n_cat, sl));
-                else SOLA_TRY(cast_auto(dY, ldy, dy_sp, rows, n_cat, sl));
+                if (sc) SOLA_TRY(ocast.scaled(dY, ldy, dy_sp, rows, n_cat, sl));
+                else SOLA_TRY(ocast.auto_scale(dY, ldy, dy_sp, rows, n_cat, sl));
                 d.p[0].A = dy_sp;
                 d.lda = n_cat;
             }
-            if (!cast.wt_sp_ready) SOLA_TRY(cast_fixed(wt, n_cat, ar.get(S_WT_SP), k_in, n_cat, kLinScale));  // else transpose_into wrote the operand itself
+            if (!cast.wt_sp_ready) SOLA_TRY(ocast.fixed(wt, n_cat, ar.get(S_WT_SP), k_in, n_cat, kLinScale));  // else transpose_into wrote the operand itself
             cast.wt_sp_ready = false;
             d.p[0].W = ar.get(S_WT_SP);
             d.ab = opfmt; d.out_scale = 1.f / kLinScale; d.out_scale_dev = sl + 1;
@@ -628,7 +619,7 @@ struct BwdRun {
         // by a statistics-and-cast pass that read the f32 matrix back (launch_cast_bf16_colsum); the f32 rows stay (residual stream)
         if (gn16) d.dx16 = dy16;
         d.x_fmt = c->site(l, a).res16 ? Elem::BF16 : Elem::F32;
-        return gn_bwd(d, layer_prefix(l) + "norm." + std::to_string(a));
+        return gn_bwd(d, norm_name(l, a));
     }
 
     // common tail of every sub-block: out_proj backward  (res = resid + attn * Wo^T + bo): dWo, dbo, dattn = dres Wo
@@ -815,7 +806,7 @@ struct BwdRun {
         const ConvGeom& g = e.g;
         const int i = e.i;
         float* const dW = dwstd + c->ws_off[i];  // dwstd is laid out as the context's standardised weights
-        float* const db = G("short_motion_encoder." + std::to_string(kConvIdx[i]) + ".bias");
+        float* const db = G(enc_name(kConvIdx[i]) + ".bias");
         if (tns_fits(e.rows, g.cout, g.k * g.cin, 1)) {
             SOLA_TRY(stats(dy, g.cout, e.rows, g.cout, &e.scc, true, enc_dy16 ? dy16 : nullptr));
             GemmTnSplitDesc d{};
@@ -874,8 +865,8 @@ struct BwdRun {
         if (split && g.cout % 128 == 0 && g.cin % 8 == 0 && (size_t)rows * g.cout <= std::max((size_t)M, (size_t)BW) * 3 * D) {
             float* sl = e.scc ? e.scc : scal;
             if (e.scc && cast.holds(dy, g.cout, g.cout)) {}  // the statistics pass left the cast (bf16)
-            else if (e.scc) SOLA_TRY(cast_scaled(dy, g.cout, ar.get(S_DY_SP), rows, g.cout, sl));
-            else SOLA_TRY(cast_auto(dy, g.cout, ar.get(S_DY_SP), rows, g.cout, sl));
+            else if (e.scc) SOLA_TRY(ocast.scaled(dy, g.cout, ar.get(S_DY_SP), rows, g.cout, sl));
+            else SOLA_TRY(ocast.auto_scale(dy, g.cout, ar.get(S_DY_SP), rows, g.cout, sl));
             if (op16) SOLA_TRY(launch_cast_f16_t(w_std, g.k * g.cin, ar.get(S_WT_SP), g.cout, g.cout, g.k * g.cin, nullptr, opfmt, s));
             else SOLA_TRY(launch_cast_sp16_t(w_std, g.k * g.cin, ar.get(S_WT_SP), g.cout, g.cout, g.k * g.cin, nullptr, s));
             zd.p[0].A = ar.get(S_DY_SP); zd.p[0].W = ar.get(S_WT_SP);
@@ -927,7 +918,7 @@ struct BwdRun {
         d.C = g.cin; d.groups = c->cfg.n_groups; d.leaky = 1;
         d.drop = c->enc_drop(i - 1);
         if (enc_dy16) d.dx16 = dy16;
-        SOLA_TRY(gn_bwd(d, "short_motion_encoder." + std::to_string(kNormIdx[i - 1])));
+        SOLA_TRY(gn_bwd(d, enc_name(kNormIdx[i - 1])));
         dy = enc[1];  // dact (enc[0]) is consumed; the next stage's dX may overwrite it, its GN backward overwrites enc[1]
         return SOLA_OK;
     }
@@ -939,7 +930,7 @@ struct BwdRun {
         SOLA_TRY(join_side());               // dwstd is the side stream's
         WsBwdLayer layers[6];
         for (int i = 0; i < 6; ++i) {
-            const std::string cp = "short_motion_encoder." + std::to_string(kConvIdx[i]);
+            const std::string cp = enc_name(kConvIdx[i]);
             layers[i] = WsBwdLayer{W(cp + ".weight"), dwstd + c->ws_off[i], G(cp + ".weight"), c->conv[i].cout, c->conv[i].cin, c->conv[i].k};
         }
         SOLA_TRY(launch_ws_backward(layers, 6, s));

@@ -97,7 +97,7 @@ struct SolaCtx {
     }
     // inference precision: 0 = exact f32 MFMA; 1 = split-f16 operands, 3 x f16 MFMA with f32 accumulation (cast.hip).
     // ctx-owned split-f16 copies of the weights: standardised conv weights (same offsets as ws_buf) and the
-    // 12 * n_layers linear weights pre-scaled by 64 (index (layer * 3 + attn) * 4 + proj, D*D floats each).
+    // 12 * n_layers linear weights pre-scaled by 64 (index (layer * 3 + attn) * 4 + proj, D*D floats each): read through ws16_weight / lin16_weight below.
     int precision = 0;
     bool lin16_dirty = true;  // split copies of the projection weights are stale
     float* ws16_buf = nullptr;
@@ -116,12 +116,14 @@ struct SolaCtx {
     std::vector<X16Entry> x16;
     char* x16_arena = nullptr;  // BORROWED from the caller (sola_set_x16_arena); null = nothing is kept, the backward casts as before
     size_t x16_cap = 0, x16_used = 0, x16_need = 0;  // x16_need: what the last training forward asked for in total (fitting or not)
-    void* x16_alloc(size_t bytes) {  // null = no room this step (the caller uses its shared buffer and lists nothing)
-        bytes = (bytes + 255) & ~(size_t)255;
+    // a slot for the 16-bit rows of `src`, listed by it; null = no room this step (the caller uses its shared buffer and lists nothing)
+    void* x16_keep(const float* src, long long rows, int cols, Elem fmt) {
+        const size_t bytes = ((size_t)rows * cols * 2 + 255) & ~(size_t)255;
         x16_need += bytes;
         if (x16_used + bytes > x16_cap) return nullptr;
         void* r = x16_arena + x16_used;
         x16_used += bytes;
+        x16.push_back(X16Entry{src, r, cols, fmt});
         return r;
     }
     const void* x16_find(const float* src, int cols, Elem fmt) const {
@@ -187,7 +189,43 @@ static const int kConvIdx[6] = {0, 4, 8, 12, 16, 20};
 static const int kNormIdx[5] = {1, 5, 9, 13, 17};
 static const char* const kAttnShort[3] = {"obj", "mot", "o2l"};
 static const char* const kAttnLong[3] = {"obj_attn", "motion_attn", "object2lang_attn"};
+static const char* const kProj[4] = {"q_proj", "k_proj", "v_proj", "out_proj"};
 constexpr float kLinScale = 64.f;  // backward only (transposed weight casts): linear weights are U(-1/32, 1/32)-sized
+
+// ---- the parameters' names, by index
+inline std::string enc_name(int module_idx) { return "short_motion_encoder." + std::to_string(module_idx); }  // kConvIdx[i] / kNormIdx[i]
+inline std::string layer_prefix(int l) { return "object_lang_align_layers." + std::to_string(l) + "."; }
+inline std::string norm_name(int l, int site) { return layer_prefix(l) + "norm." + std::to_string(site); }
+inline std::string lin_name(int l, int site, int proj) { return layer_prefix(l) + kAttnLong[site] + "." + kProj[proj]; }
+
+// ---- the ctx-owned 16-bit operand copies of the weights, by index (their per-matrix inverse scales: SolaCtx::lin_inv_scale).
+// Projection `proj` (kProj) of site `site` in layer `layer`: split pairs (SP16) at D*D floats per matrix, plain rows (F16 / BF16) at D*D halfs
+// packed in the first half of the buffer.
+inline float* lin16_weight(const SolaCtx* c, Elem fmt, int layer, int site, int proj) {
+    const size_t at = ((size_t)(layer * 3 + site) * 4 + proj) * c->cfg.lang_token_dim * c->cfg.lang_token_dim;
+    return is_row16(fmt) ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(c->lin16_buf) + at) : c->lin16_buf + at;
+}
+// Standardised matrix of encoder conv `conv`, at ws_buf's offsets in floats (SP16) or halfs.  Exact f32 reads ws_buf itself.
+inline float* ws16_weight(const SolaCtx* c, Elem fmt, int conv) {
+    return is_row16(fmt) ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(c->ws16_buf) + c->ws_off[conv]) : c->ws16_buf + c->ws_off[conv];
+}
+
+// The row-major operand casts of a 16-bit step (forward.hip, backward.hip): `in` [rows][K] at pitch ld -> `out`, dense, in the step's
+// operand format - split pairs or plain f16 / bfloat16 rows.  scaled: by the power of two that `sc` holds; auto_scale: found on the
+// device and left in `sc`; fixed: the given one (side16, split pairs only: also the hi halves as plain f16 rows).
+struct OperandCast {
+    Elem opfmt;
+    hipStream_t s;
+    int scaled(const float* in, int ld, float* out, long long rows, int K, float* sc) const {
+        return is_row16(opfmt) ? launch_cast_f16_scaled(in, ld, out, K, rows, K, sc, opfmt, s) : launch_cast_sp16_scaled(in, ld, out, K, rows, K, sc, s);
+    }
+    int auto_scale(const float* in, int ld, float* out, long long rows, int K, float* sc) const {
+        return is_row16(opfmt) ? launch_cast_f16(in, ld, out, K, rows, K, 0.f, sc, opfmt, s) : launch_cast_sp16_auto(in, ld, out, K, rows, K, sc, s);
+    }
+    int fixed(const float* in, int ld, float* out, long long rows, int K, float scale, void* side16 = nullptr) const {
+        return is_row16(opfmt) ? launch_cast_f16(in, ld, out, K, rows, K, scale, nullptr, opfmt, s) : launch_cast_sp16(in, ld, out, K, rows, K, scale, s, side16);
+    }
+};
 // (re)builds the split-f16 copies of the projection weights with a per-matrix power-of-two scale and runs the weight-time
 // range check; no-op unless the copies are stale
 int sola_refresh_lin16(SolaCtx* c, hipStream_t s);

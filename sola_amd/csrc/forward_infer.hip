@@ -36,37 +36,36 @@
 int sola_refresh_lin16(SolaCtx* c, hipStream_t s) {
     if (!c->lin16_dirty) return SOLA_OK;
     SOLA_ARG(c->lin16_buf && c->scal_buf, "split-f16 weights requested before sola_set_precision(ctx, 1)");
-    static const char* pn[4] = {"q_proj", "k_proj", "v_proj", "out_proj"};
     const int D = c->cfg.lang_token_dim;
+    const Elem fmt = operand_format(c->precision);
     std::vector<const float*> in;
     std::vector<float*> out;
     for (int l = 0; l < c->cfg.n_layers; ++l)
         for (int a = 0; a < 3; ++a)
             for (int j = 0; j < 4; ++j) {
-                const std::string nm = "object_lang_align_layers." + std::to_string(l) + "." + kAttnLong[a] + "." + pn[j] + ".weight";
+                const std::string nm = lin_name(l, a, j) + ".weight";
                 const float* w = ctx_weight(c, nm);
                 if (!w) {
                     sola_set_error("forward: weight '%s' has not been set", nm.c_str());
                     return SOLA_ERR_WEIGHT;
                 }
                 in.push_back(w);
-                out.push_back(c->lin16_buf + ((size_t)(l * 3 + a) * 4 + j) * D * D);
+                out.push_back(lin16_weight(c, fmt, l, a, j));
             }
-    if (const Elem fmt = operand_format(c->precision); is_row16(fmt)) {  // 16-bit storage mode / 16-bit GEMM operands: plain f16 / bfloat16 copies, same per-matrix
-        std::vector<void*> outh;  // scales, packed in the first half of the buffer
-        for (size_t i = 0; i < out.size(); ++i) outh.push_back(reinterpret_cast<_Float16*>(c->lin16_buf) + i * (size_t)D * D);
+    if (is_row16(fmt)) {  // 16-bit storage mode / 16-bit GEMM operands: plain f16 / bfloat16 copies, same per-matrix scales
+        const std::vector<void*> outh(out.begin(), out.end());
         SOLA_TRY(launch_cast_f16_auto_multi(in.data(), outh.data(), (int)in.size(), D, D, c->scal_pair(2), fmt, s));
     } else {
         SOLA_TRY(launch_cast_sp16_auto_multi(in.data(), out.data(), (int)in.size(), D, D, c->scal_pair(2), s));
     }
     std::vector<NormPair> norms;
     for (int i = 0; i < 5; ++i) {
-        const std::string np = "short_motion_encoder." + std::to_string(kNormIdx[i]);
+        const std::string np = enc_name(kNormIdx[i]);
         norms.push_back(NormPair{ctx_weight(c, np + ".weight"), ctx_weight(c, np + ".bias"), c->conv[i].cout});
     }
     for (int l = 0; l < c->cfg.n_layers; ++l)
         for (int j = 0; j < 3; ++j) {
-            const std::string np = "object_lang_align_layers." + std::to_string(l) + ".norm." + std::to_string(j);
+            const std::string np = norm_name(l, j);
             norms.push_back(NormPair{ctx_weight(c, np + ".weight"), ctx_weight(c, np + ".bias"), D});
         }
     for (const NormPair& n : norms)
@@ -89,7 +88,7 @@ int sola_refresh_conv_weights(SolaCtx* c, Elem fmt, bool force, hipStream_t s) {
     if (!force && !c->ws_dirty && !c->ws_every_forward && (fmt == Elem::F32 || c->ws16_fmt == fmt)) return SOLA_OK;
     WsLayer layers[6];
     for (int i = 0; i < 6; ++i) {
-        const std::string nm = "short_motion_encoder." + std::to_string(kConvIdx[i]) + ".weight";
+        const std::string nm = enc_name(kConvIdx[i]) + ".weight";
         layers[i] = WsLayer{ctx_weight(c, nm), c->ws_buf + c->ws_off[i], c->conv[i].cout, c->conv[i].cin, c->conv[i].k};
     }
     SOLA_TRY(launch_ws_standardize(layers, 6, s));
@@ -151,8 +150,6 @@ int g_attn_split_min_keys = 96;
 int g_lang_shared_neg = 1;  // sola_tune "lang_shared_neg": 0 = the negative tokens repeated per sample through the text-side projections (A/B)
 
 namespace {
-
-const char* const kProj[4] = {"q_proj", "k_proj", "v_proj", "out_proj"};
 
 // What the two inference sequences below (uniform batch, ragged batch) have in common: the ctx's precision mode, written ONCE
 // into every descriptor.  The geometry - strides or unit tables, instance counts, sequence lengths - comes from sites.h: the encoder
@@ -228,19 +225,10 @@ struct InferBuilder {
     }
 
     // ---- the weights in the mode's operand format: f32 as set, split-f16 pairs (D*D floats per matrix) or plain f16 (D*D halfs)
-    const float* ws_w(int i) const {
-        if (h16) return reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->ws16_buf) + c->ws_off[i]);
-        return sp ? c->ws16_buf + c->ws_off[i] : c->ws_buf + c->ws_off[i];
-    }
-    std::string lin_name(int layer, int attn_i, int proj) const {
-        return "object_lang_align_layers." + std::to_string(layer) + "." + kAttnLong[attn_i] + "." + kProj[proj];
-    }
+    const float* ws_w(int i) const { return op16 ? ws16_weight(c, opfmt, i) : c->ws_buf + c->ws_off[i]; }
     GemmProblem lin_problem(const float* a, int layer, int attn_i, int proj, const float* r, float* out) const {
         const std::string nm = lin_name(layer, attn_i, proj);
-        const size_t at = ((size_t)(layer * 3 + attn_i) * 4 + proj) * D * D;
-        const float* w = sp ? c->lin16_buf + at
-                       : h16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(c->lin16_buf) + at)
-                             : W(nm + ".weight");
+        const float* w = op16 ? lin16_weight(c, opfmt, layer, attn_i, proj) : W(nm + ".weight");
         return GemmProblem{a, w, W(nm + ".bias"), r, out, op16 ? c->lin_inv_scale(layer, attn_i, proj) : nullptr};
     }
 
@@ -280,7 +268,7 @@ struct InferBuilder {
         const ConvGeom& g = c->conv[i];
         GemmDesc gd = gemm(rows, g.cout, g.k * g.cin);
         gd.nprob = 1;
-        gd.p[0] = GemmProblem{x, ws_w(i), W("short_motion_encoder." + std::to_string(kConvIdx[i]) + ".bias"), nullptr, out};
+        gd.p[0] = GemmProblem{x, ws_w(i), W(enc_name(kConvIdx[i]) + ".bias"), nullptr, out};
         gd.lda = g.cin;
         gd.conv = g.k > 1 ? 1 : 0;
         gd.stride = g.stride; gd.pad = g.pad; gd.Cin = g.cin;
@@ -352,14 +340,13 @@ struct InferBuilder {
         return nd;
     }
     GroupNormDesc encoder_norm(int i, const float* x, float* y) const {
-        GroupNormDesc nd = norm("short_motion_encoder." + std::to_string(kNormIdx[i]), x, y, c->conv[i].cout, c->cfg.n_groups, true);
+        GroupNormDesc nd = norm(enc_name(kNormIdx[i]), x, y, c->conv[i].cout, c->cfg.n_groups, true);
         nd.slope = 0.01f; nd.leaky = 1;
         if (h16 && i == 0) nd.in_scale_dev = c->scal_pair(0) + 1;  // conv0's output is in the scaled units of the tokens
         return nd;
     }
     GroupNormDesc layer_norm(int layer, int idx, float* y, float* y2, bool out16) const {  // y2: optional y + positional encoding
-        GroupNormDesc nd = norm("object_lang_align_layers." + std::to_string(layer) + ".norm." + std::to_string(idx), res, y, D,
-                                c->cfg.n_groups_module, out16);
+        GroupNormDesc nd = norm(norm_name(layer, idx), res, y, D, c->cfg.n_groups_module, out16);
         nd.y2 = y2; nd.pe = y2 ? pe : nullptr;
         return nd;
     }
@@ -457,7 +444,7 @@ int sola_forward_infer_impl(SolaCtx* c, const float* obj, const float* lang, int
             GemmDesc probe = gd;
             probe.c = Elem::SP16;
             if (gemm_gn_fusable(probe, c->conv[i].cout / c->cfg.n_groups, p.Tl[i])) {
-                const std::string np = "short_motion_encoder." + std::to_string(kNormIdx[i]);
+                const std::string np = enc_name(kNormIdx[i]);
                 gd.c = Elem::SP16;
                 gd.p[0].C = buf("act" + is);
                 gd.gn_gamma = b.W(np + ".weight"); gd.gn_beta = b.W(np + ".bias");

@@ -239,7 +239,8 @@ void __hipUnregisterFatBinary(void**) {}
 }
 
 // ---- cases ----------------------------------------------------------------------------------------------------------------------------------
-static const SolaConfig kFull = {256, 1024, 2, 100, 32, 8, 8, 8}, kSmall = {32, 128, 2, 100, 4, 8, 8, 8};
+static const SolaConfig kFull = {256, 1024, 2, 100, 32, 8, 8, 8}, kSmall = {32, 128, 2, 100, 4, 8, 8, 8},
+                        kDeep = {256, 1024, 11, 100, 32, 8, 8, 8};
 static char *g_obj, *g_lang, *g_sm, *g_st_out, *g_ws, *g_scratch, *g_dsm, *g_dst, *g_w, *g_g, *g_arena;
 
 static SolaCtx* make_ctx(const SolaConfig& cfg, int precision, bool grads, bool arena) {
@@ -386,6 +387,15 @@ static void train_cases() {
         sola_tune("train_bf16_store", 2);
         status("backward (train_bf16_store changed)", sola_backward(c, (float*)g_dsm, (float*)g_dst, g_ws, g_scratch, (size_t)1 << 36, nullptr));
         sola_tune("train_bf16_store", 3);
+        sola_ctx_destroy(c);
+    }
+    // more than ten layers, the reduced-precision steps: every layer's projections read their own 16-bit copies and scales (ctx.h: lin16_weight)
+    for (int prec = 1; prec <= 3; ++prec) {
+        SolaCtx* c = make_ctx(kDeep, prec, true, true);
+        printf("== train deep precision %d uniform %d %d %d %d\n", prec, shapes[4].B, shapes[4].N, shapes[4].T, shapes[4].L);
+        train_step(c, shapes[4], nullptr);
+        printf("== train deep precision %d ragged 0\n", prec);
+        train_step(c, Uni{}, &rags[0]);
         sola_ctx_destroy(c);
     }
 }
