@@ -445,6 +445,30 @@ int sola_group_norm_backward(const float* dev_x, const float* dev_dy, const floa
                              int n_inst, int inner, int64_t outer_stride, int64_t inner_stride, int64_t tok_stride,
                              int ntok, int C, int groups, float eps, float leaky_slope, int apply_leaky,
                              void* dev_scratch, size_t scratch_bytes, void* stream);
+/* GroupNorm with every field of its descriptors (tests).  Formats are the codes of sola_set_precision's operand formats (0 f32, 1 split-f16
+ * pairs, 2 f16, 3 bfloat16); 16-bit rows have the pitch C counted in their own elements.
+ *   sola_group_norm_ex: sola_group_norm on in_fmt rows (0, 2, 3) writing out_fmt rows (0, 1, 2).  dev_units (NULL or n_inst int32 quadruples:
+ *     first row, row stride, token count, pe row) replaces the strided pattern, ntok is then the largest count.  dev_in_scale: optional device
+ *     scalar multiplied into x.  dev_guard: range guard word of 16-bit outputs (set to 1 by a value of 65000 or more; never cleared).
+ *     dev_y_cast / dev_y2_cast: beside f32 outputs, the same values as cast_fmt (2, 3) rows.  dev_slice_ws: 8 bytes per (instance, group, slice)
+ *     for units beyond the register shapes (NULL: the library's own).  dev_stats_out: where that shape leaves (mean, rstd) per (instance,
+ *     group); *stats_written (host) is set to 1 when it did.
+ *   sola_group_norm_backward_ex: sola_group_norm_backward with dev_units, x as x_fmt rows (0, 3), dy2 as dy2_fmt rows (0, 3), dx once more
+ *     as bfloat16 rows (dev_dx16) and the forward's statistics (dev_stats_in, read by the shape beyond the register shapes only).
+ *   sola_group_norm_shape: the kernel shape of a unit of ntok tokens x cg channels under the present sola_tune switches; direction 0 forward,
+ *     1 backward (which ignores the formats); out5 = (kind: 0 wave, 1 block, 2 sliced, 3 three-pass; token slots per lane; threads per block;
+ *     channels per lane; slices per unit).  Host only: needs no device. */
+int sola_group_norm_ex(const void* dev_x, void* dev_y, void* dev_y2, const float* dev_pe, const float* dev_gamma, const float* dev_beta,
+                       int n_inst, int inner, int64_t outer_stride, int64_t inner_stride, int64_t tok_stride, int ntok, int C, int groups,
+                       float eps, float leaky_slope, int apply_leaky, int in_fmt, int out_fmt, const int32_t* dev_units,
+                       const float* dev_in_scale, int* dev_guard, void* dev_y_cast, void* dev_y2_cast, int cast_fmt, void* dev_slice_ws,
+                       size_t slice_ws_bytes, void* dev_stats_out, int* stats_written, void* stream);
+int sola_group_norm_backward_ex(const void* dev_x, const float* dev_dy, const void* dev_dy2, const float* dev_gamma, const float* dev_beta,
+                                float* dev_dx, float* dev_dgamma, float* dev_dbeta, int n_inst, int inner, int64_t outer_stride,
+                                int64_t inner_stride, int64_t tok_stride, int ntok, int C, int groups, float eps, float leaky_slope,
+                                int apply_leaky, const int32_t* dev_units, int x_fmt, int dy2_fmt, void* dev_dx16, const void* dev_stats_in,
+                                void* dev_scratch, size_t scratch_bytes, void* stream);
+int sola_group_norm_shape(int direction, int ntok, int cg, int in_fmt, int out_fmt, int dropout, int out5[5]);
 int sola_attention_backward(const float* dev_q, int ldq, const float* dev_k, int ldk, const float* dev_v, int ldv,
                             const float* dev_o, const float* dev_dout, int ldo, const float* dev_lse,
                             float* dev_dq, float* dev_dk, float* dev_dv, float* dev_dvec /* [q rows, H] scratch */,

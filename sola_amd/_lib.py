@@ -117,6 +117,11 @@ SIGNATURES = {
     "sola_conv1d_cl_backward_split_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "sola_conv1d_cl_backward_split": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "sola_group_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _i64, _i, _i, _i, _f, _f, _i, _vp, _sz, _vp]),
+    "sola_group_norm_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _i64, _i, _i, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i,
+                                _vp, _sz, _vp, C.POINTER(_i), _vp]),
+    "sola_group_norm_backward_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _i64, _i, _i, _i, _f, _f, _i, _vp, _i, _i, _vp,
+                                         _vp, _vp, _sz, _vp]),
+    "sola_group_norm_shape": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sola_attention_backward": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i,
                                      _i64, _i64, _i64, _i64, _i64, _i64, _f, _vp]),
     "sola_attention_backward_scratch_floats": (_sz, [_i64, _i, _i, _i]),

@@ -11,6 +11,7 @@
 
 #include "ragged.h"
 #include "tune.h"
+#include "gn_common.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // errors
@@ -1126,6 +1127,69 @@ extern "C" int sola_group_norm_backward(const float* x, const float* dy, const f
     SOLA_TRY(launch_group_norm_bwd(d, s));
     SOLA_TRY(launch_colsum(gp, dgamma, 1, n_inst, C, C, 1.f, 0, nullptr, 0, s));
     return launch_colsum(bp, dbeta, 1, n_inst, C, C, 1.f, 0, nullptr, 0, s);
+}
+
+// GroupNorm with every field of its descriptors (tests): the two entry points above plus the row formats, ragged units, the input scale, the
+// range guard, the operand casts, the caller's slice scratch and the statistics hand-over.  Formats are Elem codes (0 f32, 1 split-f16 pairs,
+// 2 f16, 3 bfloat16); 16-bit rows have the pitch C in their own elements.  No arithmetic here: descriptors in, launchers out.
+static bool elem_code_ok(int e) { return e >= (int)Elem::F32 && e <= (int)Elem::BF16; }
+extern "C" int sola_group_norm_ex(const void* x, void* y, void* y2, const float* pe, const float* gamma, const float* beta, int n_inst, int inner,
+                                  int64_t outer_stride, int64_t inner_stride, int64_t tok_stride, int ntok, int C, int groups, float eps,
+                                  float slope, int leaky, int in_fmt, int out_fmt, const int32_t* units, const float* in_scale_dev, int* guard,
+                                  void* y_cast, void* y2_cast, int cast_fmt, void* slice_ws, size_t slice_ws_bytes, void* stats_out,
+                                  int* stats_written, void* stream_) {
+    SOLA_ARG(x && y && gamma && beta, "group_norm_ex: null argument");
+    SOLA_ARG(elem_code_ok(in_fmt) && elem_code_ok(out_fmt) && elem_code_ok(cast_fmt), "group_norm_ex: formats %d, %d, %d", in_fmt, out_fmt, cast_fmt);
+    GroupNormDesc d{static_cast<const float*>(x), static_cast<float*>(y), static_cast<float*>(y2), pe, gamma, beta, n_inst, inner, outer_stride,
+                    inner_stride, tok_stride, ntok, C, groups, eps, slope, leaky};
+    d.drop = g_stage_drop;
+    d.in = static_cast<Elem>(in_fmt); d.out = static_cast<Elem>(out_fmt);
+    d.guard = guard;
+    d.units = reinterpret_cast<const int4*>(units);
+    d.in_scale_dev = in_scale_dev;
+    d.slice_ws = slice_ws; d.slice_ws_bytes = slice_ws_bytes;
+    d.y_cast = y_cast; d.y2_cast = y2_cast; d.cast = static_cast<Elem>(cast_fmt);
+    d.stats_out = stats_out; d.stats_written = stats_written;
+    return launch_group_norm(d, as_stream(stream_));
+}
+
+// dgamma / dbeta [C]; scratch: 2 * n_inst * C floats, as sola_group_norm_backward
+extern "C" int sola_group_norm_backward_ex(const void* x, const float* dy, const void* dy2, const float* gamma, const float* beta, float* dx,
+                                           float* dgamma, float* dbeta, int n_inst, int inner, int64_t outer_stride, int64_t inner_stride,
+                                           int64_t tok_stride, int ntok, int C, int groups, float eps, float slope, int leaky,
+                                           const int32_t* units, int x_fmt, int dy2_fmt, void* dx16, const void* stats_in, void* scratch,
+                                           size_t scratch_bytes, void* stream_) {
+    SOLA_ARG(x && dy && gamma && beta && dx && dgamma && dbeta && scratch, "group_norm_backward_ex: null argument");
+    SOLA_ARG(elem_code_ok(x_fmt) && elem_code_ok(dy2_fmt), "group_norm_backward_ex: formats %d, %d", x_fmt, dy2_fmt);
+    const size_t need = (size_t)2 * n_inst * C * sizeof(float);
+    if (scratch_bytes < need) {
+        sola_set_error("group_norm_backward_ex: scratch %zu < %zu", scratch_bytes, need);
+        return SOLA_ERR_WORKSPACE;
+    }
+    float* gp = static_cast<float*>(scratch);
+    float* bp = gp + (size_t)n_inst * C;
+    GroupNormBwdDesc d{static_cast<const float*>(x), dy, static_cast<const float*>(dy2), gamma, beta, dx, gp, bp, n_inst, inner, outer_stride,
+                       inner_stride, tok_stride, ntok, C, groups, eps, slope, leaky};
+    d.drop = g_stage_drop;
+    d.units = reinterpret_cast<const int4*>(units);
+    d.x_fmt = static_cast<Elem>(x_fmt); d.dy2_fmt = static_cast<Elem>(dy2_fmt);
+    d.dx16 = dx16; d.stats_in = stats_in;
+    hipStream_t s = as_stream(stream_);
+    SOLA_TRY(launch_group_norm_bwd(d, s));
+    SOLA_TRY(launch_colsum(gp, dgamma, 1, n_inst, C, C, 1.f, 0, nullptr, 0, s));
+    return launch_colsum(bp, dbeta, 1, n_inst, C, C, 1.f, 0, nullptr, 0, s);
+}
+
+// The kernel shape a unit of ntok tokens x cg channels takes under the live sola_tune switches (tests; host only): direction 0 = forward
+// (gn_fwd_shape), 1 = backward (gn_bwd_shape); out5 = (kind: 0 wave, 1 block, 2 sliced, 3 three-pass; R; threads; channels per lane; slices)
+extern "C" int sola_group_norm_shape(int direction, int ntok, int cg, int in_fmt, int out_fmt, int dropout, int out5[5]) {
+    SOLA_ARG(out5 && (direction == 0 || direction == 1) && ntok > 0 && cg > 0 && cg % 4 == 0 && cg / 4 <= 256, "group_norm_shape: bad argument");
+    SOLA_ARG(elem_code_ok(in_fmt) && elem_code_ok(out_fmt), "group_norm_shape: formats %d, %d", in_fmt, out_fmt);
+    const GnShape sh = direction == 0 ? gn_fwd_shape(ntok, cg, static_cast<Elem>(in_fmt), static_cast<Elem>(out_fmt), dropout != 0, g_gn_variant,
+                                                     g_gn_wide, g_gn_slices, g_gn_h8)
+                                      : gn_bwd_shape(ntok, cg, g_gn_bwd_reg);
+    out5[0] = (int)sh.kind; out5[1] = sh.R; out5[2] = sh.nthr; out5[3] = sh.cpl; out5[4] = sh.slices;
+    return SOLA_OK;
 }
 
 extern "C" int sola_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,

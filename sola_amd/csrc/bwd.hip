@@ -681,6 +681,8 @@ bool group_norm_bwd_dy2_bf16_supported(int ntok, int C, int groups) {
 }
 
 int launch_group_norm_bwd(const GroupNormBwdDesc& d, hipStream_t s) {
+    // ORDER: the format checks and the bfloat16-dy2 check stand in front of the SolaProfScope and the launch - a refused call never touches
+    // the device (tests/test_gn_cpu.py sends refused combinations with host pointers and relies on it)
     SOLA_ARG(d.groups > 0 && d.C % d.groups == 0, "group_norm_bwd: C=%d groups=%d", d.C, d.groups);
     const int cg = d.C / d.groups;
     SOLA_ARG(cg % 4 == 0 && cg / 4 <= 256, "group_norm_bwd: channels per group %d unsupported", cg);

@@ -23,13 +23,14 @@ constexpr int GN_SLICE_R = 32;  // float4 per thread and slice of the sliced sha
 // token slots per lane when `lanes` lanes of `lpt` lanes per token share a unit (none where the lanes do not divide into tokens)
 constexpr int gn_slots(int ntok, int lanes, int lpt) { return lanes % lpt == 0 ? (ntok + lanes / lpt - 1) / (lanes / lpt) : 1 << 30; }
 
-// Forward.  in / out / dropout select the eight-channel form (16-bit rows in, f16 rows out, inference); gn_variant, gn_wide, gn_slices and
+// Forward.  in / out / dropout select the eight-channel form (f16 rows in, f16 rows out, inference); gn_variant, gn_wide, gn_slices and
 // gn_h8 are the sola_tune switches of the same names.  A Sliced result still needs its scratch: the launcher falls back to ThreePass.
 constexpr GnShape gn_fwd_shape(int ntok, int cg, Elem in, Elem out, bool dropout, int gn_variant, int gn_wide, int gn_slices, int gn_h8) {
     const GnShape three_pass{GnKind::ThreePass, 0, 256, 4, 0};
     if (!gn_variant) return three_pass;
     const int f4 = cg / 4;
-    if (gn_h8 && in != Elem::F32 && out == Elem::F16 && !dropout && cg % 8 == 0) {
+    // (f16 rows only: the eight-channel kernel widens its loads as _Float16; bfloat16 rows take the four-channel shapes, which widen them)
+    if (gn_h8 && in == Elem::F16 && out == Elem::F16 && !dropout && cg % 8 == 0) {
         const int f8 = cg / 8;
         const int rw8 = gn_slots(ntok, 64, f8), rb8 = gn_slots(ntok, 256, f8), rk8 = gn_slots(ntok, 1024, f8);
         if (rw8 <= 2) return {GnKind::Wave, rw8, 256, 8, 0};
@@ -94,6 +95,7 @@ static_assert(fwd8(65, 128) == block(4, 1024, 8) && fwd8(256, 128) == block(4, 1
 static_assert(fwd8(4, 128, 0) == wave(2) && fwd8(8, 128, 0) == wave(4) && fwd8(32, 128, 0) == block(4) && fwd8(64, 128, 0) == block(8));
 static_assert(fwd8(65, 128, 0) == block(16) && fwd8(256, 128, 0) == block(8, 1024) && fwd8(257, 128, 0) == sliced(2));
 static_assert(gn_fwd_shape(4, 128, Elem::F16, Elem::F16, true, 1, 1, 1, 1) == wave(2) && gn_fwd_shape(4, 128, Elem::F32, Elem::F16, false, 1, 1, 1, 1) == wave(2));
+static_assert(gn_fwd_shape(4, 128, Elem::BF16, Elem::F16, false, 1, 1, 1, 1) == wave(2) && gn_fwd_shape(65, 128, Elem::BF16, Elem::F16, false, 1, 1, 1, 1) == block(16));
 // backward, 16 channels per group
 static_assert(bwd(16, 16) == wave(1) && bwd(32, 16) == wave(2) && bwd(64, 16) == wave(4) && bwd(65, 16) == block(2) && bwd(128, 16) == block(2));
 static_assert(bwd(256, 16) == block(4) && bwd(512, 16) == block(8) && bwd(513, 16) == block(8, 512) && bwd(1024, 16) == block(8, 512));

@@ -340,7 +340,8 @@ __global__ __launch_bounds__(NTHR) void group_norm_reg_kernel(const GnArgs a, lo
 // 16-byte store per lane and token slot instead of 8-byte ones.  With four channels per lane a unit keeps half as many bytes in
 // flight as in the f32 modes and the f16 norms ran at 77 % of the f32 norms' TIME for half their bytes.
 // R = token slots of 8 channels per lane; same statistics (two passes over the registers), affine, LeakyReLU, y + pe side output
-// and range guard as gn_apply_store's f16 branch.  Inference only (no dropout).
+// and range guard as gn_apply_store's f16 branch.  Inference only (no dropout).  x is read as _Float16 whatever a.in_f16 says: bfloat16
+// rows never get here, gn_fwd_shape (gn_common.h) sends them to the four-channel shapes.
 template <int R, bool WAVE, int NTHR = 256>
 __global__ __launch_bounds__(NTHR) void group_norm_reg_h8_kernel(const GnArgs a, long long n_units) {
     __shared__ float red[NTHR / 64];
@@ -705,6 +706,8 @@ static float2* gn_slice_scratch(size_t bytes, hipStream_t s) {
 int g_gn_h8 = 1;  // sola_tune "gn_h8": 0 = four channels per lane in the 16-bit storage mode too (A/B)
 
 int launch_group_norm(const GroupNormDesc& d, hipStream_t s) {
+    // ORDER: the size and format checks stand in front of the SolaProfScope and the launches - a call refused for its formats never
+    // touches the device (tests/test_gn_cpu.py sends refused format combinations with host pointers and relies on it)
     SOLA_ARG(d.groups > 0 && d.C % d.groups == 0, "group_norm: C=%d groups=%d", d.C, d.groups);
     const int cg = d.C / d.groups;
     SOLA_ARG(cg % 4 == 0 && cg / 4 <= 256, "group_norm: channels per group %d must be a multiple of 4 and <= 1024", cg);
